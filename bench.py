@@ -2,7 +2,7 @@
 """Headline benchmark of the RepCONC PQ hot path on MI355X (BASELINE.json metric:
 "constrained-cluster assignments/sec + ADC queries/sec, 8.8M x 768d M=48 K=256").
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,7 @@ resident in HBM (fp32, synthetic N(0,1)) before the timed region.  With N ranks,
 [r*B/N, (r+1)*B/N) and the row sums are all-gathered every iteration (strong scaling of a step).
 
 `value` = constrained assignments (document vectors) per second, whole job.  The ADC leg (second
-half of the metric) is reported in the `adc` object of the same JSON line: PQ inner-product top-1000
+half of the metric; --full) is reported in the `adc` object of the same JSON line: PQ inner-product top-1000
 search of 1200-query batches over a resident 8,841,823 x 48-byte index; with N ranks the index is
 replicated and the queries are split (the reference's co.shard=False, evaluate_repconc.py:131-134).
 
@@ -22,8 +22,13 @@ replicated and the queries are split (the reference's co.shard=False, evaluate_r
 bytes per launch = B_local*M*K*4 (one fp32 read of the K centred distances of every (vector,
 sub-quantiser)) divided by its average launch duration, measured with HIP events
 recorded around every launch inside the timed region (rc_profile_*, on the launch stream).
-`cpu_baseline` times the oracle's C port of the reference algorithm on the host cores (rank 0,
+`cpu_baseline` (--full) times the oracle's C port of the reference algorithm on the host cores (rank 0,
 N=1 only) on a bounded sample.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR)
+and prints the line.  Everything else — the ADC / IVF / index-build / OPQ / k-means legs, the
+per_rank_6144 shape, the CPU baselines, the live PMC traffic passes and, with N > 1, the
+sharded-vs-unsharded and recipe-batch checks and the stand-alone ceiling — runs only with --full.
 """
 import argparse
 import json
@@ -68,7 +73,24 @@ def parse():
                     help="development: run the N>1 code path (RCCL collectives, staged sweeps) with one rank")
     ap.add_argument("--dist-driver", choices=("auto", "staged"), default="auto",
                     help="N>1: auto = native RCCL loop if it passes the self-check, staged = torch.distributed loop")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check (ADC / IVF / index-build / OPQ / k-means legs, per_rank_6144, "
+                         "CPU baselines, live PMC traffic; N > 1: the unsharded and recipe-batch checks, the stand-alone ceiling); "
+                         "the --no-* options above select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): codes "
+                         "[global batch, M] and flags [one per rank]")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
+
+
+def dump_outputs(dirname, arrays):
+    """{name: numpy array} -> dirname/<name>.npy as float32 (every value here is an integer below 2^24: exact)."""
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(dirname, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def pmc_traffic(kernel):
@@ -376,7 +398,7 @@ def main():
         gathered = [torch.empty_like(c_staged) for _ in range(world)]
         dist.all_gather(gathered, c_staged)
         unsharded_equal = None
-        if rank == 0:
+        if rank == 0 and args.full:
             ref_codes, _ = ops.assign_sinkhorn(torch.from_numpy(xs_full).to(dev), C, EPS, ITERS, torch.uint8)
             unsharded_equal = bool(torch.equal(torch.cat(gathered, 0), ref_codes))
         dist_check = {"global_batch": gb,
@@ -384,35 +406,36 @@ def main():
                                  "python-staged torch.distributed loop"),
                       "transport": chosen, "native_equals_staged": native_all if candidates else None,
                       "transport_notes": notes or None, "sharded_equals_unsharded": unsharded_equal}
-        # (3) the recipe's own batch against the REFERENCE: the 49 152-row batch of
-        # tests/golden/headline_b49152_m48_sample.npz, `world` equal row blocks through the driver chosen above, compared with
-        # what the reference's distributed branch returned on eight gloo ranks (recipe8_b49152_m48_sample.npz — identical to
-        # its one-process codes, so the expected codes do not depend on the number of ranks)
-        golden = os.path.join(ROOT, "tests", "golden")
-        try:
-            import zlib
-            from oracle import synth                         # input synthesis from seeds (shared with the fixtures), no arithmetic
-            hg = np.load(os.path.join(golden, "headline_b49152_m48_sample.npz"))
-            r8 = np.load(os.path.join(golden, "recipe8_b49152_m48_sample.npz"))
-            Bh = int(hg["B"])
-            if Bh % world == 0:
-                xh = synth.clustered_embeddings(int(hg["x_seed"]), Bh, n_clusters=int(hg["n_clusters"]))
-                Ch = hg["centroids"] if "centroids" in hg.files else synth.sample_centroids(int(hg["c_seed"]), xh, M)
-                assert zlib.crc32(np.ascontiguousarray(Ch).tobytes()) == int(hg["centroids_crc"])
-                want = hg["codes_constrained"] ^ r8["codes_xor_one_process"]
-                blh = Bh // world
-                xh_l = torch.from_numpy(np.ascontiguousarray(xh[rank * blh:(rank + 1) * blh])).to(dev)
-                del xh
-                ch_l, fl_h = assign_sinkhorn_sharded(xh_l, torch.from_numpy(np.ascontiguousarray(Ch)).to(dev), EPS, ITERS, comm,
-                                                     dtype=torch.uint8)
-                torch.cuda.synchronize()
-                bad_h = int((ch_l.cpu().numpy() != want[rank * blh:(rank + 1) * blh]).sum()) + (0 if int(fl_h.item()) == 0 else 1)
-                dist_check["recipe_batch_equals_the_references_8_rank_run"] = all_ranks(bad_h == 0)
-                dist_check["recipe_batch"] = f"{Bh} x 768, M=48: {blh} rows per rank on {world} ranks, every code compared"
-                del xh_l, ch_l
-        except FileNotFoundError as e:
-            dist_check["recipe_batch_equals_the_references_8_rank_run"] = None
-            dist_check["recipe_batch"] = f"fixture missing: {e}"
+        if args.full:
+            # (3) the recipe's own batch against the REFERENCE: the 49 152-row batch of
+            # tests/golden/headline_b49152_m48_sample.npz, `world` equal row blocks through the driver chosen above, compared with
+            # what the reference's distributed branch returned on eight gloo ranks (recipe8_b49152_m48_sample.npz — identical to
+            # its one-process codes, so the expected codes do not depend on the number of ranks)
+            golden = os.path.join(ROOT, "tests", "golden")
+            try:
+                import zlib
+                from oracle import synth                         # input synthesis from seeds (shared with the fixtures), no arithmetic
+                hg = np.load(os.path.join(golden, "headline_b49152_m48_sample.npz"))
+                r8 = np.load(os.path.join(golden, "recipe8_b49152_m48_sample.npz"))
+                Bh = int(hg["B"])
+                if Bh % world == 0:
+                    xh = synth.clustered_embeddings(int(hg["x_seed"]), Bh, n_clusters=int(hg["n_clusters"]))
+                    Ch = hg["centroids"] if "centroids" in hg.files else synth.sample_centroids(int(hg["c_seed"]), xh, M)
+                    assert zlib.crc32(np.ascontiguousarray(Ch).tobytes()) == int(hg["centroids_crc"])
+                    want = hg["codes_constrained"] ^ r8["codes_xor_one_process"]
+                    blh = Bh // world
+                    xh_l = torch.from_numpy(np.ascontiguousarray(xh[rank * blh:(rank + 1) * blh])).to(dev)
+                    del xh
+                    ch_l, fl_h = assign_sinkhorn_sharded(xh_l, torch.from_numpy(np.ascontiguousarray(Ch)).to(dev), EPS, ITERS, comm,
+                                                         dtype=torch.uint8)
+                    torch.cuda.synchronize()
+                    bad_h = int((ch_l.cpu().numpy() != want[rank * blh:(rank + 1) * blh]).sum()) + (0 if int(fl_h.item()) == 0 else 1)
+                    dist_check["recipe_batch_equals_the_references_8_rank_run"] = all_ranks(bad_h == 0)
+                    dist_check["recipe_batch"] = f"{Bh} x 768, M=48: {blh} rows per rank on {world} ranks, every code compared"
+                    del xh_l, ch_l
+            except FileNotFoundError as e:
+                dist_check["recipe_batch_equals_the_references_8_rank_run"] = None
+                dist_check["recipe_batch"] = f"fixture missing: {e}"
         # (4) who sits where: one line per rank (device index, PCI bus id), and whether every rank has a device of its own — an
         # IPC transport that passed above between ranks on DISTINCT devices has mapped a peer device's buffer
         # (hipIpcOpenMemHandle across devices) and exchanged through it
@@ -425,18 +448,19 @@ def main():
         dist_check["one_device_per_rank"] = distinct
         dist_check["ipc_between_peer_devices"] = (bool(distinct and any(t.startswith("ipc") for t in measured)) if candidates else None)
         # (5) the ceiling of this rank count: this rank's share of the batch solved stand-alone (no exchange at all)
-        for _ in range(2):
-            ops.assign_sinkhorn(pool[0], C, EPS, ITERS, torch.uint8)
-        barrier()
-        tt0 = time.perf_counter()
-        for i in range(3):
-            ops.assign_sinkhorn(pool[i % n_pool], C, EPS, ITERS, torch.uint8)
-        barrier()
-        alone_ms = max_over_ranks(time.perf_counter() - tt0) * 1e3 / 3
-        dist_check["standalone_share"] = {"rows": bl, "ms_per_step": round(alone_ms, 3),
-                                          "ceiling_vectors_per_sec": round(B / (alone_ms * 1e-3), 1),
-                                          "what": "every rank solves its own rows with NO exchange (a different problem: the "
-                                                  "constraint is per rank): the time a sharded step cannot beat"}
+        if args.full:
+            for _ in range(2):
+                ops.assign_sinkhorn(pool[0], C, EPS, ITERS, torch.uint8)
+            barrier()
+            tt0 = time.perf_counter()
+            for i in range(3):
+                ops.assign_sinkhorn(pool[i % n_pool], C, EPS, ITERS, torch.uint8)
+            barrier()
+            alone_ms = max_over_ranks(time.perf_counter() - tt0) * 1e3 / 3
+            dist_check["standalone_share"] = {"rows": bl, "ms_per_step": round(alone_ms, 3),
+                                              "ceiling_vectors_per_sec": round(B / (alone_ms * 1e-3), 1),
+                                              "what": "every rank solves its own rows with NO exchange (a different problem: the "
+                                                      "constraint is per rank): the time a sharded step cannot beat"}
         if native_all:
             exchange = {"transport": chosen, "chains": measured[chosen]["chains"],
                         "bytes_per_rank": (M // measured[chosen]["chains"]) * K * 8,
@@ -470,7 +494,21 @@ def main():
         codes, flags = step(args.warmup + i)
     barrier()
     dt = time.perf_counter() - t0
-    if not profile_timed:
+    if args.dump_outputs:
+        # what the timed path returned in its last step, before any other launch: the codes of the whole batch (rank blocks in
+        # rank order) and each rank's flags
+        if use_dist:
+            parts = [torch.empty_like(codes) for _ in range(world)]
+            dist.all_gather(parts, codes)
+            fparts = [torch.empty_like(flags) for _ in range(world)]
+            dist.all_gather(fparts, flags)
+            codes_all, flags_all = torch.cat(parts, 0), torch.cat(fparts, 0)
+        else:
+            codes_all, flags_all = codes, flags
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"codes": codes_all.cpu().numpy(), "flags": flags_all.cpu().numpy()})
+        del codes_all, flags_all
+    if not profile_timed and args.full:
         lib.rc_profile_enable(h, 1)
         step(args.warmup + args.steps)
         barrier()
@@ -493,7 +531,8 @@ def main():
                           "priority rotating with the clock)",
                 "measured_in": "timed region: one HIP-event pair around each step's 98 back-to-back sweep launches (t >= 2, "
                                "replayed from the hipGraph), divided by 98 - inter-launch gaps included" if profile_timed else
-                               "one extra profiled step after the timed region (the timed region replays the hipGraph)",
+                               "one extra profiled step after the timed region (the timed region replays the hipGraph)" if args.full else
+                               "not measured: N > 1 needs an extra profiled step, run with --full",
                 "bound": "hbm", "achieved": round(achieved, 1),
                 "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                 "traffic": pmc_traffic("sk_sweep_kernel"),
@@ -544,7 +583,7 @@ def main():
                             "walk through the N > 1 code, not a measurement")
 
     # ------------------------------------------------------------------ the 8-GPU recipe's per-rank shape on this GPU
-    if not use_dist and B == B_GLOBAL and not args.no_per_rank:
+    if args.full and not use_dist and B == B_GLOBAL and not args.no_per_rank:
         blr = B_GLOBAL // 8
         xr = pool[0][:blr].contiguous()
         for _ in range(2):
@@ -571,7 +610,7 @@ def main():
                          "launches_timed": n_l.value}}
 
     # ------------------------------------------------------------------ ADC search leg
-    if not args.no_adc:
+    if args.full and not args.no_adc:
         del pool
         torch.cuda.empty_cache()
         gen = torch.Generator(device=dev).manual_seed(20222)
@@ -652,7 +691,7 @@ def main():
                          "traffic_source": "profiles/pmc_summary.json, not this run"},
         }
 
-    if not args.no_adc:
+    if args.full and not args.no_adc:
         # k in {10, 200} at M = 48 and the M = 96 index (BASELINE configs[3] flat leg), one batch each
         sweep = {}
         for kk in (10, 200):
@@ -751,7 +790,7 @@ def main():
         out["adc"]["other_shapes_queries_per_sec"] = sweep
 
     # ------------------------------------------------------------------ IVF leg (BASELINE configs[3]: M = 96, nlist = 5000)
-    if not args.no_adc and world == 1:
+    if args.full and not args.no_adc and world == 1:
         from repconc_amd.ivf import IVFPQIndex, coarse_assign
         M3, nlist = 96, 5000
         g3 = torch.Generator(device=dev).manual_seed(20227)
@@ -980,7 +1019,7 @@ def main():
         torch.cuda.empty_cache()
 
     # ------------------------------------------------------------------ index-build leg (nearest codes, a-1/a-5)
-    if not args.no_adc:
+    if args.full and not args.no_adc:
         nb = 1 << 20                                           # rows per rank per pass (a 1 M-passage encode chunk)
         xb = torch.randn((nb, D), device=dev, generator=torch.Generator(device=dev).manual_seed(20225 + rank))
         ib = {}
@@ -1020,7 +1059,7 @@ def main():
         del xb
 
     # ------------------------------------------------------------------ warm-up leg (OPQ + PQ training, a-12)
-    if world == 1 and not args.no_adc and not args.no_opq:
+    if args.full and world == 1 and not args.no_adc and not args.no_opq:
         from repconc_amd.train.run_warmup import MAX_TRAIN_POINTS, _xt_y, train_opq, train_pq
         gw = torch.Generator(device=dev).manual_seed(20226)
         xt = torch.randn((MAX_TRAIN_POINTS, D), device=dev, generator=gw)
@@ -1118,7 +1157,7 @@ def main():
     # ------------------------------------------------------------------ k-means sufficient statistics (GPU leg)
     # at the sizes the path runs it on: the 65 536 training rows of the warm-up (run_warmup.py:92-113) and a 2^20-row corpus
     # chunk (corpus-sharded k-means, BASELINE configs[2]); the CPU port is timed beside it in the cpu_baseline block
-    if world == 1:
+    if args.full and world == 1:
         ks_sizes = {}
         gk = torch.Generator(device=dev).manual_seed(20228)
         for rows in (1 << 16, 1 << 20):
@@ -1158,7 +1197,7 @@ def main():
                                                     "cannot amortise (2^20 rows: 0.52-0.61)"}
 
     # ------------------------------------------------------------------ CPU baseline (rank 0, N=1)
-    if world == 1 and not args.no_cpu:
+    if args.full and world == 1 and not args.no_cpu:
         from oracle import c_oracle, torch_port
         # threads = what the host really gives this process: the GPU boxes of the pool show 256 logical CPUs but run the
         # container under a cgroup quota of 16 (cpu.max "1600000 100000"): 128 OpenMP threads time-sliced on 16 CPUs is what made
@@ -1295,7 +1334,7 @@ def main():
 
     # ------------------------------------------------------------------ roofline.traffic measured by THIS run (N = 1)
     under_profiler = any("rocprof" in os.environ.get(v_, "") for v_ in ("LD_PRELOAD", "ROCP_TOOL_LIBRARIES"))   # no nesting
-    if world == 1 and not args.no_traffic and B == B_GLOBAL and not under_profiler:
+    if args.full and world == 1 and not args.no_traffic and B == B_GLOBAL and not under_profiler:
         torch.cuda.empty_cache()
         live = measure_sweep_traffic(B)
         if live is not None:
@@ -1317,7 +1356,8 @@ def main():
     if rank == 0:
         # the LAST key of the line (what a tail of the output keeps): the second headline metric and the other legs in one
         # compact object — the full objects are `adc`, `ivf`, `index_build`, `kmeans_stats` above
-        out["headline2"] = _headline2(out)
+        if args.full:
+            out["headline2"] = _headline2(out)
         os.write(real_stdout, (json.dumps(out) + "\n").encode())
     os.close(real_stdout)
 

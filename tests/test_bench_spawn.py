@@ -109,3 +109,24 @@ def test_launcher_contract_and_defaults(monkeypatch):
         assert a.batch % n == 0
     for f in ("headline_b49152_m48_sample.npz", "recipe8_b49152_m48_sample.npz"):
         assert os.path.exists(os.path.join(ROOT, "tests", "golden", f))
+
+
+def test_full_and_dump_outputs_options(monkeypatch, tmp_path):
+    """A plain run is lean: --full (off by default) adds the side legs; --dump-outputs DIR writes float32 .npy files;
+    --steps really is the number of timed steps, so 0 is refused."""
+    bench = _bench()
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    a = bench.parse()
+    assert a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path), "--steps", "3", "--warmup", "0"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path) and (a.steps, a.warmup) == (3, 0)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    import numpy as np
+    codes = np.arange(12, dtype=np.uint8).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / "out"), {"codes": codes, "flags": np.zeros(1, np.int32)})
+    got = np.load(tmp_path / "out" / "codes.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, codes)
+    assert np.load(tmp_path / "out" / "flags.npy").dtype == np.float32

@@ -2507,3 +2507,31 @@ def test_empty_cluster_rule_is_the_published_faiss_rule_on_both_sides():
     assert int(ns.item()) == n_want
     assert np.array_equal(Ct.cpu().numpy().view(np.uint32), want.view(np.uint32))
     assert np.array_equal(want[[1, 3]], C[[1, 3]])
+
+
+def test_bench_plain_run_dumps_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` without --full: one JSON line with the contract keys and none of the side legs, and
+    DIR/codes.npy = the codes of the last timed step's batch (pool[(warmup + steps - 1) % 3], seeded) solved again here."""
+    import json
+    import subprocess
+    import sys
+    from repconc_amd import ops
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    B, D, M, K, warmup, steps = 8192, 768, 48, 256, 1, 2
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", str(steps), "--warmup", str(warmup),
+                        "--batch", str(B), "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["value"] > 0 and d["dtype"] == "f64"
+    assert not {"adc", "ivf", "index_build", "cpu_baseline", "per_rank_6144", "headline2"} & set(d)
+    rng = np.random.default_rng(20220)
+    xs = [rng.standard_normal((B, D), dtype=np.float32) for _ in range(3)]
+    cent = np.ascontiguousarray(xs[0][np.random.default_rng(20221).permutation(B)[:K]].reshape(K, M, D // M).transpose(1, 0, 2))
+    want, flags = ops.assign_sinkhorn(_t(xs[(warmup + steps - 1) % 3]), _t(cent), EPS, ITERS, torch.uint8)
+    codes = np.load(out / "codes.npy")
+    assert codes.dtype == np.float32 and codes.shape == (B, M)
+    assert np.array_equal(codes, want.cpu().numpy().astype(np.float32))
+    assert np.array_equal(np.load(out / "flags.npy"), flags.cpu().numpy().astype(np.float32))

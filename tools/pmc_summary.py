@@ -19,7 +19,7 @@ ALG = {  # SURVEY 8(d) per-unit bytes x units per launch
     "kmeans_stats_kernel": ("kmeans_stats_px_kernel<0>", NB * (768 * 4 + M)),   # launch A, 2^20-row launches only (kmeans_raw.json)
 }
 out = {"_how": "tools/pmc_collect.sh: rocprofv3 --pmc <group> --kernel-trace, one pass per counter group, over "
-               "`python bench.py --steps 1 --warmup 1 --no-cpu --no-per-rank --no-opq --adc-batches 1`; means per launch. FETCH_SIZE/WRITE_SIZE are "
+               "`python bench.py --full --steps 1 --warmup 1 --no-cpu --no-per-rank --no-opq --adc-batches 1`; means per launch. FETCH_SIZE/WRITE_SIZE are "
                "KiB; FETCH_SIZE doubled per the gfx950 note in MI355X_MICROARCH.md. " + note}
 for key, (kname, alg) in ALG.items():
     src = raw
