@@ -11,13 +11,14 @@ models/jpq/finetune_jpq.py) are replaced as a whole by their `repconc_amd` count
     faiss.copy_array_to_vector(c, index.pq.centroids)   evaluate/run_repconc_eval.py:126
     faiss.omp_set_num_threads(n)                    evaluate/run_repconc_eval.py:149
     faiss.IndexPQ / faiss.IndexIVFPQ                type annotations (run_repconc_eval.py:123, finetune_jpq.py:145)
+    faiss.IndexFlatIP                               type annotation and index of models/dense/evaluate_dense.py:84-129
     import faiss.contrib.torch_utils                finetune_jpq.py:9 (tensor in / tensor out is what PQIndex.search does)
 
 This is `repconc_amd.faiss_compat` under Faiss's name; anything else (`index_factory`, `StandardGpuResources`, …) is not
 provided and raises AttributeError — those call sites live in the modules listed above.  A real Faiss installation, if
 present later on the path, is shadowed only because this directory was put first on purpose.
 """
-from repconc_amd.faiss_compat import (METRIC_INNER_PRODUCT, METRIC_L2, IndexPQ, copy_array_to_vector, downcast_index,  # noqa: F401
+from repconc_amd.faiss_compat import (METRIC_INNER_PRODUCT, METRIC_L2, IndexFlatIP, IndexPQ, copy_array_to_vector, downcast_index,  # noqa: F401
                                       omp_set_num_threads, read_index, vector_to_array, write_index)
 from repconc_amd.index import PQIndex as _PQIndex
 

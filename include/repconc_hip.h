@@ -360,6 +360,32 @@ int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t N, int M, i
 int rc_adc_lut(rc_handle_t h, const float* C, const float* q, int nq, int D, int M, int K,
                float* lut, rc_stream_t stream);
 
+/* ------------------------------------------------------------------ dense flat search
+ * Exact inner-product top-k over an fp32 corpus: the GPU faiss.IndexFlatIP (useFloat16 = False) of
+ * models/dense/evaluate_dense.py:84-129 (create_index, dense_search, batch_dense_search).
+ * Score s(q, n) = fp32 fmaf chain over d = 0 .. D-1 ascending from +0.0f, s = fmaf(q[d], x[n][d], s) (the fp32 matrix cores
+ * compute exactly this), so ids AND score bits are defined; the min(k, N) best rows sorted (score desc, row asc),
+ * ids = row + id_offset, -inf / -1 in the slots past N.
+ * x: [N, ldx] fp32, ldx >= D; q: [nq, D] fp32 contiguous; scores [nq, k] fp32, ids [nq, k] int64.  Any D >= 1 (D % 16 == 0
+ * is the fast path; then x and q must be 16-byte aligned and ldx % 4 == 0, else RC_EINVAL); N < 2^32 and 1 <= k <= 8192,
+ * else RC_ESHAPE — both before anything is enqueued.  Finite inputs are assumed.
+ * rc_dense_search_q: N <= 131072 takes the exact route below.  Above, the sampled-threshold route of rc_adc_search_q: the
+ *   r-th best of 32768 exactly scored strided sample rows is the per-query threshold (r and sel_slack as at rc_adc_search;
+ *   the Python wrapper passes 3), a GEMM over the whole corpus appends every row scoring >= it to the query's candidate
+ *   list, the lists are sorted.  status (device int) / qstatus (nq device ints, may be NULL), both zeroed by the caller, get
+ *   bit0 for a query that collected fewer than min(k, N) candidates and bit1 for one whose list overflowed (16384): repeat
+ *   those queries with another sel_slack or answer them by rc_dense_search_exact.  ws: rc_dense_search_ws_bytes(N, D, nq, k).
+ * rc_dense_search_exact: full score rows of a chunk of queries, then the 8-pass radix select of rc_adc_search_exact over the
+ *   64-bit keys.  No status: terminates with the same answer for any content (all rows identical, k >= N, ...).
+ *   ws: rc_dense_search_exact_ws_bytes(N, D, nq, k) (at most 256 MiB of score rows plus 128 KiB per query of a chunk). */
+size_t rc_dense_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
+                      int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus,
+                      void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
+                          int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream);
+
 /* ------------------------------------------------------------------ a-9 … a-11, stateful form
  * The index object the reference keeps inside Faiss (initialize_index / add_docs / index.search,
  * models/repconc/evaluate_repconc.py:78-98,182; JPQ's per-step synchronize_model_index, models/jpq/finetune_jpq.py:209-214),

@@ -102,6 +102,10 @@ PROTOTYPES = {
     "rc_ivf_search_ws_bytes": (_sz, [_i, _i64]),
     "rc_ivf_search": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rc_adc_lut": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "rc_dense_search_ws_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rc_dense_search_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_search_exact_ws_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rc_dense_search_exact": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "rc_index_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     "rc_index_destroy": (_i, [_vp]),
     "rc_index_set_centroids": (_i, [_vp, _vp, _vp]),

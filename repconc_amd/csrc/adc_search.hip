@@ -1243,6 +1243,31 @@ static int adc_qt_for(int M) {
     return 1;                // M=96: 96 KiB
 }
 
+// threshold stage, shared with the dense flat search (dense_search.hip): thr[q] = r-th largest of sample[q][0..S)
+int rc_adc_launch_threshold(rc_handle_t h, const float* sample, int64_t S, int nq, int r, float* thr, hipStream_t s) {
+    const size_t tl = (size_t)S * sizeof(unsigned);
+    RC_HIP_CHECK(h, hipFuncSetAttribute((const void*)adc_threshold_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                        (int)tl));
+    hipLaunchKernelGGL(adc_threshold_kernel, dim3((unsigned)nq), dim3(1024), tl, s, sample, S, r, thr);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+// rank of the sample score used as the candidate threshold (header text at rc_adc_search); shared with dense_search.hip
+int rc_adc_sample_rank(int64_t N, int64_t S, int k, double sel_slack) {
+    if (N <= ADC_CAND_CAP) return 0;   // tau = -inf: every row is a candidate, the select kernel sorts them all
+    if (S == N) return k;              // the sample is the whole index: tau is the exact k-th score
+    const double mu = (double)k * (double)S / (double)N;
+    int r = (int)(mu + sel_slack * sqrt(mu + 1.0) + 4.0) + 1;
+    // large k: keep the expected candidate count (r N / S) below ~80 % of the list capacity as long as that still
+    // leaves 2.5 sigma of head-room over k
+    const double r_cap = 0.8 * (double)ADC_CAND_CAP * (double)S / (double)N;
+    if ((double)r > r_cap && r_cap >= mu + 2.5 * sqrt(mu + 1.0) + 2.0) r = (int)r_cap;
+    if (r > S) r = (int)S;
+    if (r < 1) r = 1;       // a (hugely) negative slack: the best sample score
+    return r;
+}
+
 struct adc_bufs {
     float* lut; float* sample; float* thr; unsigned* cnt; unsigned long long* cand;
     uint8_t* qlut; int* tint; unsigned* idcnt; unsigned* ids; float* qstat;
@@ -1259,11 +1284,8 @@ static int adc_launch_scans(rc_handle_t h, const uint8_t* codes, const uint8_t* 
     hipLaunchKernelGGL(ksample, dim3(qg, (unsigned)((S + ADC_TILE_DOCS - 1) / ADC_TILE_DOCS)), dim3(ADC_THREADS), lds, s,
                        codes, N, b.lut, nq, S, b.sample, b.thr, b.cnt, b.cand);
     RC_LAUNCH_CHECK(h);
-    const size_t tl = (size_t)S * sizeof(unsigned);
-    RC_HIP_CHECK(h, hipFuncSetAttribute((const void*)adc_threshold_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                        (int)tl));
-    hipLaunchKernelGGL(adc_threshold_kernel, dim3((unsigned)nq), dim3(1024), tl, s, b.sample, S, r, b.thr);
-    RC_LAUNCH_CHECK(h);
+    const int trc = rc_adc_launch_threshold(h, b.sample, S, nq, r, b.thr, s);
+    if (trc != RC_OK) return trc;
     const unsigned tiles = (unsigned)((N + ADC_TILE_DOCS - 1) / ADC_TILE_DOCS);
     // small indexes: exact scan (the screen's fixed costs do not pay)
     if (N < ADC_SCREEN_MIN_N) {
@@ -1439,21 +1461,7 @@ extern "C" int rc_adc_search_q(rc_handle_t h, const uint8_t* codes, const uint8_
     if (rc != RC_OK) return rc;
     RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
     // rank of the sample score used as the filter threshold
-    int r;
-    if (N <= ADC_CAND_CAP) {
-        r = 0;  // tau = -inf: every row is a candidate, the select kernel sorts them all
-    } else if (L.S == N) {
-        r = k;  // the sample is the whole index: tau is the exact k-th score
-    } else {
-        const double mu = (double)k * (double)L.S / (double)N;
-        r = (int)(mu + sel_slack * sqrt(mu + 1.0) + 4.0) + 1;
-        // large k: keep the expected candidate count (r N / S) below ~80 % of the list capacity as long as that still
-        // leaves 2.5 sigma of head-room over k
-        const double r_cap = 0.8 * (double)ADC_CAND_CAP * (double)L.S / (double)N;
-        if ((double)r > r_cap && r_cap >= mu + 2.5 * sqrt(mu + 1.0) + 2.0) r = (int)r_cap;
-        if (r > L.S) r = (int)L.S;
-        if (r < 1) r = 1;       // a (hugely) negative slack: the best sample score
-    }
+    const int r = rc_adc_sample_rank(N, L.S, k, sel_slack);
     switch (M) {
         ADC_CASE(8, 4) ADC_CASE(12, 4) ADC_CASE(16, 4) ADC_CASE(24, 4) ADC_CASE(32, 4)
         ADC_CASE(48, 2) ADC_CASE(64, 2) ADC_CASE(96, 1)
@@ -1544,6 +1552,30 @@ __global__ __launch_bounds__(256) void adc_exact_collect_kernel(const float* __r
     }
 }
 
+// The select stage of the exact route for nx queries whose full score rows sc[nx][N] are written: the min(k, N) best
+// 64-bit keys by the 8-pass radix select, compacted and sorted + emitted.  Shared with the dense flat search
+// (dense_search.hip).  hist [nx][256], prefix [nx], rank [nx], cnt [nx], cand [nx][ADC_CAND_CAP]; status: a device int.
+int rc_adc_launch_exact_select(rc_handle_t h, const float* sc, int64_t N, int nx, int k, int64_t id_offset, unsigned* hist,
+                               unsigned long long* prefix, unsigned* rank, unsigned* cnt, unsigned long long* cand,
+                               int* status, float* scores, int64_t* ids, hipStream_t s) {
+    const unsigned want = (unsigned)((int64_t)k < N ? (int64_t)k : N);
+    unsigned slices = (unsigned)((N + 256 * 64 - 1) / (256 * 64));
+    if (slices > 2048) slices = 2048;
+    hipLaunchKernelGGL(adc_exact_init_kernel, dim3((unsigned)nx), dim3(256), 0, s, hist, prefix, rank, cnt, want);
+    RC_LAUNCH_CHECK(h);
+    for (int pass = 0; pass < 8; ++pass) {
+        hipLaunchKernelGGL(adc_exact_hist_kernel, dim3(slices, (unsigned)nx), dim3(256), 0, s, sc, N,
+                           (const unsigned long long*)prefix, pass, hist);
+        RC_LAUNCH_CHECK(h);
+        hipLaunchKernelGGL(adc_exact_pick_kernel, dim3((unsigned)nx), dim3(256), 0, s, hist, prefix, rank, pass);
+        RC_LAUNCH_CHECK(h);
+    }
+    hipLaunchKernelGGL(adc_exact_collect_kernel, dim3(slices, (unsigned)nx), dim3(256), 0, s, sc, N,
+                       (const unsigned long long*)prefix, cnt, cand);
+    RC_LAUNCH_CHECK(h);
+    return rc_adc_launch_select(h, cand, cnt, nx, N, k, id_offset, scores, ids, status, s);
+}
+
 struct adc_exact_layout { size_t lut, sc, hist, prefix, rank, cnt, cand, status, total; };
 static adc_exact_layout adc_exact_ws(int64_t N, int M, int nq) {
     adc_exact_layout L;
@@ -1620,9 +1652,6 @@ extern "C" int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t 
     int* status = (int*)(w + L.status);
     int rc = rc_adc_lut(h, C, q, nq, D, M, K, lut, stream);
     if (rc != RC_OK) return rc;
-    const unsigned want = (unsigned)((int64_t)k < N ? (int64_t)k : N);
-    unsigned slices = (unsigned)((N + 256 * 64 - 1) / (256 * 64));
-    if (slices > 2048) slices = 2048;
     for (int q0 = 0; q0 < nq; q0 += ADC_EXACT_QX) {
         const int nx = nq - q0 < ADC_EXACT_QX ? nq - q0 : ADC_EXACT_QX;
         const float* lq = lut + (size_t)q0 * M * RC_K;
@@ -1637,19 +1666,8 @@ extern "C" int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t 
                 rc = RC_OK;
         }
         if (rc != RC_OK) return rc;
-        hipLaunchKernelGGL(adc_exact_init_kernel, dim3((unsigned)nx), dim3(256), 0, s, hist, prefix, rank, cnt, want);
-        RC_LAUNCH_CHECK(h);
-        for (int pass = 0; pass < 8; ++pass) {
-            hipLaunchKernelGGL(adc_exact_hist_kernel, dim3(slices, (unsigned)nx), dim3(256), 0, s, (const float*)sc, N,
-                               (const unsigned long long*)prefix, pass, hist);
-            RC_LAUNCH_CHECK(h);
-            hipLaunchKernelGGL(adc_exact_pick_kernel, dim3((unsigned)nx), dim3(256), 0, s, hist, prefix, rank, pass);
-            RC_LAUNCH_CHECK(h);
-        }
-        hipLaunchKernelGGL(adc_exact_collect_kernel, dim3(slices, (unsigned)nx), dim3(256), 0, s, (const float*)sc, N,
-                           (const unsigned long long*)prefix, cnt, cand);
-        RC_LAUNCH_CHECK(h);
-        rc = rc_adc_launch_select(h, cand, cnt, nx, N, k, id_offset, scores + (size_t)q0 * k, ids + (size_t)q0 * k, status, s);
+        rc = rc_adc_launch_exact_select(h, sc, N, nx, k, id_offset, hist, prefix, rank, cnt, cand, status,
+                                        scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
         if (rc != RC_OK) return rc;
     }
     return RC_OK;

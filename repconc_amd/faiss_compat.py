@@ -7,6 +7,7 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
                                                                         finetune_jpq.py:211-213
     faiss.vector_to_array(index.pq.centroids) / (index.codes)           run_warmup.py:124-125, finetune_jpq.py:161
     faiss.IndexPQ(D, M, 8, faiss.METRIC_INNER_PRODUCT)                  evaluate_repconc.py:81
+    faiss.IndexFlatIP(d)                                                evaluate_dense.py:116 (exact fp32, dense_index.py)
     faiss.write_index(index, path) / faiss.read_index(path)             run_warmup.py:187, run_repconc_eval.py:42
     faiss.omp_set_num_threads(n)                                        run_repconc_eval.py:149 (no-op: the scan runs on the GPU)
 
@@ -18,6 +19,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
+from .dense_index import FlatIPIndex
 from .faiss_io import read_index, write_index  # noqa: F401  (re-exported)
 from .index import METRIC_INNER_PRODUCT, PQIndex
 
@@ -26,6 +28,9 @@ METRIC_L2 = 1
 
 def IndexPQ(d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT) -> PQIndex:
     return PQIndex(d, M, nbits, metric)
+
+
+IndexFlatIP = FlatIPIndex      # faiss.IndexFlatIP(d): exact inner product over fp32 vectors resident on the device
 
 
 def copy_array_to_vector(array, vector: torch.Tensor) -> None:

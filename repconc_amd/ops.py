@@ -866,3 +866,95 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
     pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
                             stream=torch.cuda.current_stream(dev))
     return pending if defer else pending.result()
+
+
+# ---------------------------------------------------------------------------------------------------------------- dense
+DENSE_SEL_SLACK = ADC_SEL_SLACK     # head-room of the dense search's sampled threshold (same rank formula, rc_dense_search_q)
+DENSE_MAX_K = 8192                  # the select's cap (ADC_CAND_CAP / 2)
+DENSE_QCHUNK = 2048                 # queries per library call: <= 2048 x 256 KiB of sample scores and candidate keys
+
+
+def _dense_args(x: torch.Tensor, q: torch.Tensor, k: int):
+    _need_cuda(x, q)
+    if x.dim() != 2 or q.dim() != 2 or x.shape[1] != q.shape[1]:
+        raise ValueError("dense search: x [N, D] and q [nq, D] with the same D")
+    if not 1 <= int(k) <= DENSE_MAX_K:
+        raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
+    if x.dtype != torch.float32 or x.stride(1) != 1 or x.stride(0) % 4 != 0 or x.data_ptr() % 16 != 0:
+        x = x.float().contiguous()
+    if x.shape[0] >= 1 << 32:
+        raise ValueError("dense search: N must be < 2^32")
+    q = q.to(x.device, torch.float32).contiguous()
+    return x, q
+
+
+def dense_search_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+    """The same answer as `dense_search` by the route that cannot fail (rc_dense_search_exact): full score rows and a radix
+    select of the min(k, N) best keys."""
+    x, q = _dense_args(x, q, k)
+    N, D = x.shape
+    nq = q.shape[0]
+    lib, h, s, _ = _ctx(q)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    if nq == 0 or N == 0:
+        scores.fill_(float("-inf"))
+        ids.fill_(-1)
+        return scores, ids
+    wsb = lib.rc_dense_search_exact_ws_bytes(N, D, nq, int(k))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+    _lib.check(lib.rc_dense_search_exact(h, _p(x), x.stride(0), N, D, _p(q), nq, int(k), int(id_offset), _p(scores), _p(ids),
+                                         _p(ws), wsb, s), "rc_dense_search_exact", h)
+    return scores, ids
+
+
+def dense_search(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
+                 defer: bool = False, method: str = "auto", max_retries: int = 2):
+    """Exact top-k inner-product search of `q` [nq, D] against the fp32 corpus `x` [N, D] (faiss.IndexFlatIP,
+    evaluate_dense.py:84-129).  Returns (scores [nq, k] fp32, ids [nq, k] int64 = row + id_offset), sorted (score desc, id
+    asc); -inf / -1 past N.  Scores are the fp32 fmaf chain over d ascending (include/repconc_hip.h), bit for bit.
+    method="exact": the exact route only.  defer: a `PendingSearch` (queries the sampled threshold fails are repeated, then
+    answered by the exact route; `.stats`).  Query sets larger than DENSE_QCHUNK are split into several library calls."""
+    if method not in ("auto", "exact"):
+        raise ValueError("method must be 'auto' or 'exact'")
+    x, q = _dense_args(x, q, k)
+    if sel_slack is None:
+        sel_slack = DENSE_SEL_SLACK
+    N, D = x.shape
+    nq = q.shape[0]
+    if method == "exact" or nq == 0 or N == 0:
+        got = dense_search_exact(x, q, k, id_offset)
+        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
+    lib, h, _, dev = _ctx(q)
+
+    def launch(qq, slack, out_s, out_i, status, qstatus):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for c0 in range(0, qq.shape[0], DENSE_QCHUNK):
+            n = min(DENSE_QCHUNK, qq.shape[0] - c0)
+            wsb = lib.rc_dense_search_ws_bytes(N, D, n, int(k))
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)     # released in stream order
+            _lib.check(lib.rc_dense_search_q(h, _p(x), x.stride(0), N, D, _p(qq[c0:c0 + n]), n, int(k), int(id_offset),
+                                             float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]), _p(status),
+                                             _p(qstatus[c0:c0 + n]), _p(ws), wsb, st), "rc_dense_search_q", h)
+
+    def rerun(idx, slack, exact):
+        qq = q[idx].contiguous()
+        if exact:
+            s_, i_ = dense_search_exact(x, qq, k, id_offset)
+            return s_, i_, None
+        s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q.device)
+        i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q.device)
+        status = torch.zeros((1,), dtype=torch.int32, device=q.device)
+        qs = torch.zeros((qq.shape[0],), dtype=torch.int32, device=q.device)
+        launch(qq, slack, s_, i_, status, qs)
+        return s_, i_, qs
+
+    _warm_retry_ops(q.device)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=q.device)
+    qstatus = torch.zeros((nq,), dtype=torch.int32, device=q.device)
+    launch(q, float(sel_slack), scores, ids, status, qstatus)
+    pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
+                            stream=torch.cuda.current_stream(dev))
+    return pending if defer else pending.result()

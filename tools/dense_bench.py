@@ -1,0 +1,176 @@
+"""Dense flat inner-product search (csrc/dense_search.hip) at the reference's scale: the MS MARCO passage corpus shape
+(8 841 823 x 768 fp32, 27.2 GB), the 6 980 dev queries in batches of 1 200 (evaluate_dense.py:93-112), k = 100 / 1000, and
+small query batches (1, 32, 128) against the HBM bound.  Synthetic seeded data generated on the device.
+
+    python tools/dense_bench.py [--out profiles/dense_bench.json] [--quick] [--no-torch]
+    rocprofv3 --kernel-trace --stats -d DIR -o dense -- python tools/dense_bench.py --quick
+    python tools/dense_bench.py --report DIR/.../dense_kernel_stats.csv      # the screen kernel's TFLOP/s from that run
+
+Prints ms per batch, queries/s, repeated / exact query counts, the same search as a chunked torch.mm + torch.topk
+composition on the same device (ids compared where the score margins allow), and a sample of queries checked against the
+fmaf-chain oracle of tests/test_dense_flat.py.  The screen's TFLOP/s and the time outside it come from the kernel trace
+(--report): a screen launch over nq queries does 2 nq N D flop."""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+PEAK_TF = 157.3          # fp32 matrix peak, MI355X
+HBM_TBS = 8.0            # HBM3E peak
+
+
+def report(path, n, d, batch, nq):
+    """Kernel statistics of a `--quick` run: its screen launches cover the warm-up batch and the query set twice."""
+    queries = batch + 2 * nq
+    rows = list(csv.DictReader(open(path)))
+    # the search's own kernels (the corpus generation and host copies of the run are not part of a search)
+    tot = sum(float(r["TotalDurationNs"]) for r in rows if r["Name"].startswith(("void dense_", "void adc_", "dense_", "adc_")))
+    out = {}
+    for r in rows:
+        name = r["Name"]
+        if "dense_gemm_kernel<1" in name or "dense_gemm_kernelILi1E" in name:
+            out["screen_calls"] = int(r["Calls"])
+            out["screen_ms_each"] = float(r["AverageNs"]) / 1e6
+            out["screen_ms_total"] = float(r["TotalDurationNs"]) / 1e6
+    if "screen_calls" in out:
+        out["search_kernels_ms_total"] = tot / 1e6
+        out["outside_screen_ms_total"] = (tot - out["screen_ms_total"] * 1e6) / 1e6
+        out["screened_queries"] = queries
+        out["screen_tflops"] = 2.0 * queries * n * d / (out["screen_ms_total"] * 1e-3) / 1e12
+        out["screen_share_of_peak"] = out["screen_tflops"] / PEAK_TF
+        out["screen_ms_per_1200_queries"] = 2.0 * 1200 * n * d / (out["screen_tflops"] * 1e12) * 1e3
+        out["outside_screen_ms_per_call"] = out["outside_screen_ms_total"] / out["screen_calls"]
+    print(json.dumps(out, indent=1))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=8841823)
+    ap.add_argument("--d", type=int, default=768)
+    ap.add_argument("--nq", type=int, default=6980)
+    ap.add_argument("--batch", type=int, default=1200)
+    ap.add_argument("--ks", default="100,1000")
+    ap.add_argument("--small", default="1,32,128")
+    ap.add_argument("--verify", type=int, default=16, help="queries checked against the fmaf-chain oracle")
+    ap.add_argument("--quick", action="store_true", help="k = 1000, one pass over the queries, no torch leg, no small batches")
+    ap.add_argument("--no-torch", action="store_true")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--report", default=None, help="a rocprofv3 kernel_stats.csv of a --quick run")
+    a = ap.parse_args()
+    if a.report:
+        report(a.report, a.n, a.d, a.batch, a.nq)
+        return
+    import numpy as np
+    import torch
+    from repconc_amd import ops
+    from repconc_amd.dense_index import FlatIPIndex
+    from repconc_amd.models.dense.evaluate_dense import batch_dense_search
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    index = FlatIPIndex(a.d, device=dev)
+    index.reserve(a.n)
+    step = 1 << 20
+    for r0 in range(0, a.n, step):
+        index.add(torch.randn((min(step, a.n - r0), a.d), generator=g, device=dev))
+    q = torch.randn((a.nq, a.d), generator=g, device=dev)
+    qn = q.cpu().numpy()
+    corpus_ids = np.arange(a.n)
+    query_ids = np.arange(a.nq)
+    ks = [1000] if a.quick else [int(v) for v in a.ks.split(",")]
+    res = {"n": a.n, "d": a.d, "nq": a.nq, "batch": a.batch, "corpus_gb": a.n * a.d * 4 / 1e9,
+           "flop_per_batch_t": 2.0 * a.batch * a.n * a.d / 1e12, "roofline_ms_per_batch": 2.0 * a.batch * a.n * a.d / PEAK_TF / 1e9,
+           "hbm_bound_ms": a.n * a.d * 4 / HBM_TBS / 1e9, "runs": []}
+    nb = -(-a.nq // a.batch)
+    for k in ks:
+        batch_dense_search(query_ids[:a.batch], qn[:a.batch], corpus_ids, index, k, a.batch)      # warm-up
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pend, pstats = [], []
+        for part in np.array_split(qn, nb):
+            pend.append(index.search_async(part, k))
+            pstats.append(index.last_search)
+        outs = [f() for f in pend]
+        torch.cuda.synchronize()
+        t = time.perf_counter() - t0
+        ids = np.concatenate([o[1] for o in outs])
+        sc = np.concatenate([o[0] for o in outs])
+        run = {"k": k, "batches": nb, "s_total": t, "ms_per_batch": 1e3 * t / nb, "queries_per_s": a.nq / t,
+               "retried_queries": sum(p.stats["retried_queries"] for p in pstats),
+               "exact_queries": sum(p.stats["exact_queries"] for p in pstats)}
+        # the public path end to end (host numpy in / out, every batch enqueued first)
+        t0 = time.perf_counter()
+        bs, bi = batch_dense_search(query_ids, qn, corpus_ids, index, k, a.batch)
+        run["batch_dense_search_s"] = time.perf_counter() - t0
+        assert np.array_equal(bi, ids)
+        if not (a.quick or a.no_torch):
+            # chunked torch.mm + torch.topk on the same device
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            tops, topi = [], []
+            x = index.xb
+            for part in torch.split(q, a.batch):
+                best_s, best_i = None, None
+                for r0 in range(0, a.n, 1 << 21):
+                    s = torch.mm(part, x[r0:r0 + (1 << 21)].T)
+                    v, i = torch.topk(s, k, dim=1)
+                    i += r0
+                    if best_s is not None:
+                        v, j = torch.topk(torch.cat([best_s, v], 1), k, dim=1)
+                        i = torch.gather(torch.cat([best_i, i], 1), 1, j)
+                    best_s, best_i = v, i
+                tops.append(best_s)
+                topi.append(best_i)
+            ts, ti = torch.cat(tops).cpu().numpy(), torch.cat(topi).cpu().numpy()
+            torch.cuda.synchronize()
+            run["torch_mm_topk_s"] = time.perf_counter() - t0
+            run["speedup_vs_torch"] = run["torch_mm_topk_s"] / run["batch_dense_search_s"]
+            # ids compared at the ranks whose score differs from both neighbours by more than a chain error bound
+            margin = 4 * a.d * 2.0 ** -24 * np.abs(sc).max()
+            gap = np.minimum(np.abs(np.diff(sc, axis=1, prepend=np.inf)), np.abs(np.diff(sc, axis=1, append=-np.inf)))
+            sure = gap > margin
+            run["torch_ids_compared"] = int(sure.sum())
+            run["torch_ids_equal"] = int((ti[sure] == ids[sure]).sum())
+        res["runs"].append(run)
+        print(json.dumps(run), flush=True)
+    if a.verify:
+        from test_dense_flat import oracle_topk
+        k = ks[-1]
+        sel = np.linspace(0, a.nq - 1, a.verify).astype(int)
+        ws, wi = oracle_topk(index.xb, q[sel], k, qblock=16, rblock=1 << 20)
+        gs, gi = index.search(qn[sel], k)
+        res["verified_queries"] = int(len(sel))
+        res["verified_equal"] = bool(np.array_equal(gi, wi) and np.array_equal(gs.view(np.uint32), ws.view(np.uint32)))
+        print("oracle check:", res["verified_equal"], flush=True)
+    if not a.quick:
+        res["small"] = []
+        for nq in [int(v) for v in a.small.split(",")]:
+            qq = q[:nq].contiguous()
+            for _ in range(2):
+                ops.dense_search(index.xb, qq, 100)
+            torch.cuda.synchronize()
+            reps = 10
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                ops.dense_search(index.xb, qq, 100)
+            torch.cuda.synchronize()
+            ms = 1e3 * (time.perf_counter() - t0) / reps
+            row = {"nq": nq, "k": 100, "ms": ms, "hbm_bound_ms": res["hbm_bound_ms"],
+                   "corpus_read_tbs": a.n * a.d * 4 / (ms * 1e-3) / 1e12,
+                   "roofline_ms": max(res["hbm_bound_ms"], 2.0 * nq * a.n * a.d / PEAK_TF / 1e9)}
+            res["small"].append(row)
+            print(json.dumps(row), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()
