@@ -12,6 +12,8 @@ any state), so the reference's callers keep their imports:
     from repconc.models.dense import AutoDense;  from repconc.train.run_warmup import warmup_from_embeds
     from repconc.utils.eval_utils import load_corpus, load_queries, TextDataset, get_collator_func
 
+`python -m repconc.X` runs repconc_amd.X as __main__ (the recipes' `python -m repconc.evaluate.run_repconc_eval ...`).
+
 Not on the path by default: a checkout of the reference next to this repo keeps importing its own `repconc`.
 """
 import importlib
@@ -45,6 +47,19 @@ class _AliasLoader(importlib.abc.Loader):
             except (AttributeError, TypeError):
                 pass
 
+    def _real_spec(self):
+        # the module's own spec: restored by exec_module, and untouched when runpy asks before any alias import
+        return self._saved.get("__spec__") or self._module.__spec__
+
+    def get_code(self, fullname):
+        """`python -m repconc.X`: runpy runs the code of repconc_amd.X as __main__ under the alias spec, so relative
+        imports inside it (`from .. import ops`) resolve through this finder to the very modules repconc_amd.X uses."""
+        spec = self._real_spec()
+        return spec.loader.get_code(spec.name)
+
+    def is_package(self, fullname):
+        return hasattr(self._module, "__path__")
+
 
 class _AliasFinder(importlib.abc.MetaPathFinder):
     _prefix = __name__ + "."
@@ -56,7 +71,9 @@ class _AliasFinder(importlib.abc.MetaPathFinder):
             module = importlib.import_module("repconc_amd." + fullname[len(self._prefix):])
         except ModuleNotFoundError:
             return None
-        return importlib.util.spec_from_loader(fullname, _AliasLoader(module), is_package=hasattr(module, "__path__"))
+        real = module.__spec__
+        return importlib.util.spec_from_loader(fullname, _AliasLoader(module), origin=getattr(real, "origin", None),
+                                               is_package=hasattr(module, "__path__"))
 
 
 if not any(isinstance(f, _AliasFinder) for f in sys.meta_path):

@@ -21,6 +21,9 @@ def _pool(hidden, attention_mask, how):
 
 
 class _DenseMixin:
+    """Each subclass ends its __init__ with `post_init()`: transformers 5's `from_pretrained` needs the attributes it sets
+    (`all_tied_weights_keys`, ...).  The backbone is initialised already, so it draws no random numbers and changes no
+    weight."""
     backbone_attr = None
 
     def forward(self, input_ids, attention_mask, return_dict=False):
@@ -44,6 +47,7 @@ class BertDense(_DenseMixin, BertPreTrainedModel):
     def __init__(self, config):
         BertPreTrainedModel.__init__(self, config)
         self.bert = BertModel(config, add_pooling_layer=False)
+        self.post_init()
 
 
 class RobertaDense(_DenseMixin, RobertaPreTrainedModel):
@@ -52,6 +56,7 @@ class RobertaDense(_DenseMixin, RobertaPreTrainedModel):
     def __init__(self, config):
         RobertaPreTrainedModel.__init__(self, config)
         self.roberta = RobertaModel(config, add_pooling_layer=False)
+        self.post_init()
 
 
 class DistilBertDense(_DenseMixin, DistilBertPreTrainedModel):
@@ -60,6 +65,7 @@ class DistilBertDense(_DenseMixin, DistilBertPreTrainedModel):
     def __init__(self, config):
         DistilBertPreTrainedModel.__init__(self, config)
         self.distilbert = DistilBertModel(config)
+        self.post_init()
 
 
 class AutoDense:
