@@ -1,172 +1,17 @@
-// Shared pieces of the flat ADC search (adc_search.hip) and the list-centric IVF search (ivf_lists.hip): limits, the
-// order-preserving score key, the k-th-largest selection, the conflict-free slot rule, the 8-bit quantiser and the exact
-// rescoring kernel.  Device functions and templates only (no -fgpu-rdc: every translation unit compiles its own copy).
+// Shared pieces of the flat ADC search (adc_search.hip) and the list-centric IVF search (ivf_lists.hip, ivfs_screen16.h) that are
+// about ADC tables and codes: limits, the conflict-free slot rule, the 16-query slot rule, the 8-bit quantiser, the IVF task
+// list, the exact rescoring kernel and the supported-width predicates.  The selection stage (score keys, k-th largest, the
+// candidate-list limits, top-k host interface) is topk.h.  Device functions and templates only (no -fgpu-rdc: every
+// translation unit compiles its own copy).
 #pragma once
-#include "rc_common.h"
+#include "topk.h"
 #include <limits.h>
 
 #define ADC_THREADS 1024
-#define ADC_SAMPLE_MAX 32768
-#define ADC_KTH_LIST 4096            // members of the selected value bin kept in LDS by adc_kth_largest_v
-#define ADC_CAND_CAP 16384
 #define ADC_TILE_DOCS 32768
 #define ADC_SCREEN_MIN_N (1 << 18)
 #define ADC_ID_CAP 32768
 #define ADC_QSTAT_STRIDE 128          // floats per query: lo[0..M), sum of lo as a double at [124], delta at [127]
-
-__device__ __forceinline__ unsigned adc_order_key(float s) {
-    const unsigned u = __float_as_uint(s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float adc_unorder_key(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
-
-// One step of the 8-bit radix select: from the 256-bin histogram of the keys that match `prefix`, the bin that holds the
-// need-th largest key, i.e. the largest b with sum_{j >= b} hist[j] >= need — computed by 256 threads with a wave scan.
-// (One thread walking down from bin 255 is a chain of dependent LDS reads: ~10 us per pass, 40 of the 46 us a threshold
-// block took.)  Called by every thread of a block of >= 256 threads; `need` must have been read before; ends in a barrier.
-__device__ __forceinline__ void adc_pick_bin(const unsigned* hist, unsigned need, unsigned prefix, int shift, unsigned* s_scan,
-                                             unsigned* sel_prefix, unsigned* sel_rank) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    unsigned v = 0u, incl = 0u;
-    if (tid < 256) {
-        v = hist[255 - tid];                                  // thread t owns bin 255 - t: prefix over t = suffix over bins
-        incl = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned t = (unsigned)__shfl_up((int)incl, o);
-            if (lane >= o) incl += t;
-        }
-        if (lane == 63) s_scan[wv] = incl;
-    }
-    __syncthreads();
-    if (tid < 256) {
-#pragma unroll
-        for (int w = 0; w < 3; ++w) incl += (w < wv) ? s_scan[w] : 0u;
-        const unsigned excl = incl - v;
-        if (incl >= need && excl < need) {
-            *sel_prefix = prefix | ((unsigned)(255 - tid) << shift);
-            *sel_rank = need - excl;
-        } else if (tid == 255 && incl < need) {               // fewer matching keys than asked for: what the walk did
-            *sel_prefix = prefix;
-            *sel_rank = need - incl;
-        }
-    }
-    __syncthreads();
-}
-
-// rank-th largest of n 32-bit keys (key_at(i), i < n; rank in [1, n]) by radix select, 8 bits per pass — but only over the
-// bits in which the keys DIFFER: a block min / max first, the common leading bits are the result's.  Scores of one query's
-// candidates share their sign / exponent byte (often the next one too): a pass over such a byte sends every key to ONE
-// histogram bin, i.e. n LDS atomics on one address, one after the other (round 3: two of the four passes of the 32 768-key
-// threshold kernel, ~100 of its 130 us per 1200 queries).  Called by every thread of a block of >= 256 threads; `hist`
-// [256], `s_scan` [4], `s_sel` [2], `s_mm` [2] in LDS.
-template <typename KeyAt>
-__device__ __forceinline__ unsigned adc_kth_largest(KeyAt key_at, int64_t n, unsigned rank, unsigned* hist, unsigned* s_scan,
-                                                    unsigned* s_sel, unsigned* s_mm) {
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    if (tid == 0) { s_mm[0] = 0xFFFFFFFFu; s_mm[1] = 0u; }
-    __syncthreads();
-    unsigned mn = 0xFFFFFFFFu, mx = 0u;
-    for (int64_t i = tid; i < n; i += nthr) {
-        const unsigned k = key_at(i);
-        mn = k < mn ? k : mn;
-        mx = k > mx ? k : mx;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned a = (unsigned)__shfl_xor((int)mn, o), b = (unsigned)__shfl_xor((int)mx, o);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-    }
-    if ((tid & 63) == 0) { atomicMin(&s_mm[0], mn); atomicMax(&s_mm[1], mx); }
-    __syncthreads();
-    const unsigned lo = s_mm[0], hi_key = s_mm[1];
-    if (lo == hi_key) return hi_key;                          // all keys equal (block-uniform)
-    const int top = 31 - __clz((int)(lo ^ hi_key));          // highest bit in which two keys differ
-    int undecided = top + 1;                                  // bits [0, undecided)
-    if (tid == 0) { s_sel[0] = hi_key & ~((2u << top) - 1u); s_sel[1] = rank; }
-    __syncthreads();
-    while (undecided > 0) {
-        const int width = undecided < 8 ? undecided : 8, shift = undecided - width;
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        const unsigned prefix = s_sel[0], need = s_sel[1];
-        const unsigned himask = undecided >= 32 ? 0u : (0xFFFFFFFFu << undecided), dmask = (1u << width) - 1u;
-        for (int64_t i = tid; i < n; i += nthr) {
-            const unsigned k = key_at(i);
-            if ((k & himask) == prefix) atomicAdd(&hist[(k >> shift) & dmask], 1u);
-        }
-        __syncthreads();
-        adc_pick_bin(hist, need, prefix, shift, s_scan, &s_sel[0], &s_sel[1]);
-        undecided = shift;
-    }
-    return s_sel[0];
-}
-
-// The same answer, faster on real score distributions: bit-radix passes see a float's sign / exponent structure — a
-// near-Gaussian sample puts half of its keys into one or two bins of the first pass whatever window of bits it uses
-// (measured: skipping the common leading bits alone made the kernels SLOWER, the min / max pass cost more than it saved).
-// So the first cut is made in VALUE space: 256 equal bins over [min, max] of the scores (a monotone function of the key:
-// bin(s) = min(255, int((s - smin) scale)), so "the bin that holds the rank-th largest" is well defined) — the fullest bin of
-// a Gaussian sample holds ~1.3 % of it — then the members of that one bin (a few dozen in the tail where the thresholds
-// live) are collected into `list` and the bit-radix select above runs on them.  Non-finite extremes, a degenerate range or
-// a bin longer than list_cap: the plain bit-radix select over everything.  `s_aux`: 8 words of LDS.
-// MM_READY: the caller has already reduced the keys' minimum / maximum into s_aux[2] / s_aux[3] (e.g. while loading them),
-// zeroed hist and s_aux[4], and synchronised.
-template <bool MM_READY = false, typename KeyAt>
-__device__ __forceinline__ unsigned adc_kth_largest_v(KeyAt key_at, int64_t n, unsigned rank, unsigned* hist, unsigned* s_scan,
-                                                      unsigned* s_aux, unsigned* list, int list_cap) {
-    const int tid = threadIdx.x, nthr = blockDim.x;
-    unsigned* s_sel = s_aux, *s_mm = s_aux + 2, *s_cnt = s_aux + 4;
-    if constexpr (!MM_READY) {
-        if (tid == 0) { s_mm[0] = 0xFFFFFFFFu; s_mm[1] = 0u; *s_cnt = 0u; }
-        if (tid < 256) hist[tid] = 0u;
-        __syncthreads();
-        unsigned mn = 0xFFFFFFFFu, mx = 0u;
-        for (int64_t i = tid; i < n; i += nthr) {
-            const unsigned k = key_at(i);
-            mn = k < mn ? k : mn;
-            mx = k > mx ? k : mx;
-        }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) {
-            const unsigned a = (unsigned)__shfl_xor((int)mn, o), b = (unsigned)__shfl_xor((int)mx, o);
-            mn = a < mn ? a : mn;
-            mx = b > mx ? b : mx;
-        }
-        if ((tid & 63) == 0) { atomicMin(&s_mm[0], mn); atomicMax(&s_mm[1], mx); }
-        __syncthreads();
-    }
-    const unsigned lo = s_mm[0], hi_key = s_mm[1];
-    if (lo == hi_key) return hi_key;
-    const float smin = adc_unorder_key(lo), smax = adc_unorder_key(hi_key);
-    const float scale = 256.0f / (smax - smin);
-    const bool linear = (smin - smin == 0.f) && (smax - smax == 0.f) && (scale - scale == 0.f);     // all finite (block-uniform)
-    if (!linear) {
-        __syncthreads();
-        return adc_kth_largest(key_at, n, rank, hist, s_scan, s_sel, s_mm);
-    }
-    auto bin_of = [&](unsigned k) {
-        const int b = (int)((adc_unorder_key(k) - smin) * scale);
-        return b > 255 ? 255 : b;
-    };
-    for (int64_t i = tid; i < n; i += nthr) atomicAdd(&hist[bin_of(key_at(i))], 1u);
-    __syncthreads();
-    adc_pick_bin(hist, rank, 0u, 0, s_scan, &s_sel[0], &s_sel[1]);    // s_sel[0] = bin, s_sel[1] = rank inside it (ends in a barrier)
-    const int b = (int)s_sel[0];
-    const unsigned inside = s_sel[1], members = hist[b];
-    __syncthreads();
-    if ((int)members > list_cap)
-        return adc_kth_largest(key_at, n, rank, hist, s_scan, s_sel, s_mm);
-    for (int64_t i = tid; i < n; i += nthr) {
-        const unsigned k = key_at(i);
-        if (bin_of(k) == b) list[atomicAdd(s_cnt, 1u)] = k;
-    }
-    __syncthreads();
-    return adc_kth_largest([&](int64_t i) { return list[i]; }, (int64_t)members, inside, hist, s_scan, s_sel, s_mm);
-}
 
 // ---- conflict-free slot rule (round 2; today the table phases of the IVF screen, ivf_lists.hip) ------------------
 // The sum over sub-quantisers is commutative, so the lanes of a wave need not visit them in the same order: byte tables are
@@ -202,11 +47,6 @@ __host__ __device__ inline void adc_cf_step(int PM, int s, int r, int g, int& sl
     slot = base + ml + S * (lam / S);                      // S = 16: second copy for lanes 16-31
 }
 
-// image[n][phase][g][s] = codes[n][phase * PM + m(s; n mod 16, g)] for rows n0 <= n < n0 + cnt.
-// tile_rows > 0 (flat-search image of a two-phase M, round 3): the image is stored tile by tile, PHASE-MAJOR inside a tile of
-// tile_rows rows — [n / T][phase][n % T][PM] — so that a pass over one phase streams dense PM-byte rows (with 96-byte
-// rows a wave's 16-row code load touches twelve half-used cache lines instead of six full ones).  The layout does not
-
 __device__ __forceinline__ unsigned adc_quant8(float v, float lo, float delta) {
     int l = (int)floorf((v - lo) / delta + 0.5f);           // nearest: the screen's one-sided slack is M / 2 + 2 steps, not M + 2
     l = l < 0 ? 0 : (l > 255 ? 255 : l);
@@ -216,7 +56,6 @@ __device__ __forceinline__ unsigned adc_quant8(float v, float lo, float delta) {
 typedef int adc_i32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned adc_u32x2v __attribute__((ext_vector_type(2)));
 
-// Tasks of the list-centric IVF search: a task = (coarse cell, up to 8 of the queries that probe it)
 // 16-query gathers (ds_read_b128; adc_search.hip 4b'', ivfs_screen16.h): position of a lane inside its service group of 16
 // lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32), and the sub-quantiser (within its phase of 16) = LDS slot
 // that lane `lane` of a wave reads in step j — distinct inside every service group, the four lanes of a row cover all 16
@@ -225,6 +64,7 @@ __host__ __device__ constexpr int adc_q16_pos(int h32) {
 }
 __host__ __device__ constexpr int adc_q16_slot(int lane, int j) { return (adc_q16_pos(lane & 31) + j + 4 * (lane >> 5)) & 15; }
 
+// Tasks of the list-centric IVF search: a task = (coarse cell, up to 8 of the queries that probe it)
 struct adc_ivf_tasks {
     const int* task_list;        // [tasks] cell of the task
     const int* task_qstart;      // [tasks] first entry of the task's queries in sorted_q
@@ -340,8 +180,7 @@ __global__ __launch_bounds__(1024) void adc_rescore_kernel(const uint8_t* __rest
                 if (pass && slot < ADC_CAND_CAP) {
                     // IVF: rows are stored cell-major; the key carries the row's corpus position so ties order by corpus id
                     const unsigned id = rowmap ? (unsigned)rowmap[n] : n;
-                    cand[(size_t)qi * ADC_CAND_CAP + slot] =
-                        ((unsigned long long)adc_order_key(sc) << 32) | (unsigned long long)(0xFFFFFFFFu - id);
+                    cand[(size_t)qi * ADC_CAND_CAP + slot] = adc_exact_key(sc, id);
                 }
             }
         }
@@ -356,7 +195,3 @@ static inline bool adc_search_supported(int M) {
     return M == 8 || M == 12 || M == 16 || M == 24 || M == 32 || M == 48 || M == 64 || M == 96;
 }
 static inline bool adc_cf_supported(int M) { return M == 16 || M == 32 || M == 48 || M == 64 || M == 96; }
-
-// adc_search.hip: sort + emit of the per-query key lists
-int rc_adc_launch_select(rc_handle_t h, unsigned long long* cand, const unsigned* cnt, int nq, int64_t N, int k,
-                         int64_t id_offset, float* scores, int64_t* ids, int* status, hipStream_t s, int* qstatus = nullptr);

@@ -16,13 +16,13 @@
 //
 // Fast route (N > 4 S):
 //   1. dense_gemm_kernel<STORE> over the strided sample j -> row j N / S, S = min(N, 32768) rows: the same chain
-//   2. adc_threshold_kernel (adc_search.hip): thr[q] = the r-th best sample score, r by the ADC formula (rc_adc_sample_rank)
+//   2. adc_threshold_kernel (topk.hip): thr[q] = the r-th best sample score, r by the ADC formula (rc_adc_sample_rank)
 //   3. dense_gemm_kernel<FILTER> over all N rows
 //   4. adc_select_kernel (rc_adc_launch_select): sort + emit; qstatus bit0 = fewer than min(k, N) candidates, bit1 = overflow
 // Exact route (small N, and the queries the fast route gives up on): dense_gemm_kernel<STORE> writes the full score rows of a
 // chunk of queries, then the 8-pass radix select over the 64-bit keys of rc_adc_search_exact (rc_adc_launch_exact_select).
 // It terminates with the same answer for any content (all rows identical, k >= N, ...).
-#include "adc_common.h"
+#include "topk.h"
 
 #include <stdint.h>
 
@@ -145,9 +145,7 @@ __global__ __launch_bounds__(256) void dense_gemm_kernel(const float* __restrict
                             if (pass) {
                                 const unsigned slot = base + (unsigned)__popc(hm & ((1u << col) - 1u));
                                 if (slot < ADC_CAND_CAP)
-                                    cand[(int64_t)qi * ADC_CAND_CAP + slot] =
-                                        ((unsigned long long)adc_order_key(s) << 32) |
-                                        (unsigned long long)(0xFFFFFFFFu - (unsigned)j);
+                                    cand[(int64_t)qi * ADC_CAND_CAP + slot] = adc_exact_key(s, j);
                             }
                         }
                     }
@@ -156,13 +154,6 @@ __global__ __launch_bounds__(256) void dense_gemm_kernel(const float* __restrict
         __syncthreads();                                           // the next query tile overwrites buffer 0 and s_thr
     }
 }
-
-// adc_search.hip (rc_adc_launch_select: adc_common.h)
-int rc_adc_launch_threshold(rc_handle_t h, const float* sample, int64_t S, int nq, int r, float* thr, hipStream_t s);
-int rc_adc_sample_rank(int64_t N, int64_t S, int k, double sel_slack);
-int rc_adc_launch_exact_select(rc_handle_t h, const float* sc, int64_t N, int nx, int k, int64_t id_offset, unsigned* hist,
-                               unsigned long long* prefix, unsigned* rank, unsigned* cnt, unsigned long long* cand,
-                               int* status, float* scores, int64_t* ids, hipStream_t s);
 
 template <int MODE>
 static int dense_launch_gemm(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
@@ -181,7 +172,7 @@ static int dense_launch_gemm(rc_handle_t h, const float* x, int64_t ldx, int64_t
 
 static bool dense_exact_route(int64_t N) { return N <= DENSE_EXACT_MAX_N; }
 
-struct dense_exact_layout { size_t sc, hist, prefix, rank, cnt, cand, status, total; int qx; };
+struct dense_exact_layout { size_t sc; topk_exact_layout sel; int qx; };      // sel.total = bytes of the whole workspace
 static dense_exact_layout dense_exact_ws(int64_t N, int nq) {
     dense_exact_layout L;
     int64_t qx = (int64_t)(DENSE_EXACT_SC_BYTES / ((uint64_t)N * sizeof(float)));
@@ -189,15 +180,8 @@ static dense_exact_layout dense_exact_ws(int64_t N, int nq) {
     if (qx > DENSE_EXACT_QX_MAX) qx = DENSE_EXACT_QX_MAX;
     if (qx > nq) qx = nq;
     L.qx = (int)qx;
-    size_t o = 0;
-    L.sc = o;     o += rc_align_up((size_t)qx * (size_t)N * sizeof(float), 256);
-    L.hist = o;   o += rc_align_up((size_t)qx * 256 * sizeof(unsigned), 256);
-    L.prefix = o; o += rc_align_up((size_t)qx * sizeof(unsigned long long), 256);
-    L.rank = o;   o += rc_align_up((size_t)qx * sizeof(unsigned), 256);
-    L.cnt = o;    o += rc_align_up((size_t)qx * sizeof(unsigned), 256);
-    L.cand = o;   o += rc_align_up((size_t)qx * ADC_CAND_CAP * sizeof(unsigned long long), 256);
-    L.status = o; o += 256;
-    L.total = o;
+    L.sc = 0;
+    L.sel = topk_exact_ws(rc_align_up((size_t)qx * (size_t)N * sizeof(float), 256), L.qx);
     return L;
 }
 
@@ -225,29 +209,22 @@ static int dense_check(rc_handle_t h, const float* x, int64_t ldx, int64_t N, in
 
 extern "C" size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
     if (N <= 0 || N > 0xFFFFFFFFll || D <= 0 || nq <= 0 || k <= 0 || k > ADC_CAND_CAP / 2) return 0;
-    return dense_exact_ws(N, nq).total;
+    return dense_exact_ws(N, nq).sel.total;
 }
 
 extern "C" size_t rc_dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
     if (N <= 0 || N > 0xFFFFFFFFll || D <= 0 || nq <= 0 || k <= 0 || k > ADC_CAND_CAP / 2) return 0;
-    return dense_exact_route(N) ? dense_exact_ws(N, nq).total : dense_fast_ws(N, nq).total;
+    return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total;
 }
 
 static int dense_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
                        int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s) {
-    float* sc = (float*)(w + L.sc);
-    unsigned* hist = (unsigned*)(w + L.hist);
-    unsigned long long* prefix = (unsigned long long*)(w + L.prefix);
-    unsigned* rank = (unsigned*)(w + L.rank);
-    unsigned* cnt = (unsigned*)(w + L.cnt);
-    unsigned long long* cand = (unsigned long long*)(w + L.cand);
-    int* status = (int*)(w + L.status);         // never set: exactly min(k, N) keys are collected
+    float* sc = (float*)(w + L.sc);             // (the select's status word is never set: exactly min(k, N) keys are collected)
     for (int q0 = 0; q0 < nq; q0 += L.qx) {
         const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
         int rc = dense_launch_gemm<DENSE_STORE>(h, x, ldx, N, N, 0, q + (int64_t)q0 * D, nx, D, nullptr, sc, nullptr, nullptr, s);
         if (rc != RC_OK) return rc;
-        rc = rc_adc_launch_exact_select(h, sc, N, nx, k, id_offset, hist, prefix, rank, cnt, cand, status,
-                                        scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
+        rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
         if (rc != RC_OK) return rc;
     }
     return RC_OK;
@@ -261,7 +238,7 @@ extern "C" int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx,
     if (crc != RC_OK) return crc;
     if (nq == 0) return RC_OK;
     const dense_exact_layout L = dense_exact_ws(N, nq);
-    if (!ws || ws_bytes < L.total) return RC_EWORKSPACE;
+    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
     return dense_exact(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
 }
 

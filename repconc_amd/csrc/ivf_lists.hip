@@ -1248,11 +1248,6 @@ extern "C" size_t rc_ivf_search_probes_ws_bytes(int M, int nq, int nprobe, int n
 // a query's sample array, >= the largest possible number of sampled rows of nprobe cells (a cell of n rows contributes
 // 16 floor(n / 16 ss) + min(16, n mod 16 ss)); sel_slack: standard deviations of head-room in the threshold rank;
 // keep_all_rows: queries probing no more rows than this re-score every row.  Same status bits, same results.
-extern "C" int rc_ivf_search_probes_q(rc_handle_t h, const uint8_t* codes, const uint8_t* image, const int64_t* list_off,
-                                      const int64_t* rowmap, int64_t N, int nlist, int M, int K, const float* lut, int nq,
-                                      const int* probes, int nprobe, int64_t sstride, int ss, int k, double sel_slack,
-                                      int keep_all_rows, float* scores, int64_t* out_ids, int* status, int* qstatus, void* ws,
-                                      size_t ws_bytes, rc_stream_t stream);
 extern "C" int rc_ivf_search_probes(rc_handle_t h, const uint8_t* codes, const uint8_t* image, const int64_t* list_off,
                                     const int64_t* rowmap, int64_t N, int nlist, int M, int K, const float* lut, int nq,
                                     const int* probes, int nprobe, int64_t sstride, int ss, int k, double sel_slack,

@@ -10,18 +10,8 @@
 //                          of every row of the probed lists -> dense[qi][pos], rowid[qi][pos]
 //   ivf_kth_kernel         per query: exact k-th largest of its dense scores (4-pass radix select over global memory)
 //   ivf_filter_kernel      per query: rows with score >= that value -> 64-bit keys (ordered score, ~id)
-//   adc_select_kernel      (adc_search.hip) sorts the keys and emits the top-k — same tie rule as the flat search
-#include "rc_common.h"
-
-#define IVF_CAND_CAP 16384
-
-__device__ __forceinline__ unsigned ivf_order_key(float s) {
-    const unsigned u = __float_as_uint(s);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float ivf_unorder_key(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k);
-}
+//   adc_select_kernel      (topk.hip) sorts the keys and emits the top-k — same tie rule as the flat search
+#include "topk.h"
 
 // grid (nq, slices).  probes [nq][nprobe] list ids, base [nq][nprobe] position of each probe's first row in the
 // query's dense arrays.
@@ -75,7 +65,7 @@ __global__ __launch_bounds__(1024) void ivf_kth_kernel(const float* __restrict__
         const unsigned prefix = sel_prefix;
         const unsigned himask = (pass == 0) ? 0u : (0xFFFFFFFFu << (shift + 8));
         for (int i = tid; i < n; i += 1024) {
-            const unsigned key = ivf_order_key(row[i]);
+            const unsigned key = adc_order_key(row[i]);
             if ((key & himask) == prefix) atomicAdd(&hist[(key >> shift) & 0xFFu], 1u);
         }
         __syncthreads();
@@ -91,7 +81,7 @@ __global__ __launch_bounds__(1024) void ivf_kth_kernel(const float* __restrict__
         }
         __syncthreads();
     }
-    if (tid == 0) thr[qi] = ivf_unorder_key(sel_prefix);
+    if (tid == 0) thr[qi] = adc_unorder_key(sel_prefix);
 }
 
 // grid (nq, chunks).  Keys of the rows with score >= thr[qi]; id = ids[rowid] (the corpus position of the row).
@@ -120,18 +110,13 @@ __global__ __launch_bounds__(256) void ivf_filter_kernel(const float* __restrict
             if (lane == (int)__builtin_ctzll(mask)) b = atomicAdd(cand_count + qi, (unsigned)__popcll(mask));
             b = __shfl(b, (int)__builtin_ctzll(mask));
             const unsigned slot = b + rank;
-            if (pass && slot < IVF_CAND_CAP) {
+            if (pass && slot < ADC_CAND_CAP) {
                 const unsigned id = (unsigned)ids[rid[i]];
-                cand[(size_t)qi * IVF_CAND_CAP + slot] =
-                    ((unsigned long long)ivf_order_key(s) << 32) | (unsigned long long)(0xFFFFFFFFu - id);
+                cand[(size_t)qi * ADC_CAND_CAP + slot] = adc_exact_key(s, id);
             }
         }
     }
 }
-
-// adc_search.hip: sort the candidate keys and emit the top-k
-int rc_adc_launch_select(rc_handle_t h, unsigned long long* cand, const unsigned* cnt, int nq, int64_t N, int k,
-                         int64_t id_offset, float* scores, int64_t* ids, int* status, hipStream_t s, int* qstatus = nullptr);
 
 extern "C" size_t rc_ivf_search_ws_bytes(int nq, int64_t stride) {
     if (nq <= 0 || stride <= 0) return 0;
@@ -140,7 +125,7 @@ extern "C" size_t rc_ivf_search_ws_bytes(int nq, int64_t stride) {
     o += rc_align_up((size_t)nq * stride * sizeof(int), 256);     // rowid
     o += rc_align_up((size_t)nq * sizeof(float), 256);            // thr
     o += rc_align_up((size_t)nq * sizeof(unsigned), 256);         // cand_count
-    o += rc_align_up((size_t)nq * IVF_CAND_CAP * sizeof(unsigned long long), 256);
+    o += rc_align_up((size_t)nq * ADC_CAND_CAP * sizeof(unsigned long long), 256);
     return o;
 }
 
@@ -170,7 +155,7 @@ extern "C" int rc_ivf_search(rc_handle_t h, const uint8_t* codes, const int64_t*
     if (!h || !codes || !list_off || !ids || !lut || !probes || !base || !count || !scores || !out_ids || !status ||
         N <= 0 || nq < 0 || nprobe <= 0 || stride <= 0 || k <= 0)
         return RC_EINVAL;
-    if (K != RC_K || k > IVF_CAND_CAP / 2 || N > 0xFFFFFFFFll) return RC_ESHAPE;
+    if (K != RC_K || k > ADC_CAND_CAP / 2 || N > 0xFFFFFFFFll) return RC_ESHAPE;
     if (nq == 0) return RC_OK;
     if (!ws || ws_bytes < rc_ivf_search_ws_bytes(nq, stride)) return RC_EWORKSPACE;
     char* w = (char*)ws;

@@ -53,8 +53,6 @@ extern "C" int rc_create(rc_handle_t* out, int device) {
     return RC_OK;
 }
 
-extern "C" int rc_comm_destroy(rc_handle_t h);
-
 extern "C" int rc_destroy(rc_handle_t h) {
     if (h) {
         (void)rc_comm_destroy(h);

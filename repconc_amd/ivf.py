@@ -298,7 +298,7 @@ class IVFPQIndex:
     # nprobe 32 / 128: 4.71 -> 4.13, 8.32 -> 7.87; 1 200 queries: 1.08 -> 0.99, 1.59 -> 1.52; no query answered again by the scan
     # (profiles/r06m_ivf_sample_rows.txt)
     SAMPLE_ROWS = 1536
-    CAND_CAP = 16384                # candidate keys per query (ADC_CAND_CAP)
+    CAND_CAP = 16384                # candidate keys per query (ADC_CAND_CAP, csrc/topk.h)
     KEEP_ALL_ROWS = 4096            # queries probing no more rows than this re-score every row (no threshold)
     MAX_QUERY_BATCH = 16384         # queries per C call (rc_ivf_search_lists / _probes refuse more than 32768)
     LISTS_MIN_BYTES = 576000        # "auto": average probed code bytes per query from which the list-centric search pays (round 3, 1200 queries: the two meet at ~6.5 k rows for M = 96, ~10.6 k for M = 48)

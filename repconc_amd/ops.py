@@ -870,7 +870,7 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
 
 # ---------------------------------------------------------------------------------------------------------------- dense
 DENSE_SEL_SLACK = ADC_SEL_SLACK     # head-room of the dense search's sampled threshold (same rank formula, rc_dense_search_q)
-DENSE_MAX_K = 8192                  # the select's cap (ADC_CAND_CAP / 2)
+DENSE_MAX_K = 8192                  # the select's cap (ADC_CAND_CAP / 2, csrc/topk.h)
 DENSE_QCHUNK = 2048                 # queries per library call: <= 2048 x 256 KiB of sample scores and candidate keys
 
 
