@@ -106,8 +106,9 @@ __device__ __forceinline__ unsigned adc_kth_largest(KeyAt key_at, int64_t n, uns
 // So the first cut is made in VALUE space: 256 equal bins over [min, max] of the scores (a monotone function of the key:
 // bin(s) = min(255, int((s - smin) scale)), so "the bin that holds the rank-th largest" is well defined) — the fullest bin of
 // a Gaussian sample holds ~1.3 % of it — then the members of that one bin (a few dozen in the tail where the thresholds
-// live) are collected into `list` and the bit-radix select above runs on them.  Non-finite extremes, a degenerate range or
-// a bin longer than list_cap: the plain bit-radix select over everything.  `s_aux`: 8 words of LDS.
+// live) are collected into `list` and the bit-radix select above runs on them.  Non-finite extremes, a degenerate range
+// (256 / (smax - smin) inf or 0: a sub-normal or an overflowing range) or a bin longer than list_cap: the plain bit-radix
+// select over everything.  `s_aux`: 8 words of LDS.
 // MM_READY: the caller has already reduced the keys' minimum / maximum into s_aux[2] / s_aux[3] (e.g. while loading them),
 // zeroed hist and s_aux[4], and synchronised.
 template <bool MM_READY = false, typename KeyAt>
@@ -138,7 +139,8 @@ __device__ __forceinline__ unsigned adc_kth_largest_v(KeyAt key_at, int64_t n, u
     if (lo == hi_key) return hi_key;
     const float smin = adc_unorder_key(lo), smax = adc_unorder_key(hi_key);
     const float scale = 256.0f / (smax - smin);
-    const bool linear = (smin - smin == 0.f) && (smax - smax == 0.f) && (scale - scale == 0.f);     // all finite (block-uniform)
+    // all finite (block-uniform); scale == 0: smax - smin overflowed, s - smin can be inf and inf * 0 has no bin
+    const bool linear = (smin - smin == 0.f) && (smax - smax == 0.f) && (scale - scale == 0.f) && scale > 0.f;
     if (!linear) {
         __syncthreads();
         return adc_kth_largest(key_at, n, rank, hist, s_scan, s_sel, s_mm);

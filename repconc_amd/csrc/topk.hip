@@ -6,6 +6,13 @@
 //   key        64 bits per candidate row: adc_order_key(score) << 32 | ~id (adc_exact_key), id < 2^32 the row's corpus
 //              position.  adc_order_key maps fp32 scores to unsigned integers of the same order, so a DESCENDING sort of the
 //              keys is (score descending, id ascending) — the tie rule of every search: equal scores, lower id first.
+//              The order is TOTAL on the bit patterns, which "score descending" does not say: -0.0 sorts directly below
+//              +0.0 (two different keys: a row scoring +0.0 precedes every row scoring -0.0 whatever their ids, and the
+//              emitted score keeps its sign bit), +inf above and -inf below every finite score, a NaN with the sign bit
+//              clear above +inf and one with it set below -inf.  Sub-normal scores are ordinary keys.  The dense producer
+//              never emits -0.0 for a corpus whose rows hold no tiny values: its fmaf chain starts at +0.0 and x + (+0.0) is
+//              never -0.0; only a product that underflows to zero from below leaves -0.0 in the chain, and it survives
+//              only if every later term q[d] x[n][d] is -0.0 as well.
 //   lists      cand[nq][ADC_CAND_CAP] keys and cnt[nq] (zeroed by the caller) per query.  A producer appends by an atomic add
 //              on cnt[q] and stores only slots < ADC_CAND_CAP: cnt[q] may exceed the capacity, the list never does.
 //   status     one device int per call, qstatus (optional) one per query, both OR-ed into, never cleared here:
