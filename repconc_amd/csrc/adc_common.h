@@ -11,7 +11,7 @@
 #define ADC_TILE_DOCS 32768
 #define ADC_SCREEN_MIN_N (1 << 18)
 #define ADC_ID_CAP 32768
-#define ADC_QSTAT_STRIDE 128          // floats per query: lo[0..M), sum of lo as a double at [124], delta at [127]
+#define ADC_QSTAT_STRIDE 128          // floats per query: lo[0..M), doubles B at [122] and A at [124] (adc_screen_tint), delta at [127]
 
 // ---- conflict-free slot rule (round 2; today the table phases of the IVF screen, ivf_lists.hip) ------------------
 // The sum over sub-quantisers is commutative, so the lanes of a wave need not visit them in the same order: byte tables are
@@ -47,10 +47,50 @@ __host__ __device__ inline void adc_cf_step(int PM, int s, int r, int g, int& sl
     slot = base + ml + S * (lam / S);                      // S = 16: second copy for lanes 16-31
 }
 
+// ---- the 8-bit screen's step, bytes and integer threshold (flat search: adc_qlut_kernel, adc_qstats_kernel; IVF search:
+// ivfs_qprep_kernel + ivf_rank_select_kernel).  This is the one place where the bound is stated and computed.
+//
+// A query's tables LUT[m][c] (fp32) have lo_m = min_c, hi_m = max_c.  One step per query, delta = max_m (hi_m - lo_m) / 255
+// (adc_screen_delta), bytes l_m(c) = adc_quant8(LUT[m][c], lo_m, delta), and a row n with codes c_m is kept by the screen when
+// S_int(n) = sum_m l_m(c_m) >= T.  The search promises that the screen drops NO row whose exact score is >= tau, where the
+// exact score is the contract's fp32 sum  s(n) = fl(...fl(fl(L_0 + L_1) + L_2)... + L_{M-1}),  L_m = LUT[m][c_m], m ascending
+// from 0 (adc_rescore_row, the oracle).  Write R = sum_m L_m (real numbers), A = sum_m lo_m, B = sum_m max(|lo_m|, |hi_m|).
+//  (1) bytes.  x = fl(fl(L_m - lo_m) / delta) and l = floor(fl(x + 0.5)) are three roundings of values below 256, each off by
+//      at most 2^-24 of its result: l >= (L_m - lo_m) / delta - 1/2 - e with e < 1e-4.  The clamps do not enter: 0 only raises
+//      l, and adc_screen_delta guarantees (hi_m - lo_m) / delta <= 255.25, which rounds to 255.  Summed over the M entries of a
+//      row:  S_int >= (R - A) / delta - M / 2 - M e.
+//  (2) the exact score is not R.  Its M - 1 rounded additions (0 + L_0 is exact; fp32 addition cannot underflow, a sub-normal
+//      sum is exact) give  |s - R| <= g sum_m |L_m| <= g B  with g = (M - 1) u / (1 - (M - 1) u), u = 2^-24 (Higham, Accuracy
+//      and Stability of Numerical Algorithms, 4.2).  The integer sum follows R, the test it stands in for is on s: when the
+//      tables carry an offset that is large against their range, g B is many steps.  E = M u B >= g B + (the rounding of A and
+//      B themselves, summed in double: at most M 2^-53 B each) for every M <= 128.
+//  (1) + (2):  s >= tau  =>  R >= tau - E  =>  S_int >= (tau - A - E) / delta - M / 2 - M e.
+//  T = ceil((tau - A - E) / delta - M / 2) - 2 is at least 1 below that; the 1 covers M e <= 0.013 and the roundings of this
+//  double expression (|value| <= 2e9 or the result saturates: below 1e-6).  (S_int is an integer, so - 1 would do; - 2 is the
+//  value the screens were tuned and measured with.)  So the bound is rigorous about exactly this: for
+//  finite tables no row with fp32 score >= tau fails the integer test.  It says nothing about how FEW rows pass: E / delta is
+//  0.02 .. 0.1 steps on zero-mean tables (ranges of a few sigma), but with an offset of 1e5 ranges the threshold falls by
+//  thousands of steps, the survivor list overflows (status bit 1) and the search's repeat -> exact route answers instead.
+//  delta = inf (a range that overflows fp32): every byte is 0, T < 0, every row passes — the same route.
+__device__ __forceinline__ float adc_screen_delta(float maxrange) {
+    float delta = maxrange / 255.0f;
+    if (!(delta > 0.f)) delta = 1.0f;                       // constant tables: every byte 0
+    // a sub-normal quotient has lost bits: a step rounded DOWN by 2^-4 would let the clamp at 255 cut more than half a step off
+    // the largest entries.  One ulp up restores 255 delta >= maxrange (never taken by a normal quotient: it is within 2^-24).
+    if ((double)maxrange > 255.25 * (double)delta) delta = __uint_as_float(__float_as_uint(delta) + 1u);
+    return delta;
+}
 __device__ __forceinline__ unsigned adc_quant8(float v, float lo, float delta) {
-    int l = (int)floorf((v - lo) / delta + 0.5f);           // nearest: the screen's one-sided slack is M / 2 + 2 steps, not M + 2
+    int l = (int)floorf((v - lo) / delta + 0.5f);           // nearest: (1) above costs M / 2 steps, not M
     l = l < 0 ? 0 : (l > 255 ? 255 : l);
     return (unsigned)l;
+}
+// t = tau, A = sum of lo_m and B = sum of max(|lo_m|, |hi_m|), both accumulated in double, m ascending
+__device__ __forceinline__ int adc_screen_tint(float t, double A, double B, float delta, int M) {
+    if (t == -INFINITY) return INT_MIN;                     // no threshold: every row is a candidate
+    const double E = (double)M * 5.9604644775390625e-8 * B; // M 2^-24 B
+    const double v = ceil(((double)t - A - E) / (double)delta - 0.5 * (double)M) - 2.0;
+    return v < -2.0e9 ? INT_MIN : (v > 2.0e9 ? INT_MAX : (int)v);
 }
 
 typedef int adc_i32x4v __attribute__((ext_vector_type(4)));

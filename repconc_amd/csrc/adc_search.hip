@@ -18,8 +18,10 @@
 //        a. adc_scan_kernel<FILTER>: exact fp32 scores for every row (small indexes);
 //        b. integer screening (N >= 2^18): each query's tables are quantised to 8 bits with a common step Delta_q
 //           (l = round((LUT - min_m)/Delta_q)); the screen sums the bytes and keeps every row with S_int >= T_q, where
-//           T_q = ceil((tau_q - sum_m min_m)/Delta_q - M/2) - 2 is a RIGOROUS lower bound (each of the M entries is off by
-//           at most half a step, plus float rounding), so no row with exact score >= tau_q is ever lost;
+//           T_q = ceil((tau_q - sum_m min_m - E_q)/Delta_q - M/2) - 2 is a lower bound that is RIGOROUS about this: no row
+//           whose fp32 score (m ascending) is >= tau_q fails it.  M/2: every byte is off by at most half a step; E_q = M 2^-24
+//           sum_m max|LUT_m|: the fp32 score is not the real-number sum the bytes follow; - 2: the float roundings of the
+//           quantiser and of T_q itself.  Derivation and code: adc_screen_tint, adc_common.h;
 //           adc_rescore_kernel (adc_common.h) then computes the exact fp32 score of the survivors (~1.4x the final
 //           candidates) and applies the exact test.  The candidate set, hence the result, is the same as (a).
 //           Screens: adc_screen_q16_kernel for the M with a permuted image (16, 32, 48, 64, 96: 16 queries per conflict-free
@@ -196,7 +198,7 @@ __global__ __launch_bounds__(ADC_THREADS) void adc_scan_kernel(const uint8_t* __
 __global__ __launch_bounds__(RC_K) void adc_qlut_kernel(const float* __restrict__ lut, const float* __restrict__ thr,
                                                         int M, int QS, uint8_t* __restrict__ qlut,
                                                         int* __restrict__ tint) {
-    __shared__ float lo_m[128];
+    __shared__ float lo_m[128], ab_m[128];
     __shared__ float red_lo[4], red_hi[4];
     __shared__ float s_delta;
     const int qi = blockIdx.x, c = threadIdx.x;
@@ -214,35 +216,21 @@ __global__ __launch_bounds__(RC_K) void adc_qlut_kernel(const float* __restrict_
         __syncthreads();
         lo = fminf(fminf(red_lo[0], red_lo[1]), fminf(red_lo[2], red_lo[3]));
         hi = fmaxf(fmaxf(red_hi[0], red_hi[1]), fmaxf(red_hi[2], red_hi[3]));
-        if (c == 0) lo_m[m] = lo;
+        if (c == 0) { lo_m[m] = lo; ab_m[m] = fmaxf(fabsf(lo), fabsf(hi)); }
         maxrange = fmaxf(maxrange, hi - lo);
         __syncthreads();
     }
     if (c == 0) {
-        float delta = maxrange / 255.0f;
-        if (!(delta > 0.f)) delta = 1.0f;
+        const float delta = adc_screen_delta(maxrange);
         s_delta = delta;
-        double A = 0.0;
-        for (int m = 0; m < M; ++m) A += (double)lo_m[m];
-        const float t = thr[qi];
-        int T;
-        if (t == -INFINITY) {
-            T = INT_MIN;
-        } else {
-            const double v = ceil(((double)t - A) / (double)delta - 0.5 * (double)M) - 2.0;   // entries rounded to NEAREST: |error| <= 1/2 each
-            T = v < -2.0e9 ? INT_MIN : (v > 2.0e9 ? INT_MAX : (int)v);
-        }
-        tint[qi] = T;
+        double A = 0.0, B = 0.0;
+        for (int m = 0; m < M; ++m) { A += (double)lo_m[m]; B += (double)ab_m[m]; }
+        tint[qi] = adc_screen_tint(thr[qi], A, B, delta, M);
     }
     __syncthreads();
     const float delta = s_delta;
     uint8_t* dst = qlut + (size_t)(qi / QS) * M * RC_K * QS + (qi % QS);
-    for (int m = 0; m < M; ++m) {
-        const float v = (lq[m * RC_K + c] - lo_m[m]) / delta;
-        int l = (int)floorf(v + 0.5f);
-        l = l < 0 ? 0 : (l > 255 ? 255 : l);
-        dst[((size_t)m * RC_K + c) * QS] = (uint8_t)l;
-    }
+    for (int m = 0; m < M; ++m) dst[((size_t)m * RC_K + c) * QS] = (uint8_t)adc_quant8(lq[m * RC_K + c], lo_m[m], delta);
 }
 
 // grid (query groups of QS, doc tiles).  LDS: [M][256] entries of QS bytes (uint2 for QS = 8, uint for 4).
@@ -479,6 +467,7 @@ __global__ __launch_bounds__(RC_K) void adc_qstats_kernel(const float* __restric
                                                           int M, float* __restrict__ qstat, int* __restrict__ tint) {
     __shared__ float s_lo[ADC_QSTAT_STRIDE];
     __shared__ float s_rng[ADC_QSTAT_STRIDE];
+    __shared__ float s_abs[ADC_QSTAT_STRIDE];
     const int qi = blockIdx.x, c = threadIdx.x, lane = c & 63, wv = c >> 6;
     const float* lq = lut + (size_t)qi * M * RC_K;
     // a wave owns sub-quantisers wv, wv + 4, ...: four codes per lane, one wave reduction per sub-quantiser
@@ -494,28 +483,21 @@ __global__ __launch_bounds__(RC_K) void adc_qstats_kernel(const float* __restric
             qstat[(size_t)qi * ADC_QSTAT_STRIDE + m] = lo;
             s_lo[m] = lo;
             s_rng[m] = hi - lo;
+            s_abs[m] = fmaxf(fabsf(lo), fabsf(hi));
         }
     }
     __syncthreads();
     if (c == 0) {
         float maxrange = 0.f;
-        double A = 0.0;
+        double A = 0.0, B = 0.0;
         for (int m = 0; m < M; ++m) {
             maxrange = fmaxf(maxrange, s_rng[m]);
             A += (double)s_lo[m];
+            B += (double)s_abs[m];
         }
-        float delta = maxrange / 255.0f;
-        if (!(delta > 0.f)) delta = 1.0f;
+        const float delta = adc_screen_delta(maxrange);
         qstat[(size_t)qi * ADC_QSTAT_STRIDE + ADC_QSTAT_STRIDE - 1] = delta;
-        const float t = thr[qi];
-        int T;
-        if (t == -INFINITY) {
-            T = INT_MIN;
-        } else {
-            const double v = ceil(((double)t - A) / (double)delta - 0.5 * (double)M) - 2.0;   // entries rounded to NEAREST: |error| <= 1/2 each
-            T = v < -2.0e9 ? INT_MIN : (v > 2.0e9 ? INT_MAX : (int)v);
-        }
-        tint[qi] = T;
+        tint[qi] = adc_screen_tint(thr[qi], A, B, delta, M);
     }
 }
 

@@ -115,7 +115,7 @@ extern "C" int rc_adc_scan_image_rows(rc_handle_t h, const uint8_t* codes, int64
 // per-query byte tables, [phase][code][PMp] one biased byte per sub-quantiser (phase p starts at byte 256 * 32 p):
 // Round 4: adc_qstats_kernel + ivfs_qbyte_write_kernel in one pass over the query's LUT.  Block (256 codes, M / 16): thread
 // (c, b) keeps lut[16 b + j][c], j < 16, in registers; lo / hi per sub-quantiser by wave reductions + LDS, delta = the
-// largest range / 255 (the arithmetic of adc_qstats_kernel), then the bytes are quantised from the registers.  The integer
+// largest range / 255 (adc_screen_delta), then the bytes are quantised from the registers.  The integer
 // threshold needs tau and is computed where tau is (ivf_rank_select_kernel).  One read of the LUT instead of two, one launch
 // instead of two, 6 x the threads (26 + 42 -> ~25 us per 1200 queries at M = 96).
 __global__ __launch_bounds__(1024) void ivfs_qprep_kernel(const float* __restrict__ lut, int M, float* __restrict__ qstat,
@@ -164,19 +164,21 @@ __global__ __launch_bounds__(1024) void ivfs_qprep_kernel(const float* __restric
         s_mlo[t] = lo;
         qstat[(size_t)qi * ADC_QSTAT_STRIDE + t] = lo;
         s_lo[0][t] = hi - lo;
+        s_hi[0][t] = fmaxf(fabsf(lo), fabsf(hi));
     }
     __syncthreads();
     if (t == 0) {
         float maxrange = 0.f;
-        double A = 0.0;
+        double A = 0.0, B = 0.0;
         for (int m = 0; m < M; ++m) {
             maxrange = fmaxf(maxrange, s_lo[0][m]);
             A += (double)s_mlo[m];
+            B += (double)s_hi[0][m];
         }
-        float delta = maxrange / 255.0f;
-        if (!(delta > 0.f)) delta = 1.0f;
+        const float delta = adc_screen_delta(maxrange);
         qstat[(size_t)qi * ADC_QSTAT_STRIDE + ADC_QSTAT_STRIDE - 1] = delta;
         *reinterpret_cast<double*>(qstat + (size_t)qi * ADC_QSTAT_STRIDE + ADC_QSTAT_STRIDE - 4) = A;   // sum of lo, m ascending
+        *reinterpret_cast<double*>(qstat + (size_t)qi * ADC_QSTAT_STRIDE + ADC_QSTAT_STRIDE - 6) = B;   // sum of max(|lo|, |hi|)
         s_delta = delta;
     }
     __syncthreads();
@@ -195,13 +197,10 @@ __global__ __launch_bounds__(1024) void ivfs_qprep_kernel(const float* __restric
     }
 }
 
-// the integer threshold of a query from tau and the statistics of its tables (the arithmetic of adc_qstats_kernel)
+// the integer threshold of a query from tau and the statistics ivfs_qprep_kernel left of its tables (adc_screen_tint, adc_common.h)
 __device__ __forceinline__ int adc_tint_from(float t, const float* __restrict__ st, int M) {
-    if (t == -INFINITY) return INT_MIN;
-    const double A = *reinterpret_cast<const double*>(st + ADC_QSTAT_STRIDE - 4);     // written by ivfs_qprep_kernel
-    const double delta = (double)st[ADC_QSTAT_STRIDE - 1];
-    const double v = ceil(((double)t - A) / delta - 0.5 * (double)M) - 2.0;   // entries rounded to NEAREST: |error| <= 1/2 each
-    return v < -2.0e9 ? INT_MIN : (v > 2.0e9 ? INT_MAX : (int)v);
+    return adc_screen_tint(t, *reinterpret_cast<const double*>(st + ADC_QSTAT_STRIDE - 4),
+                           *reinterpret_cast<const double*>(st + ADC_QSTAT_STRIDE - 6), st[ADC_QSTAT_STRIDE - 1], M);
 }
 
 struct ivfs_task {

@@ -794,7 +794,9 @@ def test_faiss_indexpq_file_round_trip(tmp_path):
                                       (64, 262144, 4, 50), (24, 500000, 11, 200), (12, 262145, 2, 1)])
 def test_adc_integer_screening_path_is_exact(M, N, nq, k):
     """N >= 2^18 takes the 8-bit screening + exact rescoring path; ids and score bits must still equal the
-    brute-force oracle (the integer threshold is a rigorous bound)."""
+    brute-force oracle (the integer threshold is a rigorous bound, DESIGN.md §4.6: rigorous about the rows whose fp32
+    m-ascending score reaches tau — half a step per byte plus the accumulation error of that score, adc_screen_tint in
+    csrc/adc_common.h; these zero-mean tables strain neither term, tests/test_screen_bound.py does)."""
     from repconc_amd import ops
     C, codes, q = _adc_case(M, N, nq, seed=M * 7 + N)
     codes[N // 2: N // 2 + 300] = codes[:300]          # duplicated rows: ties across the candidate boundary
