@@ -386,6 +386,39 @@ size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k);
 int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
                           int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream);
 
+/* ------------------------------------------------------------------ dense flat search, fp16 storage
+ * The same search over a corpus stored as IEEE fp16 (faiss GpuClonerOptions.useFloat16): x [N, ldx] and q [nq, D] are fp16
+ * bit patterns (uint16_t), finite.  Score s(q, n) = fp32 fmaf chain over d = 0 .. D-1 ascending from +0.0f over the widened
+ * values, s = fmaf((float)q[d], (float)x[n][d], s): ids AND score bits equal rc_dense_search_q on the widened arrays.
+ * Order, padding (-inf / -1), id_offset and the limits (N < 2^32, 1 <= k <= 8192, else RC_ESHAPE) as above.  Any D >= 1;
+ * D % 16 == 0 requires x and q 16-byte aligned and ldx % 8 == 0 (else RC_EINVAL); the f16 screen reads rows with 16-byte loads
+ * when D % 8 == 0, ldx % 8 == 0 and both pointers are 16-byte aligned, element by element otherwise.
+ * rc_dense_f16_search_q: N <= 131072 takes the exact route below.  Above: the f16 matrix cores compute approximate scores s~
+ *   (their summation order is not the chain's); the r-th best s~ of 32768 strided sample rows is the threshold thr~ (r and
+ *   sel_slack as at rc_adc_search), every row with s~ >= thr~ becomes a candidate, the candidates are rescored by the chain
+ *   and sorted.  xnorm_max: DEVICE pointer to one float X >= the largest Euclidean row norm of x (read on the stream, no host
+ *   synchronisation).  With E_q = 4 * D_pad * 2^-24 * ||q||_2 * X (D_pad = D rounded up to 16; every |s~ - s| <= E_q) and t =
+ *   the query's k-th exact score, t >= thr~ + E_q, all rounded upwards, proves that no row outside the list can reach the
+ *   top-k or tie with its last member.  status (device int) / qstatus (nq device ints, may be NULL), both zeroed by the caller:
+ *   bit0 = fewer than min(k, N) candidates, bit1 = the list overflowed (16384), bit2 = not certified (t < thr~ + E_q): repeat
+ *   those queries with another sel_slack or answer them by rc_dense_f16_search_exact.  ws: rc_dense_f16_search_ws_bytes.
+ * rc_dense_f16_search_exact: full score rows from the fp32 matrix cores over rows widened on load (the chain itself), then the
+ *   radix select; no status.  ws: rc_dense_f16_search_exact_ws_bytes(N, D, nq, k).
+ * rc_dense_f16_scores (test hook): the screen's raw s~, out [nq][N] fp32.
+ * rc_dense_f16_error_constant: the factor 4 of E_q as the certificate kernel was compiled with it (no GPU needed).
+ * rc_dense_f16_screen_form: 32 if the screen runs on v_mfma_f32_32x32x16_f16, 16 if on v_mfma_f32_16x16x32_f16. */
+size_t rc_dense_f16_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_f16_search_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                          const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores, int64_t* ids,
+                          int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_dense_f16_search_exact_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_f16_search_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq, int k,
+                              int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq, float* out,
+                        rc_stream_t stream);
+double rc_dense_f16_error_constant(void);
+int rc_dense_f16_screen_form(void);
+
 /* ------------------------------------------------------------------ a-9 … a-11, stateful form
  * The index object the reference keeps inside Faiss (initialize_index / add_docs / index.search,
  * models/repconc/evaluate_repconc.py:78-98,182; JPQ's per-step synchronize_model_index, models/jpq/finetune_jpq.py:209-214),

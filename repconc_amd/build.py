@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "librepconc_hip.so")
-SOURCES = ["pq_distance.hip", "pq_assign_mfma.hip", "sinkhorn.hip", "sinkhorn_f64.hip", "pq_misc.hip", "kmeans.hip", "topk.hip", "adc_search.hip", "dense_search.hip", "ivf_lists.hip", "ivf_search.hip", "index.hip", "comm.hip"]
+SOURCES = ["pq_distance.hip", "pq_assign_mfma.hip", "sinkhorn.hip", "sinkhorn_f64.hip", "pq_misc.hip", "kmeans.hip", "topk.hip", "adc_search.hip", "dense_search.hip", "dense_search_f16.hip", "ivf_lists.hip", "ivf_search.hip", "index.hip", "comm.hip"]
 # -ffp-contract=off: the fp32 distance arithmetic must round every sub/mul/add separately
 # (bit parity with the torch-CPU oracle); fused multiply-adds are written explicitly where wanted.
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
@@ -36,7 +36,7 @@ def _stale(target, deps):
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "rc_common.h"), os.path.join(CSRC, "topk.h"), os.path.join(CSRC, "adc_common.h"), os.path.join(CSRC, "ivfs_screen16.h"),
+    headers = [os.path.join(CSRC, "rc_common.h"), os.path.join(CSRC, "topk.h"), os.path.join(CSRC, "adc_common.h"), os.path.join(CSRC, "dense_gemm.h"), os.path.join(CSRC, "ivfs_screen16.h"),
                os.path.join(os.path.dirname(HERE), "include", "repconc_hip.h")]
     objs, jobs = [], []
     for src in SOURCES:

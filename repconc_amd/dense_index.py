@@ -1,10 +1,14 @@
-"""Exact inner-product index resident in HBM: the GPU `faiss.IndexFlatIP` (useFloat16 = False) of the reference's dense
-evaluation, models/dense/evaluate_dense.py:84-129.
+"""Exact inner-product index resident in HBM: the GPU `faiss.IndexFlatIP` of the reference's dense evaluation,
+models/dense/evaluate_dense.py:84-129 (useFloat16 = False by default, `storage="float16"` for useFloat16 = True).
 
 `FlatIPIndex` is duck-typed like that object (`d`, `ntotal`, `metric_type`, `is_trained`, `add`, `reset`, `search`) and
 searches with `ops.dense_search` (csrc/dense_search.hip): scores are the fp32 fmaf chain over d ascending, bit for bit,
 ties broken by the lower id.  The vectors live in ONE fp32 [capacity, d] device tensor appended to in place: the first
 `add` allocates exactly, later growth is 1.5x (`reserve` sets the capacity up front).
+
+`storage="float16"`: `add` rounds every value to IEEE fp16 (round to nearest even) and keeps fp16, half the bytes; `search`
+rounds the queries the same way and answers with `ops.dense_search_f16` (csrc/dense_search_f16.hip): the scores are the same
+fmaf chain over the rounded values, bit for bit what the fp32 index returns for `x.half().float()`, `q.half().float()`.
 """
 from __future__ import annotations
 
@@ -18,7 +22,13 @@ from .index import METRIC_INNER_PRODUCT
 
 
 class FlatIPIndex:
-    def __init__(self, d: int, device: Optional[torch.device] = None):
+    STORAGE = {"float32": torch.float32, "float16": torch.float16}
+
+    def __init__(self, d: int, device: Optional[torch.device] = None, storage: str = "float32"):
+        if storage not in self.STORAGE:
+            raise ValueError(f"storage must be one of {sorted(self.STORAGE)}, got {storage!r}")
+        self.storage = storage
+        self._dtype = self.STORAGE[storage]
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -29,17 +39,18 @@ class FlatIPIndex:
         self.id_offset = 0       # global id of local row 0
         self.sel_slack = ops.DENSE_SEL_SLACK
         self.last_search = None
-        self._x = torch.empty((0, self.d), dtype=torch.float32, device=self.device)
+        self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
+        self._xnorm_max = None   # float16 storage: device fp32 [1] >= the largest row norm held (the search's certificate)
 
     @property
     def xb(self) -> torch.Tensor:
-        """fp32 [ntotal, d] view of the stored vectors."""
+        """[ntotal, d] view of the stored vectors, in the storage type."""
         return self._x[: self.ntotal]
 
     def reserve(self, n: int) -> None:
         """Capacity for `n` rows in total (the rows held so far are kept)."""
         if n > self._x.shape[0]:
-            grown = torch.empty((int(n), self.d), dtype=torch.float32, device=self.device)
+            grown = torch.empty((int(n), self.d), dtype=self._dtype, device=self.device)
             grown[: self.ntotal] = self._x[: self.ntotal]
             self._x = grown
 
@@ -49,18 +60,30 @@ class FlatIPIndex:
             raise ValueError(f"add: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
         n = xt.shape[0]
         need = self.ntotal + n
+        xnorm = None
+        if self.storage == "float16":
+            # rounded and checked before anything is stored or grown; one host read per add
+            xt = xt.to(self.device).to(torch.float16)
+            if n and not bool(torch.isfinite(xt).all()):
+                raise ValueError("add: float16 storage needs finite values of magnitude < 65520 (fp16 rounds the rest to inf)")
+            if n:
+                xnorm = ops.dense_f16_xnorm_max(xt)
         if need > self._x.shape[0]:
             self.reserve(need if self.ntotal == 0 else max(need, int(self._x.shape[0] * 1.5)))
-        self._x[self.ntotal:need] = xt.to(self.device, torch.float32)
+        self._x[self.ntotal:need] = xt.to(self.device, self._dtype)
         self.ntotal = need
+        if xnorm is not None:
+            self._xnorm_max = xnorm if self._xnorm_max is None else torch.maximum(self._xnorm_max, xnorm)
 
     def reset(self) -> None:
         self.ntotal = 0
-        self._x = torch.empty((0, self.d), dtype=torch.float32, device=self.device)
+        self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
+        self._xnorm_max = None
 
     def search(self, x, k: int):
         """(scores [nq, k], ids [nq, k]); numpy in -> numpy out (evaluate_dense.py:74), CUDA tensors in -> CUDA tensors
-        out (faiss.contrib.torch_utils)."""
+        out (faiss.contrib.torch_utils).  float16 storage rounds the queries to fp16 without a range check: a query value of
+        magnitude >= 65520 becomes inf (`ops.dense_search_f16`)."""
         return self.search_async(x, k)()
 
     def search_async(self, x, k: int):
@@ -76,6 +99,9 @@ class FlatIPIndex:
             scores = torch.full((q.shape[0], k), float("-inf"), dtype=torch.float32, device=self.device)
             ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
             pending = ops.PendingSearch(None, scores, ids, None, None, 0.0, 0)
+        elif self.storage == "float16":
+            pending = ops.dense_search_f16(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
+                                           xnorm_max=self._xnorm_max)
         else:
             pending = ops.dense_search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True)
         self.last_search = pending           # .stats: queries repeated / answered by the exact route

@@ -55,6 +55,8 @@ class EvalArguments(TrainingArguments):
     topk: int = field(default=100)
     search_threads: int = field(default=60)
     search_batch: int = field(default=1200)
+    index_float16: bool = field(default=False, metadata={"help": "store the corpus as fp16 (half the memory; vectors and "
+                                                                  "queries are rounded to fp16, the search stays exact)"})
     remove_unused_columns: Optional[bool] = field(default=False)
 
 
@@ -99,7 +101,7 @@ def load_or_encode_corpus(model, tokenizer, model_args, data_args, eval_args):
 def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_ids, out_metric_path, out_query_dir,
                                qrel_path, eval_args):
     """Exact search on the GPU, run.tsv, and with a qrels file metric.json.  run_dense_eval.py:111-127."""
-    index = create_index(corpus_embeds)
+    index = create_index(corpus_embeds, use_float16=getattr(eval_args, "index_float16", False))
     all_topk_scores, all_topk_ids = batch_dense_search(query_ids, query_embeds, corpus_ids, index, eval_args.topk,
                                                        batch_size=eval_args.search_batch)
     out_run_path = os.path.join(out_query_dir, "run.tsv")

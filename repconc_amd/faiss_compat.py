@@ -7,7 +7,8 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
                                                                         finetune_jpq.py:211-213
     faiss.vector_to_array(index.pq.centroids) / (index.codes)           run_warmup.py:124-125, finetune_jpq.py:161
     faiss.IndexPQ(D, M, 8, faiss.METRIC_INNER_PRODUCT)                  evaluate_repconc.py:81
-    faiss.IndexFlatIP(d)                                                evaluate_dense.py:116 (exact fp32, dense_index.py)
+    faiss.IndexFlatIP(d)                                                evaluate_dense.py:116 (exact fp32, dense_index.py;
+                                                                        useFloat16: FlatIPIndex(d, storage="float16"))
     faiss.write_index(index, path) / faiss.read_index(path)             run_warmup.py:187, run_repconc_eval.py:42
     faiss.omp_set_num_threads(n)                                        run_repconc_eval.py:149 (no-op: the scan runs on the GPU)
 

@@ -703,9 +703,12 @@ class PendingSearch:
                     self._left -= 1
                     self.stats["retried_queries"] += int(bad.numel())
                     slack_few = max(slack_few, 0.0) * 3.0 + 2.0          # bit0: too few candidates -> wider
-                    slack_many = max(slack_many / 3.0, 0.0)              # bit1 only: a list overflowed -> tighter
+                    slack_many = max(slack_many / 3.0, 0.0)              # bit1 without bit0: a list overflowed -> tighter
                     still, still_bits = [], []
-                    for sel, slack in (((bits & 1) != 0, slack_few), ((bits & 1) == 0, slack_many)):
+                    # bit2 (dense fp16 search: the threshold is too close to the k-th score to certify) wants a lower threshold
+                    # like bit0, unless the list overflowed as well
+                    few = ((bits & 1) != 0) | ((bits & 6) == 4)
+                    for sel, slack in ((few, slack_few), (~few, slack_many)):
                         idx = bad[sel]
                         if idx.numel() == 0:
                             continue
@@ -955,6 +958,138 @@ def dense_search(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, s
     status = torch.zeros((1,), dtype=torch.int32, device=q.device)
     qstatus = torch.zeros((nq,), dtype=torch.int32, device=q.device)
     launch(q, float(sel_slack), scores, ids, status, qstatus)
+    pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
+                            stream=torch.cuda.current_stream(dev))
+    return pending if defer else pending.result()
+
+
+# --------------------------------------------------------------------------------------------------- dense, fp16 storage
+def dense_f16_error_constant() -> float:
+    """The factor of E_q as the certificate kernel was compiled with it (DENSE_F16_ERR_C, csrc/dense_search_f16.hip)."""
+    return float(_lib.load().rc_dense_f16_error_constant())
+
+
+def dense_f16_error_bound(D: int, qnorm, xmax):
+    """E = 4 D_pad 2^-24 ||q||_2 X, D_pad = D rounded up to 16: the bound on |s~ - s| between ANY fp32 accumulation s~ of the D
+    exact products q_d x_d (the f16 matrix cores' screen) and the fmaf chain s that the certificate of `dense_search_f16` uses
+    (include/repconc_hip.h, rc_dense_f16_search_q).  Either sum errs by at most D - 1 roundings of at most 2^-23 (truncation)
+    of a partial sum <= sum_d |q_d x_d| <= ||q|| ||x||.  Plain float / numpy arithmetic: `qnorm`, `xmax` scalars or arrays."""
+    dpad = (int(D) + 15) // 16 * 16
+    return dense_f16_error_constant() * dpad * 2.0 ** -24 * qnorm * xmax
+
+
+def dense_f16_xnorm_max(x16: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
+    """Device fp32 scalar [1] >= the largest Euclidean row norm of the fp16 matrix `x16` (fp64 sums, rounded upwards); the
+    `xnorm_max` of `dense_search_f16`.  No host synchronisation."""
+    best = torch.zeros((), dtype=torch.float64, device=x16.device)
+    for r0 in range(0, x16.shape[0], rows_per_step):
+        best = torch.maximum(best, x16[r0:r0 + rows_per_step].double().square_().sum(1).max())
+    return (best.sqrt() * (1.0 + 2.0 ** -20)).float().reshape(1)
+
+
+def _dense_f16_args(x16: torch.Tensor, q: torch.Tensor, k: int):
+    _need_cuda(x16, q)
+    if x16.dim() != 2 or q.dim() != 2 or x16.shape[1] != q.shape[1]:
+        raise ValueError("dense search: x [N, D] and q [nq, D] with the same D")
+    if x16.dtype != torch.float16:
+        raise ValueError("dense_search_f16: the corpus must be float16 (FlatIPIndex(storage='float16') rounds and checks it)")
+    if not 1 <= int(k) <= DENSE_MAX_K:
+        raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
+    if x16.stride(1) != 1 or (x16.shape[1] % 16 == 0 and (x16.stride(0) % 8 != 0 or x16.data_ptr() % 16 != 0)):
+        x16 = x16.clone(memory_format=torch.contiguous_format)      # a strided or misaligned view: a fresh allocation is aligned
+    if x16.shape[0] >= 1 << 32:
+        raise ValueError("dense search: N must be < 2^32")
+    q16 = q.to(x16.device).to(torch.float16).contiguous()           # round to nearest even, as the corpus was
+    return x16, q16
+
+
+def dense_search_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+    """The same answer as `dense_search_f16` by the route that cannot fail (rc_dense_f16_search_exact)."""
+    x16, q16 = _dense_f16_args(x16, q, k)
+    N, D = x16.shape
+    nq = q16.shape[0]
+    lib, h, s, _ = _ctx(q16)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
+    if nq == 0 or N == 0:
+        scores.fill_(float("-inf"))
+        ids.fill_(-1)
+        return scores, ids
+    wsb = lib.rc_dense_f16_search_exact_ws_bytes(N, D, nq, int(k))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=q16.device)
+    _lib.check(lib.rc_dense_f16_search_exact(h, _p(x16), x16.stride(0), N, D, _p(q16), nq, int(k), int(id_offset), _p(scores),
+                                             _p(ids), _p(ws), wsb, s), "rc_dense_f16_search_exact", h)
+    return scores, ids
+
+
+def dense_f16_scores(x16: torch.Tensor, q16: torch.Tensor) -> torch.Tensor:
+    """The raw approximate scores s~ [nq, N] of the f16 matrix-core screen (rc_dense_f16_scores): a test hook, never a result."""
+    x16, q16 = _dense_f16_args(x16, q16, 1)
+    lib, h, s, _ = _ctx(q16)
+    out = torch.empty((q16.shape[0], x16.shape[0]), dtype=torch.float32, device=q16.device)
+    if out.numel():
+        _lib.check(lib.rc_dense_f16_scores(h, _p(x16), x16.stride(0), x16.shape[0], x16.shape[1], _p(q16), q16.shape[0],
+                                           _p(out), s), "rc_dense_f16_scores", h)
+    return out
+
+
+def dense_search_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
+                     defer: bool = False, method: str = "auto", max_retries: int = 2,
+                     xnorm_max: Optional[torch.Tensor] = None):
+    """Exact top-k inner-product search of `q` [nq, D] against the FINITE fp16 corpus `x16` [N, D] (faiss.IndexFlatIP with
+    useFloat16).  The queries are rounded to fp16 (round to nearest even; a component of magnitude >= 65520 becomes inf and is
+    not checked for: such a query gets no certificate and the exact route gives it the chain's inf / NaN scores); scores are
+    the fp32 fmaf chain over d ascending of
+    the widened values: ids and score bits equal `dense_search(x16.float(), q.half().float(), k)`.  The f16 matrix cores only
+    screen; candidates are rescored by the chain and every answer of the fast route carries a certificate (qstatus bit2 when
+    it cannot be given: such queries are repeated, then answered by the exact route — `.stats` of the `PendingSearch`).
+    xnorm_max: device fp32 [1], >= the largest row norm of x16 (`dense_f16_xnorm_max`, computed here when None).
+    Everything else as `dense_search`."""
+    if method not in ("auto", "exact"):
+        raise ValueError("method must be 'auto' or 'exact'")
+    x16, q16 = _dense_f16_args(x16, q, k)
+    if sel_slack is None:
+        sel_slack = DENSE_SEL_SLACK
+    N, D = x16.shape
+    nq = q16.shape[0]
+    if method == "exact" or nq == 0 or N == 0:
+        got = dense_search_f16_exact(x16, q16, k, id_offset)
+        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
+    lib, h, _, dev = _ctx(q16)
+    if xnorm_max is None:
+        xnorm_max = dense_f16_xnorm_max(x16)
+    _need_cuda(xnorm_max)
+    xnorm_max = xnorm_max.to(torch.float32).reshape(1)
+
+    def launch(qq, slack, out_s, out_i, status, qstatus):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for c0 in range(0, qq.shape[0], DENSE_QCHUNK):
+            n = min(DENSE_QCHUNK, qq.shape[0] - c0)
+            wsb = lib.rc_dense_f16_search_ws_bytes(N, D, n, int(k))
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=q16.device)     # released in stream order
+            _lib.check(lib.rc_dense_f16_search_q(h, _p(x16), x16.stride(0), N, D, _p(qq[c0:c0 + n]), n, _p(xnorm_max), int(k),
+                                                 int(id_offset), float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]),
+                                                 _p(status), _p(qstatus[c0:c0 + n]), _p(ws), wsb, st),
+                       "rc_dense_f16_search_q", h)
+
+    def rerun(idx, slack, exact):
+        qq = q16[idx].contiguous()
+        if exact:
+            s_, i_ = dense_search_f16_exact(x16, qq, k, id_offset)
+            return s_, i_, None
+        s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q16.device)
+        i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q16.device)
+        status = torch.zeros((1,), dtype=torch.int32, device=q16.device)
+        qs = torch.zeros((qq.shape[0],), dtype=torch.int32, device=q16.device)
+        launch(qq, slack, s_, i_, status, qs)
+        return s_, i_, qs
+
+    _warm_retry_ops(q16.device)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=q16.device)
+    qstatus = torch.zeros((nq,), dtype=torch.int32, device=q16.device)
+    launch(q16, float(sel_slack), scores, ids, status, qstatus)
     pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
                             stream=torch.cuda.current_stream(dev))
     return pending if defer else pending.result()

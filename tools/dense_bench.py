@@ -2,14 +2,19 @@
 (8 841 823 x 768 fp32, 27.2 GB), the 6 980 dev queries in batches of 1 200 (evaluate_dense.py:93-112), k = 100 / 1000, and
 small query batches (1, 32, 128) against the HBM bound.  Synthetic seeded data generated on the device.
 
-    python tools/dense_bench.py [--out profiles/dense_bench.json] [--quick] [--no-torch]
+    python tools/dense_bench.py [--out profiles/dense_bench.json] [--quick] [--no-torch] [--storage float16 [--f16-only]]
     rocprofv3 --kernel-trace --stats -d DIR -o dense -- python tools/dense_bench.py --quick
     python tools/dense_bench.py --report DIR/.../dense_kernel_stats.csv      # the screen kernel's TFLOP/s from that run
 
 Prints ms per batch, queries/s, repeated / exact query counts, the same search as a chunked torch.mm + torch.topk
 composition on the same device (ids compared where the score margins allow), and a sample of queries checked against the
 fmaf-chain oracle of tests/test_dense_flat.py.  The screen's TFLOP/s and the time outside it come from the kernel trace
-(--report): a screen launch over nq queries does 2 nq N D flop."""
+(--report): a screen launch over nq queries does 2 nq N D flop.
+
+--storage float16 (csrc/dense_search_f16.hip): the fp32 leg runs first, then the same vectors rounded to fp16 in the same
+process on the same card; every figure is reported for both and the result carries the float16 / float32 ratios.
+--f16-only skips the fp32 leg: --report on a trace of such a --quick run gives the f16 screen's TFLOP/s against the f16
+matrix peak and the shares of the sample, threshold, rescoring, select and certificate kernels."""
 import argparse
 import csv
 import json
@@ -22,30 +27,59 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 PEAK_TF = 157.3          # fp32 matrix peak, MI355X
+PEAK_F16_TF = 2500.0     # f16 matrix peak, dense
 HBM_TBS = 8.0            # HBM3E peak
 
 
 def report(path, n, d, batch, nq):
-    """Kernel statistics of a `--quick` run: its screen launches cover the warm-up batch and the query set twice."""
+    """Kernel statistics of a `--quick` run: its screen launches cover the warm-up batch and the query set twice.  The
+    select and threshold kernels are shared by both storages, so per-storage shares need a trace of one leg alone: the plain
+    run for fp32, `--storage float16 --f16-only` for fp16.  A trace that holds both legs is reported with "mixed_legs"."""
     queries = batch + 2 * nq
     rows = list(csv.DictReader(open(path)))
+    ms = lambda r: float(r["TotalDurationNs"]) / 1e6
     # the search's own kernels (the corpus generation and host copies of the run are not part of a search)
-    tot = sum(float(r["TotalDurationNs"]) for r in rows if r["Name"].startswith(("void dense_", "void adc_", "dense_", "adc_")))
+    # rocprofv3 leaves the template kernels mangled (_Z21dense_f16_gemm_kernelILi1ELb0ELb1EE...) and demangles the plain ones
+    search = [r for r in rows if any(t in r["Name"] for t in ("dense_gemm_kernel", "dense_f16_", "adc_threshold_kernel", "adc_select_kernel", "adc_exact_"))]
+    tot = sum(ms(r) for r in search)
+    has32 = any("dense_gemm_kernel<1" in r["Name"] or "dense_gemm_kernelILi1E" in r["Name"] for r in search)
+    has16 = any("dense_f16_gemm_kernel<1" in r["Name"] or "dense_f16_gemm_kernelILi1E" in r["Name"] for r in search)
     out = {}
-    for r in rows:
-        name = r["Name"]
-        if "dense_gemm_kernel<1" in name or "dense_gemm_kernelILi1E" in name:
-            out["screen_calls"] = int(r["Calls"])
-            out["screen_ms_each"] = float(r["AverageNs"]) / 1e6
-            out["screen_ms_total"] = float(r["TotalDurationNs"]) / 1e6
-    if "screen_calls" in out:
-        out["search_kernels_ms_total"] = tot / 1e6
-        out["outside_screen_ms_total"] = (tot - out["screen_ms_total"] * 1e6) / 1e6
+    if has32 and has16:
+        out["mixed_legs"] = True
+    if has32:
+        r = next(r for r in search if "dense_gemm_kernel<1" in r["Name"] or "dense_gemm_kernelILi1E" in r["Name"])
+        out["screen_calls"] = int(r["Calls"])
+        out["screen_ms_each"] = float(r["AverageNs"]) / 1e6
+        out["screen_ms_total"] = ms(r)
+        if not has16:
+            out["search_kernels_ms_total"] = tot
+            out["outside_screen_ms_total"] = tot - out["screen_ms_total"]
+            out["outside_screen_ms_per_call"] = out["outside_screen_ms_total"] / out["screen_calls"]
         out["screened_queries"] = queries
         out["screen_tflops"] = 2.0 * queries * n * d / (out["screen_ms_total"] * 1e-3) / 1e12
         out["screen_share_of_peak"] = out["screen_tflops"] / PEAK_TF
         out["screen_ms_per_1200_queries"] = 2.0 * 1200 * n * d / (out["screen_tflops"] * 1e12) * 1e3
-        out["outside_screen_ms_per_call"] = out["outside_screen_ms_total"] / out["screen_calls"]
+    if has16:
+        f16 = {}
+        for r in search:
+            for key, tags in (("screen", ("dense_f16_gemm_kernel<1", "dense_f16_gemm_kernelILi1E")),
+                              ("sample", ("dense_f16_gemm_kernel<0", "dense_f16_gemm_kernelILi0E")),
+                              ("rescore", ("dense_f16_rescore_kernel",)), ("certify", ("dense_f16_certify_kernel",)),
+                              ("select", ("adc_select_kernel",)), ("threshold", ("adc_threshold_kernel",))):
+                if any(tag in r["Name"] for tag in tags):
+                    f16[key + "_ms_total"] = f16.get(key + "_ms_total", 0.0) + ms(r)
+                    f16[key + "_calls"] = f16.get(key + "_calls", 0) + int(r["Calls"])
+        f16["screened_queries"] = queries
+        f16["screen_tflops"] = 2.0 * queries * n * d / (f16["screen_ms_total"] * 1e-3) / 1e12
+        f16["screen_share_of_f16_peak"] = f16["screen_tflops"] / PEAK_F16_TF
+        f16["screen_ms_per_1200_queries"] = 2.0 * 1200 * n * d / (f16["screen_tflops"] * 1e12) * 1e3
+        if not has32:
+            f16["search_kernels_ms_total"] = tot
+            for key in ("screen", "sample", "threshold", "rescore", "select", "certify"):
+                f16[key + "_share"] = f16.get(key + "_ms_total", 0.0) / tot
+                f16[key + "_ms_per_1200_queries"] = f16.get(key + "_ms_total", 0.0) * 1200 / queries
+        out["float16"] = f16
     print(json.dumps(out, indent=1))
     return out
 
@@ -63,31 +97,76 @@ def main():
     ap.add_argument("--no-torch", action="store_true")
     ap.add_argument("--out", default=None)
     ap.add_argument("--report", default=None, help="a rocprofv3 kernel_stats.csv of a --quick run")
+    ap.add_argument("--storage", default="float32", choices=["float32", "float16"],
+                    help="float16: the fp32 leg first, then the fp16-storage index in the same process, and their ratios")
+    ap.add_argument("--f16-only", action="store_true",
+                    help="with --storage float16: skip the fp32 leg (a kernel trace of the fp16 leg alone, or an A/B of two builds)")
     a = ap.parse_args()
     if a.report:
         report(a.report, a.n, a.d, a.batch, a.nq)
         return
-    import numpy as np
     import torch
-    from repconc_amd import ops
+    from repconc_amd import _lib
     from repconc_amd.dense_index import FlatIPIndex
-    from repconc_amd.models.dense.evaluate_dense import batch_dense_search
     dev = torch.device("cuda", 0)
     g = torch.Generator(device=dev)
     g.manual_seed(1234)
-    index = FlatIPIndex(a.d, device=dev)
-    index.reserve(a.n)
     step = 1 << 20
-    for r0 in range(0, a.n, step):
-        index.add(torch.randn((min(step, a.n - r0), a.d), generator=g, device=dev))
-    q = torch.randn((a.nq, a.d), generator=g, device=dev)
+    q = None
+    res = None
+    if not (a.storage == "float16" and a.f16_only):
+        index = FlatIPIndex(a.d, device=dev)
+        index.reserve(a.n)
+        for r0 in range(0, a.n, step):
+            index.add(torch.randn((min(step, a.n - r0), a.d), generator=g, device=dev))
+        q = torch.randn((a.nq, a.d), generator=g, device=dev)
+        res = measure(a, index, q)
+    if a.storage == "float16":
+        half = FlatIPIndex(a.d, device=dev, storage="float16")
+        half.reserve(a.n)
+        if res is None:                                  # the same random stream as the fp32 leg draws
+            for r0 in range(0, a.n, step):
+                half.add(torch.randn((min(step, a.n - r0), a.d), generator=g, device=dev))
+            q = torch.randn((a.nq, a.d), generator=g, device=dev)
+        else:
+            for r0 in range(0, a.n, step):
+                half.add(index.xb[r0:r0 + step])
+            del index
+        torch.cuda.empty_cache()
+        r16 = measure(a, half, q)
+        r16["screen_form"] = "v_mfma_f32_%s_f16" % {32: "32x32x16", 16: "16x16x32"}[_lib.load().rc_dense_f16_screen_form()]
+        if res is None:
+            res = {"float16": r16}
+        else:
+            f32 = res
+            res = {"float32": f32, "float16": r16, "float16_over_float32_queries_per_s": {
+                str(u["k"]): v["queries_per_s"] / u["queries_per_s"] for u, v in zip(f32["runs"], r16["runs"])}}
+            if "small" in r16:
+                res["float16_over_float32_small_ms"] = {str(u["nq"]): v["ms"] / u["ms"] for u, v in zip(f32["small"], r16["small"])}
+            print(json.dumps({k: v for k, v in res.items() if k.startswith("float16_over")}), flush=True)
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        json.dump(res, open(a.out, "w"), indent=1)
+
+
+def measure(a, index, q):
+    """Every figure of one index (fp32 or fp16 storage) over the query set `q`."""
+    import numpy as np
+    import torch
+    from repconc_amd import ops
+    from repconc_amd.models.dense.evaluate_dense import batch_dense_search
+    f16 = index.storage == "float16"
+    esize = 2 if f16 else 4
+    peak = PEAK_F16_TF if f16 else PEAK_TF
+    search = (lambda qq, k: ops.dense_search_f16(index.xb, qq, k, xnorm_max=index._xnorm_max)) if f16 else \
+        (lambda qq, k: ops.dense_search(index.xb, qq, k))
     qn = q.cpu().numpy()
     corpus_ids = np.arange(a.n)
     query_ids = np.arange(a.nq)
     ks = [1000] if a.quick else [int(v) for v in a.ks.split(",")]
-    res = {"n": a.n, "d": a.d, "nq": a.nq, "batch": a.batch, "corpus_gb": a.n * a.d * 4 / 1e9,
-           "flop_per_batch_t": 2.0 * a.batch * a.n * a.d / 1e12, "roofline_ms_per_batch": 2.0 * a.batch * a.n * a.d / PEAK_TF / 1e9,
-           "hbm_bound_ms": a.n * a.d * 4 / HBM_TBS / 1e9, "runs": []}
+    res = {"storage": index.storage, "n": a.n, "d": a.d, "nq": a.nq, "batch": a.batch, "corpus_gb": a.n * a.d * esize / 1e9,
+           "flop_per_batch_t": 2.0 * a.batch * a.n * a.d / 1e12, "roofline_ms_per_batch": 2.0 * a.batch * a.n * a.d / peak / 1e9,
+           "hbm_bound_ms": a.n * a.d * esize / HBM_TBS / 1e9, "runs": []}
     nb = -(-a.nq // a.batch)
     for k in ks:
         batch_dense_search(query_ids[:a.batch], qn[:a.batch], corpus_ids, index, k, a.batch)      # warm-up
@@ -110,7 +189,7 @@ def main():
         bs, bi = batch_dense_search(query_ids, qn, corpus_ids, index, k, a.batch)
         run["batch_dense_search_s"] = time.perf_counter() - t0
         assert np.array_equal(bi, ids)
-        if not (a.quick or a.no_torch):
+        if not (a.quick or a.no_torch or f16):
             # chunked torch.mm + torch.topk on the same device
             torch.cuda.synchronize()
             t0 = time.perf_counter()
@@ -144,7 +223,8 @@ def main():
         from test_dense_flat import oracle_topk
         k = ks[-1]
         sel = np.linspace(0, a.nq - 1, a.verify).astype(int)
-        ws, wi = oracle_topk(index.xb, q[sel], k, qblock=16, rblock=1 << 20)
+        # (fp16 storage: the oracle over the stored values widened and the rounded queries, rows widened block by block)
+        ws, wi = oracle_topk(index.xb, q[sel].half().float() if f16 else q[sel], k, qblock=16, rblock=1 << 20)
         gs, gi = index.search(qn[sel], k)
         res["verified_queries"] = int(len(sel))
         res["verified_equal"] = bool(np.array_equal(gi, wi) and np.array_equal(gs.view(np.uint32), ws.view(np.uint32)))
@@ -154,22 +234,20 @@ def main():
         for nq in [int(v) for v in a.small.split(",")]:
             qq = q[:nq].contiguous()
             for _ in range(2):
-                ops.dense_search(index.xb, qq, 100)
+                search(qq, 100)
             torch.cuda.synchronize()
             reps = 10
             t0 = time.perf_counter()
             for _ in range(reps):
-                ops.dense_search(index.xb, qq, 100)
+                search(qq, 100)
             torch.cuda.synchronize()
             ms = 1e3 * (time.perf_counter() - t0) / reps
             row = {"nq": nq, "k": 100, "ms": ms, "hbm_bound_ms": res["hbm_bound_ms"],
-                   "corpus_read_tbs": a.n * a.d * 4 / (ms * 1e-3) / 1e12,
-                   "roofline_ms": max(res["hbm_bound_ms"], 2.0 * nq * a.n * a.d / PEAK_TF / 1e9)}
+                   "corpus_read_tbs": a.n * a.d * esize / (ms * 1e-3) / 1e12,
+                   "roofline_ms": max(res["hbm_bound_ms"], 2.0 * nq * a.n * a.d / peak / 1e9)}
             res["small"].append(row)
             print(json.dumps(row), flush=True)
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        json.dump(res, open(a.out, "w"), indent=1)
+    return res
 
 
 if __name__ == "__main__":
