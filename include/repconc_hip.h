@@ -419,6 +419,30 @@ int rc_dense_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N
 double rc_dense_f16_error_constant(void);
 int rc_dense_f16_screen_form(void);
 
+/* ------------------------------------------------------------------ dense flat search, fp32 corpus, bf16x3 screen
+ * rc_dense_search_q's arguments, limits and RESULTS (ids and score bits) for finite x and q whose bf16 rounding is finite
+ * (|v| < 2^128 - 2^119); x is not checked, a query outside the range is never certified.  Only the screen differs: every
+ * operand is split a = a_h + a_l + r, a_h = bf16(a), a_l = bf16(a - a_h), round to nearest even, and the bf16 matrix cores
+ * compute s~ = sum_d (q_h x_h + q_h x_l + q_l x_h).  The corpus is split as it is staged, the queries once per call.
+ * rc_dense_bf16x3_search_q: N <= 131072 takes the route of rc_dense_search_exact.  Above: threshold thr~ from the s~ of 32768
+ *   strided sample rows, every row with s~ >= thr~ a candidate, candidates rescored by the chain and sorted.  xnorm_max: DEVICE
+ *   pointer to one float X >= the largest Euclidean row norm of x.  With D_pad = D rounded up to 16 and the constants c[0..3] of
+ *   rc_dense_bf16x3_error_constants,
+ *     E_q = (c0 D_pad 2^-24 + c1 2^-16) ||q||_2 X + c2 sqrt(D_pad) (||q||_2 + X) + c3 D_pad      (every |s~ - s| <= E_q),
+ *   t >= thr~ + E_q for t = the query's k-th exact score proves the answer.  status / qstatus as rc_dense_f16_search_q: bit0,
+ *   bit1, bit2 = not certified (also: a non-finite value anywhere, a query value that rounds to inf, D > 65536): repeat those
+ *   queries with another sel_slack or answer them by rc_dense_search_exact.  ws (16-byte aligned): rc_dense_bf16x3_search_ws_bytes.
+ * rc_dense_bf16x3_scores (test hook): the screen's raw s~, out [nq][N] fp32; ws: rc_dense_bf16x3_scores_ws_bytes(D, nq).
+ * rc_dense_bf16x3_error_constants: c[4] = {8, 4, 2^-133, 4 * 2^-149} as the certificate kernel was compiled (no GPU needed). */
+size_t rc_dense_bf16x3_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_bf16x3_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                             const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores, int64_t* ids,
+                             int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_dense_bf16x3_scores_ws_bytes(int D, int nq);
+int rc_dense_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
+                           void* ws, size_t ws_bytes, rc_stream_t stream);
+void rc_dense_bf16x3_error_constants(double* c);
+
 /* ------------------------------------------------------------------ a-9 … a-11, stateful form
  * The index object the reference keeps inside Faiss (initialize_index / add_docs / index.search,
  * models/repconc/evaluate_repconc.py:78-98,182; JPQ's per-step synchronize_model_index, models/jpq/finetune_jpq.py:209-214),

@@ -9,6 +9,10 @@ ties broken by the lower id.  The vectors live in ONE fp32 [capacity, d] device 
 `storage="float16"`: `add` rounds every value to IEEE fp16 (round to nearest even) and keeps fp16, half the bytes; `search`
 rounds the queries the same way and answers with `ops.dense_search_f16` (csrc/dense_search_f16.hip): the scores are the same
 fmaf chain over the rounded values, bit for bit what the fp32 index returns for `x.half().float()`, `q.half().float()`.
+
+`screen="bf16x3"` (float32 storage only): the vectors stay fp32 and `search` returns the same ids and score bits as the default
+index, but the candidates are chosen on the bf16 matrix cores by `ops.dense_search_bf16x3` (csrc/dense_search_bf16x3.hip).
+`add` then refuses values whose bf16 rounding is not finite (magnitude >= 2^128 - 2^119, inf, NaN).
 """
 from __future__ import annotations
 
@@ -23,11 +27,22 @@ from .index import METRIC_INNER_PRODUCT
 
 class FlatIPIndex:
     STORAGE = {"float32": torch.float32, "float16": torch.float16}
+    SCREENS = ("fp32", "bf16x3")
 
-    def __init__(self, d: int, device: Optional[torch.device] = None, storage: str = "float32"):
-        if storage not in self.STORAGE:
-            raise ValueError(f"storage must be one of {sorted(self.STORAGE)}, got {storage!r}")
+    @classmethod
+    def check_options(cls, storage: str, screen: str) -> None:
+        """ValueError for an unknown storage or screen, or a combination that does not exist; touches no device."""
+        if storage not in cls.STORAGE:
+            raise ValueError(f"storage must be one of {sorted(cls.STORAGE)}, got {storage!r}")
+        if screen not in cls.SCREENS:
+            raise ValueError(f"screen must be one of {list(cls.SCREENS)}, got {screen!r}")
+        if screen == "bf16x3" and storage != "float32":
+            raise ValueError("screen='bf16x3' needs storage='float32'")
+
+    def __init__(self, d: int, device: Optional[torch.device] = None, storage: str = "float32", screen: str = "fp32"):
+        self.check_options(storage, screen)
         self.storage = storage
+        self.screen = screen
         self._dtype = self.STORAGE[storage]
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
@@ -40,7 +55,8 @@ class FlatIPIndex:
         self.sel_slack = ops.DENSE_SEL_SLACK
         self.last_search = None
         self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
-        self._xnorm_max = None   # float16 storage: device fp32 [1] >= the largest row norm held (the search's certificate)
+        # float16 storage / bf16x3 screen: device fp32 [1] >= the largest row norm held (the search's certificate)
+        self._xnorm_max = None
 
     @property
     def xb(self) -> torch.Tensor:
@@ -68,6 +84,13 @@ class FlatIPIndex:
                 raise ValueError("add: float16 storage needs finite values of magnitude < 65520 (fp16 rounds the rest to inf)")
             if n:
                 xnorm = ops.dense_f16_xnorm_max(xt)
+        elif self.screen == "bf16x3":
+            # checked before anything is stored or grown; one host read per add
+            xt = xt.to(self.device, torch.float32)
+            if n and not bool(torch.isfinite(xt.to(torch.bfloat16)).all()):
+                raise ValueError("add: the bf16x3 screen needs finite values of magnitude < 2^128 - 2^119 (bf16 rounds the rest to inf)")
+            if n:
+                xnorm = ops.dense_xnorm_max(xt)
         if need > self._x.shape[0]:
             self.reserve(need if self.ntotal == 0 else max(need, int(self._x.shape[0] * 1.5)))
         self._x[self.ntotal:need] = xt.to(self.device, self._dtype)
@@ -102,6 +125,9 @@ class FlatIPIndex:
         elif self.storage == "float16":
             pending = ops.dense_search_f16(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
                                            xnorm_max=self._xnorm_max)
+        elif self.screen == "bf16x3":
+            pending = ops.dense_search_bf16x3(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
+                                              xnorm_max=self._xnorm_max)
         else:
             pending = ops.dense_search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True)
         self.last_search = pending           # .stats: queries repeated / answered by the exact route

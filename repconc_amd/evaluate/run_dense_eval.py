@@ -20,6 +20,7 @@ import transformers
 from transformers import AutoConfig, AutoTokenizer, HfArgumentParser, TrainingArguments, set_seed
 from transformers.trainer_utils import is_main_process
 
+from ..dense_index import FlatIPIndex
 from ..models.dense import AutoDense
 from ..models.dense.evaluate_dense import batch_dense_search, create_index, encode_dense_corpus, encode_dense_query
 from ..utils.eval_utils import load_corpus, load_queries, pytrec_evaluate, write_run
@@ -57,6 +58,8 @@ class EvalArguments(TrainingArguments):
     search_batch: int = field(default=1200)
     index_float16: bool = field(default=False, metadata={"help": "store the corpus as fp16 (half the memory; vectors and "
                                                                   "queries are rounded to fp16, the search stays exact)"})
+    index_screen: str = field(default="fp32", metadata={"help": "fp32, or bf16x3: the fp32 index with its candidates chosen on "
+                                                                "the bf16 matrix cores (same results; not with index_float16)"})
     remove_unused_columns: Optional[bool] = field(default=False)
 
 
@@ -101,7 +104,8 @@ def load_or_encode_corpus(model, tokenizer, model_args, data_args, eval_args):
 def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_ids, out_metric_path, out_query_dir,
                                qrel_path, eval_args):
     """Exact search on the GPU, run.tsv, and with a qrels file metric.json.  run_dense_eval.py:111-127."""
-    index = create_index(corpus_embeds, use_float16=getattr(eval_args, "index_float16", False))
+    index = create_index(corpus_embeds, use_float16=getattr(eval_args, "index_float16", False),
+                         screen=getattr(eval_args, "index_screen", "fp32"))
     all_topk_scores, all_topk_ids = batch_dense_search(query_ids, query_embeds, corpus_ids, index, eval_args.topk,
                                                        batch_size=eval_args.search_batch)
     out_run_path = os.path.join(out_query_dir, "run.tsv")
@@ -119,6 +123,7 @@ def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_id
 def main(argv=None):
     parser = HfArgumentParser((ModelArguments, DataArguments, EvalArguments))
     model_args, data_args, eval_args = parser.parse_args_into_dataclasses(argv)
+    FlatIPIndex.check_options("float16" if eval_args.index_float16 else "float32", eval_args.index_screen)   # before encoding
     main_process = is_main_process(eval_args.local_rank)
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s -   %(message)s", datefmt="%m/%d/%Y %H:%M:%S",
                         level=logging.INFO if main_process else logging.WARN)

@@ -120,11 +120,13 @@ def batch_dense_search(query_ids: np.ndarray, query_embeds, corpus_ids: np.ndarr
     return np.concatenate(all_scores, axis=0), np.concatenate(all_ids, axis=0)
 
 
-def create_index(corpus_embeds, single_gpu_id=None, use_float16=False) -> FlatIPIndex:
+def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="fp32") -> FlatIPIndex:
     """An exact inner-product index holding `corpus_embeds`, on device `single_gpu_id` or the current device.
     use_float16: store the vectors as fp16 (GpuClonerOptions.useFloat16, which the reference leaves False).
+    screen="bf16x3" (fp32 storage only): the same results, candidates chosen on the bf16 matrix cores.
     evaluate_dense.py:115-129."""
+    FlatIPIndex.check_options("float16" if use_float16 else "float32", screen)                # before a device is looked at
     dev = torch.device("cuda", single_gpu_id if single_gpu_id is not None else torch.cuda.current_device())
-    index = FlatIPIndex(corpus_embeds.shape[1], device=dev, storage="float16" if use_float16 else "float32")
+    index = FlatIPIndex(corpus_embeds.shape[1], device=dev, storage="float16" if use_float16 else "float32", screen=screen)
     index.add(corpus_embeds)
     return index

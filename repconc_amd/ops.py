@@ -874,6 +874,7 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
 # ---------------------------------------------------------------------------------------------------------------- dense
 DENSE_SEL_SLACK = ADC_SEL_SLACK     # head-room of the dense search's sampled threshold (same rank formula, rc_dense_search_q)
 DENSE_MAX_K = 8192                  # the select's cap (ADC_CAND_CAP / 2, csrc/topk.h)
+DENSE_EXACT_MAX_N = 131072          # up to here every dense search takes the exact route (csrc/dense_gemm.h)
 DENSE_QCHUNK = 2048                 # queries per library call: <= 2048 x 256 KiB of sample scores and candidate keys
 
 
@@ -1090,6 +1091,112 @@ def dense_search_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int 
     status = torch.zeros((1,), dtype=torch.int32, device=q16.device)
     qstatus = torch.zeros((nq,), dtype=torch.int32, device=q16.device)
     launch(q16, float(sel_slack), scores, ids, status, qstatus)
+    pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
+                            stream=torch.cuda.current_stream(dev))
+    return pending if defer else pending.result()
+
+
+# ------------------------------------------------------------------------------------ dense, fp32 corpus, bf16x3 screen
+def dense_xnorm_max(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
+    """Device fp32 scalar [1] >= the largest Euclidean row norm of the floating-point matrix `x` of any dtype (fp64 sums,
+    rounded upwards; +inf if the norm exceeds fp32): the `xnorm_max` of `dense_search_bf16x3` and `dense_search_f16`.  No host
+    synchronisation."""
+    if not x.dtype.is_floating_point:
+        raise ValueError("dense_xnorm_max: a floating-point matrix")
+    best = torch.zeros((), dtype=torch.float64, device=x.device)
+    for r0 in range(0, x.shape[0], rows_per_step):
+        best = torch.maximum(best, x[r0:r0 + rows_per_step].double().square_().sum(1).max())
+    # the fp64 -> fp32 conversion rounds to nearest, by a factor of at most 1 + 2^-24: the 2^-20 covers it
+    return (best.sqrt() * (1.0 + 2.0 ** -20)).float().reshape(1)
+
+
+def dense_bf16x3_error_constants():
+    """(c_sum, c_split, c_sub, c_under) of E_q as the certificate kernel was compiled with them (csrc/dense_search_bf16x3.hip)."""
+    c = (C.c_double * 4)()
+    _lib.load().rc_dense_bf16x3_error_constants(c)
+    return tuple(float(v) for v in c)
+
+
+def dense_bf16x3_error_bound(D: int, qnorm, xmax):
+    """E = (8 D_pad 2^-24 + 4 * 2^-16) ||q|| X + 2^-133 sqrt(D_pad) (||q|| + X) + 4 D_pad 2^-149, D_pad = D rounded up to 16:
+    the bound on |s~ - s| between the bf16x3 screen (any fp32 accumulation of the 3 D products q_h x_h + q_h x_l + q_l x_h of the
+    round-to-nearest-even bf16 splits) and the fmaf chain s that the certificate of `dense_search_bf16x3` uses; derivation in
+    the header comment of csrc/dense_search_bf16x3.hip.  The constants are the library's.  Plain float / numpy arithmetic."""
+    c_sum, c_split, c_sub, c_under = dense_bf16x3_error_constants()
+    dpad = (int(D) + 15) // 16 * 16
+    return (c_sum * dpad * 2.0 ** -24 + c_split * 2.0 ** -16) * qnorm * xmax + c_sub * dpad ** 0.5 * (qnorm + xmax) + c_under * dpad
+
+
+def dense_bf16x3_scores(x: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """The raw approximate scores s~ [nq, N] of the bf16x3 matrix-core screen (rc_dense_bf16x3_scores): a test hook, never a
+    result."""
+    x, q = _dense_args(x, q, 1)
+    lib, h, s, _ = _ctx(q)
+    out = torch.empty((q.shape[0], x.shape[0]), dtype=torch.float32, device=q.device)
+    if out.numel():
+        wsb = lib.rc_dense_bf16x3_scores_ws_bytes(x.shape[1], q.shape[0])
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        _lib.check(lib.rc_dense_bf16x3_scores(h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], _p(out),
+                                              _p(ws), wsb, s), "rc_dense_bf16x3_scores", h)
+    return out
+
+
+def dense_search_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
+                        defer: bool = False, method: str = "auto", max_retries: int = 2,
+                        xnorm_max: Optional[torch.Tensor] = None):
+    """`dense_search` with the screen on the bf16 matrix cores: the same ids and score bits for a FINITE fp32 corpus `x` whose
+    values round to finite bf16 (magnitude < 2^128 - 2^119; `FlatIPIndex(screen="bf16x3")` checks it) and any queries.
+    Nothing is rounded in the result: the screen's three-term bf16 split only chooses candidates, which are rescored by the
+    fp32 fmaf chain, and every answer of the fast route carries a certificate (qstatus bit2 when it cannot be given — also for
+    a query with a non-finite value or one that rounds to a bf16 inf: such queries are repeated, then answered by
+    `dense_search_exact`; `.stats` of the `PendingSearch`).  xnorm_max: device fp32 [1], >= the largest row norm of x
+    (`dense_xnorm_max`, computed here when None).  Everything else as `dense_search`."""
+    if method not in ("auto", "exact"):
+        raise ValueError("method must be 'auto' or 'exact'")
+    x, q = _dense_args(x, q, k)
+    if sel_slack is None:
+        sel_slack = DENSE_SEL_SLACK
+    N, D = x.shape
+    nq = q.shape[0]
+    if method == "exact" or nq == 0 or N == 0:
+        got = dense_search_exact(x, q, k, id_offset)
+        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
+    lib, h, _, dev = _ctx(q)
+    if xnorm_max is None:
+        # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the norm
+        xnorm_max = dense_xnorm_max(x) if N > DENSE_EXACT_MAX_N else torch.zeros((1,), dtype=torch.float32, device=x.device)
+    _need_cuda(xnorm_max)
+    xnorm_max = xnorm_max.to(torch.float32).reshape(1)
+
+    def launch(qq, slack, out_s, out_i, status, qstatus):
+        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for c0 in range(0, qq.shape[0], DENSE_QCHUNK):
+            n = min(DENSE_QCHUNK, qq.shape[0] - c0)
+            wsb = lib.rc_dense_bf16x3_search_ws_bytes(N, D, n, int(k))
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)     # released in stream order
+            _lib.check(lib.rc_dense_bf16x3_search_q(h, _p(x), x.stride(0), N, D, _p(qq[c0:c0 + n]), n, _p(xnorm_max), int(k),
+                                                    int(id_offset), float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]),
+                                                    _p(status), _p(qstatus[c0:c0 + n]), _p(ws), wsb, st),
+                       "rc_dense_bf16x3_search_q", h)
+
+    def rerun(idx, slack, exact):
+        qq = q[idx].contiguous()
+        if exact:
+            s_, i_ = dense_search_exact(x, qq, k, id_offset)
+            return s_, i_, None
+        s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q.device)
+        i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q.device)
+        status = torch.zeros((1,), dtype=torch.int32, device=q.device)
+        qs = torch.zeros((qq.shape[0],), dtype=torch.int32, device=q.device)
+        launch(qq, slack, s_, i_, status, qs)
+        return s_, i_, qs
+
+    _warm_retry_ops(q.device)
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    status = torch.zeros((1,), dtype=torch.int32, device=q.device)
+    qstatus = torch.zeros((nq,), dtype=torch.int32, device=q.device)
+    launch(q, float(sel_slack), scores, ids, status, qstatus)
     pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
                             stream=torch.cuda.current_stream(dev))
     return pending if defer else pending.result()
