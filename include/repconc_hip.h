@@ -406,7 +406,7 @@ int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N,
  *   radix select; no status.  ws: rc_dense_f16_search_exact_ws_bytes(N, D, nq, k).
  * rc_dense_f16_scores (test hook): the screen's raw s~, out [nq][N] fp32.
  * rc_dense_f16_error_constant: the factor 4 of E_q as the certificate kernel was compiled with it (no GPU needed).
- * rc_dense_f16_screen_form: 32 if the screen runs on v_mfma_f32_32x32x16_f16, 16 if on v_mfma_f32_16x16x32_f16. */
+ * rc_dense_f16_screen_form: 16, the screen runs on v_mfma_f32_16x16x32_f16 (32 named the retired v_mfma_f32_32x32x16_f16 form). */
 size_t rc_dense_f16_search_ws_bytes(int64_t N, int D, int nq, int k);
 int rc_dense_f16_search_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
                           const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores, int64_t* ids,

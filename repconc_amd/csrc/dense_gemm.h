@@ -1,7 +1,8 @@
-// What the two dense flat searches share (dense_search.hip: fp32 corpus, dense_search_f16.hip: fp16 corpus): the GEMM on the
+// What the dense flat searches share (dense_search.hip: fp32 corpus, dense_search_f16.hip: fp16 corpus): the GEMM on the
 // fp32 matrix cores whose result IS the score definition (the fp32 fmaf chain over d ascending), the workspace layouts and
 // the exact route.  T is the storage type of x and q: float, or _Float16 widened to fp32 on load (exact).  Device code:
-// every translation unit compiles its own copy, no -fgpu-rdc.
+// every translation unit that uses it compiles its own copy, no -fgpu-rdc.  The route of a search and what the screened
+// searches share on top of this are in dense_screen.h.
 #pragma once
 #include "topk.h"
 
@@ -227,3 +228,6 @@ static int dense_exact(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D,
     }
     return RC_OK;
 }
+// dense_exact<float>, defined once in dense_search.hip: the exact route of both searches over an fp32 corpus
+int dense_exact_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
+                    int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s);

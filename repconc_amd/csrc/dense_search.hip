@@ -14,25 +14,32 @@
 //   DENSE_FILTER  the 64-bit key (ordered score << 32 | ~row) of every s >= thr[q] is appended to q's candidate list:
 //                 one ballot per (tile, register), one global atomic per query and 32-row half-wave that has survivors
 //
-// Fast route (N > 4 S):
-//   1. dense_gemm_kernel<STORE> over the strided sample j -> row j N / S, S = min(N, 32768) rows: the same chain
-//   2. adc_threshold_kernel (topk.hip): thr[q] = the r-th best sample score, r by the ADC formula (rc_adc_sample_rank)
-//   3. dense_gemm_kernel<FILTER> over all N rows
-//   4. adc_select_kernel (rc_adc_launch_select): sort + emit; qstatus bit0 = fewer than min(k, N) candidates, bit1 = overflow
-// Exact route (small N, and the queries the fast route gives up on): dense_gemm_kernel<STORE> writes the full score rows of a
-// chunk of queries, then the 8-pass radix select over the 64-bit keys of rc_adc_search_exact (rc_adc_launch_exact_select).
-// It terminates with the same answer for any content (all rows identical, k >= N, ...).
-// The GEMM kernel, the workspace layouts and the exact route are in dense_gemm.h, shared with the fp16-storage search.
-#include "dense_gemm.h"
+// The route of a search (sample -> threshold -> FILTER -> select, or the exact route for small N) is dense_search_route
+// (dense_screen.h) with this unit's variant: the fp32 GEMM is sample screen, FILTER screen and exact route at once, its scores
+// are the chain, so nothing is rescored or certified.  The GEMM kernel, the workspace layouts and the exact route are in
+// dense_gemm.h.
+#include "dense_screen.h"
 
-extern "C" size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
-    if (N <= 0 || N > 0xFFFFFFFFll || D <= 0 || nq <= 0 || k <= 0 || k > ADC_CAND_CAP / 2) return 0;
-    return dense_exact_ws(N, nq).sel.total;
+int dense_exact_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
+                    int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s) {
+    return dense_exact<float>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, L, s);
 }
 
+struct dense_f32_variant {
+    typedef float T;
+    typedef float Q;
+    static constexpr bool approximate = false;
+    static size_t extra_ws_bytes(int, int) { return 0; }
+    static int prepass(rc_handle_t, const float* q, int, int, char*, const float** qs, hipStream_t) { *qs = q; return RC_OK; }
+    template <int MODE, typename... A>
+    static int launch_gemm(A... a) { return dense_launch_gemm<MODE, float>(a...); }
+    static constexpr auto* exact = &dense_exact_f32;
+};
+
+extern "C" size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
+
 extern "C" size_t rc_dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
-    if (N <= 0 || N > 0xFFFFFFFFll || D <= 0 || nq <= 0 || k <= 0 || k > ADC_CAND_CAP / 2) return 0;
-    return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total;
+    return dense_search_ws_bytes<dense_f32_variant>(N, D, nq, k);
 }
 
 extern "C" int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
@@ -44,7 +51,7 @@ extern "C" int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx,
     if (nq == 0) return RC_OK;
     const dense_exact_layout L = dense_exact_ws(N, nq);
     if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
-    return dense_exact(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
+    return dense_exact_f32(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
 }
 
 extern "C" int rc_dense_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
@@ -56,20 +63,6 @@ extern "C" int rc_dense_search_q(rc_handle_t h, const float* x, int64_t ldx, int
     if (!status) return RC_EINVAL;
     if (nq == 0) return RC_OK;
     if (!ws || ws_bytes < rc_dense_search_ws_bytes(N, D, nq, k)) return RC_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dense_exact_route(N)) return dense_exact(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, dense_exact_ws(N, nq), s);
-    const dense_fast_layout L = dense_fast_ws(N, nq);
-    char* w = (char*)ws;
-    float* sample = (float*)(w + L.sample);
-    float* thr = (float*)(w + L.thr);
-    unsigned* cnt = (unsigned*)(w + L.cnt);
-    unsigned long long* cand = (unsigned long long*)(w + L.cand);
-    int rc = dense_launch_gemm<DENSE_STORE>(h, x, ldx, N, L.S, L.S, q, nq, D, nullptr, sample, nullptr, nullptr, s);
-    if (rc != RC_OK) return rc;
-    rc = rc_adc_launch_threshold(h, sample, L.S, nq, rc_adc_sample_rank(N, L.S, k, sel_slack), thr, s);
-    if (rc != RC_OK) return rc;
-    RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
-    rc = dense_launch_gemm<DENSE_FILTER>(h, x, ldx, N, N, 0, q, nq, D, thr, nullptr, cnt, cand, s);
-    if (rc != RC_OK) return rc;
-    return rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, scores, ids, status, s, qstatus);
+    return dense_search_route<dense_f32_variant>(h, x, ldx, N, D, q, nq, nullptr, k, id_offset, sel_slack, scores, ids, status,
+                                                 qstatus, (char*)ws, (hipStream_t)stream);
 }

@@ -1,6 +1,8 @@
 // Exact dense inner-product top-k search over an fp32 corpus with a bf16x3 matrix-core screen: the results of
 // dense_search.hip (ids AND score bits of rc_dense_search_q), the corpus stays fp32, only the screen leaves the fp32 matrix
-// cores.  The route is dense_search_f16.hip's: screen -> candidates -> exact rescoring -> select -> per-query certificate.
+// cores.  The route is dense_search_route (dense_screen.h) with this unit's variant: dense_bf16x3_split_kernel is its query
+// pre-pass, dense_bf16x3_gemm_kernel screens, the candidates are rescored by the chain and every answer carries a certificate
+// with the E_q derived below.  Exact route: dense_exact_f32 (dense_search.hip), i.e. rc_dense_search_exact.
 //
 // Score (unchanged): s(q, n) = fp32 fmaf chain over d = 0 .. D-1 ascending from +0.0f on the fp32 values.
 //
@@ -10,19 +12,6 @@
 // values has 16 significant bits: exact in fp32 unless it underflows.  The corpus is split while it is staged global -> LDS
 // (no second copy in HBM); the queries are split once per call into two bf16 planes in the workspace, zero-padded to a
 // multiple of 32 columns (dense_bf16x3_split_kernel: the bytes of q again).
-//
-// Fast route (N > 131072):
-//   0. dense_bf16x3_split_kernel: q -> q_h, q_l
-//   1. dense_bf16x3_gemm_kernel<STORE> over the strided sample (S = 32768 rows): s~ of the sample
-//   2. adc_threshold_kernel (topk.hip): thr~[q] = the r-th best s~ of the sample (rc_adc_sample_rank)
-//   3. dense_bf16x3_gemm_kernel<FILTER> over all N rows: the key (s~, row) of every s~ >= thr~[q] -> q's candidate list
-//   4. dense_bf16x3_rescore_kernel: the score half of every candidate key is replaced by the chain, literal fmaf calls
-//   5. adc_select_kernel (rc_adc_launch_select, unchanged): sort + emit; qstatus bit0 / bit1 as in dense_search.hip
-//   6. dense_bf16x3_certify_kernel: t = the query's k-th exact score.  A row outside the list has s~ < thr~, hence
-//      s < thr~ + E_q: if t >= thr~ + E_q (everything in fp64, rounded upwards) no such row can enter the top-k or tie with
-//      its last member, and the answer is proven equal to the exact route's.  Otherwise qstatus bit2, "not certified".
-// Exact route (N <= 131072, and the queries the fast route gives up on): dense_gemm_kernel<STORE, PAD, float>, i.e.
-// rc_dense_search_exact.
 //
 // The bound |s~ - s| <= E_q.  Write P = sum_d |q_d x_d| <= ||q||_2 ||x||_2 <= ||q||_2 X.
 //   split:     |a - a_h| <= 2^-9 |a|, |a_l| <= 2^-9 (1 + 2^-8) |a|, |r| <= 2^-9 |a - a_h| <= 2^-18 |a| while a_l is a normal
@@ -45,15 +34,12 @@
 //              operands or results to zero; see DENSE_B3_C_SUB below.
 //   E_q = E_rel + E_abs.  The four constants are exported (rc_dense_bf16x3_error_constants) and are what
 //   ops.dense_bf16x3_error_bound evaluates.
-#include "dense_gemm.h"
+#include "dense_screen.h"
 
 typedef __bf16 dense_bf16x8 __attribute__((ext_vector_type(8)));
-typedef float dense_b3_f32x4 __attribute__((ext_vector_type(4)));
 #define DENSE_B3_KC 32                                   // K per LDS stage: one v_mfma_f32_16x16x32_bf16 step
-// one operand's tile: 128 rows of 128 bytes = [32 bf16 high plane | 32 bf16 low plane], 8 chunks of 16 bytes — the row
-// length of the f16 screen, so its swizzle carries over unchanged
-#define DENSE_B3_OPERAND_BYTES (DENSE_TILE * 128)
-#define DENSE_B3_LDS_BYTES (4 * DENSE_B3_OPERAND_BYTES)                         // 2 operands x 2 buffers: 64 KB, two blocks per CU
+// one operand's tile row (dense_screen.h): 128 bytes = [32 bf16 high plane | 32 bf16 low plane]; chunks 0 - 3 hold
+// k = 8c .. 8c + 7 of the high plane, 4 - 7 the same k of the low plane
 #define DENSE_B3_C_SUM 8.0                               // E_rel = (C_SUM D_pad 2^-24 + C_SPLIT 2^-16) ||q|| X
 #define DENSE_B3_C_SPLIT 4.0
 // E_abs = C_SUB sqrt(D_pad) (||q|| + X) + C_UNDER D_pad, for hardware that does not flush.  Measured on the MI355X (the subnormal
@@ -63,13 +49,6 @@ typedef float dense_b3_f32x4 __attribute__((ext_vector_type(4)));
 #define DENSE_B3_C_SUB 0x1p-133
 #define DENSE_B3_C_UNDER 0x1p-147
 #define DENSE_B3_MAX_D 65536                             // the certificate's second-order terms are bounded up to here
-#define DENSE_B3_RESCORE_QCHUNK 1024                     // query values staged in LDS by the rescoring kernel
-
-// byte offset of the 16-byte chunk c of tile row `row`: chunks 0 - 3 hold k = 8c .. 8c + 7 of the high plane, 4 - 7 the same
-// k of the low plane.  XOR swizzle with (row / 2) % 8 as dense_f16_lds_off: two rows share 256 bytes = all 64 banks, and any 16
-// lanes that hold 16 consecutive rows of one chunk index (a quarter of a ds_read_b128 of the 16x16x32 operand map) cover all
-// 64 banks once.
-__device__ __forceinline__ int dense_b3_lds_off(int row, int c) { return row * 128 + ((c ^ ((row >> 1) & 7)) << 4); }
 
 __device__ __forceinline__ void dense_b3_split8(const float* a, dense_bf16x8& h, dense_bf16x8& l) {
 #pragma unroll
@@ -100,9 +79,8 @@ __global__ __launch_bounds__(256) void dense_bf16x3_split_kernel(const float* __
 // grid: ceil(nrows / 128) blocks of 256 threads, two per CU (64 KB of LDS each).  Arguments as dense_gemm_kernel, except that
 // the queries arrive split: qs [2][nq][D32] (dense_bf16x3_split_kernel).  !PAD: D % 8 == 0 and 16-byte aligned corpus rows; PAD
 // reads the corpus element by element.  The block owns 128 corpus rows and walks every tile of 128 queries; wave (wr, wc) owns
-// 64 queries x 64 rows as 4 x 4 tiles of v_mfma_f32_16x16x32_bf16 (the form the f16 screen's A/B chose), three per tile and K
-// step: lane l holds k = 8 (l / 16) .. + 7 of row l % 16 of both operands, one 16-byte LDS read per operand tile, plane and K
-// step.  Result element r of lane l is corpus row l % 16 and query 4 (l / 16) + r of the tile; dense_emit is the epilogue.
+// 64 queries x 64 rows as 4 x 4 tiles of v_mfma_f32_16x16x32_bf16 (tiling, operand map and epilogue as laid out in
+// dense_screen.h), three per tile and K step, one 16-byte LDS read per operand tile, plane and K step.
 template <int MODE, bool PAD>
 __global__ __launch_bounds__(256, 2) void dense_bf16x3_gemm_kernel(const float* __restrict__ x, int64_t ldx, int64_t N,
                                                                 int64_t nrows, int64_t smap, const __bf16* __restrict__ qs,
@@ -110,9 +88,9 @@ __global__ __launch_bounds__(256, 2) void dense_bf16x3_gemm_kernel(const float* 
                                                                 float* __restrict__ out, unsigned* __restrict__ cnt,
                                                                 unsigned long long* __restrict__ cand) {
     constexpr int TM = 16, NT = 4;
-    __shared__ __attribute__((aligned(16))) unsigned char dense_b3_smem[DENSE_B3_LDS_BYTES];
+    __shared__ __attribute__((aligned(16))) unsigned char dense_b3_smem[DENSE_SCREEN_LDS_BYTES];
     unsigned char* sa = dense_b3_smem;                                      // [2][128 rows][128 bytes] queries
-    unsigned char* sb = dense_b3_smem + 2 * DENSE_B3_OPERAND_BYTES;         // [2][128 rows][128 bytes] corpus
+    unsigned char* sb = dense_b3_smem + 2 * DENSE_SCREEN_OPERAND_BYTES;         // [2][128 rows][128 bytes] corpus
     const int tid = threadIdx.x, l = tid & 63, wv = tid >> 6;
     const int wr = wv >> 1, wc = wv & 1;
     const int col = l % TM, grp = l / TM;
@@ -126,18 +104,16 @@ __global__ __launch_bounds__(256, 2) void dense_bf16x3_gemm_kernel(const float* 
         const int64_t jl = (j0 + lrow + 64 * i < nrows) ? j0 + lrow + 64 * i : nrows - 1;
         const int64_t xrow = smap ? (int64_t)((uint64_t)jl * (uint64_t)N / (uint64_t)smap) : jl;
         xp[i] = x + xrow * ldx;
-        so[i] = dense_b3_lds_off(lrow + 64 * i, lc);
+        so[i] = dense_screen_lds_off(lrow + 64 * i, lc);
     }
     // the low-plane chunk 4 + lc of the same row: (4 + lc) ^ m = (lc ^ m) ^ 4 for any 3-bit m
     const int nkc = (D + DENSE_B3_KC - 1) / DENSE_B3_KC;                    // == D32 / 32
-    // the thresholds of a query tile go where the operand buffer that the last K stage did not read lies
-    float* s_thr = reinterpret_cast<float*>(sa + (nkc & 1) * DENSE_B3_OPERAND_BYTES);
     const __bf16* ql = qs + (int64_t)nq * D32;
     for (int qt = 0; qt < nq; qt += DENSE_TILE) {
         int64_t qo_[2];
 #pragma unroll
         for (int i = 0; i < 2; ++i) qo_[i] = (int64_t)((qt + lrow + 64 * i < nq) ? qt + lrow + 64 * i : nq - 1) * D32 + lc * 8;
-        dense_b3_f32x4 acc[NT][NT];
+        dense_f32x4 acc[NT][NT];
 #pragma unroll
         for (int a = 0; a < NT; ++a)
 #pragma unroll
@@ -168,10 +144,10 @@ __global__ __launch_bounds__(256, 2) void dense_bf16x3_gemm_kernel(const float* 
             for (int i = 0; i < 2; ++i) {
                 dense_bf16x8 h, lo;
                 dense_b3_split8(rb[i], h, lo);
-                *reinterpret_cast<dense_bf16x8*>(sa + buf * DENSE_B3_OPERAND_BYTES + so[i]) = rah[i];
-                *reinterpret_cast<dense_bf16x8*>(sa + buf * DENSE_B3_OPERAND_BYTES + (so[i] ^ 64)) = ral[i];
-                *reinterpret_cast<dense_bf16x8*>(sb + buf * DENSE_B3_OPERAND_BYTES + so[i]) = h;
-                *reinterpret_cast<dense_bf16x8*>(sb + buf * DENSE_B3_OPERAND_BYTES + (so[i] ^ 64)) = lo;
+                *reinterpret_cast<dense_bf16x8*>(sa + buf * DENSE_SCREEN_OPERAND_BYTES + so[i]) = rah[i];
+                *reinterpret_cast<dense_bf16x8*>(sa + buf * DENSE_SCREEN_OPERAND_BYTES + (so[i] ^ 64)) = ral[i];
+                *reinterpret_cast<dense_bf16x8*>(sb + buf * DENSE_SCREEN_OPERAND_BYTES + so[i]) = h;
+                *reinterpret_cast<dense_bf16x8*>(sb + buf * DENSE_SCREEN_OPERAND_BYTES + (so[i] ^ 64)) = lo;
             }
         };
         // query tiles that hold only padding skip their MFMAs, wave-uniformly
@@ -184,12 +160,12 @@ __global__ __launch_bounds__(256, 2) void dense_bf16x3_gemm_kernel(const float* 
         for (int kc = 0; kc < nkc; ++kc) {
             const int buf = kc & 1;
             if (kc + 1 < nkc) gload(kc + 1);
-            const unsigned char* pa = sa + buf * DENSE_B3_OPERAND_BYTES;
-            const unsigned char* pb = sb + buf * DENSE_B3_OPERAND_BYTES;
+            const unsigned char* pa = sa + buf * DENSE_SCREEN_OPERAND_BYTES;
+            const unsigned char* pb = sb + buf * DENSE_SCREEN_OPERAND_BYTES;
             dense_bf16x8 fah[NT], fal[NT], fbh[NT], fbl[NT];
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
-                const int oa = dense_b3_lds_off(wr * 64 + t * TM + col, grp), ob = dense_b3_lds_off(wc * 64 + t * TM + col, grp);
+                const int oa = dense_screen_lds_off(wr * 64 + t * TM + col, grp), ob = dense_screen_lds_off(wc * 64 + t * TM + col, grp);
                 fah[t] = *reinterpret_cast<const dense_bf16x8*>(pa + oa);
                 fal[t] = *reinterpret_cast<const dense_bf16x8*>(pa + (oa ^ 64));
                 fbh[t] = *reinterpret_cast<const dense_bf16x8*>(pb + ob);
@@ -214,102 +190,9 @@ __global__ __launch_bounds__(256, 2) void dense_bf16x3_gemm_kernel(const float* 
             if (kc + 1 < nkc) sstore(buf ^ 1);
             __syncthreads();
         }
-        if constexpr (MODE == DENSE_FILTER) {
-            if (tid < DENSE_TILE) s_thr[tid] = (qt + tid < nq) ? thr[qt + tid] : INFINITY;
-            __syncthreads();
-        }
-#pragma unroll
-        for (int b = 0; b < NT; ++b) {
-            const int64_t j = j0 + wc * 64 + b * TM + col;
-            const bool jv = j < nrows;
-#pragma unroll
-            for (int a = 0; a < NT; ++a)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int qo = wr * 64 + a * TM + 4 * grp + r;
-                    dense_emit<MODE, TM>(acc[a][b][r], j, jv, qt + qo, nq, MODE == DENSE_FILTER ? s_thr[qo] : 0.f, nrows, out, cnt,
-                                         cand, l);
-                }
-        }
+        const float* s_thr = dense_screen_stage_thr<MODE>(sa, nkc, thr, qt, nq, tid);
+        dense_screen_epilogue<MODE>(acc, j0, wr, wc, col, grp, qt, nq, s_thr, nrows, out, cnt, cand, l);
         __syncthreads();                                           // the next query tile overwrites buffer 0 and s_thr
-    }
-}
-
-// grid: (nq, ADC_CAND_CAP / 256) blocks of 256 threads; one lane per candidate key of query blockIdx.x.  The key's score half
-// (the screen's s~) is replaced by the chain: literal fmaf calls, d ascending, one accumulator.  VEC: 16-byte aligned rows.
-template <bool VEC>
-__global__ __launch_bounds__(256) void dense_bf16x3_rescore_kernel(const float* __restrict__ x, int64_t ldx, int D,
-                                                                   const float* __restrict__ q,
-                                                                   const unsigned* __restrict__ cnt,
-                                                                   unsigned long long* __restrict__ cand) {
-    __shared__ float sq[DENSE_B3_RESCORE_QCHUNK];
-    const int qi = blockIdx.x, tid = threadIdx.x;
-    const unsigned raw = cnt[qi];
-    const unsigned n = raw > ADC_CAND_CAP ? ADC_CAND_CAP : raw;
-    if (blockIdx.y * 256u >= n) return;                                // block-uniform
-    const unsigned i = blockIdx.y * 256u + tid;
-    const bool mine = i < n;
-    unsigned long long* kp = cand + (size_t)qi * ADC_CAND_CAP + i;
-    const unsigned row = mine ? 0xFFFFFFFFu - (unsigned)(*kp & 0xFFFFFFFFull) : 0u;
-    const float* xp = x + (int64_t)row * ldx;
-    const float* qp = q + (int64_t)qi * D;
-    float s = 0.f;
-    for (int d0 = 0; d0 < D; d0 += DENSE_B3_RESCORE_QCHUNK) {
-        const int dn = D - d0 < DENSE_B3_RESCORE_QCHUNK ? D - d0 : DENSE_B3_RESCORE_QCHUNK;
-        __syncthreads();
-        for (int d = tid; d < dn; d += 256) sq[d] = qp[d0 + d];
-        __syncthreads();
-        if (mine) {
-            int d = 0;
-            if constexpr (VEC) {
-                for (; d + 8 <= dn; d += 8) {
-                    float v[8];
-                    dense_load8(xp + d0 + d, v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) s = __builtin_fmaf(sq[d + e], v[e], s);
-                }
-            }
-            for (; d < dn; ++d) s = __builtin_fmaf(sq[d], xp[d0 + d], s);
-        }
-    }
-    if (mine) *kp = adc_exact_key(s, (int64_t)row);
-}
-
-// grid: nq blocks of 64 threads.  Sets bit2 of status / qstatus[q] unless t >= thr~ + E_q is proven (header comment): the norm,
-// E_q and the sum are evaluated in fp64 and pushed upwards by more than their rounding errors; a NaN or inf anywhere, a query
-// value whose bf16 rounding is infinite (|v| >= 2^128 - 2^119) or D > 65536 is "not certified".
-__global__ __launch_bounds__(64) void dense_bf16x3_certify_kernel(const float* __restrict__ q, int D, int k,
-                                                                  const float* __restrict__ thr,
-                                                                  const float* __restrict__ xnorm_max,
-                                                                  const float* __restrict__ scores, int* __restrict__ status,
-                                                                  int* __restrict__ qstatus) {
-    const int qi = blockIdx.x, lane = threadIdx.x;
-    const float* qp = q + (int64_t)qi * D;
-    double ss = 0.0;
-    int wide = 0;
-    for (int d = lane; d < D; d += 64) {
-        const float f = qp[d];
-        wide |= (__float_as_uint(f) & 0x7FFFFFFFu) >= 0x7F7F8000u;
-        const double v = (double)f;
-        ss += v * v;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ss += __shfl_xor(ss, o);
-        wide |= __shfl_xor(wide, o);
-    }
-    if (lane != 0) return;
-    const double up = 1.0 + 0x1p-30;
-    const double dpad = (double)((D + 15) / 16 * 16);
-    const double qn = sqrt(ss) * up, X = (double)xnorm_max[0] * up;
-    const double eq = ((DENSE_B3_C_SUM * dpad * 0x1p-24 + DENSE_B3_C_SPLIT * 0x1p-16) * qn * X * up +
-                       DENSE_B3_C_SUB * sqrt(dpad) * up * (qn + X) + DENSE_B3_C_UNDER * dpad) * up;
-    const double sum = (double)thr[qi] + eq;
-    const double bound = sum + fabs(sum) * 0x1p-30;
-    const double t = (double)scores[(size_t)qi * k + (k - 1)];
-    if (wide || D > DENSE_B3_MAX_D || !(t >= bound)) {
-        atomicOr(status, 4);
-        if (qstatus) atomicOr(qstatus + qi, 4);
     }
 }
 
@@ -340,6 +223,31 @@ static int dense_b3_launch_gemm(rc_handle_t h, const float* x, int64_t ldx, int6
     return RC_OK;
 }
 
+// The certificate refuses a query value whose bf16 rounding is infinite (|v| >= 2^128 - 2^119; inf and NaN with it) and D > 65536.
+struct dense_b3_variant {
+    typedef float T;
+    typedef __bf16 Q;
+    static constexpr bool approximate = true;
+    static size_t extra_ws_bytes(int nq, int D) { return dense_b3_split_bytes(nq, D); }
+    static int prepass(rc_handle_t h, const float* q, int nq, int D, char* tail, const Q** qs, hipStream_t s) {
+        *qs = (const __bf16*)tail;                       // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
+        return dense_b3_launch_split(h, q, nq, D, (__bf16*)tail, s);
+    }
+    template <int MODE, typename... A>
+    static int launch_gemm(A... a) { return dense_b3_launch_gemm<MODE>(a...); }
+    static constexpr auto* exact = &dense_exact_f32;
+    __device__ static bool refuse(float v, int D) {
+        return (__float_as_uint(v) & 0x7FFFFFFFu) >= 0x7F7F8000u || D > DENSE_B3_MAX_D;
+    }
+    __device__ static double eq(int D, double ss, double xnorm) {
+        const double up = 1.0 + 0x1p-30;
+        const double dpad = (double)((D + 15) / 16 * 16);
+        const double qn = sqrt(ss) * up, X = xnorm * up;
+        return ((DENSE_B3_C_SUM * dpad * 0x1p-24 + DENSE_B3_C_SPLIT * 0x1p-16) * qn * X * up +
+                DENSE_B3_C_SUB * sqrt(dpad) * up * (qn + X) + DENSE_B3_C_UNDER * dpad) * up;
+    }
+};
+
 extern "C" void rc_dense_bf16x3_error_constants(double* c) {
     c[0] = DENSE_B3_C_SUM;
     c[1] = DENSE_B3_C_SPLIT;
@@ -348,8 +256,7 @@ extern "C" void rc_dense_bf16x3_error_constants(double* c) {
 }
 
 extern "C" size_t rc_dense_bf16x3_search_ws_bytes(int64_t N, int D, int nq, int k) {
-    if (!dense_shape_ok(N, D, nq, k)) return 0;
-    return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total + dense_b3_split_bytes(nq, D);
+    return dense_search_ws_bytes<dense_b3_variant>(N, D, nq, k);
 }
 
 extern "C" size_t rc_dense_bf16x3_scores_ws_bytes(int D, int nq) {
@@ -378,34 +285,6 @@ extern "C" int rc_dense_bf16x3_search_q(rc_handle_t h, const float* x, int64_t l
     if (!status || !xnorm_max) return RC_EINVAL;
     if (nq == 0) return RC_OK;
     if (!ws || ((uintptr_t)ws & 15u) || ws_bytes < rc_dense_bf16x3_search_ws_bytes(N, D, nq, k)) return RC_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    if (dense_exact_route(N)) return dense_exact(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, dense_exact_ws(N, nq), s);
-    const dense_fast_layout L = dense_fast_ws(N, nq);
-    char* w = (char*)ws;
-    float* sample = (float*)(w + L.sample);
-    float* thr = (float*)(w + L.thr);
-    unsigned* cnt = (unsigned*)(w + L.cnt);
-    unsigned long long* cand = (unsigned long long*)(w + L.cand);
-    __bf16* qs = (__bf16*)(w + L.total);
-    int rc = dense_b3_launch_split(h, q, nq, D, qs, s);
-    if (rc != RC_OK) return rc;
-    rc = dense_b3_launch_gemm<DENSE_STORE>(h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
-    if (rc != RC_OK) return rc;
-    rc = rc_adc_launch_threshold(h, sample, L.S, nq, rc_adc_sample_rank(N, L.S, k, sel_slack), thr, s);
-    if (rc != RC_OK) return rc;
-    RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
-    rc = dense_b3_launch_gemm<DENSE_FILTER>(h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
-    if (rc != RC_OK) return rc;
-    const dim3 rgrid((unsigned)nq, ADC_CAND_CAP / 256);
-    if (ldx % 4 == 0 && !((uintptr_t)x & 15u))
-        hipLaunchKernelGGL(dense_bf16x3_rescore_kernel<true>, rgrid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
-    else
-        hipLaunchKernelGGL(dense_bf16x3_rescore_kernel<false>, rgrid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
-    RC_LAUNCH_CHECK(h);
-    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, scores, ids, status, s, qstatus);
-    if (rc != RC_OK) return rc;
-    hipLaunchKernelGGL(dense_bf16x3_certify_kernel, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, thr, xnorm_max, scores, status,
-                       qstatus);
-    RC_LAUNCH_CHECK(h);
-    return RC_OK;
+    return dense_search_route<dense_b3_variant>(h, x, ldx, N, D, q, nq, xnorm_max, k, id_offset, sel_slack, scores, ids, status,
+                                                qstatus, (char*)ws, (hipStream_t)stream);
 }

@@ -57,6 +57,8 @@ class FlatIPIndex:
         self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
         # float16 storage / bf16x3 screen: device fp32 [1] >= the largest row norm held (the search's certificate)
         self._xnorm_max = None
+        self._search = ops.dense_search_f16 if storage == "float16" else ops.dense_search_bf16x3 if screen == "bf16x3" \
+            else ops.dense_search
 
     @property
     def xb(self) -> torch.Tensor:
@@ -122,14 +124,9 @@ class FlatIPIndex:
             scores = torch.full((q.shape[0], k), float("-inf"), dtype=torch.float32, device=self.device)
             ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
             pending = ops.PendingSearch(None, scores, ids, None, None, 0.0, 0)
-        elif self.storage == "float16":
-            pending = ops.dense_search_f16(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
-                                           xnorm_max=self._xnorm_max)
-        elif self.screen == "bf16x3":
-            pending = ops.dense_search_bf16x3(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
-                                              xnorm_max=self._xnorm_max)
         else:
-            pending = ops.dense_search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True)
+            norm = {} if self._search is ops.dense_search else {"xnorm_max": self._xnorm_max}
+            pending = self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True, **norm)
         self.last_search = pending           # .stats: queries repeated / answered by the exact route
 
         def finish():

@@ -6,6 +6,7 @@ all arithmetic happens in librepconc_hip.so.  CPU tensors are rejected: there is
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 from typing import Optional, Tuple
 
@@ -892,10 +893,33 @@ def _dense_args(x: torch.Tensor, q: torch.Tensor, k: int):
     return x, q
 
 
-def dense_search_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
-    """The same answer as `dense_search` by the route that cannot fail (rc_dense_search_exact): full score rows and a radix
-    select of the min(k, N) best keys."""
-    x, q = _dense_args(x, q, k)
+def _dense_f16_args(x16: torch.Tensor, q: torch.Tensor, k: int):
+    _need_cuda(x16, q)
+    if x16.dim() != 2 or q.dim() != 2 or x16.shape[1] != q.shape[1]:
+        raise ValueError("dense search: x [N, D] and q [nq, D] with the same D")
+    if x16.dtype != torch.float16:
+        raise ValueError("dense_search_f16: the corpus must be float16 (FlatIPIndex(storage='float16') rounds and checks it)")
+    if not 1 <= int(k) <= DENSE_MAX_K:
+        raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
+    if x16.stride(1) != 1 or (x16.shape[1] % 16 == 0 and (x16.stride(0) % 8 != 0 or x16.data_ptr() % 16 != 0)):
+        x16 = x16.clone(memory_format=torch.contiguous_format)      # a strided or misaligned view: a fresh allocation is aligned
+    if x16.shape[0] >= 1 << 32:
+        raise ValueError("dense search: N must be < 2^32")
+    q16 = q.to(x16.device).to(torch.float16).contiguous()           # round to nearest even, as the corpus was
+    return x16, q16
+
+
+# One dense search in three variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
+# library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes; exact: rc_<exact>_search_exact / ..._ws_bytes, the route that
+# cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate).
+_DenseVariant = collections.namedtuple("_DenseVariant", "args entry exact normed")
+_DENSE_F32 = _DenseVariant(_dense_args, "dense", "dense", False)
+_DENSE_F16 = _DenseVariant(_dense_f16_args, "dense_f16", "dense_f16", True)
+_DENSE_BF16X3 = _DenseVariant(_dense_args, "dense_bf16x3", "dense", True)
+
+
+def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int):
+    x, q = v.args(x, q, k)
     N, D = x.shape
     nq = q.shape[0]
     lib, h, s, _ = _ctx(q)
@@ -905,46 +929,51 @@ def dense_search_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int 
         scores.fill_(float("-inf"))
         ids.fill_(-1)
         return scores, ids
-    wsb = lib.rc_dense_search_exact_ws_bytes(N, D, nq, int(k))
+    name = f"rc_{v.exact}_search_exact"
+    wsb = getattr(lib, name + "_ws_bytes")(N, D, nq, int(k))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-    _lib.check(lib.rc_dense_search_exact(h, _p(x), x.stride(0), N, D, _p(q), nq, int(k), int(id_offset), _p(scores), _p(ids),
-                                         _p(ws), wsb, s), "rc_dense_search_exact", h)
+    _lib.check(getattr(lib, name)(h, _p(x), x.stride(0), N, D, _p(q), nq, int(k), int(id_offset), _p(scores), _p(ids),
+                                  _p(ws), wsb, s), name, h)
     return scores, ids
 
 
-def dense_search(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
-                 defer: bool = False, method: str = "auto", max_retries: int = 2):
-    """Exact top-k inner-product search of `q` [nq, D] against the fp32 corpus `x` [N, D] (faiss.IndexFlatIP,
-    evaluate_dense.py:84-129).  Returns (scores [nq, k] fp32, ids [nq, k] int64 = row + id_offset), sorted (score desc, id
-    asc); -inf / -1 past N.  Scores are the fp32 fmaf chain over d ascending (include/repconc_hip.h), bit for bit.
-    method="exact": the exact route only.  defer: a `PendingSearch` (queries the sampled threshold fails are repeated, then
-    answered by the exact route; `.stats`).  Query sets larger than DENSE_QCHUNK are split into several library calls."""
+def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int, sel_slack: Optional[float],
+                  defer: bool, method: str, max_retries: int, xnorm_max: Optional[torch.Tensor] = None):
     if method not in ("auto", "exact"):
         raise ValueError("method must be 'auto' or 'exact'")
-    x, q = _dense_args(x, q, k)
+    x, q = v.args(x, q, k)
     if sel_slack is None:
         sel_slack = DENSE_SEL_SLACK
     N, D = x.shape
     nq = q.shape[0]
     if method == "exact" or nq == 0 or N == 0:
-        got = dense_search_exact(x, q, k, id_offset)
+        got = _dense_search_exact(v, x, q, k, id_offset)
         return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
     lib, h, _, dev = _ctx(q)
+    norm = ()                                 # the tensors behind the entry's extra pointer arguments
+    if v.normed:
+        if xnorm_max is None:
+            # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the norm
+            xnorm_max = dense_xnorm_max(x) if N > DENSE_EXACT_MAX_N else torch.zeros((1,), dtype=torch.float32, device=x.device)
+        _need_cuda(xnorm_max)
+        norm = (xnorm_max.to(torch.float32).reshape(1),)
+    name = f"rc_{v.entry}_search_q"
+    search_q, ws_bytes = getattr(lib, name), getattr(lib, f"rc_{v.entry}_search_ws_bytes")
 
     def launch(qq, slack, out_s, out_i, status, qstatus):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for c0 in range(0, qq.shape[0], DENSE_QCHUNK):
             n = min(DENSE_QCHUNK, qq.shape[0] - c0)
-            wsb = lib.rc_dense_search_ws_bytes(N, D, n, int(k))
+            wsb = ws_bytes(N, D, n, int(k))
             ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)     # released in stream order
-            _lib.check(lib.rc_dense_search_q(h, _p(x), x.stride(0), N, D, _p(qq[c0:c0 + n]), n, int(k), int(id_offset),
-                                             float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]), _p(status),
-                                             _p(qstatus[c0:c0 + n]), _p(ws), wsb, st), "rc_dense_search_q", h)
+            _lib.check(search_q(h, _p(x), x.stride(0), N, D, _p(qq[c0:c0 + n]), n, *map(_p, norm), int(k), int(id_offset),
+                                float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]), _p(status), _p(qstatus[c0:c0 + n]),
+                                _p(ws), wsb, st), name, h)
 
     def rerun(idx, slack, exact):
         qq = q[idx].contiguous()
         if exact:
-            s_, i_ = dense_search_exact(x, qq, k, id_offset)
+            s_, i_ = _dense_search_exact(v, x, qq, k, id_offset)
             return s_, i_, None
         s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q.device)
         i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q.device)
@@ -964,6 +993,35 @@ def dense_search(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, s
     return pending if defer else pending.result()
 
 
+def dense_xnorm_max(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
+    """Device fp32 scalar [1] >= the largest Euclidean row norm of the floating-point matrix `x` of any dtype (fp64 sums,
+    rounded upwards; +inf if the norm exceeds fp32): the `xnorm_max` of `dense_search_bf16x3` and `dense_search_f16`.  No host
+    synchronisation."""
+    if not x.dtype.is_floating_point:
+        raise ValueError("dense_xnorm_max: a floating-point matrix")
+    best = torch.zeros((), dtype=torch.float64, device=x.device)
+    for r0 in range(0, x.shape[0], rows_per_step):
+        best = torch.maximum(best, x[r0:r0 + rows_per_step].double().square_().sum(1).max())
+    # the fp64 -> fp32 conversion rounds to nearest, by a factor of at most 1 + 2^-24: the 2^-20 covers it
+    return (best.sqrt() * (1.0 + 2.0 ** -20)).float().reshape(1)
+
+
+def dense_search_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+    """The same answer as `dense_search` by the route that cannot fail (rc_dense_search_exact): full score rows and a radix
+    select of the min(k, N) best keys."""
+    return _dense_search_exact(_DENSE_F32, x, q, k, id_offset)
+
+
+def dense_search(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
+                 defer: bool = False, method: str = "auto", max_retries: int = 2):
+    """Exact top-k inner-product search of `q` [nq, D] against the fp32 corpus `x` [N, D] (faiss.IndexFlatIP,
+    evaluate_dense.py:84-129).  Returns (scores [nq, k] fp32, ids [nq, k] int64 = row + id_offset), sorted (score desc, id
+    asc); -inf / -1 past N.  Scores are the fp32 fmaf chain over d ascending (include/repconc_hip.h), bit for bit.
+    method="exact": the exact route only.  defer: a `PendingSearch` (queries the sampled threshold fails are repeated, then
+    answered by the exact route; `.stats`).  Query sets larger than DENSE_QCHUNK are split into several library calls."""
+    return _dense_search(_DENSE_F32, x, q, k, id_offset, sel_slack, defer, method, max_retries)
+
+
 # --------------------------------------------------------------------------------------------------- dense, fp16 storage
 def dense_f16_error_constant() -> float:
     """The factor of E_q as the certificate kernel was compiled with it (DENSE_F16_ERR_C, csrc/dense_search_f16.hip)."""
@@ -979,48 +1037,12 @@ def dense_f16_error_bound(D: int, qnorm, xmax):
     return dense_f16_error_constant() * dpad * 2.0 ** -24 * qnorm * xmax
 
 
-def dense_f16_xnorm_max(x16: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
-    """Device fp32 scalar [1] >= the largest Euclidean row norm of the fp16 matrix `x16` (fp64 sums, rounded upwards); the
-    `xnorm_max` of `dense_search_f16`.  No host synchronisation."""
-    best = torch.zeros((), dtype=torch.float64, device=x16.device)
-    for r0 in range(0, x16.shape[0], rows_per_step):
-        best = torch.maximum(best, x16[r0:r0 + rows_per_step].double().square_().sum(1).max())
-    return (best.sqrt() * (1.0 + 2.0 ** -20)).float().reshape(1)
-
-
-def _dense_f16_args(x16: torch.Tensor, q: torch.Tensor, k: int):
-    _need_cuda(x16, q)
-    if x16.dim() != 2 or q.dim() != 2 or x16.shape[1] != q.shape[1]:
-        raise ValueError("dense search: x [N, D] and q [nq, D] with the same D")
-    if x16.dtype != torch.float16:
-        raise ValueError("dense_search_f16: the corpus must be float16 (FlatIPIndex(storage='float16') rounds and checks it)")
-    if not 1 <= int(k) <= DENSE_MAX_K:
-        raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
-    if x16.stride(1) != 1 or (x16.shape[1] % 16 == 0 and (x16.stride(0) % 8 != 0 or x16.data_ptr() % 16 != 0)):
-        x16 = x16.clone(memory_format=torch.contiguous_format)      # a strided or misaligned view: a fresh allocation is aligned
-    if x16.shape[0] >= 1 << 32:
-        raise ValueError("dense search: N must be < 2^32")
-    q16 = q.to(x16.device).to(torch.float16).contiguous()           # round to nearest even, as the corpus was
-    return x16, q16
+dense_f16_xnorm_max = dense_xnorm_max      # the `xnorm_max` of `dense_search_f16`
 
 
 def dense_search_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
     """The same answer as `dense_search_f16` by the route that cannot fail (rc_dense_f16_search_exact)."""
-    x16, q16 = _dense_f16_args(x16, q, k)
-    N, D = x16.shape
-    nq = q16.shape[0]
-    lib, h, s, _ = _ctx(q16)
-    scores = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
-    if nq == 0 or N == 0:
-        scores.fill_(float("-inf"))
-        ids.fill_(-1)
-        return scores, ids
-    wsb = lib.rc_dense_f16_search_exact_ws_bytes(N, D, nq, int(k))
-    ws = torch.empty((wsb,), dtype=torch.uint8, device=q16.device)
-    _lib.check(lib.rc_dense_f16_search_exact(h, _p(x16), x16.stride(0), N, D, _p(q16), nq, int(k), int(id_offset), _p(scores),
-                                             _p(ids), _p(ws), wsb, s), "rc_dense_f16_search_exact", h)
-    return scores, ids
+    return _dense_search_exact(_DENSE_F16, x16, q, k, id_offset)
 
 
 def dense_f16_scores(x16: torch.Tensor, q16: torch.Tensor) -> torch.Tensor:
@@ -1046,70 +1068,10 @@ def dense_search_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int 
     it cannot be given: such queries are repeated, then answered by the exact route — `.stats` of the `PendingSearch`).
     xnorm_max: device fp32 [1], >= the largest row norm of x16 (`dense_f16_xnorm_max`, computed here when None).
     Everything else as `dense_search`."""
-    if method not in ("auto", "exact"):
-        raise ValueError("method must be 'auto' or 'exact'")
-    x16, q16 = _dense_f16_args(x16, q, k)
-    if sel_slack is None:
-        sel_slack = DENSE_SEL_SLACK
-    N, D = x16.shape
-    nq = q16.shape[0]
-    if method == "exact" or nq == 0 or N == 0:
-        got = dense_search_f16_exact(x16, q16, k, id_offset)
-        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
-    lib, h, _, dev = _ctx(q16)
-    if xnorm_max is None:
-        xnorm_max = dense_f16_xnorm_max(x16)
-    _need_cuda(xnorm_max)
-    xnorm_max = xnorm_max.to(torch.float32).reshape(1)
-
-    def launch(qq, slack, out_s, out_i, status, qstatus):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for c0 in range(0, qq.shape[0], DENSE_QCHUNK):
-            n = min(DENSE_QCHUNK, qq.shape[0] - c0)
-            wsb = lib.rc_dense_f16_search_ws_bytes(N, D, n, int(k))
-            ws = torch.empty((wsb,), dtype=torch.uint8, device=q16.device)     # released in stream order
-            _lib.check(lib.rc_dense_f16_search_q(h, _p(x16), x16.stride(0), N, D, _p(qq[c0:c0 + n]), n, _p(xnorm_max), int(k),
-                                                 int(id_offset), float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]),
-                                                 _p(status), _p(qstatus[c0:c0 + n]), _p(ws), wsb, st),
-                       "rc_dense_f16_search_q", h)
-
-    def rerun(idx, slack, exact):
-        qq = q16[idx].contiguous()
-        if exact:
-            s_, i_ = dense_search_f16_exact(x16, qq, k, id_offset)
-            return s_, i_, None
-        s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q16.device)
-        i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q16.device)
-        status = torch.zeros((1,), dtype=torch.int32, device=q16.device)
-        qs = torch.zeros((qq.shape[0],), dtype=torch.int32, device=q16.device)
-        launch(qq, slack, s_, i_, status, qs)
-        return s_, i_, qs
-
-    _warm_retry_ops(q16.device)
-    scores = torch.empty((nq, k), dtype=torch.float32, device=q16.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=q16.device)
-    status = torch.zeros((1,), dtype=torch.int32, device=q16.device)
-    qstatus = torch.zeros((nq,), dtype=torch.int32, device=q16.device)
-    launch(q16, float(sel_slack), scores, ids, status, qstatus)
-    pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
-                            stream=torch.cuda.current_stream(dev))
-    return pending if defer else pending.result()
+    return _dense_search(_DENSE_F16, x16, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max)
 
 
 # ------------------------------------------------------------------------------------ dense, fp32 corpus, bf16x3 screen
-def dense_xnorm_max(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
-    """Device fp32 scalar [1] >= the largest Euclidean row norm of the floating-point matrix `x` of any dtype (fp64 sums,
-    rounded upwards; +inf if the norm exceeds fp32): the `xnorm_max` of `dense_search_bf16x3` and `dense_search_f16`.  No host
-    synchronisation."""
-    if not x.dtype.is_floating_point:
-        raise ValueError("dense_xnorm_max: a floating-point matrix")
-    best = torch.zeros((), dtype=torch.float64, device=x.device)
-    for r0 in range(0, x.shape[0], rows_per_step):
-        best = torch.maximum(best, x[r0:r0 + rows_per_step].double().square_().sum(1).max())
-    # the fp64 -> fp32 conversion rounds to nearest, by a factor of at most 1 + 2^-24: the 2^-20 covers it
-    return (best.sqrt() * (1.0 + 2.0 ** -20)).float().reshape(1)
-
-
 def dense_bf16x3_error_constants():
     """(c_sum, c_split, c_sub, c_under) of E_q as the certificate kernel was compiled with them (csrc/dense_search_bf16x3.hip)."""
     c = (C.c_double * 4)()
@@ -1151,52 +1113,4 @@ def dense_search_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int
     a query with a non-finite value or one that rounds to a bf16 inf: such queries are repeated, then answered by
     `dense_search_exact`; `.stats` of the `PendingSearch`).  xnorm_max: device fp32 [1], >= the largest row norm of x
     (`dense_xnorm_max`, computed here when None).  Everything else as `dense_search`."""
-    if method not in ("auto", "exact"):
-        raise ValueError("method must be 'auto' or 'exact'")
-    x, q = _dense_args(x, q, k)
-    if sel_slack is None:
-        sel_slack = DENSE_SEL_SLACK
-    N, D = x.shape
-    nq = q.shape[0]
-    if method == "exact" or nq == 0 or N == 0:
-        got = dense_search_exact(x, q, k, id_offset)
-        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
-    lib, h, _, dev = _ctx(q)
-    if xnorm_max is None:
-        # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the norm
-        xnorm_max = dense_xnorm_max(x) if N > DENSE_EXACT_MAX_N else torch.zeros((1,), dtype=torch.float32, device=x.device)
-    _need_cuda(xnorm_max)
-    xnorm_max = xnorm_max.to(torch.float32).reshape(1)
-
-    def launch(qq, slack, out_s, out_i, status, qstatus):
-        st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        for c0 in range(0, qq.shape[0], DENSE_QCHUNK):
-            n = min(DENSE_QCHUNK, qq.shape[0] - c0)
-            wsb = lib.rc_dense_bf16x3_search_ws_bytes(N, D, n, int(k))
-            ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)     # released in stream order
-            _lib.check(lib.rc_dense_bf16x3_search_q(h, _p(x), x.stride(0), N, D, _p(qq[c0:c0 + n]), n, _p(xnorm_max), int(k),
-                                                    int(id_offset), float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]),
-                                                    _p(status), _p(qstatus[c0:c0 + n]), _p(ws), wsb, st),
-                       "rc_dense_bf16x3_search_q", h)
-
-    def rerun(idx, slack, exact):
-        qq = q[idx].contiguous()
-        if exact:
-            s_, i_ = dense_search_exact(x, qq, k, id_offset)
-            return s_, i_, None
-        s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q.device)
-        i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q.device)
-        status = torch.zeros((1,), dtype=torch.int32, device=q.device)
-        qs = torch.zeros((qq.shape[0],), dtype=torch.int32, device=q.device)
-        launch(qq, slack, s_, i_, status, qs)
-        return s_, i_, qs
-
-    _warm_retry_ops(q.device)
-    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
-    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
-    status = torch.zeros((1,), dtype=torch.int32, device=q.device)
-    qstatus = torch.zeros((nq,), dtype=torch.int32, device=q.device)
-    launch(q, float(sel_slack), scores, ids, status, qstatus)
-    pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
-                            stream=torch.cuda.current_stream(dev))
-    return pending if defer else pending.result()
+    return _dense_search(_DENSE_BF16X3, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max)

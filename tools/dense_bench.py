@@ -47,24 +47,31 @@ def report(path, n, d, batch, nq):
     rows = list(csv.DictReader(open(path)))
     ms = lambda r: float(r["TotalDurationNs"]) / 1e6
     # the search's own kernels (the corpus generation and host copies of the run are not part of a search)
-    # rocprofv3 leaves the template kernels mangled (_Z21dense_f16_gemm_kernelILi1ELb0ELb1EE...) and demangles the plain ones
-    search = [r for r in rows if any(t in r["Name"] for t in ("dense_gemm_kernel", "dense_f16_", "dense_bf16x3_", "adc_threshold_kernel", "adc_select_kernel", "adc_exact_"))]
+    # rocprofv3 leaves the template kernels mangled (_Z21dense_f16_gemm_kernelILi1ELb0EE...) and demangles the plain ones: a
+    # kernel is found by its name and, where variants share it, one of the two spellings of the template argument that tells
+    # them apart (dense_rescore_kernel / dense_certify_kernel, csrc/dense_screen.h, serve both screened searches)
+    def hit(r, kernel, *targs):
+        _, found, rest = r["Name"].partition(kernel)
+        return bool(found) and (not targs or any(t in rest for t in targs))
+    search = [r for r in rows if any(hit(r, t) for t in ("dense_gemm_kernel", "dense_f16_", "dense_bf16x3_", "dense_rescore_kernel",
+                                                         "dense_certify_kernel", "adc_threshold_kernel", "adc_select_kernel",
+                                                         "adc_exact_"))]
     tot = sum(ms(r) for r in search)
-    has32 = any("dense_gemm_kernel<1" in r["Name"] or "dense_gemm_kernelILi1E" in r["Name"] for r in search)
-    has16 = any("dense_f16_gemm_kernel<1" in r["Name"] or "dense_f16_gemm_kernelILi1E" in r["Name"] for r in search)
-    hasb3 = any("dense_bf16x3_gemm_kernel<1" in r["Name"] or "dense_bf16x3_gemm_kernelILi1E" in r["Name"] for r in search)
+    has32 = any(hit(r, "dense_gemm_kernel", "<1", "ILi1E") for r in search)
+    has16 = any(hit(r, "dense_f16_gemm_kernel", "<1", "ILi1E") for r in search)
+    hasb3 = any(hit(r, "dense_bf16x3_gemm_kernel", "<1", "ILi1E") for r in search)
     out = {}
     if has32 + has16 + hasb3 > 1:
         out["mixed_legs"] = True
     if hasb3:
         b3 = {}
         for r in search:
-            for key, tags in (("screen", ("dense_bf16x3_gemm_kernel<1", "dense_bf16x3_gemm_kernelILi1E")),
-                              ("sample", ("dense_bf16x3_gemm_kernel<0", "dense_bf16x3_gemm_kernelILi0E")),
-                              ("split", ("dense_bf16x3_split_kernel",)), ("rescore", ("dense_bf16x3_rescore",)),
-                              ("certify", ("dense_bf16x3_certify_kernel",)), ("select", ("adc_select_kernel",)),
+            for key, tags in (("screen", ("dense_bf16x3_gemm_kernel", "<1", "ILi1E")),
+                              ("sample", ("dense_bf16x3_gemm_kernel", "<0", "ILi0E")),
+                              ("split", ("dense_bf16x3_split_kernel",)), ("rescore", ("dense_rescore_kernel", "float>", "EfE")),
+                              ("certify", ("dense_certify_kernel", "dense_b3_variant")), ("select", ("adc_select_kernel",)),
                               ("threshold", ("adc_threshold_kernel",))):
-                if any(tag in r["Name"] for tag in tags):
+                if hit(r, *tags):
                     b3[key + "_ms_total"] = b3.get(key + "_ms_total", 0.0) + ms(r)
                     b3[key + "_calls"] = b3.get(key + "_calls", 0) + int(r["Calls"])
         b3["screened_queries"] = queries
@@ -79,7 +86,7 @@ def report(path, n, d, batch, nq):
                 b3[key + "_ms_per_1200_queries"] = b3.get(key + "_ms_total", 0.0) * 1200 / queries
         out["bf16x3"] = b3
     if has32:
-        r = next(r for r in search if "dense_gemm_kernel<1" in r["Name"] or "dense_gemm_kernelILi1E" in r["Name"])
+        r = next(r for r in search if hit(r, "dense_gemm_kernel", "<1", "ILi1E"))
         out["screen_calls"] = int(r["Calls"])
         out["screen_ms_each"] = float(r["AverageNs"]) / 1e6
         out["screen_ms_total"] = ms(r)
@@ -94,11 +101,12 @@ def report(path, n, d, batch, nq):
     if has16:
         f16 = {}
         for r in search:
-            for key, tags in (("screen", ("dense_f16_gemm_kernel<1", "dense_f16_gemm_kernelILi1E")),
-                              ("sample", ("dense_f16_gemm_kernel<0", "dense_f16_gemm_kernelILi0E")),
-                              ("rescore", ("dense_f16_rescore_kernel",)), ("certify", ("dense_f16_certify_kernel",)),
+            for key, tags in (("screen", ("dense_f16_gemm_kernel", "<1", "ILi1E")),
+                              ("sample", ("dense_f16_gemm_kernel", "<0", "ILi0E")),
+                              ("rescore", ("dense_rescore_kernel", "_Float16>", "EDF16_E")),
+                              ("certify", ("dense_certify_kernel", "dense_f16_variant")),
                               ("select", ("adc_select_kernel",)), ("threshold", ("adc_threshold_kernel",))):
-                if any(tag in r["Name"] for tag in tags):
+                if hit(r, *tags):
                     f16[key + "_ms_total"] = f16.get(key + "_ms_total", 0.0) + ms(r)
                     f16[key + "_calls"] = f16.get(key + "_calls", 0) + int(r["Calls"])
         f16["screened_queries"] = queries
