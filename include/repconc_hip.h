@@ -55,8 +55,15 @@ extern "C" {
 #define RC_FLAG_COMM 4      /* IPC transport: a peer's signal did not arrive within RC_IPC_TIMEOUT_MS (default 600000): */
                             /* the wait gave up instead of hanging the GPU; the codes of this call are garbage       */
 #define RC_FLAG_RANGE 2     /* |(L + f) N/ln2| left the range the sweep's integer split  */
-                            /* covers (eps < ~3e-4 on centred distances: the reference's */
-                            /* own exp(1/eps) overflows fp64 long before, at eps < 1.4e-3) */
+                            /* covers: eps < ~3e-4 on centred distances — or, at any eps, a row potential that is already NaN,   */
+                            /* then together with RC_FLAG_NONFINITE.                                                           */
+/* The band in eps (tests/test_sinkhorn_strain.py).  Exact parity with the reference's codes is promised for     */
+/* eps >= 0.003.  The reference's plan starts as exp(-d/eps)/tot with centred distances reaching +-1, so its smallest entries     */
+/* are subnormal or zero once 2/eps + ln(B K) > ~708 (eps < ~0.00288 at B K = 2^18; its exp(1/eps) overflows only at eps <       */
+/* 1.4e-3): below that its codes depend on its own underflow.  There this library returns the codes of the same iteration in      */
+/* potentials (log) form, which loses no single entry, with flags 0 — unless a whole COLUMN underflows (every exp(L + f) of a row  */
+/* of x is 0: max_k (L + f) < -745, e.g. one far outlier row at eps < ~0.0027), which is the reference's NaN warning case and is  */
+/* reported as RC_FLAG_NONFINITE (| RC_FLAG_RANGE from the next sweep on); the codes are then in range and repeatable, no more.  */
 
 typedef struct rc_handle_s* rc_handle_t;
 typedef void* rc_stream_t;

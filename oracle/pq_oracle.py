@@ -198,10 +198,18 @@ def codes_equal_up_to_fp64_ties(got: np.ndarray, want: np.ndarray, Q: np.ndarray
     return ok, len(bad)
 
 
-def sinkhorn_codes_logdomain(dc: np.ndarray, epsilon: float, iters: int) -> np.ndarray:
+def sinkhorn_codes_logdomain(dc: np.ndarray, epsilon: float, iters: int, return_scores: bool = False):
     """Same codes as quantize(use_constraint=True) computed with potentials instead of the
     in-place matrix (the formulation the HIP kernels use).  Used by the
-    tests as an independent cross-check of the algebra, not as the parity oracle."""
+    tests as an independent cross-check of the algebra, not as the parity oracle — except
+    below the reference's underflow edge (2/eps + ln(B K) > ~708), where the
+    reference's own codes depend on which of its plan entries became subnormal or zero and this
+    form, which loses no single entry that matters to a column, is what the HIP path is held to.
+    It is NOT free of underflow per column: a column whose best exp(L + f + g) is 0 in the first
+    normalisation (max_k (L + f) < -745, a far outlier row at eps < ~0.0027) has c = 0 and the
+    scores returned here are then not finite, as the reference's plan is not.
+    return_scores: also return the final scores L + f [M,B,K] (log of the plan up to a per-column
+    constant), so that a caller can tell a different code from a tie."""
     L = -(dc.astype(F64)) / epsilon                                     # [M,B,K]
     M, B, K = L.shape
     f = -np.log(np.exp(L).sum(axis=1))                                  # pass 0, g=0  [M,K]
@@ -211,7 +219,9 @@ def sinkhorn_codes_logdomain(dc: np.ndarray, epsilon: float, iters: int) -> np.n
         c = w.sum(axis=2)
         g = g - np.log(c)
         f = f - np.log((w / c[:, :, None]).sum(axis=1))
-    return np.argmax(L + f[:, None, :], axis=-1).T.copy()
+    S = L + f[:, None, :]
+    codes = np.argmax(S, axis=-1).T.copy()
+    return (codes, S) if return_scores else codes
 
 
 # --------------------------------------------------------------------------- a-6
