@@ -248,7 +248,8 @@ int rc_pq_assign_sinkhorn_dist(rc_handle_t h, const float* x, int64_t ldx, const
 /* ------------------------------------------------------------------ a-6
  * decode (modeling_repconc.py:168-175): out[n, m*dsub:(m+1)*dsub] = C[m, codes[n,m], :], and
  * its gradient w.r.t. C (autograd of the gather at :175): grad_C[m,codes[n,m],:] += grad_out[n,m,:].
- * code_dtype: RC_CODE_U8 or RC_CODE_I64; codes are [n, M] row-major. */
+ * code_dtype: RC_CODE_U8 or RC_CODE_I64; codes are [n, M] row-major.
+ * Only the low 8 bits of an int64 code are read (code & 255): no code can index outside the table. */
 int rc_pq_decode(rc_handle_t h, const void* codes, int code_dtype, const float* C, int64_t n,
                  int M, int K, int dsub, float* out, rc_stream_t stream);
 int rc_pq_decode_bwd(rc_handle_t h, const void* codes, int code_dtype, const float* grad_out,
@@ -261,7 +262,7 @@ int rc_normalize_centroids(rc_handle_t h, float* C, int M, int K, int dsub, rc_s
 /* ------------------------------------------------------------------ a-13
  * hist[m,k] = #{n : codes[n,m]==k} — eval_balance's 256 `.sum().item()` round trips
  * (models/repconc/finetune_repconc.py:588-592) for all sub-quantisers in one launch.
- * hist: [M,K] int32, overwritten. */
+ * hist: [M,K] int32, overwritten.  Only the low 8 bits of an int64 code are read (code & 255). */
 int rc_code_hist(rc_handle_t h, const void* codes, int code_dtype, int64_t n, int M, int K,
                  int32_t* hist, rc_stream_t stream);
 

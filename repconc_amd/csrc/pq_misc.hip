@@ -280,7 +280,9 @@ __global__ __launch_bounds__(256) void normalize_kernel(float* __restrict__ C, i
     float* p = C + r * dsub;
     float s = 0.f;
     for (int j = 0; j < dsub; ++j) s = s + p[j] * p[j];
-    const float nrm = fmaxf(sqrtf(s), 1e-12f);
+    // fmaxf returns its other operand when one is NaN; F.normalize's clamp_min keeps the NaN (the whole row becomes NaN)
+    const float rt = sqrtf(s);
+    const float nrm = (rt != rt) ? rt : fmaxf(rt, 1e-12f);
     for (int j = 0; j < dsub; ++j) p[j] = p[j] / nrm;
 }
 

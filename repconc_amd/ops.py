@@ -54,6 +54,8 @@ def _centroids(c: torch.Tensor) -> torch.Tensor:
     c = c.detach()
     if c.dtype != torch.float32 or not c.is_contiguous():
         c = c.float().contiguous()
+    if c.data_ptr() % 16 != 0:                              # a contiguous view at an odd storage offset: the kernels load float4
+        c = c.clone()
     return c
 
 
@@ -493,16 +495,22 @@ def assign_sinkhorn_dist(x: torch.Tensor, centroids: torch.Tensor, eps: float, i
 
 # --------------------------------------------------------------------------- decode
 def decode_raw(codes: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
-    _need_cuda(codes, centroids)
-    c = _centroids(centroids)
-    M, _, dsub = c.shape
+    """out[n, m*dsub:(m+1)*dsub] = centroids[m, codes[n, m]].  Only the low 8 bits of an int64 code are read."""
+    if centroids.dim() != 3 or centroids.shape[1] != K:
+        raise ValueError("centroids must be [M, 256, dsub]")
+    M, _, dsub = centroids.shape
     if codes.dim() != 2 or codes.shape[1] != M:
         raise ValueError("codes must be [n, M]")
+    code_dtype = _code_dtype(codes)
+    _need_cuda(codes, centroids)
+    c = _centroids(centroids)
     codes = codes.contiguous()
     n = codes.shape[0]
     out = torch.empty((n, M * dsub), dtype=torch.float32, device=codes.device)
+    if n == 0:
+        return out
     lib, h, s, _ = _ctx(codes)
-    _lib.check(lib.rc_pq_decode(h, _p(codes), _code_dtype(codes), _p(c), n, M, K, dsub, _p(out), s),
+    _lib.check(lib.rc_pq_decode(h, _p(codes), code_dtype, _p(c), n, M, K, dsub, _p(out), s),
                "rc_pq_decode", h)
     return out
 
@@ -525,6 +533,8 @@ class _DecodeFn(torch.autograd.Function):
         go = grad_out.float().contiguous()
         gC = torch.zeros(ctx.cshape, dtype=torch.float32, device=go.device)
         codes = codes.contiguous()
+        if codes.shape[0] == 0:
+            return None, gC.to(ctx.cdtype)
         lib, h, s, _ = _ctx(go)
         _lib.check(lib.rc_pq_decode_bwd(h, _p(codes), _code_dtype(codes), _p(go), codes.shape[0], M, K, dsub,
                                         _p(gC), s), "rc_pq_decode_bwd", h)
@@ -550,30 +560,54 @@ def normalize_centroids_(centroids: torch.Tensor) -> torch.Tensor:
 
 def code_hist(codes: torch.Tensor) -> torch.Tensor:
     """hist [M, 256] int32.  finetune_repconc.py:588-592 for every sub-quantiser."""
+    if codes.dim() != 2 or codes.shape[1] < 1:
+        raise ValueError("codes must be [n, M]")
+    code_dtype = _code_dtype(codes)
     _need_cuda(codes)
     codes = codes.contiguous()
     n, M = codes.shape
+    if n == 0:
+        return torch.zeros((M, K), dtype=torch.int32, device=codes.device)
     hist = torch.empty((M, K), dtype=torch.int32, device=codes.device)
     lib, h, s, _ = _ctx(codes)
-    _lib.check(lib.rc_code_hist(h, _p(codes), _code_dtype(codes), n, M, K, _p(hist), s), "rc_code_hist", h)
+    _lib.check(lib.rc_code_hist(h, _p(codes), code_dtype, n, M, K, _p(hist), s), "rc_code_hist", h)
     return hist
+
+
+def _stats_buffers(sums: Optional[torch.Tensor], counts: Optional[torch.Tensor], cshape) -> None:
+    """The kernels read sums as fp64 [M, K, dsub] and counts as int64 [M, K] through raw pointers: anything else is an
+    out-of-bounds read, not a conversion."""
+    M, Kc, dsub = cshape
+    if sums is not None and (sums.dtype != torch.float64 or tuple(sums.shape) != (M, Kc, dsub) or not sums.is_contiguous()):
+        raise ValueError(f"sums must be contiguous fp64 [{M}, {Kc}, {dsub}]")
+    if counts is not None and (counts.dtype != torch.int64 or tuple(counts.shape) != (M, Kc) or not counts.is_contiguous()):
+        raise ValueError(f"counts must be contiguous int64 [{M}, {Kc}]")
 
 
 def kmeans_stats(x: torch.Tensor, codes: torch.Tensor, sums: Optional[torch.Tensor] = None,
                  counts: Optional[torch.Tensor] = None):
     """Accumulate Lloyd sufficient statistics (sums [M,K,dsub] fp64, counts [M,K] int64)."""
-    _need_cuda(x, codes)
-    x = _rows_f32(x)
+    if x.dim() != 2 or codes.dim() != 2 or codes.shape[1] < 1:
+        raise ValueError("expected x [n, D] and codes [n, M]")
     n, D = x.shape
     M = codes.shape[1]
+    if codes.shape[0] != n:
+        raise ValueError(f"codes has {codes.shape[0]} rows, x has {n}")
+    if D % M != 0:
+        raise ValueError(f"embedding width {D} is not a multiple of M = {M}")
+    dsub = D // M
+    _stats_buffers(sums, counts, (M, K, dsub))
+    _need_cuda(x, codes, sums, counts)
+    x = _rows_f32(x)
     if codes.dtype != torch.uint8:
         codes = codes.to(torch.uint8)
     codes = codes.contiguous()
-    dsub = D // M
     if sums is None:
         sums = torch.zeros((M, K, dsub), dtype=torch.float64, device=x.device)
     if counts is None:
         counts = torch.zeros((M, K), dtype=torch.int64, device=x.device)
+    if n == 0:
+        return sums, counts
     lib, h, s, _ = _ctx(x)
     _lib.check(lib.rc_kmeans_stats(h, _p(x), x.stride(0), _p(codes), n, D, M, K, _p(sums), _p(counts), s),
                "rc_kmeans_stats", h)
@@ -581,6 +615,14 @@ def kmeans_stats(x: torch.Tensor, codes: torch.Tensor, sums: Optional[torch.Tens
 
 
 def kmeans_update_(sums: torch.Tensor, counts: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """centroids[m, k] <- fp32(sums[m, k] / counts[m, k]) where counts[m, k] > 0, unchanged otherwise; in place."""
+    if centroids.dim() != 3 or centroids.shape[1] != K:
+        raise ValueError("centroids must be [M, 256, dsub]")
+    if centroids.dtype != torch.float32 or not centroids.is_contiguous():
+        raise ValueError("centroids must be contiguous fp32")
+    if sums is None or counts is None:
+        raise ValueError("sums and counts are required")
+    _stats_buffers(sums, counts, tuple(centroids.shape))
     _need_cuda(sums, counts, centroids)
     M, Kc, dsub = centroids.shape
     lib, h, s, _ = _ctx(centroids)
