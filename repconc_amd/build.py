@@ -3,6 +3,7 @@ plain C-ABI shared object (include/repconc_hip.h).
 
     python -m repconc_amd.build [--force]
 """
+import glob
 import os
 import subprocess
 import sys
@@ -36,8 +37,8 @@ def _stale(target, deps):
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(LIBDIR, exist_ok=True)
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, "rc_common.h"), os.path.join(CSRC, "topk.h"), os.path.join(CSRC, "adc_common.h"), os.path.join(CSRC, "dense_gemm.h"), os.path.join(CSRC, "dense_screen.h"), os.path.join(CSRC, "ivfs_screen16.h"),
-               os.path.join(os.path.dirname(HERE), "include", "repconc_hip.h")]
+    # every header is a dependency of every source: a new csrc/*.h cannot leave stale objects behind
+    headers = sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(os.path.dirname(HERE), "include", "repconc_hip.h")]
     objs, jobs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

@@ -1,8 +1,9 @@
-// Shared pieces of the flat ADC search (adc_search.hip) and the list-centric IVF search (ivf_lists.hip, ivfs_screen16.h) that are
-// about ADC tables and codes: limits, the conflict-free slot rule, the 16-query slot rule, the 8-bit quantiser, the IVF task
-// list, the exact rescoring kernel and the supported-width predicates.  The selection stage (score keys, k-th largest, the
-// candidate-list limits, top-k host interface) is topk.h.  Device functions and templates only (no -fgpu-rdc: every
-// translation unit compiles its own copy).
+// Shared pieces of the flat ADC search (adc_search.hip) and the list-centric IVF search (ivf_lists.hip, ivfs_*.h) that are
+// about ADC tables and codes: limits, the supported widths, the conflict-free slot rule, the 16-query slot rule, the 8-bit
+// quantiser with the per-query table summary and its record, the IVF task list, the exact rescoring kernel and the launcher of
+// the image kernels.  The selection stage (score keys, k-th largest, the
+// candidate-list limits, top-k host interface) is topk.h.  Device functions, templates and static host helpers only (no -fgpu-rdc:
+// every translation unit compiles its own copy).
 #pragma once
 #include "topk.h"
 #include <limits.h>
@@ -11,7 +12,22 @@
 #define ADC_TILE_DOCS 32768
 #define ADC_SCREEN_MIN_N (1 << 18)
 #define ADC_ID_CAP 32768
-#define ADC_QSTAT_STRIDE 128          // floats per query: lo[0..M), doubles B at [122] and A at [124] (adc_screen_tint), delta at [127]
+
+// widths M with a permuted code image: the 16-query flat screen and the list-centric IVF search are compiled for exactly these
+// (every list below is generated from this one)
+#define ADC_CF_WIDTHS(X) X(16) X(32) X(48) X(64) X(96)
+__host__ __device__ constexpr bool adc_cf_supported(int M) {
+#define ADC_CF_IS(MM) || M == MM
+    return false ADC_CF_WIDTHS(ADC_CF_IS);
+#undef ADC_CF_IS
+}
+__host__ __device__ constexpr int adc_cf_max_width() {
+    int w = 0;
+#define ADC_CF_MAX(MM) w = MM > w ? MM : w;
+    ADC_CF_WIDTHS(ADC_CF_MAX)
+#undef ADC_CF_MAX
+    return w;
+}
 
 // ---- conflict-free slot rule (round 2; today the table phases of the IVF screen, ivf_lists.hip) ------------------
 // The sum over sub-quantisers is commutative, so the lanes of a wave need not visit them in the same order: byte tables are
@@ -93,6 +109,49 @@ __device__ __forceinline__ int adc_screen_tint(float t, double A, double B, floa
     return v < -2.0e9 ? INT_MIN : (v > 2.0e9 ? INT_MAX : (int)v);
 }
 
+// The summary of a query's tables: from lo_m, hi_m - lo_m and max(|lo_m|, |hi_m|) of its M sub-quantisers the step delta and the
+// sums A and B above (in double, m ascending).  Called by ONE thread of the kernels that reduce the tables (adc_qlut_kernel,
+// adc_qstats_kernel, ivfs_qprep_kernel).
+struct adc_table_sums {
+    float delta;
+    double A, B;
+};
+__device__ __forceinline__ adc_table_sums adc_table_summary(const float* lo, const float* range, const float* absmax, int M) {
+    float maxrange = 0.f;
+    adc_table_sums s = {0.f, 0.0, 0.0};
+    for (int m = 0; m < M; ++m) {
+        maxrange = fmaxf(maxrange, range[m]);
+        s.A += (double)lo[m];
+        s.B += (double)absmax[m];
+    }
+    s.delta = adc_screen_delta(maxrange);
+    return s;
+}
+__device__ __forceinline__ int adc_screen_tint(float t, const adc_table_sums& s, int M) {
+    return adc_screen_tint(t, s.A, s.B, s.delta, M);
+}
+// The qstat record of a query (adc_qstats_kernel, ivfs_qprep_kernel): ADC_QSTAT_STRIDE floats, lo_m at [m], m < M, and the
+// summary in the record's last six: B (a double) at [122], A (a double) at [124], delta at [127]
+#define ADC_QSTAT_STRIDE 128
+#define ADC_QSTAT_B (ADC_QSTAT_STRIDE - 6)
+#define ADC_QSTAT_A (ADC_QSTAT_STRIDE - 4)
+#define ADC_QSTAT_DELTA (ADC_QSTAT_STRIDE - 1)
+static_assert(adc_cf_max_width() <= ADC_QSTAT_B, "the lo_m of the widest compiled M leave the A / B / delta fields free");
+static_assert(ADC_QSTAT_B % 2 == 0 && ADC_QSTAT_A % 2 == 0 && ADC_QSTAT_B + 2 <= ADC_QSTAT_A && ADC_QSTAT_A + 2 <= ADC_QSTAT_DELTA,
+              "aligned doubles that overlap nothing");
+__device__ __forceinline__ float* adc_qstat_of(float* qstat, int qi) { return qstat + (size_t)qi * ADC_QSTAT_STRIDE; }
+__device__ __forceinline__ const float* adc_qstat_of(const float* qstat, int qi) { return qstat + (size_t)qi * ADC_QSTAT_STRIDE; }
+__device__ __forceinline__ float adc_qstat_delta(const float* st) { return st[ADC_QSTAT_DELTA]; }
+__device__ __forceinline__ void adc_qstat_put_summary(float* st, const adc_table_sums& s) {
+    st[ADC_QSTAT_DELTA] = s.delta;
+    *reinterpret_cast<double*>(st + ADC_QSTAT_A) = s.A;
+    *reinterpret_cast<double*>(st + ADC_QSTAT_B) = s.B;
+}
+__device__ __forceinline__ adc_table_sums adc_qstat_summary(const float* st) {
+    return adc_table_sums{st[ADC_QSTAT_DELTA], *reinterpret_cast<const double*>(st + ADC_QSTAT_A),
+                          *reinterpret_cast<const double*>(st + ADC_QSTAT_B)};
+}
+
 typedef int adc_i32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned adc_u32x2v __attribute__((ext_vector_type(2)));
 
@@ -104,7 +163,7 @@ __host__ __device__ constexpr int adc_q16_pos(int h32) {
 }
 __host__ __device__ constexpr int adc_q16_slot(int lane, int j) { return (adc_q16_pos(lane & 31) + j + 4 * (lane >> 5)) & 15; }
 
-// Tasks of the list-centric IVF search: a task = (coarse cell, up to 8 of the queries that probe it)
+// Tasks of the list-centric IVF search: a task = (coarse cell, up to 8 | 16 of the queries that probe it: the screen's width)
 struct adc_ivf_tasks {
     const int* task_list;        // [tasks] cell of the task
     const int* task_qstart;      // [tasks] first entry of the task's queries in sorted_q
@@ -234,4 +293,19 @@ __global__ __launch_bounds__(1024) void adc_rescore_kernel(const uint8_t* __rest
 static inline bool adc_search_supported(int M) {
     return M == 8 || M == 12 || M == 16 || M == 24 || M == 32 || M == 48 || M == 64 || M == 96;
 }
-static inline bool adc_cf_supported(int M) { return M == 16 || M == 32 || M == 48 || M == 64 || M == 96; }
+
+// (Re)build rows [n0, n0 + n) of a permuted code image from the canonical codes [N, M]: the one launcher of the three image
+// kernels (rc_adc_scan_image: the flat search's; rc_adc_scan_image_rows / _rows16: the IVF screens')
+typedef void (*adc_image_kernel_t)(const uint8_t*, int64_t, int64_t, int, uint8_t*);
+static int adc_launch_image(rc_handle_t h, adc_image_kernel_t kern, const uint8_t* codes, int64_t n0, int64_t n, int M,
+                            uint8_t* image, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (!h || !codes || !image || n0 < 0 || n < 0) return RC_EINVAL;
+    if (!adc_cf_supported(M)) return RC_ESHAPE;
+    if (n == 0) return RC_OK;
+    int64_t blocks = (n * M + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, codes, n0, n, M, image);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}

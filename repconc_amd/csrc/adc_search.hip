@@ -198,12 +198,11 @@ __global__ __launch_bounds__(ADC_THREADS) void adc_scan_kernel(const uint8_t* __
 __global__ __launch_bounds__(RC_K) void adc_qlut_kernel(const float* __restrict__ lut, const float* __restrict__ thr,
                                                         int M, int QS, uint8_t* __restrict__ qlut,
                                                         int* __restrict__ tint) {
-    __shared__ float lo_m[128], ab_m[128];
+    __shared__ float lo_m[128], rng_m[128], ab_m[128];
     __shared__ float red_lo[4], red_hi[4];
     __shared__ float s_delta;
     const int qi = blockIdx.x, c = threadIdx.x;
     const float* lq = lut + (size_t)qi * M * RC_K;
-    float maxrange = 0.f;
     for (int m = 0; m < M; ++m) {
         const float v = lq[m * RC_K + c];
         float lo = v, hi = v;
@@ -216,16 +215,13 @@ __global__ __launch_bounds__(RC_K) void adc_qlut_kernel(const float* __restrict_
         __syncthreads();
         lo = fminf(fminf(red_lo[0], red_lo[1]), fminf(red_lo[2], red_lo[3]));
         hi = fmaxf(fmaxf(red_hi[0], red_hi[1]), fmaxf(red_hi[2], red_hi[3]));
-        if (c == 0) { lo_m[m] = lo; ab_m[m] = fmaxf(fabsf(lo), fabsf(hi)); }
-        maxrange = fmaxf(maxrange, hi - lo);
+        if (c == 0) { lo_m[m] = lo; rng_m[m] = hi - lo; ab_m[m] = fmaxf(fabsf(lo), fabsf(hi)); }
         __syncthreads();
     }
     if (c == 0) {
-        const float delta = adc_screen_delta(maxrange);
-        s_delta = delta;
-        double A = 0.0, B = 0.0;
-        for (int m = 0; m < M; ++m) { A += (double)lo_m[m]; B += (double)ab_m[m]; }
-        tint[qi] = adc_screen_tint(thr[qi], A, B, delta, M);
+        const adc_table_sums sums = adc_table_summary(lo_m, rng_m, ab_m, M);
+        s_delta = sums.delta;
+        tint[qi] = adc_screen_tint(thr[qi], sums, M);
     }
     __syncthreads();
     const float delta = s_delta;
@@ -480,7 +476,7 @@ __global__ __launch_bounds__(RC_K) void adc_qstats_kernel(const float* __restric
             hi = fmaxf(hi, __shfl_xor(hi, o));
         }
         if (lane == 0) {
-            qstat[(size_t)qi * ADC_QSTAT_STRIDE + m] = lo;
+            adc_qstat_of(qstat, qi)[m] = lo;
             s_lo[m] = lo;
             s_rng[m] = hi - lo;
             s_abs[m] = fmaxf(fabsf(lo), fabsf(hi));
@@ -488,16 +484,9 @@ __global__ __launch_bounds__(RC_K) void adc_qstats_kernel(const float* __restric
     }
     __syncthreads();
     if (c == 0) {
-        float maxrange = 0.f;
-        double A = 0.0, B = 0.0;
-        for (int m = 0; m < M; ++m) {
-            maxrange = fmaxf(maxrange, s_rng[m]);
-            A += (double)s_lo[m];
-            B += (double)s_abs[m];
-        }
-        const float delta = adc_screen_delta(maxrange);
-        qstat[(size_t)qi * ADC_QSTAT_STRIDE + ADC_QSTAT_STRIDE - 1] = delta;
-        tint[qi] = adc_screen_tint(thr[qi], A, B, delta, M);
+        const adc_table_sums sums = adc_table_summary(s_lo, s_rng, s_abs, M);
+        adc_qstat_of(qstat, qi)[ADC_QSTAT_DELTA] = sums.delta;     // (the flat search needs no A / B later: tint is made here)
+        tint[qi] = adc_screen_tint(thr[qi], sums, M);
     }
 }
 
@@ -584,9 +573,8 @@ __global__ __launch_bounds__(1024) void adc_qlut16_write_kernel(const float* __r
 #pragma unroll
     for (int qq = 0; qq < 16; ++qq) {
         if (qq < nv) {
-            const int q = 16 * G + qq;
-            const unsigned l = adc_quant8(v[qq], qstat[(size_t)q * ADC_QSTAT_STRIDE + m],
-                                          qstat[(size_t)q * ADC_QSTAT_STRIDE + ADC_QSTAT_STRIDE - 1]);
+            const float* st = adc_qstat_of(qstat, 16 * G + qq);
+            const unsigned l = adc_quant8(v[qq], st[m], adc_qstat_delta(st));
             w[qq >> 2] = (w[qq >> 2] & ~(0xFFu << (8 * (qq & 3)))) | ((l ^ 0x80u) << (8 * (qq & 3)));
         }
     }
@@ -1003,15 +991,7 @@ extern "C" int rc_adc_cf_describe(int M, int lane, int step, int* slot, int* m, 
 // codes [N, M] (both pointers = row 0 of the index): rc_adc_scan_image_bytes(N, M) bytes
 extern "C" int rc_adc_scan_image(rc_handle_t h, const uint8_t* codes, int64_t n0, int64_t n, int M, uint8_t* image,
                                  rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (!h || !codes || !image || n0 < 0 || n < 0) return RC_EINVAL;
-    if (!adc_cf_supported(M)) return RC_ESHAPE;
-    if (n == 0) return RC_OK;
-    int64_t blocks = (n * M + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(adc_q16_image_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, codes, n0, n, M, image);
-    RC_LAUNCH_CHECK(h);
-    return RC_OK;
+    return adc_launch_image(h, adc_q16_image_kernel, codes, n0, n, M, image, stream);
 }
 // host-side description of the 16-query screen's layout (tests): slot read by `lane` in step j, or RC_ESHAPE
 extern "C" int rc_adc_q16_describe(int M, int lane, int step, int* slot) {
@@ -1051,8 +1031,8 @@ static int adc_launch_scans(rc_handle_t h, const uint8_t* codes, const uint8_t* 
         return RC_OK;
     }
     RC_HIP_CHECK(h, hipMemsetAsync(b.idcnt, 0, (size_t)nq * sizeof(unsigned), s));
-    // Screen variant: 8 queries per gather on the matrix cores (tables in LDS: one pass for M <= 64, two half-table
-    // phases above); M % 8 != 0 and the A/B switches RC_ADC_VALU_SCREEN / RC_ADC_ONE_PHASE use the older kernels.
+    // Screen variant: widths with an image (ADC_CF_WIDTHS) run the 16-query screen on it; without an image (M = 8, 24, or
+    // RC_ADC_OLD_SCREEN) the round-1 matrix-core screen on the canonical codes; M % 8 != 0 and RC_ADC_VALU_SCREEN the VALU one.
     const bool valu_screen = rc_env_set("RC_ADC_VALU_SCREEN");
     auto screen = [&](auto kern, int QS, size_t sl) -> int {
         hipLaunchKernelGGL(adc_qlut_kernel, dim3((unsigned)nq), dim3(RC_K), 0, s, b.lut, b.thr, M, QS, b.qlut, b.tint);
@@ -1067,7 +1047,7 @@ static int adc_launch_scans(rc_handle_t h, const uint8_t* codes, const uint8_t* 
     };
     constexpr int QS1 = (M <= 64) ? 8 : 4;                  // one-pass kernels: M * 256 * QS bytes of LDS
     int src = RC_OK;
-    constexpr bool CF = (M == 16 || M == 32 || M == 48 || M == 64 || M == 96);
+    constexpr bool CF = adc_cf_supported(M);
     if (CF && image != nullptr) {
         if constexpr (CF) {
             // 16 queries per ds_read_b128 gather, phases of 16 sub-quantisers, double-buffered tables (adc_screen_q16_kernel)

@@ -1,4 +1,5 @@
-// 16-query form of the pipelined IVF screen (round 6; included by ivf_lists.hip after ivfs_* / adc_ivf_tasks are defined).
+// 16-query form of the pipelined IVF screen (round 6; included by ivf_lists.hip; what it shares with the 8-query form,
+// ivfs_screen8.h, is ivfs_common.h).
 //
 // The 8-query screen (ivfs_screen_kernel) gathers with ds_read_b64: 8 queries per gather at ~5 cycles per gather in the real
 // kernel, and its loader waves need as long for a 64 KiB table phase (2.4-3.1 us) as the twelve gathering waves for its
@@ -17,6 +18,8 @@
 //     128-byte window, and a code's row is 256 B: lanes that stored "entry i of my item" together would hit two windows' worth of
 //     banks four times over.  Lane l therefore stores entry (j + (l >> 1)) mod 4 in step j — eight distinct 16-byte slots per
 //     group — and gets that rotation for free: the selector of the first transposition step is a per-lane register.
+#include "ivfs_common.h"
+
 #define IVFS16_R 10              // chunks of 16 rows per gathering wave and round
 typedef unsigned adc_u32x4s __attribute__((ext_vector_type(4)));
 
@@ -54,8 +57,7 @@ extern "C" int rc_debug_ivfs16_trace(unsigned long long* host) {
 struct ivfs_task16 {
     int valid;
     int qs, qc;               // the task's queries: sorted_q[qs .. qs + qc), 1 <= qc <= 16
-    unsigned t0;              // first (16-aligned) row of the range
-    unsigned row_lo, nrows;   // rows [row_lo, nrows) counted from t0 are the cell's (nrows = 0: nothing to scan)
+    ivfs_rows rows;
 };
 
 template <int M, int LW>
@@ -71,39 +73,23 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
     constexpr int NPH = M / 16, ROUND = GW * R * 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const unsigned tid = threadIdx.x;
-    const int l = (int)(tid & 63u), wv = __builtin_amdgcn_readfirstlane((int)(tid >> 6)), r = l & 15, g = l >> 4;
-    // ---- this block's tasks (as in the 8-query screen: XCD x owns a contiguous eighth of the cell-ordered list)
-    const unsigned total = (unsigned)__builtin_amdgcn_readfirstlane(T.ntasks ? *T.ntasks : ntasks_arg);
-    const unsigned xcd = blockIdx.x % 8u, jb = blockIdx.x / 8u, pxb = (gridDim.x - xcd + 7u) / 8u;
-    const unsigned tq8 = total / 8u, tr8 = total % 8u;
-    const unsigned lo = xcd < tr8 ? xcd * (tq8 + 1u) : tr8 * (tq8 + 1u) + (xcd - tr8) * tq8, cnt = tq8 + (xcd < tr8 ? 1u : 0u);
+    const int l = (int)(tid & 63u), wv = __builtin_amdgcn_readfirstlane((int)(tid >> 6)), r = l & 15;
+    const ivfs_share share = ivfs_block_share(T, ntasks_arg);
     auto load_task = [&](unsigned k) {
         ivfs_task16 d;
-        const unsigned at = jb + k * pxb;
-        d.valid = at < cnt ? 1 : 0;
-        d.qs = 0; d.qc = 0; d.t0 = 0; d.row_lo = 0; d.nrows = 0;
+        unsigned task;
+        d.valid = ivfs_share_task(share, k, task) ? 1 : 0;
+        d.qs = 0; d.qc = 0;
+        d.rows = ivfs_rows{0u, 0u, 0u};
         if (d.valid) {
-            auto sc = [](int v) { return __builtin_amdgcn_readfirstlane(v); };
-            const unsigned task = lo + at;
-            d.qs = sc(T.task_qstart[task]);
-            d.qc = sc(T.task_qcnt[task]);
-            const int cell = sc(T.task_list[task]);
-            const unsigned a = (unsigned)sc((int)T.list_off[cell]), b = (unsigned)sc((int)T.list_off[cell + 1]);   // N < 2^32
-            if (d.qc > 0 && b > a) {
-                const unsigned t0 = a & ~15u;
-                d.t0 = t0; d.row_lo = a - t0; d.nrows = b - t0;
-            }
+            d.qs = ivfs_sc(T.task_qstart[task]);
+            d.qc = ivfs_sc(T.task_qcnt[task]);
+            d.rows = ivfs_cell_rows(T, ivfs_sc(T.task_list[task]), d.qc);
         }
         return d;
     };
-    auto rounds_of = [&](const ivfs_task16& d) { return d.nrows ? (int)((d.nrows + ROUND - 1) / ROUND) : 1; };
     auto lane_q = [&](const ivfs_task16& d) { return (r < d.qc) ? T.sorted_q[d.qs + r] : -1; };
-    auto lane_thr = [&](int q) {
-        if (q < 0) return INT_MAX;
-        const int t = tint[q];
-        return (t == INT_MIN) ? INT_MIN : t - 128 * M;
-    };
-    // ---- tables: phase p16 of a task, by threads t = 0 .. NTHR - 1 (t = this thread's number), in two halves so that a loader
+    // ---- tables: phase p16 of a task, in two halves (request, then transpose and store) so that a loader
     // can request a phase one stage before it transposes it (the loads' ~1 us from the L2 / memory-side cache is then nobody's
     // critical path: with request, wait, transposition and stores inside one stage the four loader waves needed ~3 us per 64 KiB
     // phase and set the stage period — the 16-query gathers, half as many per query, gained 2 %)
@@ -117,39 +103,28 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
 #pragma unroll
         for (int j = 0; j < 16; ++j) so[j] = (unsigned)__builtin_amdgcn_readlane(qv, j) * (unsigned)(M * RC_K);
     };
-    auto fill_load = [&](auto NTHRc, int p16, const unsigned (&so)[16], unsigned t, auto& a) {
-        constexpr unsigned NTHR = decltype(NTHRc)::value;
-        constexpr int ITEMS = 1024 / NTHR;                    // items (code, quad of sub-quantisers) per thread
-        static_assert(1024 % NTHR == 0 && NTHR % 64 == 0, "whole items per thread, whole waves");
+    // The prologue's form (all 1024 threads): thread = item (code c, quad u), one dword per query
+    auto fill_load = [&](int p16, const unsigned (&so)[16], unsigned (&a)[16]) {
         const int y = p16 >> 1, hh = p16 & 1;
         const unsigned PM = (unsigned)ivfs_pm(M, y);          // the byte tables are stored in phases of 32 (last one: 16)
+        const unsigned c = tid >> 2, u = tid & 3u;
+        const unsigned voff = (unsigned)(RC_K * 32 * y) + c * PM + 16u * (unsigned)hh + 4u * u;
 #pragma unroll
-        for (int it = 0; it < ITEMS; ++it) {
-            const unsigned item = (unsigned)it * NTHR + t, c = item >> 2, u = item & 3u;
-            const unsigned voff = (unsigned)(RC_K * 32 * y) + c * PM + 16u * (unsigned)hh + 4u * u;
-#pragma unroll
-            for (int j = 0; j < 16; ++j) a[it][j] = __builtin_amdgcn_raw_buffer_load_b32(qrsrc, voff, so[j], 0);
-        }
+        for (int j = 0; j < 16; ++j) a[j] = __builtin_amdgcn_raw_buffer_load_b32(qrsrc, voff, so[j], 0);
     };
-    auto fill_store = [&](auto NTHRc, unsigned bufoff, unsigned t, const auto& a) {
-        constexpr unsigned NTHR = decltype(NTHRc)::value;
-        constexpr int ITEMS = 1024 / NTHR;
+    auto fill_store = [&](unsigned bufoff, const unsigned (&a)[16]) {
 #pragma unroll
-        for (int it = 0; it < ITEMS; ++it) {
-            const unsigned item = (unsigned)it * NTHR + t;
+        for (int j = 0; j < 4; ++j) {
+            const unsigned i = ((unsigned)j + rot) & 3u;                      // the entry this lane stores in step j
+            const unsigned sel = ((4u + i) << 8) | i;                        // (a_even.b_i, a_odd.b_i, -, -)
+            adc_u32x4s e;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const unsigned i = ((unsigned)j + rot) & 3u;                      // the entry this lane stores in step j
-                const unsigned sel = ((4u + i) << 8) | i;                        // (a_even.b_i, a_odd.b_i, -, -)
-                adc_u32x4s e;
-#pragma unroll
-                for (int gq = 0; gq < 4; ++gq) {
-                    const unsigned p01 = __builtin_amdgcn_perm(a[it][4 * gq + 1], a[it][4 * gq], sel);
-                    const unsigned p23 = __builtin_amdgcn_perm(a[it][4 * gq + 3], a[it][4 * gq + 2], sel);
-                    e[gq] = __builtin_amdgcn_perm(p23, p01, 0x05040100u);      // queries 4 gq .. 4 gq + 3 of entry (c, 4 u + i)
-                }
-                *reinterpret_cast<adc_u32x4s*>(smem + (bufoff + item * 64u + i * 16u)) = e;
+            for (int gq = 0; gq < 4; ++gq) {
+                const unsigned p01 = __builtin_amdgcn_perm(a[4 * gq + 1], a[4 * gq], sel);
+                const unsigned p23 = __builtin_amdgcn_perm(a[4 * gq + 3], a[4 * gq + 2], sel);
+                e[gq] = __builtin_amdgcn_perm(p23, p01, 0x05040100u);      // queries 4 gq .. 4 gq + 3 of entry (c, 4 u + i)
             }
+            *reinterpret_cast<adc_u32x4s*>(smem + (bufoff + tid * 64u + i * 16u)) = e;
         }
     };
     // The loader waves' form (256 threads): thread = code c, all four quads in ONE 16-byte load per query — 16 load instructions per
@@ -190,16 +165,8 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
             }
         }
     };
-    // ---- codes of one stage: chunk c of wave wv is chunk GW c + wv of the round; one dword per lane and chunk
-    auto chunks_of = [&](unsigned nrows, int rd) {            // chunks this wave owns in round rd (wave-uniform, 0 .. R)
-        const unsigned done = (unsigned)rd * ROUND;
-        if (nrows <= done) return 0;
-        unsigned nc = (nrows - done + 15u) / 16u;
-        if (nc > (unsigned)(ROUND / 16)) nc = ROUND / 16;
-        if (wv >= GW) return 0;                                // a loader wave
-        const int mine = ((int)nc - wv + GW - 1) / GW;
-        return mine < 0 ? 0 : mine;
-    };
+    // ---- codes of one stage: the wave's chunks of the round (ivfs_chunks_of); one dword per lane and chunk
+    auto chunks_of = [&](unsigned nrows, int rd) { return ivfs_chunks_of<GW, R>(nrows, rd, wv); };
     auto load_codes = [&](int p16, unsigned t0, unsigned nrows, int rd, unsigned (&w)[R]) {
         const int reff = chunks_of(nrows, rd);
         if (reff == 0) return;
@@ -241,12 +208,7 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
 #pragma unroll
         for (int c = 0; c < R; ++c) {
             if (c < reff) {                                   // wave-uniform
-#if IVFS_PRIO
-                if (c == 0) __builtin_amdgcn_s_setprio(3);
-                else if (c == R / 4) __builtin_amdgcn_s_setprio(2);
-                else if (c == R / 2) __builtin_amdgcn_s_setprio(1);
-                else if (c == 3 * R / 4) __builtin_amdgcn_s_setprio(0);
-#endif
+                ivfs_prio_at<R>(c);
                 __builtin_amdgcn_sched_barrier(0);
                 if (c + 1 < R && c + 1 < reff) gather(c + 1, (c & 1) ? ea : eb);
                 __builtin_amdgcn_sched_barrier(0);
@@ -254,78 +216,20 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
             }
         }
         __builtin_amdgcn_sched_barrier(0);
-#if IVFS_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
+        ivfs_prio_done();
     };
-    // ---- survivors: (query, row) pairs appended to the wave's own stream (see the 8-query screen); 16 query columns here
-    const __amdgpu_buffer_rsrc_t strsrc = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(stream + (size_t)(blockIdx.x * IVFS_WAVES + (unsigned)wv) * stream_cap * 2u), 0, -1, 0x00020000);
+    // ---- survivors: (query, row) pairs appended to the wave's own stream (ivfs_survivors); 16 query columns here
+    const __amdgpu_buffer_rsrc_t strsrc = ivfs_stream_rsrc(stream, stream_cap, wv);
     unsigned woff = 0;                                        // wave-uniform: pairs in the wave's stream
-    typedef unsigned u32x2s __attribute__((ext_vector_type(2)));
-    static_assert(R * 4 <= 64, "one mask bit per sum");
-    typedef typename std::conditional<(R * 4 <= 32), unsigned, unsigned long long>::type mask_t;
-    auto epilogue = [&](unsigned t0, unsigned row_lo, unsigned nrows, int rd, int tq, int myq, int reff) {
-        if (reff <= 0) return;
-        const unsigned rb = (unsigned)rd * ROUND + (unsigned)(wv * 16);      // first row of the wave's chunk 0
-        mask_t m = 0;                                         // bit 4 c + e: D[row 4 g + e of chunk c][column r] survives
-#pragma unroll
-        for (int c = 0; c < R; ++c) {
-            if (c < reff) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) m |= (acc[c][e] >= tq) ? ((mask_t)1 << (4 * c + e)) : (mask_t)0;
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < R; ++c) {
-            const unsigned cb = rb + (unsigned)(16 * GW * c);
-            if (c < reff && (cb < row_lo || cb + 16u > nrows)) {           // wave-uniform, rare: rows outside the cell
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const unsigned n = cb + 4u * g + e;
-                    if (n < row_lo || n >= nrows) m &= ~((mask_t)1 << (4 * c + e));
-                }
-            }
-        }
-        const unsigned cnt1 = (unsigned)__popcll((unsigned long long)m);
-        if (!__ballot(cnt1 != 0)) return;
-        const unsigned c0 = __shfl(cnt1, r), c1 = __shfl(cnt1, r + 16), c2 = __shfl(cnt1, r + 32), c3 = __shfl(cnt1, r + 48);
-        const unsigned tot = c0 + c1 + c2 + c3;
-        const unsigned lane_first = (g > 0 ? c0 : 0u) + (g > 1 ? c1 : 0u) + (g > 2 ? c2 : 0u);
-        unsigned inc = tot;                                   // inclusive prefix over the 16 query columns of the lane's row group
-#pragma unroll
-        for (int o = 1; o < 16; o <<= 1) {
-            const unsigned t = __shfl_up(inc, o, 16);
-            if (r >= o) inc += t;
-        }
-        const unsigned wtotal = (unsigned)__builtin_amdgcn_readlane((int)inc, 15);
-        if (woff + wtotal > stream_cap) {                     // wave-uniform; status bit 2: a stream filled up
-            if (l == 0) atomicOr(status, 4);
-            return;
-        }
-        unsigned at = (woff + (inc - tot) + lane_first) * 8u;
-        const unsigned row0 = t0 + rb + 4u * (unsigned)g;
-        while (__ballot(m != 0)) {                             // wave-uniform
-            if (m) {
-                const unsigned idx = (unsigned)__builtin_ctzll((unsigned long long)m);
-                m &= m - (mask_t)1;
-                const u32x2s v = {(unsigned)myq, row0 + (idx >> 2) * (unsigned)(16 * GW) + (idx & 3u)};
-                __builtin_amdgcn_raw_buffer_store_b64(v, strsrc, at, 0, 0);
-                at += 8u;
-            }
-        }
-        woff += wtotal;
-    };
-    auto block_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
 
     // ---- prologue: every thread takes one item of the first tables
     const ivfs_task16 first = load_task(0);
     if (!first.valid) return;                                 // block-uniform
     {
-        unsigned so[16], a0[1][16];
+        unsigned so[16], a0[16];
         task_offsets(first, so);
-        fill_load(std::integral_constant<unsigned, IVFS_THREADS>{}, 0, so, tid, a0);
-        fill_store(std::integral_constant<unsigned, IVFS_THREADS>{}, 0u, tid, a0);
+        fill_load(0, so, a0);
+        fill_store(0u, a0);
     }
     // ---- loader waves: their own walk over the stages, two stages ahead with the requests, one with the stores.  Exactly one
     // barrier per stage, as the gathering waves.
@@ -338,7 +242,7 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
             if (!p.d.valid) return n;
             if (++n.P == NPH) {
                 n.P = 0;
-                if (++n.rd == rounds_of(p.d)) { n.rd = 0; n.k = p.k + 1; n.d = load_task(n.k); }
+                if (++n.rd == ivfs_rounds_of<ROUND>(p.d.rows)) { n.rd = 0; n.k = p.k + 1; n.d = load_task(n.k); }
             }
             return n;
         };
@@ -352,9 +256,10 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
         pos p1 = next(pos{first, 0u, 0, 0});                   // the stage AFTER the one that is about to run
         if (p1.d.valid) request(p1);
         unsigned bufoff = (unsigned)IVFS_BUF;                   // where p1's tables go
-        unsigned sidx = 0;
+        unsigned sidx = 0;                                    // stage counter (trace builds only)
+        (void)sidx;
         for (;;) {
-            block_sync();                                     // a stage begins: everybody is done with the other buffer
+            ivfs_block_sync();                                // a stage begins: everybody is done with the other buffer
             IVFS16_TSTAMP(sidx, 0);
             if (!p1.d.valid) break;
             fill_store4(bufoff, lt, a);
@@ -368,67 +273,61 @@ __global__ __launch_bounds__(IVFS_THREADS, 4) void ivfs_screen16_kernel(const ui
         return;                                               // (its stream stays empty: stream_cnt was cleared by the host)
     }
     // ---- the gathering waves' walk over (task, round, phase) stages
-    auto walk = [&](auto ROLEc) {
-        constexpr bool LOADER = decltype(ROLEc)::value == 1;
-        ivfs_task16 cur = first;
-        int myq = -1, tq = INT_MAX;
-        unsigned w[R];
-        if constexpr (!LOADER) {
-            myq = lane_q(cur); tq = lane_thr(myq);
-            load_codes(0, cur.t0, cur.nrows, 0, w);
-        }
-        unsigned k = 0;
-        unsigned sidx = 0;                                    // stage counter (trace builds only)
-        (void)sidx;
-        for (;;) {                                            // tasks of this block
-            const ivfs_task16 nxt = load_task(k + 1);
-            const int nrounds = rounds_of(cur);
-            for (int rd = 0; rd < nrounds; ++rd) {
-                const bool more = rd + 1 < nrounds;           // block-uniform
-                auto stage = [&](auto Pc) {
-                    constexpr int P = decltype(Pc)::value;
-                    constexpr bool LASTP = (P == NPH - 1);
-                    constexpr int PN = LASTP ? 0 : P + 1;     // phase of the next stage
-                    block_sync();
-                    IVFS16_TSTAMP(sidx, 0);
-                    const bool to_next = LASTP && !more;      // block-uniform
-                    const bool has_next = !to_next || nxt.valid;
-                    const ivfs_task16 nd = to_next ? nxt : cur;
-                    const int nrd = to_next ? 0 : (LASTP ? rd + 1 : rd);
-                    {
-                        // the codes of the NEXT stage are requested before this stage's gathers, into a second set of ten
-                        // registers (the 8-query screen needs twenty per set and requests them after its last gather: every
-                        // stage then begins by waiting 0.7-1 us for them, profiles/r03g_ivf_timeline.txt)
-                        const int reff = chunks_of(cur.nrows, rd);
-                        unsigned wn[R];
-                        if (has_next) load_codes(PN, nd.t0, nd.nrows, nrd, wn);
-                        gathers(P == 0, w, reff);
-                        IVFS16_TSTAMP(sidx, 1);
-                        if constexpr (LASTP) epilogue(cur.t0, cur.row_lo, cur.nrows, rd, tq, myq, reff);
-                        if (has_next) {
+    ivfs_task16 cur = first;
+    int myq = lane_q(cur), tq = ivfs_lane_thr<M>(tint, myq);
+    unsigned w[R];
+    load_codes(0, cur.rows.t0, cur.rows.nrows, 0, w);
+    unsigned k = 0;
+    unsigned sidx = 0;                                        // stage counter (trace builds only)
+    (void)sidx;
+    for (;;) {                                                // tasks of this block
+        const ivfs_task16 nxt = load_task(k + 1);
+        const int nrounds = ivfs_rounds_of<ROUND>(cur.rows);
+        for (int rd = 0; rd < nrounds; ++rd) {
+            const bool more = rd + 1 < nrounds;               // block-uniform
+            auto stage = [&](auto Pc) {
+                constexpr int P = decltype(Pc)::value;
+                constexpr bool LASTP = (P == NPH - 1);
+                constexpr int PN = LASTP ? 0 : P + 1;         // phase of the next stage
+                ivfs_block_sync();
+                IVFS16_TSTAMP(sidx, 0);
+                const bool to_next = LASTP && !more;          // block-uniform
+                const bool has_next = !to_next || nxt.valid;
+                const ivfs_task16 nd = to_next ? nxt : cur;
+                const int nrd = to_next ? 0 : (LASTP ? rd + 1 : rd);
+                {
+                    // the codes of the NEXT stage are requested before this stage's gathers, into a second set of ten
+                    // registers (the 8-query screen needs twenty per set and requests them after its last gather: every
+                    // stage then begins by waiting 0.7-1 us for them, profiles/r03g_ivf_timeline.txt)
+                    const int reff = chunks_of(cur.rows.nrows, rd);
+                    unsigned wn[R];
+                    if (has_next) load_codes(PN, nd.rows.t0, nd.rows.nrows, nrd, wn);
+                    gathers(P == 0, w, reff);
+                    IVFS16_TSTAMP(sidx, 1);
+                    if constexpr (LASTP)
+                        ivfs_survivors<R, GW, 16>(acc, cur.rows, rd, tq, myq, reff, wv, l, stream_cap, status, strsrc, woff);
+                    if (has_next) {
 #pragma unroll
-                            for (int c = 0; c < R; ++c) w[c] = wn[c];
-                        }
-                        IVFS16_TSTAMP(sidx, 2);
-                        ++sidx;
+                        for (int c = 0; c < R; ++c) w[c] = wn[c];
                     }
+                    IVFS16_TSTAMP(sidx, 2);
+                    ++sidx;
+                }
 #pragma unroll
-                    for (int j = 0; j < 4; ++j) off[j] ^= (unsigned)IVFS_BUF;     // the other table buffer (64 KiB-aligned bases)
-                };
-                stage(std::integral_constant<int, 0>{});
-                if constexpr (NPH > 1) stage(std::integral_constant<int, 1>{});
-                if constexpr (NPH > 2) stage(std::integral_constant<int, 2>{});
-                if constexpr (NPH > 3) stage(std::integral_constant<int, 3>{});
-                if constexpr (NPH > 4) stage(std::integral_constant<int, 4>{});
-                if constexpr (NPH > 5) stage(std::integral_constant<int, 5>{});
-                static_assert(NPH <= 6, "M <= 96");
-            }
-            if (!nxt.valid) break;
-            cur = nxt;
-            if constexpr (!LOADER) { myq = lane_q(cur); tq = lane_thr(myq); }
-            ++k;
+                for (int j = 0; j < 4; ++j) off[j] ^= (unsigned)IVFS_BUF;     // the other table buffer (64 KiB-aligned bases)
+            };
+            stage(std::integral_constant<int, 0>{});
+            if constexpr (NPH > 1) stage(std::integral_constant<int, 1>{});
+            if constexpr (NPH > 2) stage(std::integral_constant<int, 2>{});
+            if constexpr (NPH > 3) stage(std::integral_constant<int, 3>{});
+            if constexpr (NPH > 4) stage(std::integral_constant<int, 4>{});
+            if constexpr (NPH > 5) stage(std::integral_constant<int, 5>{});
+            static_assert(NPH <= 6, "M <= 96");
         }
-    };
-    walk(std::integral_constant<int, 0>{});
+        if (!nxt.valid) break;
+        cur = nxt;
+        myq = lane_q(cur); tq = ivfs_lane_thr<M>(tint, myq);
+        ++k;
+    }
     if (l == 0) stream_cnt[blockIdx.x * IVFS_WAVES + (unsigned)wv] = woff;
 }

@@ -5,6 +5,7 @@ codes, k = N, thousands of copies of one passage) defeat any slack.  Then: per-q
 are repeated, and what still fails goes through rc_adc_search_exact — never a RepconcHipError, and the answer is the
 oracle's (score desc, id asc) top-k."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -173,7 +174,7 @@ def test_ivf_search_never_raises_on_degenerate_cells(method):
 
 @pytest.mark.parametrize("M", [32, 48, 96])
 def test_ivf_pipelined_screen_on_cells_of_several_rounds(M):
-    """Cells far larger than the 2048 rows a block screens per round (several rounds per task, ragged last chunk, first row
+    """Cells far larger than the 1920 rows (12 waves x 10 chunks x 16) a block screens per round (several rounds per task, ragged last chunk, first row
     of a cell in the middle of a chunk), cells smaller than one chunk, empty cells, fewer queries than a task holds and
     queries that keep every row: the list-centric search (persistent pipelined screen, survivor streams, bucket pass)
     equals the oracle's brute force over the probed cells."""
@@ -196,6 +197,122 @@ def test_ivf_pipelined_screen_on_cells_of_several_rounds(M):
             s, i = ivf.search(_t(q), k, nprobe, method=method)
             assert np.array_equal(i.cpu().numpy(), wi), (M, nq, nprobe, method)
             assert np.array_equal(s.cpu().numpy().view(np.uint32), ws.view(np.uint32))
+
+
+_EDGE_CELLS = (5, 0, 16, 17, 1919, 1920, 1921, 1, 3841, 15, 31, 4000, 0, 7)       # rows per cell, in cell order
+# queries probing each cell (nprobe = 3): 1, 7, 8, 9, 15, 16, 17 and 33 sit on either side of a task of 8 and of 16 queries
+_EDGE_SHARE = (1, 2, 7, 8, 15, 16, 9, 2, 17, 4, 5, 33, 1, 3)
+_EDGE_WEIGHTS = (40.0, 32.0, 24.0)                                                  # coarse scores of a query's three cells
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_case(M):
+    """Index, queries and the oracle's three answers of test_ivf_screens_on_cell_and_task_edges, constructed rather than drawn: rows dealt to the cells
+    so that set_lists yields exactly _EDGE_CELLS, coarse centroids = scaled orthonormal directions, a query = its three
+    cells' directions (weights 40 / 32 / 24 over the centroid's scale: those are its coarse scores) + N(0, 0.25) noise, whose
+    coarse scores stay below ~3.  The triples: every query takes the three cells with the most probes left (ties: lower
+    cell), which meets any _EDGE_SHARE whose largest entry is at most a third of its sum.  Computed once per M and shared by
+    the two screen widths: nobody writes to it."""
+    from oracle import pq_oracle
+    sizes = np.array(_EDGE_CELLS)
+    nlist, N = len(sizes), int(sizes.sum())
+    rng = np.random.default_rng(5200 + M)
+    cells = rng.permutation(np.repeat(np.arange(nlist), sizes))
+    codes = synth.uniform_codes(5201 + M, N, M)
+    C = synth.gaussian(5202 + M, (M, 256, 768 // M))
+    basis = np.linalg.qr(synth.gaussian(5203, (768, nlist)).astype(np.float64))[0].T           # [nlist, 768], orthonormal rows
+    scale = np.linspace(0.8, 1.25, nlist)
+    coarse = (basis * scale[:, None]).astype(np.float32)
+    left = np.array(_EDGE_SHARE)
+    assert left.sum() % 3 == 0 and 3 * left.max() <= left.sum()
+    triples = []
+    while left.sum():
+        t = np.lexsort((np.arange(nlist), -left))[:3]
+        assert (left[t] > 0).all()
+        left[t] -= 1
+        triples.append(t)
+    triples = np.array(triples)                                                     # [nq, 3], a query's cells by weight
+    q = synth.gaussian(5204 + M, (len(triples), 768)).astype(np.float64) * 0.5
+    for j, wgt in enumerate(_EDGE_WEIGHTS):
+        q += (wgt / scale[triples[:, j]])[:, None] * basis[triples[:, j]]
+    q = q.astype(np.float32)
+    two = [0, int(np.nonzero(triples[:, 0] != triples[0, 0])[0][0])]               # two queries with different first cells
+    want = {"k4096": pq_oracle.ivf_search(q, C, codes, cells, coarse, 4096, 3),
+            "k10": pq_oracle.ivf_search(q, C, codes, cells, coarse, 10, 3),
+            "two": pq_oracle.ivf_search(q[two], C, codes, cells, coarse, 10, 1)}
+    for a in (C, codes, cells, coarse, q, triples, *[x for w in want.values() for x in w]):
+        a.setflags(write=False)
+    return C, codes, cells, coarse, q, triples, two, want
+
+
+@pytest.mark.parametrize("method", ["lists8", "lists16"])
+@pytest.mark.parametrize("M", [16, 48, 96])
+def test_ivf_screens_on_cell_and_task_edges(M, method):
+    """What the two pipelined screens share (csrc/ivfs_common.h: the block's share of the tasks, a task's cell range, a wave's
+    chunks of a round, the survivor stream), where an off-by-one would hide behind random cell sizes.  Cells of 5, 0, 16, 17,
+    1919, 1920, 1921, 1, 3841, 15, 31, 4000, 0 and 7 rows: most start off a 16-row boundary, the lengths sit on either side of
+    a chunk (16 rows), one round (12 waves x 10 chunks x 16 = 1920 rows) and two rounds.  M = 16 is one table phase of 16,
+    48 a 32-phase and a 16-phase, 96 three phases (six in the 16-query screen).  Cells probed by 1, 7, 8, 9, 15, 16, 17 and 33
+    queries: full, one-short and one-over tasks of both widths.  Against the oracle on ids and score bits:
+      * k = 4096: a query that probes no more than KEEP_ALL_ROWS rows has no threshold and must return exactly its probed rows,
+        then -1 / -inf — a row leaking in from the neighbouring cell of a shared chunk, or one dropped at a cell's edge, changes
+        the answer; and the list-centric pass itself must have answered those queries (the per-query scan that repairs a
+        flagged query would hide a dropped row);
+      * k = 10: the thresholded path, with queries probing the 3841-, 4000- and 1921-row cells (round boundaries);
+      * two queries, nprobe = 1: fewer tasks than XCDs, most blocks have none."""
+    from repconc_amd.ivf import IVFPQIndex
+
+    def dev(a):                                     # (the shared case is read-only: the device gets a copy)
+        return _t(a.copy())
+
+    C, codes, cells, coarse, q, triples, two, want = _edge_case(M)
+    sizes, nlist = np.array(_EDGE_CELLS), len(_EDGE_CELLS)
+    ivf = IVFPQIndex(768, M, nlist, device=DEV)
+    ivf.set_centroids(dev(C))
+    ivf.coarse = dev(coarse)
+    ivf.set_lists(dev(codes), dev(cells))
+    assert np.array_equal(np.diff(ivf.list_off.cpu().numpy()), sizes)
+    probes = ivf.probe(dev(q), 3, ordered=False).cpu().numpy()
+    assert np.array_equal(probes, np.sort(triples, 1))
+    share = np.bincount(probes.ravel(), minlength=nlist)
+    assert np.array_equal(share, _EDGE_SHARE) and {1, 7, 8, 9, 15, 16, 17, 33} <= set(share.tolist())
+    probed_rows = sizes[probes].sum(1)
+    keep_all = probed_rows <= ivf.KEEP_ALL_ROWS
+    assert keep_all.sum() >= 8 and (~keep_all).sum() >= 8
+    assert {4, 5, 6}.issubset(set(probes[keep_all].ravel().tolist()))                 # the 1919 / 1920 / 1921-row cells unthresholded
+    for big in (6, 8, 11):                                                           # 1921, 3841, 4000 rows: thresholded at k = 10
+        assert (probes[~keep_all] == big).any()
+
+    scanned = []                                    # queries handed to the per-query scan, by the k of the call
+    search = ivf.search
+
+    def spy(x, k, nprobe=None, method="auto"):
+        if method == "scan":
+            scanned.append((int(k), x.cpu().numpy()))
+        return search(x, k, nprobe, method)
+
+    ivf.search = spy
+    # k = 4096
+    ws, wi = want["k4096"]
+    for j in np.nonzero(keep_all)[0]:                                                # (the oracle itself: exactly the probed rows)
+        n = int(probed_rows[j])
+        assert np.array_equal(np.sort(wi[j, :n]), np.nonzero(np.isin(cells, probes[j]))[0]) and (wi[j, n:] == -1).all()
+        assert np.isneginf(ws[j, n:]).all()
+    s, i = spy(dev(q), 4096, 3, method)
+    _same(s, i, ws, wi)
+    repaired = [x for kk, x in scanned if kk == 4096]
+    for x in repaired:
+        assert not (x[:, None, :] == q[keep_all][None]).all(2).any(), "a query without threshold was answered by the scan"
+    # k = 10
+    ws, wi = want["k10"]
+    s, i = spy(dev(q), 10, 3, method)
+    _same(s, i, ws, wi)
+    # two queries, nprobe = 1
+    assert (sizes[triples[two, 0]] > 0).all()
+    ws, wi = want["two"]
+    assert (wi[:, 0] >= 0).all() and (cells[wi[:, 0]] == triples[two, 0]).all()
+    s, i = spy(dev(q[two]), 10, 1, method)
+    _same(s, i, ws, wi)
 
 
 def test_ivf_survivor_stream_overflow_is_answered_not_raised(monkeypatch):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-wave timeline of the pipelined IVF screen (development tool, GPU box): builds a variant of the library with
--DRC_IVF_TRACE (wall-clock stamps at the stage boundaries of the 8-QUERY screen, csrc/ivf_lists.hip; the 16-query
+-DRC_IVF_TRACE (wall-clock stamps at the stage boundaries of the 8-QUERY screen, csrc/ivfs_screen8.h, compiled through csrc/ivf_lists.hip; the 16-query
 screen has tools/ivf16_timeline.py), runs the BASELINE configs[3] shape at
 nprobe = argv[1] (default 128) and prints, per table phase, what the gathering and the loader waves spend where.
     python tools/ivf_timeline.py [nprobe]"""
