@@ -557,6 +557,28 @@ int rc_ivf_search(rc_handle_t h, const uint8_t* codes, const int64_t* list_off, 
                   int nprobe, int64_t stride, int k, float* scores, int64_t* out_ids, int* status, void* ws,
                   size_t ws_bytes, rc_stream_t stream);
 
+/* ------------------------------------------------------------------ JPQ scoring head (csrc/jpq_head.hip)
+ * Scores of (query, document id) pairs straight from the resident codes, and their gradients (stage 2 of the recipe,
+ * models/jpq/finetune_jpq.py:176-189, without the decoded embeddings and without atomics on values).
+ * q [nq, D] fp32 (D = M*dsub, contiguous), codes [N, M] uint8, pids [nq, k] int64, C [M, 256, dsub] fp32, g [nq, k] fp32.
+ * An id outside [0, N) is a hole: its score is +0.0f and it contributes to no gradient.
+ * Every product is of two fp32 values taken in fp64 (exact); every sum is fp64, sequential from 0.0, rounded to fp32 once:
+ *   scores[i,t]   = fp32(sum_m (sum_j q[i, m*dsub+j] * C[m, codes[pids[i,t], m], j]))       j ascending, then m ascending
+ *   grad_q[i,d]   = fp32(sum_t g[i,t] * C[m, codes[pids[i,t], m], j]),  d = m*dsub+j          t ascending, holes skipped
+ *   grad_C[m,c,j] = fp32(sum_p g[p] * q[p div k, m*dsub+j])  over the pairs p = i*k+t with codes[pids[p], m] == c, p ascending
+ *                   (stable counting sort of the pairs by code per sub-quantiser, then one owner per (m, c) segment; a segment
+ *                   no pair hits gets +0.0f).
+ * The results are functions of the inputs alone (bit-identical from run to run).  K must be 256; any M >= 1, dsub >= 1;
+ * nq*k < 2^31, N < 2^32.  nq == 0 or k == 0: RC_OK, nothing is launched and the outputs are not touched.
+ * rc_jpq_head_bwd: grad_q [nq, D] and / or grad_C [M, 256, dsub]; a null output is not computed (both null: RC_EINVAL).
+ * ws (rc_jpq_head_ws_bytes(nq, k, M), needs no GPU) is used for grad_C only. */
+size_t rc_jpq_head_ws_bytes(int nq, int k, int M);
+int rc_jpq_head_fwd(rc_handle_t h, const float* q, const uint8_t* codes, int64_t N, const int64_t* pids, const float* C,
+                    int nq, int k, int M, int K, int dsub, float* scores, rc_stream_t stream);
+int rc_jpq_head_bwd(rc_handle_t h, const float* q, const uint8_t* codes, int64_t N, const int64_t* pids, const float* C,
+                    const float* g, int nq, int k, int M, int K, int dsub, float* grad_q, float* grad_C, void* ws,
+                    size_t ws_bytes, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

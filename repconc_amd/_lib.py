@@ -128,6 +128,9 @@ PROTOTYPES = {
     "rc_index_codes": (_vp, [_vp]),
     "rc_index_centroids": (_vp, [_vp]),
     "rc_index_search": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "rc_jpq_head_ws_bytes": (_sz, [_i, _i, _i]),
+    "rc_jpq_head_fwd": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "rc_jpq_head_bwd": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

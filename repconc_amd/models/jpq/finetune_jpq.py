@@ -30,8 +30,11 @@ from ..repconc.modeling_repconc import RepCONC
 
 class JPQ(nn.Module):
     def __init__(self, repconc: RepCONC, pq_index: PQIndex, qrels: Dict[int, List[int]], neg_top_k: int,
-                 temperature: float, gpu_id=None):
+                 temperature: float, gpu_id=None, head: str = "decode"):
         super().__init__()
+        if head not in ("decode", "fused"):
+            raise ValueError(f'head must be "decode" or "fused", got {head!r}')
+        self.head = head
         self.repconc = repconc
         self.qrels = qrels
         self.neg_top_k = neg_top_k
@@ -54,6 +57,8 @@ class JPQ(nn.Module):
                                     return_quantized_embedding=False).continuous_embeds          # [nq, D]
         with torch.no_grad():                                                                     # :176
             neg_pids = self.pq_index.search(query_embeds.detach().float().contiguous(), self.neg_top_k)[1]
+        if self.head == "fused":
+            return {"loss": self._fused_loss(query_embeds, neg_pids, qids)}
         nq, k = neg_pids.shape
         # an index with fewer than neg_top_k rows pads the result with id -1: those slots decode row 0 and are then
         # pushed out of the softmax (the reference would index with -1, i.e. silently use the LAST row)
@@ -68,6 +73,19 @@ class JPQ(nn.Module):
         query_reldoc_scores = (query_embeds * rel_doc_embeds).sum(-1, keepdim=True) / self.temperature
         loss = self.compute_loss(query_reldoc_scores, query_negdoc_scores, neg_masks)
         return {"loss": loss}
+
+    def _fused_loss(self, query_embeds: torch.Tensor, neg_pids: torch.Tensor, qids: torch.Tensor) -> torch.Tensor:
+        """head="fused": the positive and the retrieved ids scored by ONE ops.jpq_scores call on the resident codes — no
+        decoded rows, and both gradients summed in a fixed order, so the step is bit-reproducible.  The -1 padding of a
+        short index is a hole of the op (score 0, no gradient) and is pushed out of the softmax as in the decode head."""
+        neg_masks = self._compute_negative_mask(qids, neg_pids)
+        pos_pids = torch.tensor([random.choice(self.qrels[int(q)]) for q in qids.tolist()], dtype=torch.int64,
+                                device=neg_pids.device)
+        pids = torch.cat([pos_pids[:, None], neg_pids], 1)
+        scores = ops.jpq_scores(query_embeds, self.pq_index.codes, pids, self.repconc.centroids) / self.temperature
+        query_reldoc_scores = scores[:, :1]
+        query_negdoc_scores = scores[:, 1:].masked_fill(neg_pids < 0, -10000.0)
+        return self.compute_loss(query_reldoc_scores, query_negdoc_scores, neg_masks)
 
     @torch.no_grad()
     def _compute_negative_mask(self, qids: torch.Tensor, docids: torch.Tensor) -> torch.Tensor:

@@ -547,6 +547,85 @@ def decode(codes: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
     return decode_raw(codes, centroids)
 
 
+# --------------------------------------------------------------------------- JPQ scoring head
+def jpq_head_ws_bytes(nq: int, k: int, M: int) -> int:
+    """Workspace of the centroid gradient of `jpq_scores` (the pair sort); needs no GPU."""
+    return int(_lib.load().rc_jpq_head_ws_bytes(int(nq), int(k), int(M)))
+
+
+def _jpq_args(q: torch.Tensor, codes: torch.Tensor, pids: torch.Tensor, centroids: torch.Tensor):
+    if centroids.dim() != 3 or centroids.shape[1] != K:
+        raise ValueError("centroids must be [M, 256, dsub]")
+    M, _, dsub = centroids.shape
+    if q.dim() != 2 or q.shape[1] != M * dsub:
+        raise ValueError(f"q must be [nq, M*dsub = {M}*{dsub}]: centroids must be [M, 256, D/M]")
+    if codes.dim() != 2 or codes.shape[1] != M:
+        raise ValueError("codes must be [N, M]")
+    if codes.dtype != torch.uint8:
+        raise ValueError("codes must be uint8 (the index's resident array)")
+    if pids.dim() != 2 or pids.shape[0] != q.shape[0]:
+        raise ValueError("pids must be [nq, k]")
+    if pids.dtype != torch.int64:
+        raise ValueError("pids must be int64")
+    _need_cuda(q, codes, pids, centroids)
+    if not codes.is_contiguous():
+        raise ValueError("codes must be contiguous: the head reads the index's array in place")
+    return M, dsub
+
+
+class _JPQScoresFn(torch.autograd.Function):
+    """scores[i, t] = <q[i], decode(codes[pids[i, t]])> without the decoded rows; both gradients in a fixed order
+    (csrc/jpq_head.hip), so a step is bit-reproducible."""
+
+    @staticmethod
+    def forward(ctx, q, codes, pids, centroids):
+        M, _, dsub = centroids.shape
+        qc = q.detach().float().contiguous()
+        pc = pids.contiguous()
+        c = _centroids(centroids)
+        nq, k = pc.shape
+        ctx.save_for_backward(qc, codes, pc, c)
+        ctx.qdtype, ctx.cdtype, ctx.cshape = q.dtype, centroids.dtype, tuple(centroids.shape)
+        scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+        if nq == 0 or k == 0:
+            return scores
+        lib, h, s, _ = _ctx(qc)
+        _lib.check(lib.rc_jpq_head_fwd(h, _p(qc), _p(codes), codes.shape[0], _p(pc), _p(c), nq, k, M, K, dsub, _p(scores), s),
+                   "rc_jpq_head_fwd", h)
+        return scores
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        qc, codes, pc, c = ctx.saved_tensors
+        M, _, dsub = ctx.cshape
+        nq, k = pc.shape
+        want_q, want_c = ctx.needs_input_grad[0], ctx.needs_input_grad[3]
+        gq = torch.empty_like(qc) if want_q else None
+        gC = torch.empty(ctx.cshape, dtype=torch.float32, device=qc.device) if want_c else None
+        if nq == 0 or k == 0:
+            gq = None if gq is None else gq.zero_()
+            gC = None if gC is None else gC.zero_()
+        elif want_q or want_c:
+            go = grad_out.float().contiguous()
+            lib, h, s, _ = _ctx(qc)
+            wsb = lib.rc_jpq_head_ws_bytes(nq, k, M) if want_c else 0
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=qc.device) if wsb else None
+            _lib.check(lib.rc_jpq_head_bwd(h, _p(qc), _p(codes), codes.shape[0], _p(pc), _p(c), _p(go), nq, k, M, K, dsub,
+                                           _p(gq), _p(gC), _p(ws), wsb, s), "rc_jpq_head_bwd", h)
+        return (None if gq is None else gq.to(ctx.qdtype), None, None, None if gC is None else gC.to(ctx.cdtype))
+
+
+def jpq_scores(q: torch.Tensor, codes: torch.Tensor, pids: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+    """[nq, k] fp32 scores of query i against the documents pids[i, :] of a PQ index: sum_m <q_m, centroids[m, codes[pid, m]]>.
+
+    codes is the index's resident [N, M] uint8 array (read in place, never copied or widened); an id outside [0, N) — the
+    -1 padding of a short search result — is a hole: score 0.0, no gradient.  Differentiable w.r.t. q and centroids; every
+    sum runs in fp64 in a fixed order (include/repconc_hip.h, rc_jpq_head_*), so scores and gradients are bit-reproducible.
+    Temperature stays outside: `jpq_scores(...) / temperature`."""
+    _jpq_args(q, codes, pids, centroids)
+    return _JPQScoresFn.apply(q, codes, pids, centroids)
+
+
 # --------------------------------------------------------------------------- small ops
 def normalize_centroids_(centroids: torch.Tensor) -> torch.Tensor:
     _need_cuda(centroids)
