@@ -482,8 +482,10 @@ int rc_index_search(rc_index_t idx, const float* q, int nq, int k, float* scores
  * ws: rc_ivf_search_ws_bytes(nq, stride).  status bit1: more than 16384 rows tie at the k-th score. */
 /* Build side: cell[b] = argmin_l ||x_b - cent_l||^2 (first minimum) for nlist coarse centroids of the full dimension D,
  * evaluated as ||c||^2 - 2<x,c> on the fp32 matrix cores with the argmin fused in (the [B, nlist] score matrix is never
- * written).  x: [B, ldx >= D] fp32, 16-byte aligned rows, ldx % 4 == 0, D % 16 == 0; cent: [nlist, D]; cell: [B] int32;
- * ws: rc_ivf_coarse_assign_ws_bytes(nlist). */
+ * written).  x: [B, ldx >= D] fp32, 16-byte aligned rows, ldx % 4 == 0, D % 16 == 0; cent: [nlist, D], 16-byte aligned;
+ * cell: [B] int32; ws: rc_ivf_coarse_assign_ws_bytes(nlist).  A misaligned x or cent is RC_ESHAPE, nothing is launched.
+ * Score of (b, l): fl(cnorm_l - 2 acc), acc the fp32 fma chain over d ascending, cnorm_l the 64-lane strided fma chains
+ * of c_l^2 added as a butterfly.  A NaN score never wins; a row with no score below +inf goes to cell 0. */
 size_t rc_ivf_coarse_assign_ws_bytes(int nlist);
 int rc_ivf_coarse_assign(rc_handle_t h, const float* x, int64_t ldx, const float* cent, int64_t B, int D, int nlist,
                          int* cell, void* ws, size_t ws_bytes, rc_stream_t stream);
@@ -522,7 +524,10 @@ int rc_ivf_search_lists(rc_handle_t h, const uint8_t* codes, const uint8_t* imag
  * ws: rc_ivf_search_probes_ws_bytes(M, nq, nprobe, nlist, sstride). */
 /* Probe selection for the calls below: per query the nprobe cells with the largest coarse score (scores [nq,nlist] fp32,
  * e.g. q @ coarse^T from a library GEMM; ties at the boundary go to the lower cell id), written in ASCENDING CELL ORDER to
- * probes [nq,nprobe] int32 — the searches need the set of cells, not their ranking.  nlist <= 16384. */
+ * probes [nq,nprobe] int32 — the searches need the set of cells, not their ranking.  nlist <= 16384.
+ * Order of the scores: that of the numbers, -0.0 and +0.0 tie (the kernel orders the bits of s + 0.0f).  A NaN orders by
+ * its bits: above +inf with the sign bit clear, below -inf with it set, NaNs of one sign by payload; the output is nprobe
+ * distinct ascending cells whatever the scores hold. */
 int rc_ivf_select_probes(rc_handle_t h, const float* scores, int nq, int nlist, int nprobe, int* probes,
                          rc_stream_t stream);
 size_t rc_ivf_search_probes_ws_bytes(int M, int nq, int nprobe, int nlist, int64_t sstride);

@@ -644,7 +644,9 @@ __global__ __launch_bounds__(1024) void ivf_probe_select_kernel(const float* __r
     __shared__ unsigned s_scan[4];
     __shared__ int s_gt[16], s_eq[16];
     const int qi = blockIdx.x, tid = threadIdx.x;
-    for (int i = tid; i < nlist; i += 1024) keys[i] = adc_order_key(scores[(size_t)qi * nlist + i]);
+    // + 0.0f turns -0.0 into +0.0 (and changes no other number): the two zeros tie, as they do for every comparison of the
+    // scores themselves, and the lower cell wins.  adc_order_key alone orders the raw bits, -0.0 below +0.0.
+    for (int i = tid; i < nlist; i += 1024) keys[i] = adc_order_key(scores[(size_t)qi * nlist + i] + 0.0f);
     if (tid == 0) { sel_prefix = 0u; sel_rank = (unsigned)nprobe; }
     __syncthreads();
     for (int pass = 0; pass < 4; ++pass) {

@@ -323,7 +323,8 @@ __global__ __launch_bounds__(256) void ivf_cnorm_kernel(const float* __restrict_
     if (l == 0) cnorm[c] = s;
 }
 
-// x: [B, ldx >= D] fp32 (16-byte aligned rows, ldx % 4 == 0), cent: [nlist, D] fp32, cell: [B] int32.
+// x: [B, ldx >= D] fp32 (16-byte aligned rows, ldx % 4 == 0), cent: [nlist, D] fp32 (16-byte aligned), cell: [B] int32;
+// a misaligned x or cent is refused with RC_ESHAPE before anything is launched.
 // ws: nlist floats (centroid norms).  D % 16 == 0.
 extern "C" size_t rc_ivf_coarse_assign_ws_bytes(int nlist) { return nlist > 0 ? rc_align_up((size_t)nlist * sizeof(float), 256) : 0; }
 
@@ -331,7 +332,8 @@ extern "C" int rc_ivf_coarse_assign(rc_handle_t h, const float* x, int64_t ldx, 
                                     int nlist, int* cell, void* ws, size_t ws_bytes, rc_stream_t stream) {
     rc_device_guard device_guard_(h);
     if (!h || !x || !cent || !cell || B < 0 || D <= 0 || nlist <= 0 || ldx < D) return RC_EINVAL;
-    if (D % IVFC_KC != 0 || ldx % 4 != 0) return RC_ESHAPE;
+    // the kernel reads x and cent as float4: 16-byte aligned rows (rc_ivf_coarse_update checks the same)
+    if (D % IVFC_KC != 0 || ldx % 4 != 0 || ((uintptr_t)x & 15) || ((uintptr_t)cent & 15)) return RC_ESHAPE;
     if (!ws || ws_bytes < rc_ivf_coarse_assign_ws_bytes(nlist)) return RC_EWORKSPACE;
     if (B == 0) return RC_OK;
     hipStream_t s = (hipStream_t)stream;

@@ -65,6 +65,8 @@ def coarse_assign(x: torch.Tensor, cent: torch.Tensor, chunk: int = 1 << 20, as_
     ops._need_cuda(x, cent)
     xt = ops._rows_f32(x)
     cent = cent.float().contiguous()
+    if cent.data_ptr() % 16 != 0:                       # a contiguous view at an odd storage offset: the kernel loads float4
+        cent = cent.clone()
     n, D = xt.shape
     nlist = cent.shape[0]
     if D % 16 != 0:
@@ -191,15 +193,11 @@ class IVFPQIndex:
             _lib.check(lib.rc_ivf_select_probes(h, C.c_void_p(s.data_ptr()), s.shape[0], self.nlist, int(nprobe),
                                                 C.c_void_p(out.data_ptr()), st), "rc_ivf_select_probes", h)
             return out
-        if nprobe * 4 <= self.nlist:
-            # select first, then order the selected cells by (score desc, cell asc): a full stable sort of nlist scores
-            # per query costs more than the search itself at small nprobe
-            top = torch.topk(s, nprobe, dim=1, sorted=False).indices
-            top = torch.sort(top, dim=1).values
-            sel = torch.gather(s, 1, top)
-            order = torch.gather(top, 1, torch.argsort(sel, dim=1, descending=True, stable=True))
-        else:
-            order = torch.argsort(s, dim=1, descending=True, stable=True)[:, :nprobe]
+        # a stable sort of the whole row.  A torch.topk shortcut selects by the bits (-0.0 below +0.0) and promises nothing
+        # about WHICH of several equal scores it returns, so it does not keep "ties at the boundary: lower cell id"
+        # (tests/test_ivf_build.py).  The searches use the kernel above (nlist <= 16384); this path is the readable statement of
+        # the rule and the kernel's cross-check.
+        order = torch.argsort(s, dim=1, descending=True, stable=True)[:, :nprobe]
         return order.to(torch.int32).contiguous()
 
     def search(self, x, k: int, nprobe: Optional[int] = None, method: str = "auto"):
