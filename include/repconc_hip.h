@@ -254,6 +254,22 @@ int rc_pq_decode(rc_handle_t h, const void* codes, int code_dtype, const float* 
                  int M, int K, int dsub, float* out, rc_stream_t stream);
 int rc_pq_decode_bwd(rc_handle_t h, const void* codes, int code_dtype, const float* grad_out,
                      int64_t n, int M, int K, int dsub, float* grad_C, rc_stream_t stream);
+/* The same gradient summed in a fixed order (csrc/decode_det.hip; decode is modeling_repconc.py:168-184).  rc_pq_decode_bwd
+ * adds with fp32 atomics, so its last bits depend on the order in which the waves arrive; this entry computes
+ *   grad_C[m, c, j] = fp32( sum over the rows r with (codes[r, m] & 255) == c, r ascending, of (double) grad_out[r, m*dsub + j] )
+ * with every sum in fp64, sequential from 0.0, rounded to fp32 once; an (m, c) that no row hits gets exactly +0.0f.  No atomics
+ * on values: a stable counting sort of the rows by code per sub-quantiser, then one owner per output element.  The result is
+ * a function of the inputs alone (bit-identical from run to run).  Unlike rc_pq_decode_bwd it OVERWRITES grad_C
+ * [M, 256, dsub]: the caller need not zero it.  K must be 256; any M >= 1, dsub >= 1; 0 <= n < 2^31 (n >= 2^31: RC_ESHAPE).
+ * n == 0: RC_OK, nothing is launched and grad_C is not touched.  Other argument checks as rc_pq_decode_bwd.
+ * ws: rc_pq_decode_bwd_det_ws_bytes(n, M) bytes (needs no GPU; 0 for n <= 0, M <= 0 or n >= 2^31) — the sort's hist
+ * [M][ceil(n/1024)][256], count [M][256], start [M][256] and perm [M][n], all uint32, each rounded up to 256 bytes; a null or
+ * short workspace is RC_EWORKSPACE.  RC_DECODE_DET_MAX_GRID (default 65536) is a test switch: the most blocks a launch of this
+ * entry may have, so that a small input walks every grid-stride loop. */
+size_t rc_pq_decode_bwd_det_ws_bytes(int64_t n, int M);
+int rc_pq_decode_bwd_det(rc_handle_t h, const void* codes, int code_dtype, const float* grad_out,
+                         int64_t n, int M, int K, int dsub, float* grad_C, void* ws, size_t ws_bytes,
+                         rc_stream_t stream);
 
 /* ------------------------------------------------------------------ a-8
  * RepCONC.normalize_centrodis (modeling_repconc.py:112-116): C <- C / max(||C||_2, 1e-12). */

@@ -61,6 +61,8 @@ PROTOTYPES = {
     "rc_pq_assign_sinkhorn_dist": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rc_pq_decode": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp]),
     "rc_pq_decode_bwd": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp]),
+    "rc_pq_decode_bwd_det_ws_bytes": (_sz, [_i64, _i]),
+    "rc_pq_decode_bwd_det": (_i, [_vp, _vp, _i, _vp, _i64, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "rc_normalize_centroids": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "rc_code_hist": (_i, [_vp, _vp, _i, _i64, _i, _i, _vp, _vp]),
     "rc_kmeans_stats": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),

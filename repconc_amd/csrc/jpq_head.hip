@@ -14,19 +14,18 @@
 //   jpq_fwd_kernel      16 lanes per pair: lane l owns the sub-quantisers m = l, l+16, ...; the 16 partial sums of a chunk are
 //                       passed round the group and added in m order by every lane (no LDS, no shape-sized resource)
 //   jpq_gradq_kernel    thread per (query, d): walks the query's k pairs in order
-//   jpq_hist_kernel     \  stable counting sort of the pairs by code, per sub-quantiser (the pattern of
-//   jpq_scan_kernel      > rc_ivf_coarse_update, kmeans.hip): per-tile counts -> exclusive offsets -> perm[m][.] = the
-//   jpq_scatter_kernel  /  pairs of every (m, c) segment, ascending
+//   code_sort_*_kernel  stable counting sort of the pairs by code, per sub-quantiser (code_sort.h, shared with the
+//                       deterministic decode backward): perm[m][.] = the pairs of every (m, c) segment, ascending
 //   jpq_gradc_kernel    thread per (m, c, j): the one owner of its output adds its segment in order
 //
-// The only atomics of the unit are the integer tile counts of jpq_hist_kernel (order-free).  Every kernel walks its work with
+// The only atomics of the unit are the integer tile counts of the sort's hist kernel (order-free).  Every kernel walks its work with
 // a grid-stride loop, so nq*k < 2^31 needs no large grid.
 #include "rc_common.h"
+#include "code_sort.h"
 
-#define JH_TILE 1024          // pairs per sort tile: 16 wave-wide steps of one wave
-#define JH_MG 4               // sub-quantisers (= waves) per sort block
+#define JH_TILE CS_TILE       // pairs per sort tile (code_sort.h)
 #define JH_U 8                // independent loads in flight ahead of an ordered chain of adds
-#define JH_MAX_GRID 65536
+#define JH_MAX_GRID CS_MAX_GRID
 
 // ------------------------------------------------------------------------------------------------------- forward
 template <bool VEC4>
@@ -108,118 +107,17 @@ __global__ __launch_bounds__(256) void jpq_gradq_kernel(const uint8_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------- the sort
-// all lanes of the wave that are `valid` and hold the same 8-bit code as this lane (meaningless on a lane that is not valid)
-__device__ __forceinline__ unsigned long long jh_same_code(int c, bool valid) {
-    unsigned long long mask = __ballot(valid);
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (c >> b) & 1;
-        const unsigned long long bal = __ballot(bit);
-        mask &= bit ? bal : ~bal;
+// code_sort.h, over the pairs: the code of pair p under m is codes[pids[p]*M + m]; a pair whose id is outside [0, N) is a hole.
+struct jpq_code_src {
+    const uint8_t* codes;
+    int64_t N;
+    const int64_t* pids;
+    int M;
+    __device__ __forceinline__ int operator()(int64_t p, int m) const {
+        const int64_t pid = pids[p];
+        return (pid >= 0 && pid < N) ? (int)codes[pid * M + m] : -1;
     }
-    return mask;
-}
-
-// work item = (tile of JH_TILE pairs, group of JH_MG sub-quantisers); wave v of the block serves m = group*JH_MG + v.
-// hist[m][tile][c] = pairs of the tile with code c under m (holes are not counted).
-__global__ __launch_bounds__(64 * JH_MG) void jpq_hist_kernel(const uint8_t* __restrict__ codes, int64_t N,
-                                                              const int64_t* __restrict__ pids, int64_t P, int M, int64_t tiles,
-                                                              unsigned* __restrict__ hist) {
-    __shared__ unsigned cnt[JH_MG][RC_K];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int groups = (M + JH_MG - 1) / JH_MG;
-    const int64_t items = tiles * groups;
-    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
-        const int64_t tile = w / groups;
-        const int m = (int)(w - tile * groups) * JH_MG + wv;
-        const bool live = m < M;
-        for (int c = lane; c < RC_K; c += 64) cnt[wv][c] = 0u;
-        __syncthreads();
-        const int64_t p0 = tile * JH_TILE;
-        for (int s = 0; s < JH_TILE; s += 64) {
-            const int64_t p = p0 + s + lane;
-            if (live && p < P) {
-                const int64_t pid = pids[p];
-                if (pid >= 0 && pid < N) atomicAdd(&cnt[wv][codes[pid * M + m]], 1u);     // integer counts: order-free
-            }
-        }
-        __syncthreads();
-        if (live)
-            for (int c = lane; c < RC_K; c += 64) hist[((size_t)m * tiles + tile) * RC_K + c] = cnt[wv][c];
-        __syncthreads();
-    }
-}
-
-// block per sub-quantiser, thread per code: hist[m][.][c] -> exclusive offsets along the tiles, count[m][c] = the segment's
-// length, start[m][c] = its first slot in perm[m] (exclusive scan of the counts over c).
-__global__ __launch_bounds__(RC_K) void jpq_scan_kernel(unsigned* __restrict__ hist, int64_t tiles, int M,
-                                                        unsigned* __restrict__ count, unsigned* __restrict__ start) {
-    __shared__ unsigned s_w[RC_K / 64];
-    const int c = threadIdx.x, lane = c & 63, wv = c >> 6;
-    for (int m = blockIdx.x; m < M; m += gridDim.x) {
-        unsigned run = 0;
-        for (int64_t t = 0; t < tiles; ++t) {
-            const size_t at = ((size_t)m * tiles + t) * RC_K + c;
-            const unsigned v = hist[at];
-            hist[at] = run;
-            run += v;
-        }
-        count[(size_t)m * RC_K + c] = run;
-        unsigned incl = run;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned up = (unsigned)__shfl_up((int)incl, o);
-            if (lane >= o) incl += up;
-        }
-        if (lane == 63) s_w[wv] = incl;
-        __syncthreads();
-        unsigned before = 0;
-        for (int v = 0; v < wv; ++v) before += s_w[v];
-        start[(size_t)m * RC_K + c] = before + incl - run;
-        __syncthreads();
-    }
-}
-
-// Same walk as jpq_hist_kernel.  The wave steps through its tile 64 pairs at a time; a pair's slot is the running position of
-// its segment plus the number of lower lanes of the step with the same code, so perm[m] lists every segment in ascending p.
-__global__ __launch_bounds__(64 * JH_MG) void jpq_scatter_kernel(const uint8_t* __restrict__ codes, int64_t N,
-                                                                 const int64_t* __restrict__ pids, int64_t P, int M, int64_t tiles,
-                                                                 const unsigned* __restrict__ hist, const unsigned* __restrict__ start,
-                                                                 unsigned* __restrict__ perm) {
-    __shared__ unsigned pos[JH_MG][RC_K];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int groups = (M + JH_MG - 1) / JH_MG;
-    const int64_t items = tiles * groups;
-    for (int64_t w = blockIdx.x; w < items; w += gridDim.x) {
-        const int64_t tile = w / groups;
-        const int m = (int)(w - tile * groups) * JH_MG + wv;
-        const bool live = m < M;
-        if (live)
-            for (int c = lane; c < RC_K; c += 64)
-                pos[wv][c] = start[(size_t)m * RC_K + c] + hist[((size_t)m * tiles + tile) * RC_K + c];
-        __syncthreads();
-        const int64_t p0 = tile * JH_TILE;
-        for (int s = 0; s < JH_TILE; s += 64) {
-            const int64_t p = p0 + s + lane;
-            bool valid = live && p < P;
-            int c = 0;
-            if (valid) {
-                const int64_t pid = pids[p];
-                valid = pid >= 0 && pid < N;
-                if (valid) c = codes[pid * M + m];
-            }
-            const unsigned long long same = jh_same_code(c, valid);
-            const unsigned at = valid ? pos[wv][c] : 0u;
-            __syncthreads();                                                    // every lane has read before any lane advances
-            if (valid) {
-                const unsigned rank = (unsigned)__popcll(same & ((1ull << lane) - 1ull));
-                perm[(size_t)m * P + at + rank] = (unsigned)p;
-                if (lane == 63 - (int)__builtin_clzll(same)) pos[wv][c] = at + (unsigned)__popcll(same);   // last lane of the group
-            }
-            __syncthreads();
-        }
-    }
-}
+};
 
 // ------------------------------------------------------------------------------------------------------- grad_C
 // thread per (m, c, j) — the only writer of grad_C[m, c, j] — adds its segment's pairs in ascending p; an empty segment
@@ -259,20 +157,14 @@ __global__ __launch_bounds__(256) void jpq_gradc_kernel(const float* __restrict_
 }
 
 // ------------------------------------------------------------------------------------------------------- entry points
-static inline int64_t jh_tiles(int64_t P) { return (P + JH_TILE - 1) / JH_TILE; }
+static inline unsigned jh_grid(int64_t blocks) { return cs_grid(blocks, JH_MAX_GRID); }
 
-static inline unsigned jh_grid(int64_t blocks) {
-    if (blocks < 1) blocks = 1;
-    return (unsigned)(blocks > JH_MAX_GRID ? JH_MAX_GRID : blocks);
-}
-
-// hist [M][tiles][256], count [M][256], start [M][256], perm [M][nq*k] — all uint32
+// the sort's workspace over the nq*k pairs (code_sort.h)
 extern "C" size_t rc_jpq_head_ws_bytes(int nq, int k, int M) {
     if (nq <= 0 || k <= 0 || M <= 0) return 0;
     const int64_t P = (int64_t)nq * k;
     if (P > 0x7FFFFFFFll) return 0;
-    return rc_align_up((size_t)M * jh_tiles(P) * RC_K * sizeof(unsigned), 256) + 2 * rc_align_up((size_t)M * RC_K * sizeof(unsigned), 256) +
-           rc_align_up((size_t)M * P * sizeof(unsigned), 256);
+    return code_sort_ws::bytes(P, M);
 }
 
 static int jh_check(rc_handle_t h, const void* q, const void* codes, int64_t N, const void* pids, const void* C, int nq, int k, int M,
@@ -320,22 +212,12 @@ extern "C" int rc_jpq_head_bwd(rc_handle_t h, const float* q, const uint8_t* cod
         RC_LAUNCH_CHECK(h);
     }
     if (grad_C) {
-        const int64_t tiles = jh_tiles(P);
-        char* w = (char*)ws;
-        unsigned* hist = (unsigned*)w;  w += rc_align_up((size_t)M * tiles * RC_K * sizeof(unsigned), 256);
-        unsigned* count = (unsigned*)w; w += rc_align_up((size_t)M * RC_K * sizeof(unsigned), 256);
-        unsigned* start = (unsigned*)w; w += rc_align_up((size_t)M * RC_K * sizeof(unsigned), 256);
-        unsigned* perm = (unsigned*)w;
-        const unsigned sort_grid = jh_grid(tiles * ((M + JH_MG - 1) / JH_MG));
-        hipLaunchKernelGGL(jpq_hist_kernel, dim3(sort_grid), dim3(64 * JH_MG), 0, s, codes, N, pids, P, M, tiles, hist);
-        RC_LAUNCH_CHECK(h);
-        hipLaunchKernelGGL(jpq_scan_kernel, dim3(jh_grid(M)), dim3(RC_K), 0, s, hist, tiles, M, count, start);
-        RC_LAUNCH_CHECK(h);
-        hipLaunchKernelGGL(jpq_scatter_kernel, dim3(sort_grid), dim3(64 * JH_MG), 0, s, codes, N, pids, P, M, tiles,
-                           (const unsigned*)hist, (const unsigned*)start, perm);
-        RC_LAUNCH_CHECK(h);
+        const code_sort_ws L(ws, P, M);
+        const jpq_code_src src{codes, N, pids, M};
+        const int sorted = code_sort(h, src, P, M, L, JH_MAX_GRID, s);
+        if (sorted != RC_OK) return sorted;
         hipLaunchKernelGGL(jpq_gradc_kernel, dim3(jh_grid(((int64_t)D * RC_K + 255) / 256)), dim3(256), 0, s, q, g, P, k, M, dsub,
-                           (const unsigned*)perm, (const unsigned*)start, (const unsigned*)count, grad_C);
+                           (const unsigned*)L.perm, (const unsigned*)L.start, (const unsigned*)L.count, grad_C);
         RC_LAUNCH_CHECK(h);
     }
     return RC_OK;

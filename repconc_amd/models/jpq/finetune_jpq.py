@@ -50,7 +50,8 @@ class JPQ(nn.Module):
 
     def _decode_rows(self, pids: torch.Tensor) -> torch.Tensor:
         rows = self.pq_index.codes.index_select(0, pids.reshape(-1))
-        return ops.decode(rows, self.repconc.centroids)            # differentiable w.r.t. the centroids
+        # differentiable w.r.t. the centroids; the model's switch picks the backward (fixed-order when set: a reproducible step)
+        return ops.decode(rows, self.repconc.centroids, self.repconc.deterministic_decode)
 
     def forward(self, query_input_ids: torch.Tensor, query_attention_mask: torch.Tensor, qids: torch.Tensor):
         query_embeds = self.repconc(query_input_ids, query_attention_mask, return_code=False,

@@ -60,6 +60,7 @@ class RepCONCFinetuneArguments(TrainingArguments):
     not_use_constraint: bool = field(default=False)
     negative: str = field(default="random", metadata={"help": "inbatch, random, or the path of a qid -> [docid] json"})
     cache_chunk_size: int = field(default=-1)
+    deterministic_decode: bool = field(default=False, metadata={"help": "fixed-order (bit-reproducible) centroid gradient of decode"})
     seed: int = field(default=2022)
     remove_unused_columns: Optional[bool] = field(default=False)
 
@@ -162,6 +163,8 @@ class RepCONCFinetuner(Trainer):
     def __init__(self, qrels, *args, **kwargs):
         super().__init__(*args, **kwargs)
         self.qrels = qrels
+        if getattr(self.args, "deterministic_decode", False):
+            _unwrap(self.model).deterministic_decode = True
         self._gc_scaler = getattr(getattr(self, "accelerator", None), "scaler", None) if self.args.fp16 else None
         if self.args.cache_chunk_size != -1:
             self.gc = GradCache(models=[self.model], chunk_sizes=self.args.cache_chunk_size,

@@ -92,8 +92,13 @@ class RepCONC(nn.Module):
             logger.warning("Sinkhorn Algorithm returns nan/inf values.")
         return codes
 
+    # which backward `decode` takes for the centroid gradient: None follows torch.are_deterministic_algorithms_enabled(),
+    # True is the fixed-order one (bit-reproducible), False the fp32 atomics.  A plain attribute: not a constructor
+    # argument (the reference's signature) and not part of the saved state.
+    deterministic_decode: Optional[bool] = None
+
     def decode(self, codes: Tensor) -> Tensor:
-        return decode(codes, self.centroids)
+        return decode(codes, self.centroids, self.deterministic_decode)
 
     @staticmethod
     def center_distance_for_constraint(distances: Tensor) -> Tensor:
@@ -191,12 +196,13 @@ def sinkhorn_algorithm(out: Tensor, epsilon: float, sinkhorn_iterations: int, us
     return torch.softmax(out / epsilon + f[:, :, None], dim=1)
 
 
-def decode(codes: Union[np.ndarray, Tensor], centroids: Union[np.ndarray, Tensor]):
+def decode(codes: Union[np.ndarray, Tensor], centroids: Union[np.ndarray, Tensor], deterministic: Optional[bool] = None):
     """codes [n, M] -> concatenated centroids [n, D]; torch (differentiable w.r.t. centroids) or
-    numpy in / numpy out.  modeling_repconc.py:168-184.  Both variants run the HIP gather."""
+    numpy in / numpy out.  modeling_repconc.py:168-184.  Both variants run the HIP gather.  deterministic: which backward
+    the torch variant takes (ops.decode)."""
     if isinstance(codes, torch.Tensor):
         assert isinstance(centroids, torch.Tensor)
-        return ops.decode(codes, centroids)
+        return ops.decode(codes, centroids, deterministic)
     if isinstance(codes, np.ndarray):
         dev = torch.device("cuda", torch.cuda.current_device())
         c = centroids.detach() if isinstance(centroids, torch.Tensor) else torch.from_numpy(np.asarray(centroids))

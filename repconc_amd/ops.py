@@ -515,15 +515,21 @@ def decode_raw(codes: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def decode_bwd_ws_bytes(n: int, M: int) -> int:
+    """Workspace of the deterministic backward of `decode` (the row sort); needs no GPU."""
+    return int(_lib.load().rc_pq_decode_bwd_det_ws_bytes(int(n), int(M)))
+
+
 class _DecodeFn(torch.autograd.Function):
     """decode with the scatter-add gradient into the centroids (autograd of the gather at
-    modeling_repconc.py:175)."""
+    modeling_repconc.py:175): fp32 atomics, or — `deterministic` — the fixed-order fp64 sums of csrc/decode_det.hip."""
 
     @staticmethod
-    def forward(ctx, codes, centroids):
+    def forward(ctx, codes, centroids, deterministic):
         ctx.save_for_backward(codes)
         ctx.cshape = tuple(centroids.shape)
         ctx.cdtype = centroids.dtype
+        ctx.deterministic = bool(deterministic)
         return decode_raw(codes, centroids)
 
     @staticmethod
@@ -531,19 +537,31 @@ class _DecodeFn(torch.autograd.Function):
         (codes,) = ctx.saved_tensors
         M, _, dsub = ctx.cshape
         go = grad_out.float().contiguous()
-        gC = torch.zeros(ctx.cshape, dtype=torch.float32, device=go.device)
         codes = codes.contiguous()
-        if codes.shape[0] == 0:
-            return None, gC.to(ctx.cdtype)
+        n = codes.shape[0]
+        if n == 0:
+            return None, torch.zeros(ctx.cshape, dtype=ctx.cdtype, device=go.device), None
         lib, h, s, _ = _ctx(go)
-        _lib.check(lib.rc_pq_decode_bwd(h, _p(codes), _code_dtype(codes), _p(go), codes.shape[0], M, K, dsub,
-                                        _p(gC), s), "rc_pq_decode_bwd", h)
-        return None, gC.to(ctx.cdtype)
+        if ctx.deterministic:
+            gC = torch.empty(ctx.cshape, dtype=torch.float32, device=go.device)        # the entry overwrites
+            wsb = lib.rc_pq_decode_bwd_det_ws_bytes(n, M)
+            ws = torch.empty((wsb,), dtype=torch.uint8, device=go.device) if wsb else None
+            _lib.check(lib.rc_pq_decode_bwd_det(h, _p(codes), _code_dtype(codes), _p(go), n, M, K, dsub, _p(gC), _p(ws), wsb, s),
+                       "rc_pq_decode_bwd_det", h)
+        else:
+            gC = torch.zeros(ctx.cshape, dtype=torch.float32, device=go.device)
+            _lib.check(lib.rc_pq_decode_bwd(h, _p(codes), _code_dtype(codes), _p(go), n, M, K, dsub, _p(gC), s),
+                       "rc_pq_decode_bwd", h)
+        return None, gC.to(ctx.cdtype), None
 
 
-def decode(codes: torch.Tensor, centroids: torch.Tensor) -> torch.Tensor:
+def decode(codes: torch.Tensor, centroids: torch.Tensor, deterministic: Optional[bool] = None) -> torch.Tensor:
+    """decode_raw, differentiable w.r.t. the centroids.  deterministic selects the backward: False = fp32 atomics (the last
+    bits depend on the arrival order), True = fixed-order fp64 sums (include/repconc_hip.h, rc_pq_decode_bwd_det: bit-identical
+    from run to run), None = follow torch.are_deterministic_algorithms_enabled() as it stands at this call."""
     if centroids.requires_grad and torch.is_grad_enabled():
-        return _DecodeFn.apply(codes, centroids)
+        det = torch.are_deterministic_algorithms_enabled() if deterministic is None else bool(deterministic)
+        return _DecodeFn.apply(codes, centroids, det)
     return decode_raw(codes, centroids)
 
 
