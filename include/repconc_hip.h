@@ -600,6 +600,41 @@ int rc_jpq_head_bwd(rc_handle_t h, const float* q, const uint8_t* codes, int64_t
                     const float* g, int nq, int k, int M, int K, int dsub, float* grad_q, float* grad_C, void* ws,
                     size_t ws_bytes, rc_stream_t stream);
 
+/* ------------------------------------------------------------------ stage-1 contrastive loss (csrc/contrastive.hip)
+ * The in-batch softmax loss of stage 1 (models/repconc/finetune_repconc.py:398-451: compute_contrastive_loss with its false-negative
+ * and duplicate masks and the dynamic top-k cut) on a similarity matrix the caller has already computed, and its gradient w.r.t.
+ * that matrix.  No [nd, nd] compare, no [nq, nd] mask, no atomics on values.
+ * sim [nq, nd] fp32 contiguous, finite, 1 <= nq <= nd <= 262144 (the duplicate flags are an all-pairs compare of the ids:
+ * nd^2 / 2; RC_EINVAL above the limit, as for nq > nd); the label of row i is column i.  docids [nd] int64.  The positives of
+ * query i are rel_ids[rel_off[i] .. rel_off[i+1]) — rel_off [nq+1] and rel_ids [R] int64, a row may be empty, both ends are
+ * clamped into [0, R] (rel_ids may be NULL when R == 0).  0 <= topk <= nd, 0 = no cut.  Per row i:
+ *   1. dup[j]    = some i' < j has docids[i'] == docids[j]              (the later occurrences: triu(diagonal=1).any(0))
+ *   2. mask[i,j] = j != i and (dup[j] or docids[j] is one of the positives of i)
+ *   3. z1[i,j]   = fp32(sim[i,j] - 10000) where mask, sim[i,j] elsewhere
+ *   4. topk > 0: neg = z1 with neg[i,i] = -10000; keep = the topk largest of neg[i,:] (ordered as numbers, -0.0 and +0.0 tie;
+ *      ties at the cut go to the lower j; masked columns take part), plus column i;  z = z1 where keep, fp32(z1 - 10000)
+ *      elsewhere.  topk == 0: z = z1 (topk == nd keeps every column: the same).
+ *   5. with mx = max_j z[i,j], e_j = exp((double)z[i,j] - mx), off = sum_{j != i} e_j and sum = off + e_i, all fp64:
+ *      loss_i = (mx + log(sum)) - z[i,i].  off is summed in a fixed order: thread t of 256 adds the columns t, t + 256, ...
+ *      ascending, the 64 lanes of a wave are added as a butterfly, the four waves in order.
+ *      loss = fp32((sum_i loss_i) / nq), i ascending from 0.0 in fp64.
+ *   6. grad_sim[i,j] = fp32((gout * v) / nq) in fp64, v = e_j / sum for j != i and v = -(off / sum) for j == i: the diagonal
+ *      term (e_i - sum) / sum without its cancellation.
+ * z is bit-equal to the torch composition's logits wherever the cut has no tie; loss and gradient are functions of the inputs
+ * alone (bit-identical from run to run).
+ * rc_contrastive_fwd: loss = one device float; z_out [nq, nd] is written only when non-null (test hook).  It fills ws (the
+ *   duplicate flags, nq * ceil(nd / 64) 64-bit words of keep bits, four doubles per row), which
+ * rc_contrastive_bwd reads back together with the same sim, ids and topk: gout = one device float, grad_sim [nq, nd] is overwritten.
+ * ws: rc_contrastive_ws_bytes(nq, nd) bytes (needs no GPU; 0 for arguments outside the limits above); a null or short workspace
+ * is RC_EWORKSPACE. */
+size_t rc_contrastive_ws_bytes(int64_t nq, int64_t nd);
+int rc_contrastive_fwd(rc_handle_t h, const float* sim, const int64_t* docids, const int64_t* rel_off, const int64_t* rel_ids,
+                       int64_t R, int64_t nq, int64_t nd, int64_t topk, float* loss, float* z_out, void* ws, size_t ws_bytes,
+                       rc_stream_t stream);
+int rc_contrastive_bwd(rc_handle_t h, const float* sim, const int64_t* docids, const int64_t* rel_off, const int64_t* rel_ids,
+                       int64_t R, int64_t nq, int64_t nd, int64_t topk, const float* gout, float* grad_sim, const void* ws,
+                       size_t ws_bytes, rc_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

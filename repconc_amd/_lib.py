@@ -133,6 +133,9 @@ PROTOTYPES = {
     "rc_jpq_head_ws_bytes": (_sz, [_i, _i, _i]),
     "rc_jpq_head_fwd": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     "rc_jpq_head_bwd": (_i, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "rc_contrastive_ws_bytes": (_sz, [_i64, _i64]),
+    "rc_contrastive_fwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "rc_contrastive_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lib = None

@@ -61,6 +61,7 @@ class RepCONCFinetuneArguments(TrainingArguments):
     negative: str = field(default="random", metadata={"help": "inbatch, random, or the path of a qid -> [docid] json"})
     cache_chunk_size: int = field(default=-1)
     deterministic_decode: bool = field(default=False, metadata={"help": "fixed-order (bit-reproducible) centroid gradient of decode"})
+    fused_contrastive_loss: bool = field(default=False, metadata={"help": "masks, top-k cut and softmax loss in fused HIP kernels after the GEMM"})
     seed: int = field(default=2022)
     remove_unused_columns: Optional[bool] = field(default=False)
 
@@ -283,6 +284,8 @@ class RepCONCFinetuner(Trainer):
     # ------------------------------------------------------------------ loss
     def compute_contrastive_loss(self, query_embeds, doc_embeds, qids, docids):
         """In-batch softmax over every gathered document, labels on the diagonal.  finetune_repconc.py:398-431."""
+        if getattr(self.args, "fused_contrastive_loss", False):
+            return self._fused_contrastive_loss(query_embeds, doc_embeds, qids, docids)
         nq = query_embeds.shape[0]
         labels = torch.arange(nq, dtype=torch.long, device=query_embeds.device)
         mask = torch.logical_or(self._compute_mask_for_false_negative(qids, docids),
@@ -302,6 +305,27 @@ class RepCONCFinetuner(Trainer):
             drop.scatter_(1, labels[:, None], 0)
             sim = sim - 10000.0 * drop
         return F.cross_entropy(sim, labels)
+
+    def _fused_contrastive_loss(self, query_embeds, doc_embeds, qids, docids):
+        """The same loss with everything after the GEMM in ops.contrastive_loss (csrc/contrastive.hip): the similarity and its
+        two divisions are the torch ops of the composition under the ambient autocast, the positives of the batch's queries go
+        to the device as a CSR built from one `tolist()`."""
+        from ... import ops
+        sim = query_embeds @ doc_embeds.T
+        if getattr(self.model.config, "similarity_metric", None) == "METRIC_CENTROID_COS":
+            sim = sim / self.model.config.MCQ_M
+        if self.args.temperature != 1:
+            sim = sim / self.args.temperature
+        off, rel = [0], []
+        for qid in qids.tolist():
+            rel.extend(self.qrels.get(qid, ()))
+            off.append(len(rel))
+        dev = sim.device
+        topk = self.args.dynamic_topk_hard_negative
+        if topk is not None and topk > sim.shape[1]:
+            raise ValueError(f"dynamic_topk_hard_negative = {topk} exceeds the {sim.shape[1]} documents of the gathered batch")
+        return ops.contrastive_loss(sim.float(), docids, torch.tensor(off, dtype=torch.long, device=dev),
+                                    torch.tensor(rel, dtype=torch.long, device=dev), topk if topk is not None and topk > 0 else 0)
 
     @torch.no_grad()
     def _compute_mask_for_false_negative(self, qids, docids):

@@ -644,6 +644,78 @@ def jpq_scores(q: torch.Tensor, codes: torch.Tensor, pids: torch.Tensor, centroi
     return _JPQScoresFn.apply(q, codes, pids, centroids)
 
 
+# --------------------------------------------------------------------------- stage-1 contrastive loss
+def contrastive_ws_bytes(nq: int, nd: int) -> int:
+    """Workspace of `contrastive_loss` (duplicate flags, keep bits, per-row statistics); needs no GPU."""
+    return int(_lib.load().rc_contrastive_ws_bytes(int(nq), int(nd)))
+
+
+class _ContrastiveLossFn(torch.autograd.Function):
+    """The fused in-batch loss on a similarity matrix and its gradient w.r.t. that matrix (csrc/contrastive.hip); the
+    backward recomputes the logits from sim, the ids and the keep bits the forward left in the workspace."""
+
+    @staticmethod
+    def forward(ctx, sim, docids, rel_off, rel_ids, topk, return_logits):
+        nq, nd = sim.shape
+        simc = sim.detach().contiguous()
+        lib, h, s, _ = _ctx(simc)
+        wsb = lib.rc_contrastive_ws_bytes(nq, nd)
+        if wsb == 0:
+            raise ValueError(f"contrastive_loss needs 1 <= nq <= nd <= 262144 (got nq = {nq}, nd = {nd})")
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=simc.device)
+        loss = torch.empty((), dtype=torch.float32, device=simc.device)
+        z = torch.empty_like(simc) if return_logits else None
+        R = rel_ids.numel()
+        _lib.check(lib.rc_contrastive_fwd(h, _p(simc), _p(docids), _p(rel_off), _p(rel_ids) if R else _p(None), R, nq, nd, topk,
+                                          _p(loss), _p(z), _p(ws), wsb, s), "rc_contrastive_fwd", h)
+        ctx.save_for_backward(simc, docids, rel_off, rel_ids, ws)
+        ctx.topk = topk
+        if return_logits:
+            ctx.mark_non_differentiable(z)
+            return loss, z
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss, *_unused):
+        simc, docids, rel_off, rel_ids, ws = ctx.saved_tensors
+        nq, nd = simc.shape
+        go = grad_loss.detach().float().contiguous()
+        grad = torch.empty_like(simc)
+        lib, h, s, _ = _ctx(simc)
+        R = rel_ids.numel()
+        _lib.check(lib.rc_contrastive_bwd(h, _p(simc), _p(docids), _p(rel_off), _p(rel_ids) if R else _p(None), R, nq, nd, ctx.topk,
+                                          _p(go), _p(grad), _p(ws), ws.numel(), s), "rc_contrastive_bwd", h)
+        return grad, None, None, None, None, None
+
+
+def contrastive_loss(sim: torch.Tensor, docids: torch.Tensor, rel_off: torch.Tensor, rel_ids: torch.Tensor, topk: int = 0,
+                     return_logits: bool = False):
+    """Stage 1's in-batch softmax loss on sim [nq, nd] fp32 (label of row i = column i), differentiable w.r.t. sim.
+
+    docids [nd] int64; the positives of query i are rel_ids[rel_off[i]:rel_off[i + 1]] (int64 CSR, rows may be empty).  A column
+    is masked (-10000) when its docid repeats an earlier column's or is a positive of the row, the diagonal excepted; topk > 0
+    keeps the topk largest remaining negatives of a row plus its label and pushes the rest down by another 10000 (the reference's
+    dynamic_topk_hard_negative).  Masks, cut, log-softmax and gradient are one pass of HIP kernels after the caller's GEMM, in a
+    fixed order (include/repconc_hip.h, rc_contrastive_*): bit-reproducible, no [nd, nd] or [nq, nd] mask is ever allocated.
+    return_logits: also return the fp32 logits z [nq, nd] (not differentiable; a test hook)."""
+    _need_cuda(sim, docids, rel_off, rel_ids)
+    if sim.dim() != 2 or docids.dim() != 1 or rel_off.dim() != 1 or rel_ids.dim() != 1:
+        raise ValueError("expected sim [nq, nd], docids [nd], rel_off [nq + 1], rel_ids [R]")
+    nq, nd = sim.shape
+    if any(t.device != sim.device for t in (docids, rel_off, rel_ids)):
+        raise ValueError(f"docids, rel_off and rel_ids must be on sim's device ({sim.device}): the kernels run there")
+    if sim.dtype != torch.float32:
+        raise ValueError("sim must be float32 (take .float() of an autocast GEMM's output)")
+    if docids.dtype != torch.int64 or rel_off.dtype != torch.int64 or rel_ids.dtype != torch.int64:
+        raise ValueError("docids, rel_off and rel_ids must be int64")
+    if docids.shape[0] != nd or rel_off.shape[0] != nq + 1:
+        raise ValueError(f"docids must hold nd = {nd} ids and rel_off nq + 1 = {nq + 1} offsets")
+    topk = int(topk)
+    if not 0 <= topk <= nd:
+        raise ValueError(f"topk must be in [0, nd = {nd}]")
+    return _ContrastiveLossFn.apply(sim, docids.contiguous(), rel_off.contiguous(), rel_ids.contiguous(), topk, bool(return_logits))
+
+
 # --------------------------------------------------------------------------- small ops
 def normalize_centroids_(centroids: torch.Tensor) -> torch.Tensor:
     _need_cuda(centroids)
