@@ -12,20 +12,128 @@ query_attention_mask, qids) -> {"loss"}`, `synchronize_model_index`, `normalize_
     resident uint8 codes are gathered and decoded directly (`rc_pq_decode` takes uint8), with the scatter-add backward
     into the centroids (`rc_pq_decode_bwd`).
 
-The HF-Trainer subclass (`JPQFinetuner`), its callbacks and the dataset/collator are harness and stay out of scope;
-`jpq_step_end` is what those callbacks do after each optimiser step.
+Around it, with the reference's names (finetune_jpq.py:31-139,246-373): `DataTrainingArguments`, `JPQFinetuneArguments`,
+`FinetuneQueryCollator`, `QueryDataset`, `JPQ_SyncIndex_Callback` and the HF-Trainer subclass `JPQFinetuner` on the
+transformers 5.x Trainer.  `jpq_step_end` is what the two callbacks do after each optimiser step, for callers that run
+their own loop.  Validation (`JPQFinetuner.evaluate`) searches the resident training index: no clone, no second copy of
+the codes.
 """
 from __future__ import annotations
 
+import inspect
+import logging
+import os
 import random
-from typing import Dict, List
+from collections import defaultdict
+from dataclasses import dataclass, field
+from typing import Any, Dict, List, Optional
 
+import numpy as np
 import torch
 from torch import nn
+from torch.utils.data import Dataset
+from transformers import Trainer, TrainerCallback, TrainingArguments
 
 from ... import ops
 from ...index import PQIndex
+from ..repconc.finetune_repconc import (RepCONC_Norm_Centroid_Callback, inference_settings, map_evaluation_strategy,
+                                        tokenizer_keywords, validation_max_length, validation_metrics)
 from ..repconc.modeling_repconc import RepCONC
+
+logger = logging.getLogger(__name__)
+
+
+@dataclass
+class DataTrainingArguments:
+    """finetune_jpq.py:31-37."""
+    qrel_path: str = field()
+    query_path: str = field()
+    valid_qrel_path: str = field()
+    valid_query_path: str = field()
+    max_query_len: int = field()
+
+
+@dataclass
+class JPQFinetuneArguments(TrainingArguments):
+    """finetune_jpq.py:40-49, plus this package's two switches and the two command-line compatibility fields of stage 1."""
+    dynamic_topk_negative: int = field(default=200)
+    centroid_learning_rate: float = field(default=1e-3)
+    temperature: float = field(default=1.0)
+    seed: int = field(default=2023)
+    remove_unused_columns: Optional[bool] = field(default=False)
+    head: str = field(default="decode", metadata={"help": "decode: rows decoded then scored; fused: ops.jpq_scores (deterministic)",
+                                                  "choices": ["decode", "fused"]})
+    deterministic_decode: bool = field(default=False, metadata={"help": "fixed-order (bit-reproducible) centroid gradient of decode"})
+    evaluation_strategy: Optional[str] = field(default=None, metadata={"help": "the recipes' name of --eval_strategy"})
+    overwrite_output_dir: bool = field(default=False, metadata={"help": "resume from the last checkpoint of a used output_dir"})
+
+    def __post_init__(self):
+        map_evaluation_strategy(self)
+        super().__post_init__()
+
+
+class FinetuneQueryCollator:
+    """Tokenises the queries of a batch; the query offsets travel along as `qids`.  finetune_jpq.py:53-83."""
+
+    def __init__(self, tokenizer, max_query_len: int):
+        self.tokenizer, self.max_query_len = tokenizer, max_query_len
+        try:
+            typed = "input_text_type" in inspect.signature(tokenizer.__call__).parameters
+        except (TypeError, ValueError):
+            typed = False
+        self.input_query_text_type = {"input_text_type": "query"} if typed else {}
+
+    def __call__(self, features: List[Dict[str, Any]]) -> Dict[str, Any]:
+        query_input = self.tokenizer([f["query"] for f in features], padding=True, return_tensors="pt",
+                                     add_special_tokens=True, return_attention_mask=True, return_token_type_ids=False,
+                                     truncation=True, max_length=self.max_query_len, **self.input_query_text_type)
+        return {"query_input_ids": query_input["input_ids"], "query_attention_mask": query_input["attention_mask"],
+                "qids": torch.tensor([f["qid"] for f in features], dtype=torch.long)}
+
+
+class QueryDataset(Dataset):
+    """One item per training query that has a positive: {"query", "qid"}.  Queries are addressed by line offset in
+    `query_path`, documents by their row in the index (`index_doc_ids`, the corpus_ids.npy next to the index file);
+    `get_qrels()` is {query offset: [index rows]} — what `JPQ` takes.  finetune_jpq.py:86-139."""
+
+    def __init__(self, tokenizer, qrel_path: str, query_path: str, max_query_len: int, index_doc_ids, rel_threshold=1,
+                 verbose=True):
+        super().__init__()
+        self.tokenizer = tokenizer
+        docid2offset = {str(docid): i for i, docid in enumerate(np.asarray(index_doc_ids).tolist())}
+        self.queries, qid2offset = [], {}
+        with open(query_path) as f:
+            for i, line in enumerate(f):
+                qid, query = line.split("\t")
+                qid2offset[qid] = i
+                self.queries.append(query.strip())
+        qrels = defaultdict(list)
+        with open(qrel_path) as f:
+            for lineno, line in enumerate(f, 1):
+                qid, _, docid, rel = line.split()
+                if int(rel) < rel_threshold:
+                    continue
+                if qid not in qid2offset:
+                    raise ValueError(f"{qrel_path}:{lineno}: query {qid!r} is not in {query_path}")
+                if docid not in docid2offset:
+                    raise ValueError(f"{qrel_path}:{lineno}: document {docid!r} is not among the {len(docid2offset)} ids of the index")
+                qrels[qid2offset[qid]].append(docid2offset[docid])
+        self.qrels = dict(qrels)
+        self.qids = sorted(self.qrels)
+        self.max_query_len = max_query_len
+        if verbose:
+            logger.info("%d training queries with a positive, %d queries, %d index rows", len(self.qids), len(self.queries),
+                        len(docid2offset))
+
+    def get_qrels(self):
+        return self.qrels
+
+    def __len__(self):
+        return len(self.qids)
+
+    def __getitem__(self, index):
+        qid = self.qids[index]
+        return {"query": self.queries[qid], "qid": qid}
 
 
 class JPQ(nn.Module):
@@ -127,3 +235,75 @@ def jpq_step_end(model: JPQ):
     if getattr(model.repconc.config, "similarity_metric", None) == "METRIC_CENTROID_COS":
         model.normalize_centrodis()
     model.synchronize_model_index()
+
+
+class JPQ_SyncIndex_Callback(TrainerCallback):
+    """After every optimiser step the index scores with the centroids the step produced.  finetune_jpq.py:246-252."""
+
+    def on_step_end(self, args, state, control, model=None, **kwargs):
+        model.synchronize_model_index()
+
+
+class JPQFinetuner(Trainer):
+    """`JPQFinetuner(model=JPQ, args=JPQFinetuneArguments, train_dataset=QueryDataset, data_collator=FinetuneQueryCollator,
+    tokenizer=..., eval_dataset=(corpus_ids, queries, qrels))`, finetune_jpq.py:255-373.  The training step is the stock
+    one (`JPQ.forward` returns {"loss"}).  Centroids are normalised (METRIC_CENTROID_COS) BEFORE they are copied into the
+    index: the callbacks run in the order they were added.  Checkpoints hold the wrapped RepCONC in the layout
+    `RepCONC.from_pretrained` reads; the stock loading hooks find pytorch_model.bin and hand it to `JPQ.load_state_dict`,
+    which re-synchronises the index."""
+
+    def __init__(self, *args, **kwargs):
+        tokenizer = tokenizer_keywords(kwargs)
+        super().__init__(*args, **kwargs)
+        self.tokenizer = tokenizer
+        if getattr(self.args, "deterministic_decode", False):
+            self.model.repconc.deterministic_decode = True
+        if getattr(self.model.repconc.config, "similarity_metric", None) == "METRIC_CENTROID_COS":
+            self.add_callback(RepCONC_Norm_Centroid_Callback)
+        self.add_callback(JPQ_SyncIndex_Callback)
+
+    def floating_point_ops(self, inputs):
+        return 0
+
+    def _save(self, output_dir: Optional[str] = None, state_dict=None):
+        """pytorch_model.bin (rotation, centroids, dense_encoder.*) + config + dense_encoder/ (:269-272), the tokenizer and
+        the arguments: the directory `RepCONC.from_pretrained` and run_repconc_eval's `replace_pq_centroids` read."""
+        output_dir = output_dir or self.args.output_dir
+        self.model.repconc.save_pretrained(output_dir)
+        if self.tokenizer is not None:
+            self.tokenizer.save_pretrained(output_dir)
+        torch.save(self.args, os.path.join(output_dir, "training_args.bin"))
+
+    def evaluate(self, eval_dataset=None, ignore_keys=None, metric_key_prefix: str = "eval") -> Dict[str, float]:
+        """In-training validation, finetune_jpq.py:274-319: the validation queries encoded in fp32 by the wrapped model and
+        searched at depth 10 in the resident index (its centroids are the model's after every step), trec measures at cut
+        10 logged as `<prefix>_<measure>`."""
+        from ..repconc.evaluate_repconc import batch_search, encode_query
+        corpus_ids, queries, qrels = eval_dataset if eval_dataset is not None else self.eval_dataset
+        repconc = self.model.repconc
+        with inference_settings(self.args):
+            query_embeds, query_ids = encode_query(queries, repconc, self.tokenizer, validation_max_length(repconc.config),
+                                                   self.args)
+        all_topk_scores, all_topk_ids = batch_search(query_ids, query_embeds.astype(np.float32), corpus_ids,
+                                                     self.model.pq_index, topk=10, batch_size=512)
+        metrics = validation_metrics(qrels, query_ids, all_topk_scores, all_topk_ids, metric_key_prefix)
+        self.log(dict(metrics))              # Trainer.log adds its own keys to what it is given
+        # as the stock evaluate: clears should_evaluate (else a step that ends an epoch validates twice), feeds early stopping
+        self.control = self.callback_handler.on_evaluate(self.args, self.state, self.control, metrics)
+        return metrics
+
+    def create_optimizer(self, *args, **kwargs):
+        """Three groups as in stage 1: decayed / undecayed encoder parameters, centroids at `centroid_learning_rate` without
+        decay; the rotation is a buffer and in none.  finetune_jpq.py:321-373."""
+        if self.optimizer is None:
+            named = [(n, p) for n, p in self.model.named_parameters() if p.requires_grad]
+            no_decay = {n for n, p in named if p.ndim < 2 or "bias" in n or "LayerNorm" in n or "layer_norm" in n}
+            groups = [
+                {"params": [p for n, p in named if n not in no_decay and "centroids" not in n], "weight_decay": self.args.weight_decay},
+                {"params": [p for n, p in named if n in no_decay and "centroids" not in n], "weight_decay": 0.0},
+                {"params": [p for n, p in named if "centroids" in n], "weight_decay": 0.0, "lr": self.args.centroid_learning_rate},
+            ]
+            logger.info("optimizer groups: %s", [len(g["params"]) for g in groups])
+            self.optimizer = torch.optim.AdamW(groups, lr=self.args.learning_rate, betas=(self.args.adam_beta1, self.args.adam_beta2),
+                                               eps=self.args.adam_epsilon)
+        return self.optimizer

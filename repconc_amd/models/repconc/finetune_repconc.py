@@ -9,6 +9,9 @@ the cached gradient applied to the continuous embedding (straight-through) and t
 weighted MSE), the cross-rank gather of representations and ids, the three optimiser groups, centroid re-normalisation
 for METRIC_CENTROID_COS.  What changed: no use of Trainer members that 5.x dropped (`use_amp`, `scaler`, `use_apex`,
 `sharded_ddp`, `_prepare_inputs` on nested dicts), fp16 scaling goes through the accelerator's scaler.
+`RepCONCFinetuner.evaluate` is the in-training validation (:530-577); `_save` also writes the tokenizer, so that the output
+directory and every checkpoint load with `AutoTokenizer.from_pretrained`; the recipes' `--evaluation_strategy` and
+`--overwrite_output_dir` are fields of the arguments.
 The arithmetic of quantize / decode / decode-backward / the balance statistics is `repconc_amd.ops`.
 """
 from __future__ import annotations
@@ -19,10 +22,11 @@ import logging
 import os
 import random
 from collections import defaultdict
-from contextlib import nullcontext
+from contextlib import contextmanager, nullcontext
 from dataclasses import dataclass, field
 from typing import Any, Dict, List, Optional
 
+import numpy as np
 import torch
 import torch.distributed as dist
 import torch.nn.functional as F
@@ -64,10 +68,84 @@ class RepCONCFinetuneArguments(TrainingArguments):
     fused_contrastive_loss: bool = field(default=False, metadata={"help": "masks, top-k cut and softmax loss in fused HIP kernels after the GEMM"})
     seed: int = field(default=2022)
     remove_unused_columns: Optional[bool] = field(default=False)
+    evaluation_strategy: Optional[str] = field(default=None, metadata={"help": "the recipes' name of --eval_strategy"})
+    overwrite_output_dir: bool = field(default=False, metadata={"help": "resume from the last checkpoint of a used output_dir"})
+
+    def __post_init__(self):
+        map_evaluation_strategy(self)
+        super().__post_init__()
+
+
+def map_evaluation_strategy(args):
+    """The recipes pass `--evaluation_strategy`, which TrainingArguments renamed to `eval_strategy`: the old name fills the
+    new field before TrainingArguments validates it.  Both given and different is an error."""
+    old = args.evaluation_strategy
+    if old is None:
+        return
+    new = getattr(args.eval_strategy, "value", args.eval_strategy)
+    if new not in (None, "no") and new != old:
+        raise ValueError(f"--evaluation_strategy {old} and --eval_strategy {new} disagree: pass one of them")
+    args.eval_strategy = old
 
 
 def _unwrap(model):
     return model.module if hasattr(model, "module") else model
+
+
+# the keyword the installed Trainer takes the tokenizer under (`tokenizer` until transformers 4.x, `processing_class` since)
+_TOKENIZER_KEYWORD = "processing_class" if "processing_class" in inspect.signature(Trainer.__init__).parameters else "tokenizer"
+
+
+def tokenizer_keywords(kwargs: Dict[str, Any]):
+    """Takes `tokenizer=` (the reference's call) and / or `processing_class=` out of a trainer's keyword arguments and puts
+    the tokenizer back under the name the installed Trainer takes.  Returns the tokenizer (None when neither was given)."""
+    old, new = kwargs.pop("tokenizer", None), kwargs.pop("processing_class", None)
+    if old is not None and new is not None and old is not new and old != new:
+        raise ValueError("tokenizer= and processing_class= name two different objects: pass one of them")
+    tokenizer = old if old is not None else new
+    if tokenizer is not None:
+        kwargs[_TOKENIZER_KEYWORD] = tokenizer
+    return tokenizer
+
+
+@contextmanager
+def inference_settings(args, model=None):
+    """What both trainers switch off while `evaluate` encodes (finetune_repconc.py:539-549, finetune_jpq.py:285-291):
+    the arguments' fp16 / bf16 / dataloader_drop_last and, for a model given, its `use_constraint` (validation codes are
+    the nearest ones).  Everything is put back on the way out, also when an exception passes through."""
+    saved = (args.fp16, args.bf16, args.dataloader_drop_last)
+    constraint = model.use_constraint if model is not None else None
+    args.fp16, args.bf16, args.dataloader_drop_last = False, False, False
+    if model is not None:
+        model.use_constraint = False
+    try:
+        yield
+    finally:
+        args.fp16, args.bf16, args.dataloader_drop_last = saved
+        if model is not None:
+            model.use_constraint = constraint
+
+
+def validation_max_length(config) -> int:
+    """The reference encodes the validation texts at 512 tokens (finetune_repconc.py:545-546); an encoder with fewer
+    positions takes what it has."""
+    return min(512, int(getattr(config, "max_position_embeddings", None) or 512))
+
+
+def validation_metrics(qrels, query_ids, all_topk_scores, all_topk_ids, metric_key_prefix: str) -> Dict[str, float]:
+    """Search result -> {"<prefix>_<measure>"} for every summary measure of `pytrec_evaluate` at cut 10
+    (finetune_repconc.py:560-573).  The run dictionary is built from the host arrays in one pass (`tolist()`)."""
+    from ...utils.eval_utils import pytrec_evaluate
+    run = {str(qid): dict(zip(map(str, row_ids), row_scores))
+           for qid, row_scores, row_ids in zip(np.asarray(query_ids).tolist(), np.asarray(all_topk_scores).tolist(),
+                                               np.asarray(all_topk_ids).tolist())}
+    metrics = {}
+    for category, cat_metrics in pytrec_evaluate(qrels, run, k_values=(10,), mrr_k_values=(10,)).items():
+        if category == "perquery":
+            continue
+        for metric, score in cat_metrics.items():
+            metrics[f"{metric_key_prefix}_{metric}"] = score
+    return metrics
 
 
 class FinetuneCollator:
@@ -159,10 +237,15 @@ class RepCONC_Norm_Centroid_Callback(TrainerCallback):
 
 
 class RepCONCFinetuner(Trainer):
-    """`RepCONCFinetuner(qrels, model=..., args=RepCONCFinetuneArguments, train_dataset=..., data_collator=...)`."""
+    """`RepCONCFinetuner(qrels, model=..., args=RepCONCFinetuneArguments, train_dataset=..., data_collator=...,
+    tokenizer=..., eval_dataset=(corpus, queries, qrels))`.  The tokenizer may come as `tokenizer=` (the reference's call,
+    run_train_conc.py:129-137) or `processing_class=`; `evaluate` and `_save` use it as `self.tokenizer`.  The validation
+    triple is only stored by the base class: `evaluate` is this class's own."""
 
     def __init__(self, qrels, *args, **kwargs):
+        tokenizer = tokenizer_keywords(kwargs)
         super().__init__(*args, **kwargs)
+        self.tokenizer = tokenizer
         self.qrels = qrels
         if getattr(self.args, "deterministic_decode", False):
             _unwrap(self.model).deterministic_decode = True
@@ -347,8 +430,34 @@ class RepCONCFinetuner(Trainer):
         return 0
 
     def _save(self, output_dir: Optional[str] = None, state_dict=None):
+        """pytorch_model.bin + config + dense_encoder/ (:471-474), the tokenizer and the arguments: what
+        `RepCONC.from_pretrained` / `AutoTokenizer.from_pretrained` read, and — pytorch_model.bin being the name the stock
+        `_load_from_checkpoint` / `_load_best_model` look for — what resume and `load_best_model_at_end` load back."""
         output_dir = output_dir or self.args.output_dir
-        _unwrap(self.model).save_pretrained(output_dir)          # pytorch_model.bin + config + dense_encoder/ (:466-469)
+        _unwrap(self.model).save_pretrained(output_dir)
+        if self.tokenizer is not None:
+            self.tokenizer.save_pretrained(output_dir)
+        torch.save(self.args, os.path.join(output_dir, "training_args.bin"))
+
+    def evaluate(self, eval_dataset=None, ignore_keys=None, metric_key_prefix: str = "eval") -> Dict[str, float]:
+        """In-training validation, finetune_repconc.py:530-577: the validation corpus coded by nearest centroid and the
+        queries encoded in fp32, the codes searched at depth 10, trec measures at cut 10 logged as `<prefix>_<measure>`.
+        The model is left in eval mode; `training_step` sets its own."""
+        from .evaluate_repconc import batch_search, encode_corpus, encode_query, from_pq_to_ivfpq, load_index_to_gpu
+        corpus, queries, qrels = eval_dataset if eval_dataset is not None else self.eval_dataset
+        core = _unwrap(self.model)
+        max_length = validation_max_length(core.config)
+        with inference_settings(self.args, core):
+            index, corpus_ids = encode_corpus(corpus, core, self.tokenizer, max_length, self.args)
+            query_embeds, query_ids = encode_query(queries, core, self.tokenizer, max_length, self.args)
+        index = load_index_to_gpu(from_pq_to_ivfpq(index), index.device.index)      # the model's device, as :553
+        all_topk_scores, all_topk_ids = batch_search(query_ids, query_embeds.astype(np.float32), corpus_ids, index,
+                                                     topk=10, batch_size=512)
+        metrics = validation_metrics(qrels, query_ids, all_topk_scores, all_topk_ids, metric_key_prefix)
+        self.log(dict(metrics))              # Trainer.log adds its own keys to what it is given
+        # as the stock evaluate: clears should_evaluate (else a step that ends an epoch validates twice), feeds early stopping
+        self.control = self.callback_handler.on_evaluate(self.args, self.state, self.control, metrics)
+        return metrics
 
     def create_optimizer(self, *args, **kwargs):
         """Three groups: decayed / undecayed encoder parameters, centroids at `centroid_learning_rate` without decay.
