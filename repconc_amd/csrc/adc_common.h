@@ -1,9 +1,9 @@
-// Shared pieces of the flat ADC search (adc_search.hip) and the list-centric IVF search (ivf_lists.hip, ivfs_*.h) that are
-// about ADC tables and codes: limits, the supported widths, the conflict-free slot rule, the 16-query slot rule, the 8-bit
-// quantiser with the per-query table summary and its record, the IVF task list, the exact rescoring kernel and the launcher of
-// the image kernels.  The selection stage (score keys, k-th largest, the
-// candidate-list limits, top-k host interface) is topk.h.  Device functions, templates and static host helpers only (no -fgpu-rdc:
-// every translation unit compiles its own copy).
+// Shared pieces of the flat ADC search (adc_search.hip with its screens adc_screen16.h and adc_screen_r1.h) and the list-centric
+// IVF search (ivf_lists.hip, ivfs_*.h) that are about ADC tables and codes: limits, the supported widths, the conflict-free slot
+// rule, the 16-query slot rule, the 8-bit quantiser with the per-query table summary and its record, the IVF task list, the load
+// of a row's code bytes, the exact rescoring kernel and the launcher of the image kernels.  The selection stage (score keys,
+// k-th largest, the candidate-list limits and the wave append to a list, top-k host interface) is topk.h.  Device functions,
+// templates and static host helpers only (no -fgpu-rdc: every translation unit compiles its own copy).
 #pragma once
 #include "topk.h"
 #include <limits.h>
@@ -27,6 +27,15 @@ __host__ __device__ constexpr int adc_cf_max_width() {
     ADC_CF_WIDTHS(ADC_CF_MAX)
 #undef ADC_CF_MAX
     return w;
+}
+// widths the screened flat search is compiled for, as (M, queries per block of the fp32 scan): rc_adc_search* (ADC_CASE), the
+// templated scores of rc_adc_search_exact (ADC_EXACT_CASE) and adc_search_supported are generated from this list; every other
+// divisor of D is answered by the exact scan with a run-time width (rc_adc_search_exact, adc_scan_rt_kernel)
+#define ADC_SEARCH_WIDTHS(X) X(8, 4) X(12, 4) X(16, 4) X(24, 4) X(32, 4) X(48, 2) X(64, 2) X(96, 1)
+static inline bool adc_search_supported(int M) {
+#define ADC_SEARCH_IS(MM, QQ) || M == MM
+    return false ADC_SEARCH_WIDTHS(ADC_SEARCH_IS);
+#undef ADC_SEARCH_IS
 }
 
 // ---- conflict-free slot rule (round 2; today the table phases of the IVF screen, ivf_lists.hip) ------------------
@@ -155,7 +164,7 @@ __device__ __forceinline__ adc_table_sums adc_qstat_summary(const float* st) {
 typedef int adc_i32x4v __attribute__((ext_vector_type(4)));
 typedef unsigned adc_u32x2v __attribute__((ext_vector_type(2)));
 
-// 16-query gathers (ds_read_b128; adc_search.hip 4b'', ivfs_screen16.h): position of a lane inside its service group of 16
+// 16-query gathers (ds_read_b128; adc_screen16.h, ivfs_screen16.h): position of a lane inside its service group of 16
 // lanes ({0-3,12-15,20-27}, {4-11,16-19,28-31} and the same + 32), and the sub-quantiser (within its phase of 16) = LDS slot
 // that lane `lane` of a wave reads in step j — distinct inside every service group, the four lanes of a row cover all 16
 __host__ __device__ constexpr int adc_q16_pos(int h32) {
@@ -174,18 +183,13 @@ struct adc_ivf_tasks {
     const int* ntasks;           // device-side task count when the list is padded (rc_ivf_search_probes), else NULL
 };
 
-// One block per query: exact fp32 score (m ascending, from 0) of every screened row; rows with score >= tau go
-// to the key list exactly as adc_scan_kernel<FILTER> would have put them.
-// A block's table is 4 M x 256 bytes of LDS and every survivor costs one dependent M-byte read from HBM, so the kernel lives
-// on rows in flight: the block is as large as the LDS lets the CU hold 16+ waves (adc_rescore_threads), the table and the
-// codes move in 16-byte pieces, and every thread has two rows in flight (round 4; 512 threads and 4-byte loads before:
-// M = 96 ran 8 waves per CU).
-template <int M>
-__device__ __forceinline__ float adc_rescore_row(const uint8_t* __restrict__ cp, const float* __restrict__ tab) {
-    constexpr int W = (M % 16 == 0) ? 16 : (M % 8 == 0) ? 8 : 4;  // load width in bytes
-    unsigned w[M / 4];
+// A row's NB code bytes (cp aligned to the load width) into dwords, by the widest aligned load: 16-byte loads when NB % 16 == 0,
+// 8-byte when NB % 8 == 0, else 4-byte.  The scan, the round-1 screens (the matrix-core one on half a row) and the rescorer.
+template <int NB>
+__device__ __forceinline__ void adc_load_code_bytes(const uint8_t* cp, unsigned (&w)[NB / 4]) {
+    constexpr int W = (NB % 16 == 0) ? 16 : (NB % 8 == 0) ? 8 : 4;  // load width in bytes
 #pragma unroll
-    for (int j = 0; j < M / W; ++j) {
+    for (int j = 0; j < NB / W; ++j) {
         if constexpr (W == 16) {
             const uint4 v = reinterpret_cast<const uint4*>(cp)[j];
             w[4 * j] = v.x; w[4 * j + 1] = v.y; w[4 * j + 2] = v.z; w[4 * j + 3] = v.w;
@@ -196,14 +200,21 @@ __device__ __forceinline__ float adc_rescore_row(const uint8_t* __restrict__ cp,
             w[j] = reinterpret_cast<const unsigned*>(cp)[j];
         }
     }
+}
+
+// One block per query: exact fp32 score (m ascending, from 0) of every screened row; rows with score >= tau go
+// to the key list exactly as adc_scan_kernel<FILTER> would have put them.
+// A block's table is 4 M x 256 bytes of LDS and every survivor costs one dependent M-byte read from HBM, so the kernel lives
+// on rows in flight: the block is as large as the LDS lets the CU hold 16+ waves (adc_rescore_threads), the table and the
+// codes move in 16-byte pieces, and every thread has two rows in flight (round 4; 512 threads and 4-byte loads before:
+// M = 96 ran 8 waves per CU).
+template <int M>
+__device__ __forceinline__ float adc_rescore_row(const uint8_t* __restrict__ cp, const float* __restrict__ tab) {
+    unsigned w[M / 4];
+    adc_load_code_bytes<M>(cp, w);
     float s = 0.f;
-#if defined(RC_ABL_RESCORE) && (RC_ABL_RESCORE & 2)
-#pragma unroll
-    for (int m = 0; m < M / 4; ++m) s = s + __uint_as_float(w[m]);
-#else
 #pragma unroll
     for (int m = 0; m < M; ++m) s = s + tab[m * RC_K + ((w[m >> 2] >> (8 * (m & 3))) & 0xFFu)];
-#endif
     return s;
 }
 
@@ -264,18 +275,9 @@ __global__ __launch_bounds__(1024) void adc_rescore_kernel(const uint8_t* __rest
             const float sc = h ? sb : sa;
             const unsigned n = h ? nb : na;
             const bool pass = live && (sc >= tau);
-#if defined(RC_ABL_RESCORE) && (RC_ABL_RESCORE & 1)
-            const unsigned long long mask = __ballot(pass && sc == 12345.678f);
-#else
             const unsigned long long mask = __ballot(pass);
-#endif
             if (mask) {
-                const int lane = tid & 63;
-                const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-                unsigned base = 0;
-                if (lane == (int)__builtin_ctzll(mask)) base = atomicAdd(&s_slots, (unsigned)__popcll(mask));
-                base = __shfl(base, (int)__builtin_ctzll(mask));
-                const unsigned slot = base0 + base + rank;
+                const unsigned slot = base0 + adc_wave_append(mask, &s_slots);
                 if (pass && slot < ADC_CAND_CAP) {
                     // IVF: rows are stored cell-major; the key carries the row's corpus position so ties order by corpus id
                     const unsigned id = rowmap ? (unsigned)rowmap[n] : n;
@@ -286,12 +288,6 @@ __global__ __launch_bounds__(1024) void adc_rescore_kernel(const uint8_t* __rest
     }
     __syncthreads();
     if (tid == 0 && s_slots) cand_count[qi] = base0 + s_slots;
-}
-
-// widths the screened flat search is compiled for (rc_adc_search*: ADC_CASE); every other divisor of D is answered by the exact
-// scan with a run-time width (rc_adc_search_exact, adc_scan_rt_kernel)
-static inline bool adc_search_supported(int M) {
-    return M == 8 || M == 12 || M == 16 || M == 24 || M == 32 || M == 48 || M == 64 || M == 96;
 }
 
 // (Re)build rows [n0, n0 + n) of a permuted code image from the canonical codes [N, M]: the one launcher of the three image

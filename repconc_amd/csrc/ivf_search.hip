@@ -104,12 +104,7 @@ __global__ __launch_bounds__(256) void ivf_filter_kernel(const float* __restrict
         const bool pass = live && (s >= tau);
         const unsigned long long mask = __ballot(pass);
         if (mask) {
-            const int lane = threadIdx.x & 63;
-            const int rank = __popcll(mask & ((1ull << lane) - 1ull));
-            unsigned b = 0;
-            if (lane == (int)__builtin_ctzll(mask)) b = atomicAdd(cand_count + qi, (unsigned)__popcll(mask));
-            b = __shfl(b, (int)__builtin_ctzll(mask));
-            const unsigned slot = b + rank;
+            const unsigned slot = adc_wave_append(mask, cand_count + qi);
             if (pass && slot < ADC_CAND_CAP) {
                 const unsigned id = (unsigned)ids[rid[i]];
                 cand[(size_t)qi * ADC_CAND_CAP + slot] = adc_exact_key(s, id);

@@ -170,6 +170,19 @@ __device__ __forceinline__ unsigned long long adc_exact_key(float s, int64_t i) 
     return ((unsigned long long)adc_order_key(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)i);
 }
 
+// Append by the lanes of a wave to a list whose length is `counter` (global or LDS): `mask` = __ballot of the lanes that have an
+// entry (not 0; every lane of the wave calls, in a block of whole waves whose x index numbers the lanes).  The lowest set lane
+// adds popcount(mask) with ONE atomic, the old length is broadcast, and a lane's slot is that base + its rank among the set
+// lanes below it.  The capacity test and the store are the caller's.
+__device__ __forceinline__ unsigned adc_wave_append(unsigned long long mask, unsigned* counter) {
+    const int lane = threadIdx.x & 63, leader = (int)__builtin_ctzll(mask);
+    const int rank = __popcll(mask & ((1ull << lane) - 1ull));
+    unsigned base = 0;
+    if (lane == leader) base = atomicAdd(counter, (unsigned)__popcll(mask));
+    base = __shfl(base, leader);
+    return base + rank;
+}
+
 // ---- host interface (topk.hip) ---------------------------------------------------------------------------------------
 // rank of the sample score used as the candidate threshold (header text at rc_adc_search)
 int rc_adc_sample_rank(int64_t N, int64_t S, int k, double sel_slack);

@@ -328,11 +328,7 @@ __global__ __launch_bounds__(256) void adc_exact_collect_kernel(const float* __r
         const bool pass = i < N && key >= kth;
         const unsigned long long mask = __ballot(pass);
         if (mask) {
-            const int lane = tid & 63;
-            unsigned base = 0;
-            if (lane == (int)__builtin_ctzll(mask)) base = atomicAdd(cand_count + qx, (unsigned)__popcll(mask));
-            base = __shfl(base, (int)__builtin_ctzll(mask));
-            const unsigned slot = base + (unsigned)__popcll(mask & ((1ull << lane) - 1ull));
+            const unsigned slot = adc_wave_append(mask, cand_count + qx);
             if (pass && slot < ADC_CAND_CAP) cand[(size_t)qx * ADC_CAND_CAP + slot] = key;
         }
     }

@@ -876,7 +876,7 @@ def adc_scan_image_(codes: torch.Tensor, image: torch.Tensor, n0: int = 0, n: Op
     return image
 
 
-SEARCH_SCREEN_M = frozenset((8, 12, 16, 24, 32, 48, 64, 96))      # widths of the screened flat search (csrc/adc_search.hip)
+SEARCH_SCREEN_M = frozenset((8, 12, 16, 24, 32, 48, 64, 96))      # widths of the screened flat search: the M of ADC_SEARCH_WIDTHS (csrc/adc_common.h)
 # Default head-room of the sampled candidate threshold: the threshold is the r-th best score of the 32 768-row sample,
 # r = floor(mu + slack sqrt(mu + 1) + 4) + 1 with mu = k S / N expected top-k rows in the sample (rc_adc_search_q).  A query whose
 # sample holds MORE than r - 1 of the true top-k keeps too few candidates and is repeated alone (~1 ms, PendingSearch).  Round 6:

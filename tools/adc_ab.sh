@@ -1,15 +1,15 @@
 #!/bin/bash
-# Round 6: A/B timing of the 16-query ADC screen under structural switches (development tool, GPU).
+# A/B timing of the 16-query ADC screen (csrc/adc_screen16.h) at other waves x chunks geometries (development tool, GPU).
 #   build here (no GPU):  tools/adc_ab.sh build         -> build/var/ab_<name>.so  (travels with gpurun)
 #   on the GPU box:       tools/adc_ab.sh run [M ...]   -> one table per library (tools/adc_quick_bench.py)
-# nosurv changes RESULTS (a timing probe of the kernel without its survivor path); the others are complete kernels.
-# (Round 6 also timed per-gather waits and a kernel without its code loads: no gain / slower, profiles/r06a_adc_ab.txt; removed.)
+# Every variant is a complete kernel with the shipped results; the last line times the shipped library without wave priorities.
+# (Round 6 also timed a kernel without its survivor test, the test right behind a round's last MFMAs, int16-packed accumulators,
+# per-gather waits and a kernel without its code loads: no gain / slower, profiles/r06a_adc_ab.txt, r06b_adc_late_test.txt; removed.)
 set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
-names=(nosurv late0 w12r12 w12r8 w8r16 pack12)
-flags=("-DADC_EXP_NOSURV" "-DADC_Q16_LATE_TEST=0"
-       "-DADC_Q16_WAVES=12 -DADC_Q16_R=12 -DADC_Q16_TILE=32256" "-DADC_Q16_WAVES=12 -DADC_Q16_R=8 -DADC_Q16_TILE=30720"
-       "-DADC_Q16_WAVES=8 -DADC_Q16_R=16" "-DADC_Q16_PACK=1 -DADC_Q16_R=12 -DADC_Q16_TILE=30720")
+names=(w12r12 w12r8 w8r16)
+flags=("-DADC_Q16_WAVES=12 -DADC_Q16_R=12 -DADC_Q16_TILE=32256" "-DADC_Q16_WAVES=12 -DADC_Q16_R=8 -DADC_Q16_TILE=30720"
+       "-DADC_Q16_WAVES=8 -DADC_Q16_R=16")
 if [ "$1" == "build" ]; then
   for i in "${!names[@]}"; do $root/tools/mkvar.sh ab_${names[$i]} adc_search.hip ${flags[$i]} & done
   wait
