@@ -467,6 +467,42 @@ int rc_dense_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N
                            void* ws, size_t ws_bytes, rc_stream_t stream);
 void rc_dense_bf16x3_error_constants(double* c);
 
+/* ------------------------------------------------------------------ dense flat search, L2 metric
+ * Exact squared-Euclidean top-k over an fp32 corpus: faiss.IndexFlatL2, the flat index the reference names at
+ * models/repconc/evaluate_repconc.py:102 and train/run_warmup.py:102,107.  Arguments, alignment rules and limits of
+ * rc_dense_search_q (any D >= 1, N < 2^32, 1 <= k <= 8192 else RC_ESHAPE, finite inputs).
+ * Distance d(q, n) = the fp32 chain acc = +0.0f; for j = 0 .. D-1 ascending: t = q[j] - x[n][j] (one fp32 subtraction),
+ * acc = fmaf(t, t, acc) — the direct form, so ids AND distance bits are defined.  dist [nq, k]: the min(k, N) nearest rows
+ * sorted (distance asc, row asc), every value >= +0.0f, ids = row + id_offset, +inf / -1 in the slots past N.  A distance that
+ * overflows is +inf and sorts last.
+ * rc_dense_l2_search_q (evaluate_repconc.py:102, run_warmup.py:102,107): N <= 131072 takes the exact route below.  Above: the
+ *   fp32 matrix cores screen with sigma = fmaf(2, dot(q, x_n), -xsq[n]) = ||q||^2 - d up to rounding; the r-th best sigma of
+ *   32768 strided sample rows is the threshold thr~ (r and sel_slack as at rc_adc_search), every row with sigma >= thr~ becomes a
+ *   candidate, the candidates are rescored by the chain and sorted.  xsq: DEVICE fp32 [N], the squared norm of every row (an
+ *   fp64 sum rounded to nearest); xnorm_max: DEVICE pointer to one float X >= the largest Euclidean row norm; NULL for either
+ *   is RC_EINVAL.  With D_pad = D rounded up to 16 and the constants c[0..2] of rc_dense_l2_error_constants,
+ *     E_q = c0 D_pad 2^-24 (||q||_2 + X)^2 + c1 sqrt(D_pad) (||q||_2 + X) + c2 D_pad   (every |sigma - ||q||^2 + d| <= E_q),
+ *   -t >= thr~ - ||q||^2 + E_q for t = the query's k-th distance, all rounded to the safe side, proves that no row outside the
+ *   list can reach the top-k or tie with its last member.  status (device int) / qstatus (nq device ints, may be NULL), both
+ *   zeroed by the caller: bit0 = fewer than min(k, N) candidates, bit1 = the list overflowed (16384), bit2 = not certified
+ *   (also: a non-finite query value, D > 65536, (||q||_2 + X)^2 >= 2^126): repeat those queries with another sel_slack or
+ *   answer them by rc_dense_l2_search_exact.  ws: rc_dense_l2_search_ws_bytes(N, D, nq, k).
+ * rc_dense_l2_search_exact (the same references): a vector-ALU kernel writes the full rows of -d of a chunk of queries, then the
+ *   radix select of rc_dense_search_exact; takes no norms, no status, terminates with the same answer for any content.
+ *   ws: rc_dense_l2_search_exact_ws_bytes(N, D, nq, k).
+ * rc_dense_l2_scores (test hook): the screen's raw sigma, out [nq][N] fp32.
+ * rc_dense_l2_error_constants: c[3] = {2, 4 * 2^-126, 4 * 2^-149} as the certificate kernel was compiled (no GPU needed). */
+size_t rc_dense_l2_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_l2_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, const float* xsq,
+                         const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* dist, int64_t* ids,
+                         int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_dense_l2_search_exact_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_l2_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
+                             int64_t id_offset, float* dist, int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_l2_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, const float* xsq,
+                       float* out, rc_stream_t stream);
+void rc_dense_l2_error_constants(double* c);
+
 /* ------------------------------------------------------------------ a-9 … a-11, stateful form
  * The index object the reference keeps inside Faiss (initialize_index / add_docs / index.search,
  * models/repconc/evaluate_repconc.py:78-98,182; JPQ's per-step synchronize_model_index, models/jpq/finetune_jpq.py:209-214),

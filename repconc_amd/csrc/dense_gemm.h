@@ -59,14 +59,14 @@ __device__ __forceinline__ void dense_emit(float s, int64_t j, bool jv, int qi, 
     }
 }
 
-// grid: ceil(nrows / 128) blocks of 256 threads.  Logical row j in [0, nrows) is corpus row (smap ? j N / smap : j).
-// x: [N, ldx] (16-byte aligned rows unless PAD), q: [nq, D] contiguous.  STORE: out [nq][nrows].  FILTER: thr [nq],
-// cnt [nq] (zeroed), cand [nq][ADC_CAND_CAP].
-template <int MODE, bool PAD, typename T>
-__global__ __launch_bounds__(256) void dense_gemm_kernel(const T* __restrict__ x, int64_t ldx, int64_t N, int64_t nrows,
-                                                         int64_t smap, const T* __restrict__ q, int nq, int D,
-                                                         const float* __restrict__ thr, float* __restrict__ out,
-                                                         unsigned* __restrict__ cnt, unsigned long long* __restrict__ cand) {
+// The body of dense_gemm_kernel, and of the L2 screen's kernel (dense_search_l2.hip), which is this GEMM with one more
+// operand and another epilogue: L2 emits sigma = fmaf(2, dot, -xsq[row]) instead of the dot, xsq [N] = the stored squared norm
+// of every corpus row (a lane holds one corpus row per column tile: two values, loaded once per block).  !L2: xsq is unused.
+template <int MODE, bool PAD, typename T, bool L2>
+__device__ __forceinline__ void dense_gemm_body(const T* __restrict__ x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
+                                                const T* __restrict__ q, int nq, int D, const float* __restrict__ thr,
+                                                float* __restrict__ out, unsigned* __restrict__ cnt,
+                                                unsigned long long* __restrict__ cand, const float* __restrict__ xsq) {
     __shared__ float sa[2][DENSE_TILE * DENSE_LD];     // query chunk   [128][16 (+1)]
     __shared__ float sb[2][DENSE_TILE * DENSE_LD];     // corpus chunk  [128][16 (+1)]
     __shared__ float s_thr[DENSE_TILE];
@@ -80,6 +80,15 @@ __global__ __launch_bounds__(256) void dense_gemm_kernel(const T* __restrict__ x
     const int64_t xrow = smap ? (int64_t)((uint64_t)jl * (uint64_t)N / (uint64_t)smap) : jl;
     const T* xp = x + xrow * ldx;
     const int nkc = (D + DENSE_KC - 1) / DENSE_KC;
+    float nxs[2] = {0.f, 0.f};                         // L2: minus the squared norm of this lane's row of column tile b
+    if constexpr (L2) {
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const int64_t j = j0 + wc * 64 + b * 32 + col;
+            const int64_t jc = j < nrows ? j : nrows - 1;
+            nxs[b] = -xsq[smap ? (int64_t)((uint64_t)jc * (uint64_t)N / (uint64_t)smap) : jc];
+        }
+    }
     for (int qt = 0; qt < nq; qt += DENSE_TILE) {
         const int qrow = (qt + lrow < nq) ? qt + lrow : nq - 1;
         const T* qp = q + (int64_t)qrow * D;
@@ -150,11 +159,23 @@ __global__ __launch_bounds__(256) void dense_gemm_kernel(const T* __restrict__ x
                 for (int r = 0; r < 16; ++r) {
                     const int qo = wr * 64 + a * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
                     const int qi = qt + qo;
-                    dense_emit<MODE, 32>(acc[a][b][r], j, jv, qi, nq, MODE == DENSE_FILTER ? s_thr[qo] : 0.f, nrows, out, cnt, cand, l);
+                    const float sc = L2 ? __builtin_fmaf(2.f, acc[a][b][r], nxs[b]) : acc[a][b][r];
+                    dense_emit<MODE, 32>(sc, j, jv, qi, nq, MODE == DENSE_FILTER ? s_thr[qo] : 0.f, nrows, out, cnt, cand, l);
                 }
         }
         __syncthreads();                                           // the next query tile overwrites buffer 0 and s_thr
     }
+}
+
+// grid: ceil(nrows / 128) blocks of 256 threads.  Logical row j in [0, nrows) is corpus row (smap ? j N / smap : j).
+// x: [N, ldx] (16-byte aligned rows unless PAD), q: [nq, D] contiguous.  STORE: out [nq][nrows].  FILTER: thr [nq],
+// cnt [nq] (zeroed), cand [nq][ADC_CAND_CAP].
+template <int MODE, bool PAD, typename T>
+__global__ __launch_bounds__(256) void dense_gemm_kernel(const T* __restrict__ x, int64_t ldx, int64_t N, int64_t nrows,
+                                                         int64_t smap, const T* __restrict__ q, int nq, int D,
+                                                         const float* __restrict__ thr, float* __restrict__ out,
+                                                         unsigned* __restrict__ cnt, unsigned long long* __restrict__ cand) {
+    dense_gemm_body<MODE, PAD, T, false>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, nullptr);
 }
 
 template <int MODE, typename T>

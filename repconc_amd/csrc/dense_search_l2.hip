@@ -1,0 +1,361 @@
+// Exact dense L2 top-k search (Faiss IndexFlatL2, the flat index the reference names at evaluate_repconc.py:102 and
+// run_warmup.py:102,107) over an fp32 corpus: smallest squared Euclidean distance first, lowest row first among equals.
+//
+// Distance: d(q, n) = the fp32 chain  acc = +0.0f;  for j = 0 .. D-1 ascending:  t = q[j] - x[n][j] (one fp32 subtraction),
+// acc = fmaf(t, t, acc).  The direct form, so ids AND distance bits are defined as the inner-product search defines its
+// scores; d >= +0 always (t t >= +0 and the chain starts at +0: no -0, zero-padding a chunk of K is bit-neutral).  Every stage
+// works on s = -d with the keys of topk.h (negation is exact, every zero is -0.0f, "largest s, lowest row" is "smallest d,
+// lowest row"); the entries negate the k output values once at the end: d ascending, +0.0f for a zero, +inf / -1 past N.
+//
+// Route (dense_l2_route, the sequence of dense_search_route in dense_screen.h with this unit's kernels):
+//   N <= DENSE_EXACT_MAX_N, and the queries the fast route gives up on: dense_l2_exact_kernel writes the full rows of -d of a
+//   chunk of queries (the layout and the chunking of dense_exact, dense_gemm.h), then the radix select (topk_exact_select).
+//   Above:  1. screen<STORE> over the strided sample  2. threshold  3. screen<FILTER> over all rows  4. dense_l2_rescore_kernel
+//   replaces the score half of every candidate key by -d  5. select  6. dense_certify_kernel  7. negate.
+//
+// Screen.  sigma(q, n) = fmaf(2, dot(q, x_n), -xsq[n]): dot is the fp32 MFMA accumulator of the GEMM of dense_gemm.h
+// (dense_gemm_body<.., L2 = true>), xsq[n] the caller's fp32 squared norm of row n (an fp64 sum rounded to nearest,
+// ops.dense_row_sqnorms).  sigma = ||q||^2 - d up to rounding: it differs from -d by a constant per query, so the sample, the
+// threshold and the FILTER run on sigma unchanged.  The expanded form cancels and has no defined bits: it only screens.
+//
+// The bound |sigma - ||q||^2 + d| <= E_q.  u = 2^-24, X >= the largest row norm, P = ||q|| X, R = (||q|| + X)^2, gamma_n =
+// n u / (1 - n u) <= 1.01 n u while n <= 65538 (above D = 65536 no certificate is given).
+//   chain:   t_j = (q_j - x_j)(1 + e_j), |e_j| <= u; the term t_j^2 passes at most D fmaf roundings: the chain differs from
+//            D2 = sum_j (q_j - x_j)^2 by at most gamma_{D+2} D2, and D2 = ||q - x||^2 <= R:                 <= 1.01 (D + 2) u R
+//   screen:  the MFMA accumulator is the fmaf chain of the products: |dot - q.x| <= gamma_D sum |q_j x_j| <= 1.01 D u P, and it
+//            enters twice; |xsq - ||x||^2| <= (u + D 2^-53) ||x||^2 <= 1.01 u X^2; the one fmaf rounding of sigma is at most
+//            u |sigma| <= 1.01 u (2 P + X^2):                                             <= (2.02 D + 2.02) u P + 2.02 u X^2
+//   with P <= R / 4 (arithmetic and geometric mean) and X^2 <= R:  (1.01 D + 2.02 + 0.505 D + 0.505 + 2.02) u R
+//            = (1.515 D + 4.545) u R <= 2 D_pad u R for every D >= 1, D_pad = D rounded up to 16 (D < 16: 1.515 D + 4.545 < 28 <= 32;
+//            D >= 16: 0.485 D >= 7.7).                                                                 E_rel = 2 D_pad u R
+//   flush:   a matrix core that reads an fp32 subnormal operand (|a| < 2^-126) as zero drops the product a b, |a b| < 2^-126 |b|:
+//            over the row at most 2^-126 (sum |q_j| + sum |x_j|) <= 2^-126 sqrt(D) (||q|| + X), twice in sigma; no measurement
+//            decides whether this term is needed, it is always paid:                 E_flush = 4 * 2^-126 sqrt(D_pad) (||q|| + X)
+//   under:   a result below 2^-126 is rounded to a multiple of 2^-149 instead of relatively: D roundings of the chain (the
+//            subtraction is exact there), 2 D + 1 of the screen, each <= 2^-150:                     E_under = 4 D_pad 2^-149
+//   range:   R < 2^126 keeps every intermediate finite (|dot| <= 1.01 P < 2^125, xsq <= 1.01 X^2, d <= 1.01 R).  Otherwise a
+//            sigma may be inf or NaN and fail the FILTER's comparison: no certificate, the exact route answers.
+//   E_q = E_rel + E_flush + E_under; the constants are exported (rc_dense_l2_error_constants) and are what
+//   ops.dense_l2_error_bound evaluates.
+//
+// Certificate.  A row outside the list has sigma < thr~, hence -d < thr~ - ||q||^2 + E_q: with t = the k-th best -d of the list,
+// t >= thr~ - ss_down + E_q proves that no such row enters the top-k or ties with its last member.  dense_certify_kernel adds
+// V::eq to thr~: here E_q (pushed upwards) minus the query's squared norm (pushed downwards), all in fp64.
+#include "dense_screen.h"
+
+#define DENSE_L2_C_REL 2.0                               // E_rel   = C_REL D_pad 2^-24 (||q|| + X)^2
+#define DENSE_L2_C_FLUSH 0x1p-124                        // E_flush = C_FLUSH sqrt(D_pad) (||q|| + X)        (4 * 2^-126)
+#define DENSE_L2_C_UNDER 0x1p-147                        // E_under = C_UNDER D_pad                          (4 * 2^-149)
+#define DENSE_L2_MAX_D 65536                             // gamma_n <= 1.01 n u up to here
+#define DENSE_L2_MAX_R 0x1p126                           // (||q|| + X)^2 below this: nothing overflows
+
+// ---- screen: the fp32 GEMM with the L2 epilogue ------------------------------------------------------------------------------
+// grid and arguments as dense_gemm_kernel, plus xsq [N].
+template <int MODE, bool PAD>
+__global__ __launch_bounds__(256) void dense_l2_gemm_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int64_t nrows,
+                                                            int64_t smap, const float* __restrict__ q, int nq, int D,
+                                                            const float* __restrict__ thr, float* __restrict__ out,
+                                                            unsigned* __restrict__ cnt, unsigned long long* __restrict__ cand,
+                                                            const float* __restrict__ xsq) {
+    dense_gemm_body<MODE, PAD, float, true>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, xsq);
+}
+
+template <int MODE>
+static int dense_l2_launch_gemm(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
+                                const float* q, int nq, int D, const float* xsq, const float* thr, float* out, unsigned* cnt,
+                                unsigned long long* cand, hipStream_t s) {
+    const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
+    if (D % DENSE_KC == 0)
+        hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, false>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr, out,
+                           cnt, cand, xsq);
+    else
+        hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, true>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr, out,
+                           cnt, cand, xsq);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+// ---- rescoring ---------------------------------------------------------------------------------------------------------------
+// dense_rescore_kernel<VEC, float> (dense_screen.h: grid, candidate walk, staged query, row loads) with the L2 chain: a literal
+// subtraction, then fmaf(t, t, s), d ascending; the key's score half becomes -d.
+template <bool VEC>
+__global__ __launch_bounds__(256) void dense_l2_rescore_kernel(const float* __restrict__ x, int64_t ldx, int D,
+                                                               const float* __restrict__ q, const unsigned* __restrict__ cnt,
+                                                               unsigned long long* __restrict__ cand) {
+    __shared__ float sq[DENSE_RESCORE_QCHUNK];
+    const int qi = blockIdx.x, tid = threadIdx.x;
+    const unsigned raw = cnt[qi];
+    const unsigned n = raw > ADC_CAND_CAP ? ADC_CAND_CAP : raw;
+    if (blockIdx.y * 256u >= n) return;                                // block-uniform
+    const unsigned i = blockIdx.y * 256u + tid;
+    const bool mine = i < n;
+    unsigned long long* kp = cand + (size_t)qi * ADC_CAND_CAP + i;
+    const unsigned row = mine ? 0xFFFFFFFFu - (unsigned)(*kp & 0xFFFFFFFFull) : 0u;
+    const float* xp = x + (int64_t)row * ldx;
+    const float* qp = q + (int64_t)qi * D;
+    float s = 0.f;
+    for (int d0 = 0; d0 < D; d0 += DENSE_RESCORE_QCHUNK) {
+        const int dn = D - d0 < DENSE_RESCORE_QCHUNK ? D - d0 : DENSE_RESCORE_QCHUNK;
+        __syncthreads();
+        for (int d = tid; d < dn; d += 256) sq[d] = qp[d0 + d];
+        __syncthreads();
+        if (mine) {
+            int d = 0;
+            if constexpr (VEC) {
+                for (; d + 8 <= dn; d += 8) {
+                    float v[8];
+                    dense_load8(xp + d0 + d, v);
+#pragma unroll
+                    for (int e = 0; e < 8; ++e) {
+                        const float t = sq[d + e] - v[e];
+                        s = __builtin_fmaf(t, t, s);
+                    }
+                }
+            }
+            for (; d < dn; ++d) {
+                const float t = sq[d] - xp[d0 + d];
+                s = __builtin_fmaf(t, t, s);
+            }
+        }
+    }
+    if (mine) *kp = adc_exact_key(-s, (int64_t)row);
+}
+
+static int dense_l2_launch_rescore(rc_handle_t h, const float* x, int64_t ldx, int D, const float* q, int nq,
+                                   const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
+    const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
+    if (ldx % 4 == 0 && !((uintptr_t)x & 15u))
+        hipLaunchKernelGGL(dense_l2_rescore_kernel<true>, grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
+    else
+        hipLaunchKernelGGL(dense_l2_rescore_kernel<false>, grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+// ---- the exact route's kernel ------------------------------------------------------------------------------------------------
+// The matrix cores cannot compute a chain of squared differences: this is vector-ALU work, two lane-operations per (q, n, d),
+// the subtraction and the fmaf.  grid: ceil(N / 128) blocks of 256 threads, two per CU.  A block owns 128 corpus rows and walks
+// every tile of 64 queries (the corpus is read from HBM once per launch), K in chunks of 16 through LDS, double buffered, both
+// tiles stored k-major: thread (tx = tid % 32, ty = tid / 32) owns rows 4 tx .. + 3 and queries 8 ty .. + 7 of the tiles, 32
+// accumulators that each walk d ascending, and reads per k one 16-byte vector of corpus values (32 lanes: 512 contiguous bytes)
+// and two of query values (broadcast) for 64 vector operations.  out [nq][N] = -d, the score rows topk_exact_select reads.
+// !PAD: D % 16 == 0 and 16-byte aligned rows (dense_check); PAD reads element by element and pads K with zeros.
+// (-O3 pairs the 32 independent subtractions and fmas of a k step into v_pk_add_f32 / v_pk_fma_f32: two IEEE operations per
+// instruction with the roundings of the plain forms.  Forcing v_sub_f32 + v_fmac_f32 one by one was measured slower)
+#define DENSE_L2_QT 64
+#define DENSE_L2_XLD (DENSE_TILE + 4)                    // words per k of the corpus tile: 8 k apart is 32 banks apart
+#define DENSE_L2_QLD (DENSE_L2_QT + 4)                   // words per k of the query tile: 4 k apart is 16 banks apart
+
+template <bool PAD>
+__global__ __launch_bounds__(256, 2) void dense_l2_exact_kernel(const float* __restrict__ x, int64_t ldx, int64_t N,
+                                                                const float* __restrict__ q, int nq, int D,
+                                                                float* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) float sx[2][DENSE_KC * DENSE_L2_XLD];
+    __shared__ __attribute__((aligned(16))) float sq[2][DENSE_KC * DENSE_L2_QLD];
+    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
+    const int64_t j0 = (int64_t)blockIdx.x * DENSE_TILE;
+    // loader mapping: corpus thread -> (row tid / 2, 8 consecutive k), query thread -> (row tid / 4, 4 consecutive k)
+    const int xr = tid >> 1, xk = (tid & 1) * 8, qr = tid >> 2, qk = (tid & 3) * 4;
+    const float* xp = x + ((j0 + xr < N) ? j0 + xr : N - 1) * ldx;
+    const int nkc = (D + DENSE_KC - 1) / DENSE_KC;
+    for (int qt = 0; qt < nq; qt += DENSE_L2_QT) {
+        const float* qp = q + (int64_t)((qt + qr < nq) ? qt + qr : nq - 1) * D;
+        float acc[8][4];
+#pragma unroll
+        for (int a = 0; a < 8; ++a)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[a][r] = 0.f;
+        float rx[8], rq[4];
+        auto gload = [&](int kc) {
+            const int k0 = kc * DENSE_KC;
+            if constexpr (PAD) {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) rx[i] = (k0 + xk + i < D) ? xp[k0 + xk + i] : 0.f;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) rq[i] = (k0 + qk + i < D) ? qp[k0 + qk + i] : 0.f;
+            } else {
+                dense_load8(xp + k0 + xk, rx);
+                const float4 v = *reinterpret_cast<const float4*>(qp + k0 + qk);
+                rq[0] = v.x; rq[1] = v.y; rq[2] = v.z; rq[3] = v.w;
+            }
+        };
+        auto sstore = [&](int buf) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i) sx[buf][(xk + i) * DENSE_L2_XLD + xr] = rx[i];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) sq[buf][(qk + i) * DENSE_L2_QLD + qr] = rq[i];
+        };
+        const bool act = qt + 8 * ty < nq;                           // this thread's 8 queries are not all padding
+        gload(0);
+        sstore(0);
+        __syncthreads();
+        for (int kc = 0; kc < nkc; ++kc) {
+            const int buf = kc & 1;
+            if (kc + 1 < nkc) gload(kc + 1);
+            if (act) {
+#pragma unroll
+                for (int k = 0; k < DENSE_KC; ++k) {
+                    const float4 xv = *reinterpret_cast<const float4*>(&sx[buf][k * DENSE_L2_XLD + 4 * tx]);
+                    const float4 qa = *reinterpret_cast<const float4*>(&sq[buf][k * DENSE_L2_QLD + 8 * ty]);
+                    const float4 qb = *reinterpret_cast<const float4*>(&sq[buf][k * DENSE_L2_QLD + 8 * ty + 4]);
+                    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
+                    const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
+#pragma unroll
+                    for (int a = 0; a < 8; ++a)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float t = qv[a] - xs[r];
+                            acc[a][r] = __builtin_fmaf(t, t, acc[a][r]);
+                        }
+                }
+            }
+            if (kc + 1 < nkc) sstore(buf ^ 1);
+            __syncthreads();
+        }
+#pragma unroll
+        for (int a = 0; a < 8; ++a) {
+            const int qi = qt + 8 * ty + a;
+            if (qi < nq) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int64_t j = j0 + 4 * tx + r;
+                    if (j < N) out[(int64_t)qi * N + j] = -acc[a][r];
+                }
+            }
+        }
+    }
+}
+
+static int dense_l2_launch_exact_rows(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                      float* out, hipStream_t s) {
+    const dim3 grid((unsigned)((N + DENSE_TILE - 1) / DENSE_TILE));
+    if (D % DENSE_KC == 0)
+        hipLaunchKernelGGL(dense_l2_exact_kernel<false>, grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out);
+    else
+        hipLaunchKernelGGL(dense_l2_exact_kernel<true>, grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+// -d -> d in place over the n output values: -0.0f -> +0.0f, the -inf of the padding -> +inf
+__global__ __launch_bounds__(256) void dense_l2_negate_kernel(float* __restrict__ v, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) v[i] = -v[i];
+}
+
+static int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_t s) {
+    hipLaunchKernelGGL(dense_l2_negate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, n);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+// the exact route: dense_exact (dense_gemm.h) with the rows of -d from dense_l2_exact_kernel, then the sign
+static int dense_l2_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
+                          int64_t id_offset, float* dist, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s) {
+    float* sc = (float*)(w + L.sc);
+    for (int q0 = 0; q0 < nq; q0 += L.qx) {
+        const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
+        int rc = dense_l2_launch_exact_rows(h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
+        if (rc != RC_OK) return rc;
+        rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, dist + (size_t)q0 * k, ids + (size_t)q0 * k, s);
+        if (rc != RC_OK) return rc;
+    }
+    return dense_l2_launch_negate(h, dist, (int64_t)nq * k, s);
+}
+
+// ---- certificate and route ---------------------------------------------------------------------------------------------------
+// What dense_certify_kernel needs of a variant.  The route itself is a sibling of dense_search_route, not an instance: xsq goes
+// into both screen launches, the rescorer is this unit's, and the output is negated after the certificate has read it.
+struct dense_l2_variant {
+    typedef float T;
+    __device__ static bool refuse(float v, int D) { return !(v - v == 0.f) || D > DENSE_L2_MAX_D; }
+    // E_q - ss_down: what is added to thr~ (header).  +inf (never certified) unless (||q|| + X)^2 < 2^126.
+    __device__ static double eq(int D, double ss, double xnorm) {
+        const double up = 1.0 + 0x1p-30;
+        const double dpad = (double)((D + 15) / 16 * 16);
+        const double r = (sqrt(ss) + xnorm) * up, R = r * r * up;
+        if (!(R < DENSE_L2_MAX_R)) return INFINITY;
+        const double e = (DENSE_L2_C_REL * dpad * 0x1p-24 * R + DENSE_L2_C_FLUSH * sqrt(dpad) * up * r + DENSE_L2_C_UNDER * dpad) * up;
+        return e - ss * (1.0 - 0x1p-30);
+    }
+};
+
+static size_t dense_l2_ws_bytes(int64_t N, int D, int nq, int k) {
+    if (!dense_shape_ok(N, D, nq, k)) return 0;
+    return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total;
+}
+
+// checked arguments (dense_check, status, xsq, xnorm_max, nq > 0, a workspace of dense_l2_ws_bytes)
+static int dense_l2_route(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, const float* xsq,
+                          const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* dist, int64_t* ids,
+                          int* status, int* qstatus, char* w, hipStream_t s) {
+    if (dense_exact_route(N)) return dense_l2_exact(h, x, ldx, N, D, q, nq, k, id_offset, dist, ids, w, dense_exact_ws(N, nq), s);
+    const dense_fast_layout L = dense_fast_ws(N, nq);
+    float* sample = (float*)(w + L.sample);
+    float* thr = (float*)(w + L.thr);
+    unsigned* cnt = (unsigned*)(w + L.cnt);
+    unsigned long long* cand = (unsigned long long*)(w + L.cand);
+    int rc = dense_l2_launch_gemm<DENSE_STORE>(h, x, ldx, N, L.S, L.S, q, nq, D, xsq, nullptr, sample, nullptr, nullptr, s);
+    if (rc != RC_OK) return rc;
+    rc = rc_adc_launch_threshold(h, sample, L.S, nq, rc_adc_sample_rank(N, L.S, k, sel_slack), thr, s);
+    if (rc != RC_OK) return rc;
+    RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
+    rc = dense_l2_launch_gemm<DENSE_FILTER>(h, x, ldx, N, N, 0, q, nq, D, xsq, thr, nullptr, cnt, cand, s);
+    if (rc != RC_OK) return rc;
+    rc = dense_l2_launch_rescore(h, x, ldx, D, q, nq, cnt, cand, s);
+    if (rc != RC_OK) return rc;
+    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, dist, ids, status, s, qstatus);
+    if (rc != RC_OK) return rc;
+    hipLaunchKernelGGL(dense_certify_kernel<dense_l2_variant>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, thr, xnorm_max, dist,
+                       status, qstatus);
+    RC_LAUNCH_CHECK(h);
+    return dense_l2_launch_negate(h, dist, (int64_t)nq * k, s);
+}
+
+// ---- C ABI -------------------------------------------------------------------------------------------------------------------
+extern "C" void rc_dense_l2_error_constants(double* c) {
+    c[0] = DENSE_L2_C_REL;
+    c[1] = DENSE_L2_C_FLUSH;
+    c[2] = DENSE_L2_C_UNDER;
+}
+
+extern "C" size_t rc_dense_l2_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
+
+extern "C" size_t rc_dense_l2_search_ws_bytes(int64_t N, int D, int nq, int k) { return dense_l2_ws_bytes(N, D, nq, k); }
+
+extern "C" int rc_dense_l2_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                        int k, int64_t id_offset, float* dist, int64_t* ids, void* ws, size_t ws_bytes,
+                                        rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, dist, ids);
+    if (crc != RC_OK) return crc;
+    if (nq == 0) return RC_OK;
+    const dense_exact_layout L = dense_exact_ws(N, nq);
+    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
+    return dense_l2_exact(h, x, ldx, N, D, q, nq, k, id_offset, dist, ids, (char*)ws, L, (hipStream_t)stream);
+}
+
+extern "C" int rc_dense_l2_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                    const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack,
+                                    float* dist, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                                    rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, dist, ids);
+    if (crc != RC_OK) return crc;
+    if (!status || !xsq || !xnorm_max) return RC_EINVAL;
+    if (nq == 0) return RC_OK;
+    if (!ws || ws_bytes < dense_l2_ws_bytes(N, D, nq, k)) return RC_EWORKSPACE;
+    return dense_l2_route(h, x, ldx, N, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, dist, ids, status, qstatus, (char*)ws,
+                          (hipStream_t)stream);
+}
+
+extern "C" int rc_dense_l2_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                  const float* xsq, float* out, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (N > 0xFFFFFFFFll) return RC_ESHAPE;
+    if (!h || !x || !q || !xsq || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
+    if (D % DENSE_KC == 0 && (ldx % 4 != 0 || ((uintptr_t)x & 15u) || ((uintptr_t)q & 15u))) return RC_EINVAL;
+    if (nq == 0) return RC_OK;
+    return dense_l2_launch_gemm<DENSE_STORE>(h, x, ldx, N, N, 0, q, nq, D, xsq, nullptr, out, nullptr, nullptr,
+                                             (hipStream_t)stream);
+}

@@ -22,10 +22,69 @@ import numpy as np
 import torch
 
 from . import ops
-from .index import METRIC_INNER_PRODUCT
+from .index import METRIC_INNER_PRODUCT, METRIC_L2
 
 
-class FlatIPIndex:
+class _FlatIndex:
+    """What the flat indexes share: the device, ONE [capacity, d] tensor of vectors appended to in place (the first `add`
+    allocates exactly, later growth is 1.5x), and `search` / `search_async` around the subclass's `_enqueue`."""
+    PAD = float("-inf")          # the value of the slots past ntotal
+
+    def _init_store(self, d: int, device, dtype) -> None:
+        self._dtype = dtype
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.d = int(d)
+        self.is_trained = True
+        self.ntotal = 0
+        self.id_offset = 0       # global id of local row 0
+        self.sel_slack = ops.DENSE_SEL_SLACK
+        self.last_search = None
+        self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
+
+    @property
+    def xb(self) -> torch.Tensor:
+        """[ntotal, d] view of the stored vectors, in the storage type."""
+        return self._x[: self.ntotal]
+
+    def reserve(self, n: int) -> None:
+        """Capacity for `n` rows in total (the rows held so far are kept)."""
+        if n > self._x.shape[0]:
+            grown = torch.empty((int(n), self.d), dtype=self._dtype, device=self.device)
+            grown[: self.ntotal] = self._x[: self.ntotal]
+            self._x = grown
+
+    def _grow_for(self, need: int) -> None:
+        if need > self._x.shape[0]:
+            self.reserve(need if self.ntotal == 0 else max(need, int(self._x.shape[0] * 1.5)))
+
+    def search_async(self, x, k: int):
+        """Enqueue the search and return a callable that yields what `search` returns; nothing synchronises with the host
+        until it is called (`batch_dense_search` enqueues every batch first)."""
+        as_numpy = not isinstance(x, torch.Tensor)
+        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
+        q = q.to(self.device, torch.float32, non_blocking=True)
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
+        k = int(k)
+        if self.ntotal == 0 or q.shape[0] == 0:
+            scores = torch.full((q.shape[0], k), self.PAD, dtype=torch.float32, device=self.device)
+            ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
+            pending = ops.PendingSearch(None, scores, ids, None, None, 0.0, 0)
+        else:
+            pending = self._enqueue(q, k)
+        self.last_search = pending           # .stats: queries repeated / answered by the exact route
+
+        def finish():
+            scores, ids = pending.result()
+            if as_numpy:
+                return scores.cpu().numpy(), ids.cpu().numpy()
+            return scores, ids
+        return finish
+
+
+class FlatIPIndex(_FlatIndex):
     STORAGE = {"float32": torch.float32, "float16": torch.float16}
     SCREENS = ("fp32", "bf16x3")
 
@@ -43,34 +102,12 @@ class FlatIPIndex:
         self.check_options(storage, screen)
         self.storage = storage
         self.screen = screen
-        self._dtype = self.STORAGE[storage]
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.d = int(d)
+        self._init_store(d, device, self.STORAGE[storage])
         self.metric_type = METRIC_INNER_PRODUCT
-        self.is_trained = True
-        self.ntotal = 0
-        self.id_offset = 0       # global id of local row 0
-        self.sel_slack = ops.DENSE_SEL_SLACK
-        self.last_search = None
-        self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
         # float16 storage / bf16x3 screen: device fp32 [1] >= the largest row norm held (the search's certificate)
         self._xnorm_max = None
         self._search = ops.dense_search_f16 if storage == "float16" else ops.dense_search_bf16x3 if screen == "bf16x3" \
             else ops.dense_search
-
-    @property
-    def xb(self) -> torch.Tensor:
-        """[ntotal, d] view of the stored vectors, in the storage type."""
-        return self._x[: self.ntotal]
-
-    def reserve(self, n: int) -> None:
-        """Capacity for `n` rows in total (the rows held so far are kept)."""
-        if n > self._x.shape[0]:
-            grown = torch.empty((int(n), self.d), dtype=self._dtype, device=self.device)
-            grown[: self.ntotal] = self._x[: self.ntotal]
-            self._x = grown
 
     def add(self, x) -> None:
         xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
@@ -93,8 +130,7 @@ class FlatIPIndex:
                 raise ValueError("add: the bf16x3 screen needs finite values of magnitude < 2^128 - 2^119 (bf16 rounds the rest to inf)")
             if n:
                 xnorm = ops.dense_xnorm_max(xt)
-        if need > self._x.shape[0]:
-            self.reserve(need if self.ntotal == 0 else max(need, int(self._x.shape[0] * 1.5)))
+        self._grow_for(need)
         self._x[self.ntotal:need] = xt.to(self.device, self._dtype)
         self.ntotal = need
         if xnorm is not None:
@@ -111,27 +147,63 @@ class FlatIPIndex:
         magnitude >= 65520 becomes inf (`ops.dense_search_f16`)."""
         return self.search_async(x, k)()
 
-    def search_async(self, x, k: int):
-        """Enqueue the search and return a callable that yields what `search` returns; nothing synchronises with the host
-        until it is called (`batch_dense_search` enqueues every batch first)."""
-        as_numpy = not isinstance(x, torch.Tensor)
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
-        q = q.to(self.device, torch.float32, non_blocking=True)
-        if q.dim() != 2 or q.shape[1] != self.d:
-            raise ValueError(f"search: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
-        k = int(k)
-        if self.ntotal == 0 or q.shape[0] == 0:
-            scores = torch.full((q.shape[0], k), float("-inf"), dtype=torch.float32, device=self.device)
-            ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
-            pending = ops.PendingSearch(None, scores, ids, None, None, 0.0, 0)
-        else:
-            norm = {} if self._search is ops.dense_search else {"xnorm_max": self._xnorm_max}
-            pending = self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True, **norm)
-        self.last_search = pending           # .stats: queries repeated / answered by the exact route
+    def _enqueue(self, q, k: int):
+        norm = {} if self._search is ops.dense_search else {"xnorm_max": self._xnorm_max}
+        return self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True, **norm)
 
-        def finish():
-            scores, ids = pending.result()
-            if as_numpy:
-                return scores.cpu().numpy(), ids.cpu().numpy()
-            return scores, ids
-        return finish
+
+class FlatL2Index(_FlatIndex):
+    """Exact squared-Euclidean index resident in HBM: the GPU `faiss.IndexFlatL2` the reference names at
+    models/repconc/evaluate_repconc.py:102 and train/run_warmup.py:102,107.  Duck-typed like `FlatIPIndex`, fp32 storage and
+    the fp32 screen only (no `storage` / `screen` options).  `search` answers with `ops.dense_search_l2`
+    (csrc/dense_search_l2.hip): a distance is the fp32 chain t = q_j - x_j, acc = fmaf(t, t, acc) over j ascending, bit for
+    bit, never negative; results are sorted (distance asc, id asc), +inf / -1 past ntotal.  Beside the vectors the index keeps
+    their fp32 squared norms in a capacity-sized tensor and a bound of the largest norm, both updated by `add` without a host
+    read: the screen's second operand and its certificate's X."""
+    PAD = float("inf")
+
+    def __init__(self, d: int, device: Optional[torch.device] = None):
+        self._init_store(d, device, torch.float32)
+        self.metric_type = METRIC_L2
+        self._xsq = torch.empty((0,), dtype=torch.float32, device=self.device)
+        self._xnorm_max = None
+
+    def reserve(self, n: int) -> None:
+        """Capacity for `n` rows in total (the rows and norms held so far are kept)."""
+        if n > self._x.shape[0]:
+            super().reserve(n)
+            grown = torch.empty((int(n),), dtype=torch.float32, device=self.device)
+            grown[: self.ntotal] = self._xsq[: self.ntotal]
+            self._xsq = grown
+
+    def add(self, x) -> None:
+        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        if xt.dim() != 2 or xt.shape[1] != self.d:
+            raise ValueError(f"add: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
+        n = xt.shape[0]
+        if n == 0:
+            return
+        need = self.ntotal + n
+        xt = xt.to(self.device, torch.float32)
+        self._grow_for(need)
+        self._x[self.ntotal:need] = xt
+        xsq = ops.dense_row_sqnorms(xt)
+        self._xsq[self.ntotal:need] = xsq
+        xnorm = ops._dense_l2_xnorm_max(xsq)
+        self._xnorm_max = xnorm if self._xnorm_max is None else torch.maximum(self._xnorm_max, xnorm)
+        self.ntotal = need
+
+    def reset(self) -> None:
+        self.ntotal = 0
+        self._x = torch.empty((0, self.d), dtype=torch.float32, device=self.device)
+        self._xsq = torch.empty((0,), dtype=torch.float32, device=self.device)
+        self._xnorm_max = None
+
+    def search(self, x, k: int):
+        """(distances [nq, k], ids [nq, k]); numpy in -> numpy out, CUDA tensors in -> CUDA tensors out
+        (faiss.contrib.torch_utils)."""
+        return self.search_async(x, k)()
+
+    def _enqueue(self, q, k: int):
+        return ops.dense_search_l2(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
+                                   xsq=self._xsq[: self.ntotal], xnorm_max=self._xnorm_max)

@@ -9,6 +9,8 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
     faiss.IndexPQ(D, M, 8, faiss.METRIC_INNER_PRODUCT)                  evaluate_repconc.py:81
     faiss.IndexFlatIP(d)                                                evaluate_dense.py:116 (exact fp32, dense_index.py;
                                                                         useFloat16: FlatIPIndex(d, storage="float16"))
+    faiss.IndexFlatL2(d)                                                evaluate_repconc.py:102, run_warmup.py:102,107 (exact
+                                                                        fp32 squared distances, dense_index.FlatL2Index)
     faiss.write_index(index, path) / faiss.read_index(path)             run_warmup.py:187, run_repconc_eval.py:42
     faiss.omp_set_num_threads(n)                                        run_repconc_eval.py:149 (no-op: the scan runs on the GPU)
 
@@ -20,11 +22,9 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .dense_index import FlatIPIndex
+from .dense_index import FlatIPIndex, FlatL2Index
 from .faiss_io import read_index, write_index  # noqa: F401  (re-exported)
-from .index import METRIC_INNER_PRODUCT, PQIndex
-
-METRIC_L2 = 1
+from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex  # noqa: F401  (METRIC_L2 re-exported)
 
 
 def IndexPQ(d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT) -> PQIndex:
@@ -32,6 +32,7 @@ def IndexPQ(d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT) -> PQIn
 
 
 IndexFlatIP = FlatIPIndex      # faiss.IndexFlatIP(d): exact inner product over fp32 vectors resident on the device
+IndexFlatL2 = FlatL2Index      # faiss.IndexFlatL2(d): exact squared Euclidean distance over the same storage
 
 
 def copy_array_to_vector(array, vector: torch.Tensor) -> None:

@@ -24,6 +24,7 @@ import torch
 from . import ops
 
 METRIC_INNER_PRODUCT = 0  # faiss.METRIC_INNER_PRODUCT
+METRIC_L2 = 1             # faiss.METRIC_L2 (dense_index.FlatL2Index; PQIndex takes the inner product only)
 
 
 class PQIndex:

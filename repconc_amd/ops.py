@@ -1122,11 +1122,14 @@ def _dense_f16_args(x16: torch.Tensor, q: torch.Tensor, k: int):
 
 # One dense search in three variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
 # library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes; exact: rc_<exact>_search_exact / ..._ws_bytes, the route that
-# cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate).
-_DenseVariant = collections.namedtuple("_DenseVariant", "args entry exact normed")
+# cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate);
+# rownorms: it also takes xsq, the squared norm of every row, before xnorm_max; pad: the value of the slots past N.
+_DenseVariant = collections.namedtuple("_DenseVariant", "args entry exact normed rownorms pad",
+                                       defaults=(False, float("-inf")))
 _DENSE_F32 = _DenseVariant(_dense_args, "dense", "dense", False)
 _DENSE_F16 = _DenseVariant(_dense_f16_args, "dense_f16", "dense_f16", True)
 _DENSE_BF16X3 = _DenseVariant(_dense_args, "dense_bf16x3", "dense", True)
+_DENSE_L2 = _DenseVariant(_dense_args, "dense_l2", "dense_l2", True, True, float("inf"))
 
 
 def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int):
@@ -1137,7 +1140,7 @@ def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: i
     scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
     if nq == 0 or N == 0:
-        scores.fill_(float("-inf"))
+        scores.fill_(v.pad)
         ids.fill_(-1)
         return scores, ids
     name = f"rc_{v.exact}_search_exact"
@@ -1149,7 +1152,8 @@ def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: i
 
 
 def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int, sel_slack: Optional[float],
-                  defer: bool, method: str, max_retries: int, xnorm_max: Optional[torch.Tensor] = None):
+                  defer: bool, method: str, max_retries: int, xnorm_max: Optional[torch.Tensor] = None,
+                  xsq: Optional[torch.Tensor] = None):
     if method not in ("auto", "exact"):
         raise ValueError("method must be 'auto' or 'exact'")
     x, q = v.args(x, q, k)
@@ -1168,6 +1172,13 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
             xnorm_max = dense_xnorm_max(x) if N > DENSE_EXACT_MAX_N else torch.zeros((1,), dtype=torch.float32, device=x.device)
         _need_cuda(xnorm_max)
         norm = (xnorm_max.to(torch.float32).reshape(1),)
+    if v.rownorms:
+        if xsq is None:
+            xsq = dense_row_sqnorms(x) if N > DENSE_EXACT_MAX_N else torch.zeros((N,), dtype=torch.float32, device=x.device)
+        _need_cuda(xsq)
+        if xsq.shape != (N,):
+            raise ValueError("dense search: xsq must hold one squared norm per row, [N]")
+        norm = (xsq.to(torch.float32).contiguous(),) + norm
     name = f"rc_{v.entry}_search_q"
     search_q, ws_bytes = getattr(lib, name), getattr(lib, f"rc_{v.entry}_search_ws_bytes")
 
@@ -1325,3 +1336,83 @@ def dense_search_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int
     `dense_search_exact`; `.stats` of the `PendingSearch`).  xnorm_max: device fp32 [1], >= the largest row norm of x
     (`dense_xnorm_max`, computed here when None).  Everything else as `dense_search`."""
     return _dense_search(_DENSE_BF16X3, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max)
+
+
+# ---------------------------------------------------------------------------------------------------- dense, L2 metric
+def dense_row_sqnorms(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
+    """Device fp32 [N]: the squared Euclidean norm of every row of the floating-point matrix `x`, an fp64 sum rounded to
+    nearest (+inf if it exceeds fp32): the `xsq` of `dense_search_l2`.  No host synchronisation."""
+    if not x.dtype.is_floating_point or x.dim() != 2:
+        raise ValueError("dense_row_sqnorms: a floating-point matrix")
+    out = torch.empty((x.shape[0],), dtype=torch.float32, device=x.device)
+    for r0 in range(0, x.shape[0], rows_per_step):
+        out[r0:r0 + rows_per_step] = x[r0:r0 + rows_per_step].double().square_().sum(1)
+    return out
+
+
+def _dense_l2_xnorm_max(xsq: torch.Tensor) -> torch.Tensor:
+    """Device fp32 [1] >= the largest row norm, from the rounded squared norms (the true square is at most xsq (1 + 2^-24); the
+    2^-20 covers that, the square root and the conversion).  No host synchronisation."""
+    return (xsq.max().double().sqrt() * (1.0 + 2.0 ** -20)).float().reshape(1)
+
+
+def dense_l2_error_constants():
+    """(c_rel, c_flush, c_under) of E_q as the certificate kernel was compiled with them (csrc/dense_search_l2.hip)."""
+    c = (C.c_double * 3)()
+    _lib.load().rc_dense_l2_error_constants(c)
+    return tuple(float(v) for v in c)
+
+
+def dense_l2_error_bound(D: int, qnorm, xmax):
+    """E = 2 D_pad 2^-24 (||q|| + X)^2 + 4 * 2^-126 sqrt(D_pad) (||q|| + X) + 4 D_pad 2^-149, D_pad = D rounded up to 16: the
+    bound on |sigma - ||q||^2 + d| between the L2 screen sigma = fmaf(2, dot, -xsq) and the chain d that the certificate of
+    `dense_search_l2` uses; derivation in the header comment of csrc/dense_search_l2.hip.  The constants are the library's.
+    Plain float / numpy arithmetic: `qnorm`, `xmax` scalars or arrays."""
+    c_rel, c_flush, c_under = dense_l2_error_constants()
+    dpad = (int(D) + 15) // 16 * 16
+    r = qnorm + xmax
+    return c_rel * dpad * 2.0 ** -24 * r * r + c_flush * dpad ** 0.5 * r + c_under * dpad
+
+
+def dense_l2_scores(x: torch.Tensor, q: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw screen values sigma [nq, N] = fmaf(2, dot(q, x_n), -xsq[n]) of the L2 search (rc_dense_l2_scores): a test hook,
+    never a result."""
+    x, q = _dense_args(x, q, 1)
+    lib, h, s, _ = _ctx(q)
+    if xsq is None:
+        xsq = dense_row_sqnorms(x)
+    _need_cuda(xsq)
+    xsq = xsq.to(torch.float32).contiguous()
+    if xsq.shape != (x.shape[0],):
+        raise ValueError("dense_l2_scores: xsq must hold one squared norm per row, [N]")
+    out = torch.empty((q.shape[0], x.shape[0]), dtype=torch.float32, device=q.device)
+    if out.numel():
+        _lib.check(lib.rc_dense_l2_scores(h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], _p(xsq), _p(out), s),
+                   "rc_dense_l2_scores", h)
+    return out
+
+
+def dense_search_l2_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+    """The same answer as `dense_search_l2` by the route that cannot fail (rc_dense_l2_search_exact): full rows of distances
+    from the vector-ALU kernel and a radix select of the min(k, N) nearest."""
+    return _dense_search_exact(_DENSE_L2, x, q, k, id_offset)
+
+
+def dense_search_l2(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
+                    defer: bool = False, method: str = "auto", max_retries: int = 2, xsq: Optional[torch.Tensor] = None,
+                    xnorm_max: Optional[torch.Tensor] = None):
+    """Exact top-k squared-Euclidean search of `q` [nq, D] against the fp32 corpus `x` [N, D] (faiss.IndexFlatL2,
+    evaluate_repconc.py:102, run_warmup.py:102,107).  Returns (distances [nq, k] fp32, ids [nq, k] int64 = row + id_offset),
+    sorted (distance asc, id asc); +inf / -1 past N.  A distance is the fp32 chain t = q_j - x_j, acc = fmaf(t, t, acc) over j
+    ascending (include/repconc_hip.h), bit for bit, never negative.  The matrix cores only screen with the expanded form;
+    candidates are rescored by the chain and every answer of the fast route carries a certificate (qstatus bit2 when it cannot
+    be given: such queries are repeated, then answered by `dense_search_l2_exact`; `.stats` of the `PendingSearch`).
+    xsq: device fp32 [N], the rows' squared norms (`dense_row_sqnorms`); xnorm_max: device fp32 [1] >= the largest row norm;
+    both computed here when None, and neither is read up to DENSE_EXACT_MAX_N rows.  Everything else as `dense_search`."""
+    if not 1 <= int(k) <= DENSE_MAX_K:
+        raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
+    if xnorm_max is None and x.dim() == 2 and x.shape[0] > DENSE_EXACT_MAX_N and method == "auto" and x.is_cuda:
+        if xsq is None:
+            xsq = dense_row_sqnorms(x)
+        xnorm_max = _dense_l2_xnorm_max(xsq)
+    return _dense_search(_DENSE_L2, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, xsq)
