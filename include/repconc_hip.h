@@ -383,6 +383,24 @@ int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t N, int M, i
 /* the look-up tables alone (test hook): lut [nq,M,K] fp32 */
 int rc_adc_lut(rc_handle_t h, const float* C, const float* q, int nq, int D, int M, int K,
                float* lut, rc_stream_t stream);
+/* L2 metric (faiss.IndexPQ(d, M, 8, METRIC_L2)).  Bit-defined like the inner-product search:
+ *   sub-distance T[m][c] = fp32 chain acc = +0.0f; for j = 0 .. dsub-1 ascending: t = q[m dsub + j] - C[m][c][j] (one fp32
+ *     subtraction), acc = acc + t * t (product and sum each rounded, no FMA: Faiss's scalar fvec_L2sqr);
+ *   distance d(q, n) = fp32 sum over m ascending of T[m][code[n][m]];
+ *   output: d ascending, ties by the lower id; a zero distance is +0.0f; +inf / -1 in the slots past N.
+ * The pipeline runs unchanged on s = -d: rc_adc_lut_l2 (arguments of rc_adc_lut) writes S[m][c] = 0.0f - T[m][c] — -T for T > 0,
+ * +0.0f for T = 0, so no entry is -0.0f — and a table is all a screen, a rescorer, a select or an IVF entry ever sees; the IVF
+ * entries of an L2 index take this table and their caller forms d = 0.0f - s.  rc_adc_search_l2_q / rc_adc_search_l2_exact: the
+ * arguments, workspaces, status bits and routes of rc_adc_search_q / rc_adc_search_exact with that table and one trailing kernel
+ * that replaces each of the nq * k scores by 0.0f - s.  Precondition: finite inputs and every T finite (documented, not tested). */
+int rc_adc_lut_l2(rc_handle_t h, const float* C, const float* q, int nq, int D, int M, int K,
+                  float* lut, rc_stream_t stream);
+int rc_adc_search_l2_q(rc_handle_t h, const uint8_t* codes, const uint8_t* scan_image, int64_t N, int M, int K,
+                       const float* C, int D, const float* q, int nq, int k, int64_t id_offset, double sel_slack,
+                       float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_adc_search_l2_exact(rc_handle_t h, const uint8_t* codes, int64_t N, int M, int K, const float* C, int D,
+                           const float* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                           size_t ws_bytes, rc_stream_t stream);
 
 /* ------------------------------------------------------------------ dense flat search
  * Exact inner-product top-k over an fp32 corpus: the GPU faiss.IndexFlatIP (useFloat16 = False) of
@@ -517,6 +535,9 @@ int rc_index_set_centroids(rc_index_t idx, const float* C, rc_stream_t stream);
 int rc_index_reserve(rc_index_t idx, int64_t rows, rc_stream_t stream);
 int rc_index_add_codes(rc_index_t idx, const uint8_t* codes, int64_t n, rc_stream_t stream);
 int rc_index_reset(rc_index_t idx);
+/* metric of rc_index_search: 0 inner product (the default), 1 L2 (distances ascending; empty index: +inf / -1); any other
+ * value is RC_EINVAL.  The index keeps nothing that depends on the metric, so it may be set at any time between searches. */
+int rc_index_set_metric(rc_index_t idx, int metric);
 int64_t rc_index_ntotal(rc_index_t idx);
 const uint8_t* rc_index_codes(rc_index_t idx);
 const float* rc_index_centroids(rc_index_t idx);

@@ -104,6 +104,9 @@ PROTOTYPES = {
     "rc_ivf_search_ws_bytes": (_sz, [_i, _i64]),
     "rc_ivf_search": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rc_adc_lut": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "rc_adc_lut_l2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "rc_adc_search_l2_q": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rc_adc_search_l2_exact": (_i, [_vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_search_ws_bytes": (_sz, [_i64, _i, _i, _i]),
     "rc_dense_search_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_search_exact_ws_bytes": (_sz, [_i64, _i, _i, _i]),
@@ -132,6 +135,7 @@ PROTOTYPES = {
     "rc_index_reserve": (_i, [_vp, _i64, _vp]),
     "rc_index_add_codes": (_i, [_vp, _vp, _i64, _vp]),
     "rc_index_reset": (_i, [_vp]),
+    "rc_index_set_metric": (_i, [_vp, _i]),
     "rc_index_ntotal": (_i64, [_vp]),
     "rc_index_codes": (_vp, [_vp]),
     "rc_index_centroids": (_vp, [_vp]),

@@ -1,4 +1,5 @@
-// PQ asymmetric-distance (inner-product) top-k search over raw uint8 codes.
+// PQ asymmetric-distance top-k search over raw uint8 codes: inner product, and the L2 metric as the same pipeline on tables
+// S = 0.0f - T with one trailing negate (rc_adc_lut_l2, rc_adc_search_l2_q / _exact; the definition is at adc_lut_step).
 //
 // Reference: `index.search(query_embeds, topk)` on a faiss.IndexPQ(D, M, 8, METRIC_INNER_PRODUCT)
 // or its 1-list IVFPQ clone — models/repconc/evaluate_repconc.py:78-135,180-185 and
@@ -45,7 +46,24 @@
 #include <string.h>
 
 // ------------------------------------------------------------------------------------------ 1. LUT
-// grid (nq, M), block 256 (= k).  j-ascending multiply then add, each rounded (no FMA).
+// One table entry.  Inner product: j-ascending multiply then add, each rounded (no FMA).  L2 (rc_adc_lut_l2): the sub-distance
+// T = sum_j (q_j - c_j)^2, j ascending from +0.0f, one rounded subtraction, product and sum each (Faiss's scalar fvec_L2sqr),
+// stored as S = 0.0f - T: the pipeline keeps "largest score, lowest row", and 0.0f - T is -T for T > 0 but +0.0f for T = 0, so
+// no entry is -0.0f and every scoring path (sum started from 0.f or from the first entry) gives a zero distance the same bits.
+template <bool L2>
+__device__ __forceinline__ float adc_lut_step(float s, float qj, float cj) {
+    if constexpr (L2) {
+        const float t = qj - cj;
+        return s + t * t;
+    } else {
+        return s + qj * cj;
+    }
+}
+template <bool L2>
+__device__ __forceinline__ float adc_lut_entry(float s) { return L2 ? 0.0f - s : s; }
+
+// grid (nq, M), block 256 (= k): any dsub.
+template <bool L2>
 __global__ __launch_bounds__(RC_K) void adc_lut_kernel(const float* __restrict__ C, const float* __restrict__ q,
                                                        int D, int M, float* __restrict__ lut) {
     const int qi = blockIdx.x, m = blockIdx.y, k = threadIdx.x;
@@ -53,15 +71,15 @@ __global__ __launch_bounds__(RC_K) void adc_lut_kernel(const float* __restrict__
     const float* qs = q + (size_t)qi * D + m * dsub;  // wave-uniform
     const float* c = C + ((size_t)m * RC_K + k) * dsub;
     float s = 0.f;
-    for (int j = 0; j < dsub; ++j) s = s + qs[j] * c[j];
-    lut[((size_t)qi * M + m) * RC_K + k] = s;
+    for (int j = 0; j < dsub; ++j) s = adc_lut_step<L2>(s, qs[j], c[j]);
+    lut[((size_t)qi * M + m) * RC_K + k] = adc_lut_entry<L2>(s);
 }
 
 // Same arithmetic, supported dsub: thread k keeps its centroid row in registers and walks a chunk of queries (the
 // query slice is block-uniform -> scalar loads), so the 16 KiB centroid table is read once per 32 queries instead of
 // once per query (0.40 ms -> per 1200 queries at M = 48 for the kernel above).
 #define ADC_LUT_QCHUNK 32
-template <int DSUB>
+template <int DSUB, bool L2>
 __global__ __launch_bounds__(RC_K) void adc_lut_rows_kernel(const float* __restrict__ C, const float* __restrict__ q,
                                                             int nq, int D, int M, float* __restrict__ lut) {
     const int m = blockIdx.y, k = threadIdx.x;
@@ -78,8 +96,8 @@ __global__ __launch_bounds__(RC_K) void adc_lut_rows_kernel(const float* __restr
         const float* qs = q + (size_t)qi * D + m * DSUB;   // block-uniform
         float s = 0.f;
 #pragma unroll
-        for (int j = 0; j < DSUB; ++j) s = s + qs[j] * c[j];
-        lut[((size_t)qi * M + m) * RC_K + k] = s;
+        for (int j = 0; j < DSUB; ++j) s = adc_lut_step<L2>(s, qs[j], c[j]);
+        lut[((size_t)qi * M + m) * RC_K + k] = adc_lut_entry<L2>(s);
     }
 }
 
@@ -399,7 +417,8 @@ static int adc_launch_scans(rc_handle_t h, const uint8_t* codes, const uint8_t* 
 #define ADC_CASE(MM, QQ) \
     case MM: rc = adc_launch_scans<MM, QQ>(h, codes, image, N, nq, L.S, bufs, r, k, status, qstatus, s); break;
 
-extern "C" int rc_adc_lut(rc_handle_t h, const float* C, const float* q, int nq, int D, int M, int K, float* lut,
+template <bool L2>
+static int adc_launch_lut(rc_handle_t h, const float* C, const float* q, int nq, int D, int M, int K, float* lut,
                           rc_stream_t stream) {
     rc_device_guard device_guard_(h);
     if (!h || !C || !q || !lut || nq < 0 || M <= 0 || D <= 0) return RC_EINVAL;
@@ -407,17 +426,39 @@ extern "C" int rc_adc_lut(rc_handle_t h, const float* C, const float* q, int nq,
     if (nq == 0) return RC_OK;
     const dim3 cg((unsigned)((nq + ADC_LUT_QCHUNK - 1) / ADC_LUT_QCHUNK), (unsigned)M);
     switch (D / M) {
-#define ADC_LUT_CASE(DS)                                                                                              \
-        case DS:                                                                                                      \
-            hipLaunchKernelGGL(adc_lut_rows_kernel<DS>, cg, dim3(RC_K), 0, (hipStream_t)stream, C, q, nq, D, M, lut); \
+#define ADC_LUT_CASE(DS)                                                                                                  \
+        case DS:                                                                                                          \
+            hipLaunchKernelGGL((adc_lut_rows_kernel<DS, L2>), cg, dim3(RC_K), 0, (hipStream_t)stream, C, q, nq, D, M, lut); \
             break;
         ADC_LUT_CASE(8) ADC_LUT_CASE(12) ADC_LUT_CASE(16) ADC_LUT_CASE(24) ADC_LUT_CASE(32) ADC_LUT_CASE(48)
         ADC_LUT_CASE(64) ADC_LUT_CASE(96)
 #undef ADC_LUT_CASE
         default:
-            hipLaunchKernelGGL(adc_lut_kernel, dim3((unsigned)nq, (unsigned)M), dim3(RC_K), 0, (hipStream_t)stream, C, q, D,
+            hipLaunchKernelGGL(adc_lut_kernel<L2>, dim3((unsigned)nq, (unsigned)M), dim3(RC_K), 0, (hipStream_t)stream, C, q, D,
                                M, lut);
     }
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+extern "C" int rc_adc_lut(rc_handle_t h, const float* C, const float* q, int nq, int D, int M, int K, float* lut,
+                          rc_stream_t stream) {
+    return adc_launch_lut<false>(h, C, q, nq, D, M, K, lut, stream);
+}
+// the L2 tables S = 0.0f - T (adc_lut_step): what rc_adc_search_l2_q / _exact and the IVF entries of an L2 index score with
+extern "C" int rc_adc_lut_l2(rc_handle_t h, const float* C, const float* q, int nq, int D, int M, int K, float* lut,
+                             rc_stream_t stream) {
+    return adc_launch_lut<true>(h, C, q, nq, D, M, K, lut, stream);
+}
+
+// L2 metric, the one trailing kernel: the searches ran on s = -d; d = 0.0f - s over the nq * k outputs (+0.0f for a zero
+// distance, +inf for the -inf of the slots past N)
+__global__ __launch_bounds__(256) void adc_l2_distances_kernel(float* __restrict__ v, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) v[i] = 0.0f - v[i];
+}
+static int adc_finish(rc_handle_t h, bool l2, float* scores, int64_t n, hipStream_t s) {
+    if (!l2) return RC_OK;
+    hipLaunchKernelGGL(adc_l2_distances_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, scores, n);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -426,10 +467,11 @@ extern "C" int rc_adc_lut(rc_handle_t h, const float* C, const float* q, int nq,
 // conflict-free screen applies, the image is rebuilt in the workspace on every call (one extra pass over the codes).
 // qstatus: NULL, or nq ints (zeroed by the caller) that receive the status bits PER QUERY (bit0 too few candidates, bit1 a
 // list overflowed), so that a caller repeats or re-routes only the queries concerned (rc_adc_search_exact never fails).
-extern "C" int rc_adc_search_q(rc_handle_t h, const uint8_t* codes, const uint8_t* scan_image, int64_t N, int M, int K,
-                               const float* C, int D, const float* q, int nq, int k, int64_t id_offset, double sel_slack,
-                               float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
-                               rc_stream_t stream) {
+// l2: the metric selects the table builder and the trailing adc_l2_distances_kernel, nothing in between.
+static int adc_search_body(bool l2, rc_handle_t h, const uint8_t* codes, const uint8_t* scan_image, int64_t N, int M, int K,
+                           const float* C, int D, const float* q, int nq, int k, int64_t id_offset, double sel_slack,
+                           float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                           rc_stream_t stream) {
     rc_device_guard device_guard_(h);
     if (!h || !codes || !C || !q || !scores || !ids || !status || N <= 0 || nq < 0 || k <= 0 || M <= 0 || D <= 0)
         return RC_EINVAL;
@@ -453,7 +495,7 @@ extern "C" int rc_adc_search_q(rc_handle_t h, const uint8_t* codes, const uint8_
     const adc_bufs bufs = {lut, (float*)(w + L.sample), (float*)(w + L.thr), cnt, cand, (uint8_t*)(w + L.qlut),
                            (int*)(w + L.tint), (unsigned*)(w + L.idcnt), (unsigned*)(w + L.ids), (float*)(w + L.qstat)};
     hipStream_t s = (hipStream_t)stream;
-    int rc = rc_adc_lut(h, C, q, nq, D, M, K, lut, stream);
+    int rc = l2 ? rc_adc_lut_l2(h, C, q, nq, D, M, K, lut, stream) : rc_adc_lut(h, C, q, nq, D, M, K, lut, stream);
     if (rc != RC_OK) return rc;
     RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
     // rank of the sample score used as the filter threshold
@@ -463,7 +505,25 @@ extern "C" int rc_adc_search_q(rc_handle_t h, const uint8_t* codes, const uint8_
         default: return RC_ESHAPE;
     }
     if (rc != RC_OK) return rc;
-    return rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, scores, ids, status, s, qstatus);
+    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, scores, ids, status, s, qstatus);
+    if (rc != RC_OK) return rc;
+    return adc_finish(h, l2, scores, (int64_t)nq * k, s);
+}
+
+extern "C" int rc_adc_search_q(rc_handle_t h, const uint8_t* codes, const uint8_t* scan_image, int64_t N, int M, int K,
+                               const float* C, int D, const float* q, int nq, int k, int64_t id_offset, double sel_slack,
+                               float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                               rc_stream_t stream) {
+    return adc_search_body(false, h, codes, scan_image, N, M, K, C, D, q, nq, k, id_offset, sel_slack, scores, ids, status,
+                           qstatus, ws, ws_bytes, stream);
+}
+// The same search under the L2 metric (include/repconc_hip.h): distances ascending, ties by the lower id, +inf / -1 past N
+extern "C" int rc_adc_search_l2_q(rc_handle_t h, const uint8_t* codes, const uint8_t* scan_image, int64_t N, int M, int K,
+                                  const float* C, int D, const float* q, int nq, int k, int64_t id_offset, double sel_slack,
+                                  float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                                  rc_stream_t stream) {
+    return adc_search_body(true, h, codes, scan_image, N, M, K, C, D, q, nq, k, id_offset, sel_slack, scores, ids, status,
+                           qstatus, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_adc_search_img(rc_handle_t h, const uint8_t* codes, const uint8_t* scan_image, int64_t N, int M, int K,
@@ -542,9 +602,9 @@ static int adc_exact_scores(rc_handle_t h, const uint8_t* codes, int64_t N, cons
     return RC_OK;
 }
 
-extern "C" int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t N, int M, int K, const float* C, int D,
-                                   const float* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
-                                   size_t ws_bytes, rc_stream_t stream) {
+static int adc_search_exact_body(bool l2, rc_handle_t h, const uint8_t* codes, int64_t N, int M, int K, const float* C, int D,
+                                 const float* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                                 size_t ws_bytes, rc_stream_t stream) {
     rc_device_guard device_guard_(h);
     if (!h || !codes || !C || !q || !scores || !ids || N <= 0 || nq < 0 || k <= 0 || M <= 0 || D <= 0) return RC_EINVAL;
     if (K != RC_K || D % M != 0 || N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2) return RC_ESHAPE;
@@ -555,7 +615,7 @@ extern "C" int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t 
     hipStream_t s = (hipStream_t)stream;
     float* lut = (float*)(w + L.lut);
     float* sc = (float*)(w + L.sc);
-    int rc = rc_adc_lut(h, C, q, nq, D, M, K, lut, stream);
+    int rc = l2 ? rc_adc_lut_l2(h, C, q, nq, D, M, K, lut, stream) : rc_adc_lut(h, C, q, nq, D, M, K, lut, stream);
     if (rc != RC_OK) return rc;
     for (int q0 = 0; q0 < nq; q0 += ADC_EXACT_QX) {
         const int nx = nq - q0 < ADC_EXACT_QX ? nq - q0 : ADC_EXACT_QX;
@@ -573,5 +633,16 @@ extern "C" int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t 
         rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
         if (rc != RC_OK) return rc;
     }
-    return RC_OK;
+    return adc_finish(h, l2, scores, (int64_t)nq * k, s);
+}
+
+extern "C" int rc_adc_search_exact(rc_handle_t h, const uint8_t* codes, int64_t N, int M, int K, const float* C, int D,
+                                   const float* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                                   size_t ws_bytes, rc_stream_t stream) {
+    return adc_search_exact_body(false, h, codes, N, M, K, C, D, q, nq, k, id_offset, scores, ids, ws, ws_bytes, stream);
+}
+extern "C" int rc_adc_search_l2_exact(rc_handle_t h, const uint8_t* codes, int64_t N, int M, int K, const float* C, int D,
+                                      const float* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                                      size_t ws_bytes, rc_stream_t stream) {
+    return adc_search_exact_body(true, h, codes, N, M, K, C, D, q, nq, k, id_offset, scores, ids, ws, ws_bytes, stream);
 }

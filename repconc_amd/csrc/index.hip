@@ -15,6 +15,7 @@
 struct rc_index_s {
     rc_handle_t h;
     int D, M, K;
+    int metric;          // 0 inner product (default), 1 L2: which of the two search entry pairs rc_index_search calls
     float* C;            // [M, K, D/M]
     uint8_t* codes;      // [cap, M]
     uint8_t* image;      // [cap, M] permuted copy for the conflict-free ADC screen (NULL when this M uses none)
@@ -41,7 +42,7 @@ extern "C" int rc_index_create(rc_handle_t h, int D, int M, int K, rc_index_t* o
     if (!idx) return RC_EINVAL;
     idx->h = h; idx->D = D; idx->M = M; idx->K = K;
     idx->C = nullptr; idx->codes = nullptr; idx->image = nullptr; idx->n = 0; idx->cap = 0; idx->ws = nullptr; idx->ws_bytes = 0;
-    idx->status = nullptr; idx->have_centroids = false;
+    idx->status = nullptr; idx->have_centroids = false; idx->metric = 0;
     hipError_t e = hipMalloc((void**)&idx->C, (size_t)M * K * (D / M) * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&idx->status, 256);
     if (e != hipSuccess) {
@@ -143,6 +144,15 @@ extern "C" int rc_index_reset(rc_index_t idx) {
     return RC_OK;
 }
 
+// The metric of rc_index_search: 0 = inner product (what rc_index_create leaves), 1 = L2 (distances ascending, include/
+// repconc_hip.h "L2 metric").  Nothing the index keeps depends on it — the codes, the permuted image and the centroid table are
+// the same under both, the workspace is scratch that every search rewrites — so it may be set at any time between searches.
+extern "C" int rc_index_set_metric(rc_index_t idx, int metric) {
+    if (!idx || (metric != 0 && metric != 1)) return RC_EINVAL;
+    idx->metric = metric;
+    return RC_OK;
+}
+
 // Synchronous (reads the status word between attempts).  scores [nq,k], ids [nq,k] on the device.
 extern "C" int rc_index_search(rc_index_t idx, const float* q, int nq, int k, float* scores, int64_t* ids,
                                rc_stream_t stream) {
@@ -151,12 +161,15 @@ extern "C" int rc_index_search(rc_index_t idx, const float* q, int nq, int k, fl
     if (!idx->have_centroids) return RC_EINVAL;
     if (nq == 0) return RC_OK;
     hipStream_t s = (hipStream_t)stream;
-    if (idx->n == 0) {                                   // Faiss semantics: -inf scores, -1 labels
+    const bool l2 = idx->metric == 1;
+    const auto search_q = l2 ? rc_adc_search_l2_q : rc_adc_search_q;
+    const auto search_exact = l2 ? rc_adc_search_l2_exact : rc_adc_search_exact;
+    if (idx->n == 0) {                                   // Faiss semantics: -inf scores (L2: +inf distances), -1 labels
         const size_t cnt = (size_t)nq * k;
         float* hs = (float*)malloc(cnt * sizeof(float));
         int64_t* hi = (int64_t*)malloc(cnt * sizeof(int64_t));
         if (!hs || !hi) { free(hs); free(hi); return RC_EINVAL; }
-        for (size_t i = 0; i < cnt; ++i) { hs[i] = -INFINITY; hi[i] = -1; }
+        for (size_t i = 0; i < cnt; ++i) { hs[i] = l2 ? INFINITY : -INFINITY; hi[i] = -1; }
         hipError_t e = hipMemcpyAsync(scores, hs, cnt * sizeof(float), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipMemcpyAsync(ids, hi, cnt * sizeof(int64_t), hipMemcpyHostToDevice, s);
         if (e == hipSuccess) e = hipStreamSynchronize(s);
@@ -174,8 +187,8 @@ extern "C" int rc_index_search(rc_index_t idx, const float* q, int nq, int k, fl
             RC_IDX_HIP(idx, hipMalloc(&idx->ws, need_x));
             idx->ws_bytes = need_x;
         }
-        const int rcx = rc_adc_search_exact(idx->h, idx->codes, idx->n, idx->M, idx->K, idx->C, idx->D, q, nq, k, 0, scores, ids,
-                                            idx->ws, idx->ws_bytes, stream);
+        const int rcx = search_exact(idx->h, idx->codes, idx->n, idx->M, idx->K, idx->C, idx->D, q, nq, k, 0, scores, ids,
+                                     idx->ws, idx->ws_bytes, stream);
         if (rcx != RC_OK) return rcx;
         RC_IDX_HIP(idx, hipStreamSynchronize(s));
         return RC_OK;
@@ -208,8 +221,8 @@ extern "C" int rc_index_search(rc_index_t idx, const float* q, int nq, int k, fl
     for (int attempt = 0; attempt < 2; ++attempt) {
         RC_IDX_HIP(idx, hipMemsetAsync(idx->status, 0, sizeof(int), s));
         RC_IDX_HIP(idx, hipMemsetAsync(qstatus, 0, (size_t)nq * sizeof(int), s));
-        const int rc = rc_adc_search_q(idx->h, idx->codes, idx->image, idx->n, idx->M, idx->K, idx->C, idx->D, q, nq, k, 0,
-                                       slack, scores, ids, idx->status, qstatus, idx->ws, idx->ws_bytes, stream);
+        const int rc = search_q(idx->h, idx->codes, idx->image, idx->n, idx->M, idx->K, idx->C, idx->D, q, nq, k, 0,
+                                slack, scores, ids, idx->status, qstatus, idx->ws, idx->ws_bytes, stream);
         if (rc != RC_OK) return rc;
         RC_IDX_HIP(idx, hipMemcpyAsync(&st, idx->status, sizeof(int), hipMemcpyDeviceToHost, s));
         RC_IDX_HIP(idx, hipStreamSynchronize(s));
@@ -241,8 +254,8 @@ extern "C" int rc_index_search(rc_index_t idx, const float* q, int nq, int k, fl
         e = hipMemcpyAsync(bq + (size_t)j * idx->D, q + (size_t)hq[j] * idx->D, (size_t)idx->D * sizeof(float), hipMemcpyDeviceToDevice, s);
     int rc = RC_OK;
     if (e == hipSuccess)
-        rc = rc_adc_search_exact(idx->h, idx->codes, idx->n, idx->M, idx->K, idx->C, idx->D, bq, nbad, k, 0, bs, bi, idx->ws,
-                                 idx->ws_bytes, stream);
+        rc = search_exact(idx->h, idx->codes, idx->n, idx->M, idx->K, idx->C, idx->D, bq, nbad, k, 0, bs, bi, idx->ws,
+                          idx->ws_bytes, stream);
     for (int j = 0; e == hipSuccess && rc == RC_OK && j < nbad; ++j) {
         e = hipMemcpyAsync(scores + (size_t)hq[j] * k, bs + (size_t)j * k, (size_t)k * sizeof(float), hipMemcpyDeviceToDevice, s);
         if (e == hipSuccess)

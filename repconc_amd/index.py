@@ -4,7 +4,8 @@ The reference builds `faiss.IndexPQ(D, M, 8, METRIC_INNER_PRODUCT)`, appends raw
 wraps it as a 1-list IndexIVFPQ, clones it to the GPU(s) and calls `.search`
 (models/repconc/evaluate_repconc.py:78-135,180-185; models/jpq/finetune_jpq.py:157-161,176,209-214).
 `PQIndex` is duck-typed like those objects (`search`, `ntotal`, `pq.{d,M,nbits,code_size,ksub,dsub,
-centroids}`, `codes`, `metric_type`) so the call sites keep working, but:
+centroids}`, `codes`, `metric_type`) so the call sites keep working — with `METRIC_L2` (Faiss's own default for IndexPQ)
+`search` returns squared ADC distances in ascending order, DESIGN.md "L2 metric on the PQ indexes" — but:
 
   * codes live in ONE uint8 [N, M] device tensor that is appended to in place (amortised
     doubling) instead of being round-tripped through numpy on every add (evaluate_repconc.py:94-97);
@@ -23,8 +24,8 @@ import torch
 
 from . import ops
 
-METRIC_INNER_PRODUCT = 0  # faiss.METRIC_INNER_PRODUCT
-METRIC_L2 = 1             # faiss.METRIC_L2 (dense_index.FlatL2Index; PQIndex takes the inner product only)
+METRIC_INNER_PRODUCT = ops.METRIC_INNER_PRODUCT  # 0, faiss.METRIC_INNER_PRODUCT
+METRIC_L2 = ops.METRIC_L2                        # 1, faiss.METRIC_L2: PQIndex / IVFPQIndex (ADC distances), dense_index.FlatL2Index
 
 
 class PQIndex:
@@ -32,6 +33,8 @@ class PQIndex:
                  device: Optional[torch.device] = None):
         assert nbits == 8, "256 centroids per sub-quantiser (evaluate_repconc.py:80)"
         assert d % M == 0
+        if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
+            raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -97,7 +100,7 @@ class PQIndex:
 
     # ---- search
     def search(self, x, k: int):
-        """(scores [nq,k], ids [nq,k]); numpy in -> numpy out (evaluate_repconc.py:182), CUDA tensors
+        """(scores [nq,k], ids [nq,k]) — METRIC_L2: (squared distances ascending, ids); numpy in -> numpy out (evaluate_repconc.py:182), CUDA tensors
         in -> CUDA tensors out (finetune_jpq.py:176 via faiss.contrib.torch_utils)."""
         return self.search_async(x, k)()
 
@@ -110,7 +113,8 @@ class PQIndex:
         q = q.to(self.device, torch.float32, non_blocking=True)
         # prefixes of the row-major buffers are contiguous views: nothing is copied
         pending = ops.adc_search(self._codes[: self.ntotal], self._centroids, q, int(k), id_offset=self.id_offset,
-                                 scan_image=self._image, defer=True, stats=stats, sel_slack=self.sel_slack)
+                                 scan_image=self._image, defer=True, stats=stats, sel_slack=self.sel_slack,
+                                 metric=self.metric_type)
         self.last_search = pending           # its .stats say how many queries had to be repeated / answered by the exact path
 
         def finish():

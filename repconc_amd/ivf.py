@@ -8,7 +8,10 @@ semantics are fixed here:
   * a document goes to its L2-nearest coarse centroid; its PQ code is the ORDINARY RepCONC code of the whole vector
     (`by_residual = False`), so codes produced by the model are stored unchanged;
   * a query probes the `nprobe` cells with the largest inner product <q, centroid> and scans only their rows with the
-    exact ADC arithmetic of the flat index (`rc_ivf_search`); probing every cell returns exactly the flat result.
+    exact ADC arithmetic of the flat index (`rc_ivf_search`); probing every cell returns exactly the flat result;
+  * with `metric=METRIC_L2` a query probes the `nprobe` NEAREST cells (largest 2 <q, c_l> - ||c_l||^2), the scans score with the
+    L2 tables S = 0.0f - T (`ops.adc_lut`) on s = -d, and `search` returns d = 0.0f - s ascending (+inf / -1 in unfilled slots);
+    probing every cell returns exactly the flat L2 result.
 
 Rows are stored list-major: `codes` [N,M] sorted by cell, `list_off` [nlist+1], `ids` [N] original positions.
 """
@@ -22,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .index import PQIndex
+from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex
 
 
 def coarse_kmeans(x: torch.Tensor, nlist: int, iters: int = 10, seed: int = 1234, chunk: int = 1 << 20) -> torch.Tensor:
@@ -88,7 +91,11 @@ def coarse_assign(x: torch.Tensor, cent: torch.Tensor, chunk: int = 1 << 20, as_
 
 
 class IVFPQIndex:
-    def __init__(self, d: int, M: int, nlist: int, device: Optional[torch.device] = None):
+    def __init__(self, d: int, M: int, nlist: int, device: Optional[torch.device] = None, metric=METRIC_INNER_PRODUCT):
+        if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
+            raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
+        self.metric_type = metric
+        self._coarse_sq = (None, None, None)                                # (coarse tensor, its version, ||c_l||^2): L2 probing
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
             self.device = torch.device("cuda", torch.cuda.current_device())
@@ -146,7 +153,7 @@ class IVFPQIndex:
     def from_flat(cls, flat: PQIndex, nlist: int, x=None, iters: int = 10, train_rows: int = 1 << 18):
         """IVF view of an existing flat PQ index.  Without embeddings the cells are fitted on (and rows assigned by)
         the reconstructions decode(codes) — what the reference's pipeline has at hand once the corpus is coded."""
-        ivf = cls(flat.pq.d, flat.pq.M, nlist, device=flat.device)
+        ivf = cls(flat.pq.d, flat.pq.M, nlist, device=flat.device, metric=flat.metric_type)
         ivf.set_centroids(flat.pq.centroids)
         if x is None:
             chunks = [flat.reconstruct_n(i, min(1 << 18, flat.ntotal - i)) for i in range(0, flat.ntotal, 1 << 18)]
@@ -161,7 +168,7 @@ class IVFPQIndex:
     def to(self, device) -> "IVFPQIndex":
         """A full copy of the index on another device (device-to-device copies, over xGMI where peers are connected)."""
         device = torch.device(device)
-        out = IVFPQIndex(self.d, self.M, self.nlist, device=device)
+        out = IVFPQIndex(self.d, self.M, self.nlist, device=device, metric=self.metric_type)
         out.coarse = None if self.coarse is None else self.coarse.to(device)
         out.pq_centroids = self.pq_centroids.to(device).clone()
         out.codes, out.ids = self.codes.to(device), self.ids.to(device)
@@ -181,11 +188,24 @@ class IVFPQIndex:
         return out
 
     # ---- search
+    def _coarse_sqnorms(self) -> torch.Tensor:
+        """||c_l||^2 [nlist] fp32, kept with the coarse table it was made from (`coarse` is a plain attribute: a new tensor or an
+        in-place write makes it anew)."""
+        c = self.coarse
+        held, version, sq = self._coarse_sq
+        if held is not c or version != c._version:
+            sq = (c.float() * c.float()).sum(1)
+            self._coarse_sq = (c, c._version, sq)
+        return sq
+
     def probe(self, q: torch.Tensor, nprobe: int, ordered: bool = True) -> torch.Tensor:
-        """[nq, nprobe] int32: the nprobe cells with the largest <q, centroid> (ties at the boundary: lower cell id).
+        """[nq, nprobe] int32: the nprobe cells with the largest <q, centroid> (ties at the boundary: lower cell id) — under
+        METRIC_L2 the largest 2 <q, c_l> - ||c_l||^2, i.e. the nearest cells (||q||^2 is the same for every cell), same tie rule.
         ordered=True ranks them by decreasing score (ties: lower cell id); ordered=False — what the searches use — returns
         the same set in ascending cell order from one HIP kernel (rc_ivf_select_probes) after the library GEMM."""
         s = q.float() @ self.coarse.T
+        if self.metric_type == METRIC_L2:
+            s = 2.0 * s - self._coarse_sqnorms()[None, :]
         if not ordered and self.nlist <= 16384 and q.shape[0] > 0:
             s = s.contiguous()
             out = torch.empty((q.shape[0], nprobe), dtype=torch.int32, device=s.device)
@@ -206,17 +226,33 @@ class IVFPQIndex:
         M in {16,32,48,64,96}; tasks of 8 or — when a probed cell is shared by >= WIDE_MIN_SHARE queries of the call — 16
         queries; "lists8" / "lists16" force the width); "scan" = the per-query exact scan (rc_ivf_search); "auto" = lists
         where available.
-        Both return the same (scores, ids)."""
+        Both return the same (scores, ids); METRIC_L2: (squared distances ascending, ids), +inf / -1 in unfilled slots."""
         as_numpy = not isinstance(x, torch.Tensor)
         q = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x).to(self.device, torch.float32)
         q = q.contiguous()
-        nq = q.shape[0]
         if nprobe is None:
             nprobe = self.nprobe
+        scores, ids = self._search_scores(q, k, nprobe, method)
+        if self.metric_type == METRIC_L2:
+            # every path below worked on s = -d (the L2 tables are 0.0f - T); the one place a distance is formed: +0.0f for a
+            # zero (never -0.0f: not `-scores`), +inf for the -inf of an unfilled slot
+            scores = self._flip(scores)
+        return (scores.cpu().numpy(), ids.cpu().numpy()) if as_numpy else (scores, ids)
+
+    def _flip(self, v: torch.Tensor) -> torch.Tensor:
+        """METRIC_L2: s <-> d as 0.0f - v (never `-v`: a zero stays +0.0f); inner product: v itself."""
+        return torch.zeros_like(v).sub_(v) if self.metric_type == METRIC_L2 else v
+
+    def _search_scores(self, q: torch.Tensor, k: int, nprobe: int, method: str = "auto"):
+        """`search` on device tensors, in the internal form of both metrics: (scores descending, ids) with -inf / -1 in unfilled
+        slots — under METRIC_L2 the scores are s = -d.  The repair paths below go through `search(method="scan")` as they always
+        did (callers count those calls) and take its distances back to s with `_flip`: s is -x, +0.0f or -inf, so 0.0f - (0.0f - s)
+        is s bit for bit."""
+        nq = q.shape[0]
         if nq > self.MAX_QUERY_BATCH:                      # the C entries index their per-query workspaces with 32 bits
-            parts = [self.search(q[i:i + self.MAX_QUERY_BATCH], k, nprobe, method) for i in range(0, nq, self.MAX_QUERY_BATCH)]
-            scores, ids = torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
-            return (scores.cpu().numpy(), ids.cpu().numpy()) if as_numpy else (scores, ids)
+            parts = [self._search_scores(q[i:i + self.MAX_QUERY_BATCH], k, nprobe, method)
+                     for i in range(0, nq, self.MAX_QUERY_BATCH)]
+            return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
         nprobe = min(int(nprobe), self.nlist)
         probes = self.probe(q, nprobe, ordered=False)
         if method not in ("auto", "lists", "lists8", "lists16", "lists_host_plan", "scan"):
@@ -231,14 +267,14 @@ class IVFPQIndex:
                 scores, ids = self._search_lists_host_plan(q, probes, int(k), nprobe)
             else:      # "lists": the screen's width by the call's queries per probed cell; lists8 / lists16 force it
                 scores, ids = self._search_lists(q, probes, int(k), nprobe, width={"lists8": 8, "lists16": 16}.get(method))
-            return (scores.cpu().numpy(), ids.cpu().numpy()) if as_numpy else (scores, ids)
+            return scores, ids
         sizes = (self.list_off[1:] - self.list_off[:-1])[probes.long()]                      # [nq, nprobe]
         csum = torch.cumsum(sizes, 1)
         base = (csum - sizes).to(torch.int32).contiguous()
         count = csum[:, -1].to(torch.int32).contiguous()
         stride = max(4, int(count.max().item()))
         stride = (stride + 3) // 4 * 4
-        lut = ops.adc_lut(self.pq_centroids, q)
+        lut = ops.adc_lut(self.pq_centroids, q, self.metric_type)
         lib, h = _lib.load(), _lib.handle(self.device.index)
         s = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         wsb = lib.rc_ivf_search_ws_bytes(nq, stride)
@@ -253,15 +289,14 @@ class IVFPQIndex:
         if int(status.item()) & 2:
             # more than 16384 probed rows tie at the k-th score (duplicated passages): the path without any list
             scores, ids = self._search_exact_probed(q, probes, int(k))
-        if as_numpy:
-            return scores.cpu().numpy(), ids.cpu().numpy()
         return scores, ids
 
     def _search_exact_probed(self, q: torch.Tensor, probes: torch.Tensor, k: int):
         """The answer for ANY index content (the flat search's `rc_adc_search_exact`, query by query, over the rows of the
         probed cells): exact scores of every probed row, the k best in (score desc, corpus id asc) order by radix select.
         Slow — one gather of the probed rows per query — and only reached when the faster paths cannot decide (thousands of
-        identical rows in the probed cells)."""
+        identical rows in the probed cells).  Internal form (`_search_scores`): under METRIC_L2 the distances of the flat entry go
+        back to s = 0.0f - d, bit for bit the s they were made from (s is never -0.0f)."""
         nq = q.shape[0]
         scores = torch.full((nq, k), float("-inf"), dtype=torch.float32, device=self.device)
         ids = torch.full((nq, k), -1, dtype=torch.int64, device=self.device)
@@ -277,9 +312,9 @@ class IVFPQIndex:
             order = torch.argsort(corpus)                        # local row order = corpus id order: the search's tie rule
             rows, corpus = rows[order], corpus[order]
             sub = self.codes[rows].contiguous()
-            s, i = ops.adc_search_exact(sub, self.pq_centroids, q[j:j + 1], k)
+            s, i = ops.adc_search_exact(sub, self.pq_centroids, q[j:j + 1], k, metric=self.metric_type)
             valid = i[0] >= 0
-            scores[j] = s[0]
+            scores[j] = self._flip(s[0])
             ids[j, valid] = corpus[i[0][valid]]
         return scores, ids
 
@@ -335,7 +370,7 @@ class IVFPQIndex:
         ss = self._sample_step(nprobe)
         top = self._sizes_desc[:nprobe]                                    # the nprobe largest cells bound a query's sample
         sstride = max(4, int((16 * (top // (16 * ss)) + np.minimum(top % (16 * ss), 16)).sum()))
-        lut = ops.adc_lut(self.pq_centroids, q)
+        lut = ops.adc_lut(self.pq_centroids, q, self.metric_type)
         lib, h = _lib.load(), _lib.handle(dev.index)
         s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         wsb = lib.rc_ivf_search_probes_ws_bytes(self.M, nq, nprobe, self.nlist, sstride)
@@ -369,12 +404,13 @@ class IVFPQIndex:
                 # scores around the threshold) are answered by the per-query exact scan — one bad query does not make the
                 # batch repeat
                 bs, bi = self.search(q[bad], k, nprobe, method="scan")
-                scores[bad], ids[bad] = bs, bi
+                scores[bad], ids[bad] = self._flip(bs), bi
                 return scores, ids
             # status bit 2: a survivor stream of the screen filled up (it may have dropped anybody's rows) -> fewer survivors, again
             slack = max(slack / 3.0, 0.0)
         # no slack fits the streams: the per-query exact scan decides
-        return self.search(q, k, nprobe, method="scan")
+        bs, bi = self.search(q, k, nprobe, method="scan")
+        return self._flip(bs), bi
 
     def _search_lists_host_plan(self, q: torch.Tensor, probes: torch.Tensor, k: int, nprobe: int, sel_slack: float = 6.0,
                                 max_retries: int = 3):
@@ -405,7 +441,7 @@ class IVFPQIndex:
         task_qcnt = torch.clamp(per_cell[task_cell] - 8 * within, max=8).to(torch.int32).contiguous()
         task_list = task_cell.to(torch.int32).contiguous()
         sstride = max(4, int(scount.max().item()))
-        lut = ops.adc_lut(self.pq_centroids, q)
+        lut = ops.adc_lut(self.pq_centroids, q, self.metric_type)
         lib, h = _lib.load(), _lib.handle(dev.index)
         s = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         wsb = lib.rc_ivf_search_lists_ws_bytes(self.M, nq, sstride)
@@ -435,4 +471,5 @@ class IVFPQIndex:
             if st == 0:
                 return scores, ids
             slack = max(slack, 0.0) * 3.0 + 2.0 if (st & 1) else max(slack / 3.0, 0.0)
-        return self.search(q, k, nprobe, method="scan")
+        bs, bi = self.search(q, k, nprobe, method="scan")
+        return self._flip(bs), bi

@@ -10,7 +10,7 @@ run_repconc_eval.py:93-100 then searches from the main process only.  Here:
     query order: exactly the results of a single-device search.
   * `ShardedPQIndex` — the rows are split instead (device d holds rows [off_d, off_d + n_d) with `id_offset = off_d`),
     every device scans its rows for all queries and the per-device top-k lists are merged with
-    `sharded_search.merge_topk` ((score desc, id asc), the single-index order): what SURVEY §8e asks for next to the
+    `sharded_search.merge_topk` ((score desc, id asc) — (distance asc, id asc) for an L2 index — the single-index order): what SURVEY §8e asks for next to the
     replica mode, and what makes an index larger than one GPU searchable.
 
 Both are duck-typed like `PQIndex` (`search`, `ntotal`, `pq`, `codes`, `metric_type`, `set_centroids`, `add_codes`).
@@ -25,7 +25,7 @@ from typing import List, Optional, Sequence
 import numpy as np
 import torch
 
-from .index import PQIndex
+from .index import METRIC_L2, PQIndex
 from .sharded_search import merge_topk
 
 
@@ -190,7 +190,8 @@ class ShardedPQIndex(_MultiIndex):
         q, as_numpy = self._as_tensor(x)
         res = self._run([(p, q, int(k)) for p in self.parts])
         home = self.parts[0].device
-        scores, ids = merge_topk(torch.stack([r[0].to(home) for r in res]), torch.stack([r[1].to(home) for r in res]), int(k))
+        scores, ids = merge_topk(torch.stack([r[0].to(home) for r in res]), torch.stack([r[1].to(home) for r in res]), int(k),
+                                 largest=self.metric_type != METRIC_L2)
         if as_numpy:
             return scores.cpu().numpy(), ids.cpu().numpy()
         return scores.to(q.device) if q.is_cuda else scores, ids.to(q.device) if q.is_cuda else ids

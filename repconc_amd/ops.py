@@ -811,14 +811,28 @@ def kmeans_split_empty_(centroids: torch.Tensor, counts: torch.Tensor, nsplit: O
 
 
 # --------------------------------------------------------------------------- ADC search
-def adc_lut(centroids: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+METRIC_INNER_PRODUCT, METRIC_L2 = 0, 1      # faiss.METRIC_INNER_PRODUCT / faiss.METRIC_L2 (re-exported by repconc_amd.index)
+
+
+def _adc_metric(metric) -> bool:
+    """True for the L2 metric; anything but the two Faiss values is an error."""
+    if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
+        raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
+    return metric == METRIC_L2
+
+
+def adc_lut(centroids: torch.Tensor, q: torch.Tensor, metric: int = METRIC_INNER_PRODUCT) -> torch.Tensor:
+    """The per-query tables [nq, M, 256] every ADC search scores with.  Inner product: <q_m, C[m][c]>.  METRIC_L2: S = 0.0f - T with
+    T[m][c] = the fp32 chain of (q_j - c_j)^2, j ascending — the searches run on s = -d, and no entry is -0.0f (rc_adc_lut_l2)."""
+    l2 = _adc_metric(metric)
     _need_cuda(centroids, q)
     c, q = _centroids(centroids), _rows_f32(q).contiguous()
     M, _, dsub = c.shape
     nq, D = q.shape
     lut = torch.empty((nq, M, K), dtype=torch.float32, device=q.device)
     lib, h, s, _ = _ctx(q)
-    _lib.check(lib.rc_adc_lut(h, _p(c), _p(q), nq, D, M, K, _p(lut), s), "rc_adc_lut", h)
+    fn, name = (lib.rc_adc_lut_l2, "rc_adc_lut_l2") if l2 else (lib.rc_adc_lut, "rc_adc_lut")
+    _lib.check(fn(h, _p(c), _p(q), nq, D, M, K, _p(lut), s), name, h)
     return lut
 
 
@@ -896,10 +910,13 @@ class PendingSearch:
     on degenerate data (thousands of identical codes, all rows tied).  Lets a caller enqueue every query batch before the
     first host synchronisation."""
 
-    def __init__(self, rerun, scores, ids, status, qstatus, slack, max_retries, stream=None):
+    def __init__(self, rerun, scores, ids, status, qstatus, slack, max_retries, stream=None, metric: int = 0):
         self._rerun, self._scores, self._ids, self._status, self._qstatus = rerun, scores, ids, status, qstatus
         self._slack, self._left, self._done = slack, max_retries, status is None
         self._stream = stream
+        # the metric of `scores` (ADC searches: METRIC_INNER_PRODUCT / METRIC_L2).  `rerun` repeats and hands over to the exact
+        # route under the same one, and each of those entries returns the metric's final values: rows are only ever copied here
+        self.metric = metric
         self.stats = {"retried_queries": 0, "exact_queries": 0}
 
     def result(self):
@@ -977,10 +994,12 @@ class _nullcontext:
         return False
 
 
-def adc_search_exact(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
-    """The same answer as `adc_search` by the path that cannot fail (rc_adc_search_exact): exact scores of every row and
-    a radix select of the min(k, N) best keys.  For the queries the sampled-threshold path gives up on, and a slow but
-    independent cross-check in the tests."""
+def adc_search_exact(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
+                     metric: int = METRIC_INNER_PRODUCT):
+    """The same answer as `adc_search` by the path that cannot fail (rc_adc_search_exact / rc_adc_search_l2_exact): exact scores
+    of every row and a radix select of the min(k, N) best keys.  For the queries the sampled-threshold path gives up on, and a
+    slow but independent cross-check in the tests."""
+    l2 = _adc_metric(metric)
     _need_cuda(codes, centroids, q)
     if codes.dtype != torch.uint8 or not codes.is_contiguous():
         raise ValueError("index codes must be contiguous uint8 [N, M]")
@@ -991,27 +1010,32 @@ def adc_search_exact(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tens
     scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
     if nq == 0 or N == 0:
-        scores.fill_(float("-inf"))
+        scores.fill_(float("inf") if l2 else float("-inf"))
         ids.fill_(-1)
         return scores, ids
     wsb = lib.rc_adc_search_exact_ws_bytes(N, M, K, nq, k)
     ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-    _lib.check(lib.rc_adc_search_exact(h, _p(codes), N, M, K, _p(c), D, _p(q), nq, int(k), int(id_offset), _p(scores), _p(ids),
-                                       _p(ws), wsb, s), "rc_adc_search_exact", h)
+    fn, name = (lib.rc_adc_search_l2_exact, "rc_adc_search_l2_exact") if l2 else (lib.rc_adc_search_exact, "rc_adc_search_exact")
+    _lib.check(fn(h, _p(codes), N, M, K, _p(c), D, _p(q), nq, int(k), int(id_offset), _p(scores), _p(ids), _p(ws), wsb, s), name, h)
     return scores, ids
 
 
 def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
                sel_slack: Optional[float] = None, max_retries: int = 2, scan_image: Optional[torch.Tensor] = None,
-               defer: bool = False, stats: Optional[dict] = None):
-    """Top-k inner-product ADC search of `q` [nq,D] against uint8 `codes` [N,M].
+               defer: bool = False, stats: Optional[dict] = None, metric: int = METRIC_INNER_PRODUCT):
+    """Top-k ADC search of `q` [nq,D] against uint8 `codes` [N,M].
     Returns (scores [nq,k] fp32, ids [nq,k] int64), sorted (score desc, id asc).
     evaluate_repconc.py:180-185 / finetune_jpq.py:176.
+    metric: METRIC_INNER_PRODUCT, or METRIC_L2 — then the first array holds squared distances (the fp32 sum over m ascending of
+    the sub-distances, `adc_lut`), sorted (distance asc, id asc), +0.0f for a zero, +inf / -1 past N.  The library entries of the
+    metric (rc_adc_search_l2_q / rc_adc_search_l2_exact) return distances themselves, and every path of `PendingSearch` — first
+    pass, per-query repeat, exact route — ends in exactly one of them per query: nothing is negated here.
     scan_image: the index's permuted code image (adc_scan_image_), kept by PQIndex; None = rebuilt per call.
     defer: return a `PendingSearch` instead (no host synchronisation here; `.result()` gives the pair).
     stats (measurement): receives "survivors" / "candidates" = int32 [nq] device tensors, the rows of every query that passed
     the 8-bit screen / that the exact rescoring kept in the FIRST pass (rc_adc_search_ws_counts).
     Never raises on degenerate index content: see `PendingSearch`."""
+    l2 = _adc_metric(metric)
     _need_cuda(codes, centroids, q, scan_image)
     if sel_slack is None:
         sel_slack = ADC_SEL_SLACK
@@ -1036,16 +1060,17 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
             import logging
             logging.getLogger(__name__).warning("adc_search: MCQ_M = %d has no screening kernel (%s have); using the exact scan",
                                                 M, sorted(SEARCH_SCREEN_M))
-        got = adc_search_exact(codes, c, q, k, id_offset)
-        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
+        got = adc_search_exact(codes, c, q, k, id_offset, metric)
+        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0, metric=metric) if defer else got
     scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
     if nq == 0 or N == 0:
         if nq and N == 0:
-            scores.fill_(float("-inf"))
+            scores.fill_(float("inf") if l2 else float("-inf"))
             ids.fill_(-1)
-        return PendingSearch(None, scores, ids, None, None, 0.0, 0) if defer else (scores, ids)
+        return PendingSearch(None, scores, ids, None, None, 0.0, 0, metric=metric) if defer else (scores, ids)
     ws_fn = lib.rc_adc_search_img_ws_bytes if scan_image is not None else lib.rc_adc_search_ws_bytes
+    search_fn, search_name = (lib.rc_adc_search_l2_q, "rc_adc_search_l2_q") if l2 else (lib.rc_adc_search_q, "rc_adc_search_q")
 
     def launch(qq, slack, out_s, out_i):
         # the workspace is released when this returns: the caching allocator hands it out again in stream order only
@@ -1055,9 +1080,8 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
         status = torch.zeros((1,), dtype=torch.int32, device=q.device)
         qstatus = torch.zeros((n,), dtype=torch.int32, device=q.device)
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _lib.check(lib.rc_adc_search_q(h, _p(codes), _p(scan_image), N, M, K, _p(c), D, _p(qq), n, int(k), int(id_offset),
-                                       float(slack), _p(out_s), _p(out_i), _p(status), _p(qstatus), _p(ws), wsb, st),
-                   "rc_adc_search_q", h)
+        _lib.check(search_fn(h, _p(codes), _p(scan_image), N, M, K, _p(c), D, _p(qq), n, int(k), int(id_offset),
+                             float(slack), _p(out_s), _p(out_i), _p(status), _p(qstatus), _p(ws), wsb, st), search_name, h)
         if stats is not None and "candidates" not in stats:
             so, co = C.c_size_t(0), C.c_size_t(0)
             _lib.check(lib.rc_adc_search_ws_counts(N, M, K, n, C.byref(so), C.byref(co)), "rc_adc_search_ws_counts", h)
@@ -1069,7 +1093,7 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
     def rerun(idx, slack, exact):
         qq = q[idx].contiguous()
         if exact:
-            s_, i_ = adc_search_exact(codes, c, qq, k, id_offset)
+            s_, i_ = adc_search_exact(codes, c, qq, k, id_offset, metric)
             return s_, i_, None
         s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q.device)
         i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q.device)
@@ -1079,7 +1103,7 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
     _warm_retry_ops(q.device)
     status, qstatus = launch(q, float(sel_slack), scores, ids)
     pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
-                            stream=torch.cuda.current_stream(dev))
+                            stream=torch.cuda.current_stream(dev), metric=metric)
     return pending if defer else pending.result()
 
 

@@ -12,29 +12,31 @@ from typing import Sequence
 import torch
 import torch.distributed as dist
 
-from .index import PQIndex
+from .index import METRIC_L2, PQIndex
 
 
-def merge_topk(scores_parts: torch.Tensor, ids_parts: torch.Tensor, k: int):
+def merge_topk(scores_parts: torch.Tensor, ids_parts: torch.Tensor, k: int, largest: bool = True):
     """scores_parts / ids_parts: [G, nq, k] per-shard results (ids global, -1 = empty).  Returns the merged
-    [nq, k] lists.  Two stable sorts on G*k items per query — bookkeeping, not the scan."""
+    [nq, k] lists.  Two stable sorts on G*k items per query — bookkeeping, not the scan.
+    largest=False (L2 indexes: the parts hold distances): ascending, ties by the lower id; the empty slots (+inf, -1) last."""
     G, nq, kk = scores_parts.shape
     s = scores_parts.permute(1, 0, 2).reshape(nq, G * kk)
     i = ids_parts.permute(1, 0, 2).reshape(nq, G * kk)
     big = torch.where(i < 0, torch.full_like(i, torch.iinfo(torch.int64).max), i)
     order = torch.argsort(big, dim=1, stable=True)                 # id ascending
     s, i = torch.gather(s, 1, order), torch.gather(i, 1, order)
-    order = torch.argsort(s, dim=1, descending=True, stable=True)  # then score descending, ties keep id order
+    order = torch.argsort(s, dim=1, descending=largest, stable=True)  # then by score, ties keep id order (empty slots: id max)
     return torch.gather(s, 1, order)[:, :k].contiguous(), torch.gather(i, 1, order)[:, :k].contiguous()
 
 
 def sharded_search(index: PQIndex, q: torch.Tensor, k: int, group=None):
     """`index` holds this rank's rows with `index.id_offset` = global id of its first row."""
     scores, ids = index.search(q, k)
+    largest = index.metric_type != METRIC_L2                       # an L2 index returns distances: merge ascending
     if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size(group) == 1:
         return scores, ids
     from . import ops
-    out = merge_topk(ops.all_gather(scores, group), ops.all_gather(ids, group), k)
+    out = merge_topk(ops.all_gather(scores, group), ops.all_gather(ids, group), k, largest)
     ops.comm_check(q.device)                                       # a timed-out exchange is an error, not a result
     return out
 
@@ -42,7 +44,8 @@ def sharded_search(index: PQIndex, q: torch.Tensor, k: int, group=None):
 def search_virtual_shards(shards: Sequence[PQIndex], q: torch.Tensor, k: int):
     """The same merge with the shards held by one process (single-GPU boxes, tests)."""
     parts = [sh.search(q, k) for sh in shards]
-    return merge_topk(torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts]), k)
+    return merge_topk(torch.stack([p[0] for p in parts]), torch.stack([p[1] for p in parts]), k,
+                      shards[0].metric_type != METRIC_L2)
 
 
 def replicated_search(index, q: torch.Tensor, k: int, *search_args, group=None):
