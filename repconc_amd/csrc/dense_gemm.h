@@ -1,8 +1,9 @@
-// What the dense flat searches share (dense_search.hip: fp32 corpus, dense_search_f16.hip: fp16 corpus): the GEMM on the
-// fp32 matrix cores whose result IS the score definition (the fp32 fmaf chain over d ascending), the workspace layouts and
-// the exact route.  T is the storage type of x and q: float, or _Float16 widened to fp32 on load (exact).  Device code:
-// every translation unit that uses it compiles its own copy, no -fgpu-rdc.  The route of a search and what the screened
-// searches share on top of this are in dense_screen.h.
+// What the four dense flat searches share (dense_search.hip, dense_search_f16.hip, dense_search_bf16x3.hip,
+// dense_search_l2.hip): the GEMM on the fp32 matrix cores whose result IS the inner-product score (the fp32 fmaf chain over d
+// ascending) and, with one more operand, the L2 screen; the workspace layouts and the argument checks.  T is the storage
+// type of x and q: float, or _Float16 widened to fp32 on load (exact).  Device code: every translation unit that uses it
+// compiles its own copy, no -fgpu-rdc.  The route of a search, exact route included, and what the screened searches share
+// on top of this are in dense_screen.h.
 #pragma once
 #include "topk.h"
 
@@ -235,20 +236,7 @@ static int dense_check(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D,
     return RC_OK;
 }
 
-// the exact route: full score rows of L.qx queries at a time, then the radix select
-template <typename T>
-static int dense_exact(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, int k,
-                       int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s) {
-    float* sc = (float*)(w + L.sc);             // (the select's status word is never set: exactly min(k, N) keys are collected)
-    for (int q0 = 0; q0 < nq; q0 += L.qx) {
-        const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
-        int rc = dense_launch_gemm<DENSE_STORE, T>(h, x, ldx, N, N, 0, q + (int64_t)q0 * D, nx, D, nullptr, sc, nullptr, nullptr, s);
-        if (rc != RC_OK) return rc;
-        rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
-        if (rc != RC_OK) return rc;
-    }
-    return RC_OK;
-}
-// dense_exact<float>, defined once in dense_search.hip: the exact route of both searches over an fp32 corpus
-int dense_exact_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
-                    int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s);
+// The exact route's score rows over an fp32 corpus, out [nq][N]: dense_launch_gemm<DENSE_STORE, float>, defined once in
+// dense_search.hip and shared with the bf16x3 unit, which so carries no fp32 GEMM of its own
+int dense_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
+                         hipStream_t s);

@@ -1,14 +1,17 @@
-// What the three dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
-// dense_search_f16.hip: fp16 corpus and f16 screen, dense_search_bf16x3.hip: fp32 corpus and bf16x3 screen): the route of a
-// search, the pieces common to the two 16x16x32 screen GEMMs, the rescoring kernel and the certificate kernel.  Device code:
-// every translation unit compiles its own copy, no -fgpu-rdc.
+// What the four dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
+// dense_search_f16.hip: fp16 corpus and f16 screen, dense_search_bf16x3.hip: fp32 corpus and bf16x3 screen,
+// dense_search_l2.hip: fp32 corpus, squared Euclidean distance): the route of a search and the bodies of its entries, the
+// pieces common to the two 16x16x32 screen GEMMs, the rescoring kernel and the certificate kernel.  Device code: every
+// translation unit compiles its own copy, no -fgpu-rdc.
 //
 // The route (dense_search_route).  A variant V supplies the storage type, its screen GEMM, an optional query pre-pass and,
-// if its screen only approximates the score (V::approximate), the bound E_q of its certificate.
-//   Exact route (N <= DENSE_EXACT_MAX_N, and the queries the fast route gives up on): dense_gemm_kernel<STORE> (dense_gemm.h,
-//   the fp32 matrix cores over rows widened on load, i.e. the chain itself) writes the full score rows of a chunk of queries,
-//   then the 8-pass radix select over the 64-bit keys (rc_adc_launch_exact_select).  It terminates with the same answer for
-//   any content (all rows identical, k >= N, ...).
+// if its screen only approximates the score (V::approximate), the bound E_q of its certificate.  The L2 variant (V::l2) scores
+// s = -d: its screen takes the rows' squared norms as a side operand, its chain is the one of squared differences, and
+// V::finish turns the k output values into d at the end.
+//   Exact route (N <= DENSE_EXACT_MAX_N, and the queries the fast route gives up on; dense_exact): V::exact_rows writes the
+//   full score rows of a chunk of queries, the chain itself (dense_gemm_kernel<STORE> of dense_gemm.h, the fp32 matrix cores
+//   over rows widened on load; L2: dense_l2_exact_kernel), then the 8-pass radix select over the 64-bit keys
+//   (topk_exact_select), then V::finish.  It terminates with the same answer for any content (all rows identical, k >= N, ...).
 //   Fast route (N > 4 S, S = min(N, 32768)):
 //   0. V::prepass: bf16x3 splits the queries into two bf16 planes in the tail of the workspace; nothing for the others
 //   1. screen<STORE> over the strided sample j -> row j N / S: s~ of the sample (fp32 screen: s~ = s, the chain)
@@ -20,6 +23,7 @@
 //      row outside the list has s~ < thr~, hence s < thr~ + E_q: if t >= thr~ + E_q (everything in fp64, rounded upwards) no
 //      such row can enter the top-k or tie with its last member and the answer is proven equal to the exact route's.
 //      Otherwise qstatus bit2, "not certified": the caller repeats the query with another slack or takes the exact route.
+//   7. V::finish, after the certificate has read the scores
 #pragma once
 #include "dense_gemm.h"
 
@@ -74,10 +78,21 @@ __device__ __forceinline__ void dense_screen_epilogue(const dense_f32x4 (&acc)[4
 // ---- rescoring --------------------------------------------------------------------------------------------------------------
 #define DENSE_RESCORE_QCHUNK 1024                        // query values staged in LDS
 
+// one step of the chain: s = fmaf(q, x, s), or for L2 a literal subtraction, then fmaf(t, t, s) (-ffp-contract=off: two roundings)
+template <bool L2>
+__device__ __forceinline__ float dense_chain_step(float q, float x, float s) {
+    if constexpr (L2) {
+        const float t = q - x;
+        return __builtin_fmaf(t, t, s);
+    } else {
+        return __builtin_fmaf(q, x, s);
+    }
+}
+
 // grid: (nq, ADC_CAND_CAP / 256) blocks of 256 threads; one lane per candidate key of query blockIdx.x.  The key's score half
-// (the screen's s~) is replaced by the chain: literal fmaf calls, d ascending, one accumulator, over the values widened to
-// fp32 (exact).  VEC: 16-byte aligned rows.
-template <bool VEC, typename T>
+// (the screen's s~) is replaced by the chain: dense_chain_step<L2>, d ascending, one accumulator, over the values widened to
+// fp32 (exact); L2: by -d.  VEC: 16-byte aligned rows.
+template <bool VEC, typename T, bool L2>
 __global__ __launch_bounds__(256) void dense_rescore_kernel(const T* __restrict__ x, int64_t ldx, int D, const T* __restrict__ q,
                                                             const unsigned* __restrict__ cnt,
                                                             unsigned long long* __restrict__ cand) {
@@ -105,23 +120,23 @@ __global__ __launch_bounds__(256) void dense_rescore_kernel(const T* __restrict_
                     float v[8];
                     dense_load8(xp + d0 + d, v);
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) s = __builtin_fmaf(sq[d + e], v[e], s);
+                    for (int e = 0; e < 8; ++e) s = dense_chain_step<L2>(sq[d + e], v[e], s);
                 }
             }
-            for (; d < dn; ++d) s = __builtin_fmaf(sq[d], (float)xp[d0 + d], s);
+            for (; d < dn; ++d) s = dense_chain_step<L2>(sq[d], (float)xp[d0 + d], s);
         }
     }
-    if (mine) *kp = adc_exact_key(s, (int64_t)row);
+    if (mine) *kp = adc_exact_key(L2 ? -s : s, (int64_t)row);
 }
 
-template <typename T>
+template <bool L2, typename T>
 static int dense_launch_rescore(rc_handle_t h, const T* x, int64_t ldx, int D, const T* q, int nq, const unsigned* cnt,
                                 unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
     if (ldx % (16 / (int)sizeof(T)) == 0 && !((uintptr_t)x & 15u))
-        hipLaunchKernelGGL((dense_rescore_kernel<true, T>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
+        hipLaunchKernelGGL((dense_rescore_kernel<true, T, L2>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
     else
-        hipLaunchKernelGGL((dense_rescore_kernel<false, T>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
+        hipLaunchKernelGGL((dense_rescore_kernel<false, T, L2>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -164,15 +179,29 @@ __global__ __launch_bounds__(64) void dense_certify_kernel(const typename V::T* 
 }
 
 // ---- the route --------------------------------------------------------------------------------------------------------------
-// A variant V:
+// A variant V (dense_variant_defaults holds what most of them say):
 //   typedef T                      storage type of x and q
 //   typedef Q                      what its screen reads as the query operand (T, or the bf16 planes of the pre-pass)
 //   static constexpr bool approximate
+//   static constexpr bool l2                              scores are -d: the entry takes xsq [N], the squared norm of every
+//                                                         row, and the rescorer walks dense_chain_step<true>
+//   static constexpr unsigned ws_align                    alignment the workspace must have
 //   static size_t extra_ws_bytes(nq, D)                   workspace after the fast layout, for the pre-pass
 //   static int prepass(h, q, nq, D, tail, &qs, s)         qs = the screen's query operand (tail: that extra workspace)
-//   static int launch_gemm<MODE>(h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s)
-//   static int exact(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, L, s)
+//   static int launch_gemm<MODE>(xsq, h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s)
+//                                                         xsq leads so that a screen without a side operand drops it
+//   static int exact_rows(h, x, ldx, N, D, q, nq, out, s) out [nq][N] = the chain of every pair
+//   static int finish(h, scores, n, s)                    the last step over the n output values; empty: launches nothing
 //   approximate: eq / refuse of dense_certify_kernel
+struct dense_variant_defaults {
+    static constexpr bool l2 = false;
+    static constexpr unsigned ws_align = 1;
+    static size_t extra_ws_bytes(int, int) { return 0; }
+    template <typename T>
+    static int prepass(rc_handle_t, const T* q, int, int, char*, const T** qs, hipStream_t) { *qs = q; return RC_OK; }
+    static int finish(rc_handle_t, float*, int64_t, hipStream_t) { return RC_OK; }
+};
+
 static inline size_t dense_exact_ws_bytes(int64_t N, int D, int nq, int k) {
     return dense_shape_ok(N, D, nq, k) ? dense_exact_ws(N, nq).sel.total : 0;
 }
@@ -182,12 +211,28 @@ static size_t dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
     return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total + V::extra_ws_bytes(nq, D);
 }
 
-// checked arguments (dense_check, status, xnorm_max if approximate, nq > 0, a workspace of dense_search_ws_bytes<V>)
+// the exact route: full score rows of L.qx queries at a time, then the radix select
+template <typename V>
+static int dense_exact(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q, int nq,
+                       int k, int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L,
+                       hipStream_t s) {
+    float* sc = (float*)(w + L.sc);             // (the select's status word is never set: exactly min(k, N) keys are collected)
+    for (int q0 = 0; q0 < nq; q0 += L.qx) {
+        const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
+        int rc = V::exact_rows(h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
+        if (rc != RC_OK) return rc;
+        rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
+        if (rc != RC_OK) return rc;
+    }
+    return V::finish(h, scores, (int64_t)nq * k, s);
+}
+
+// checked arguments (dense_search_entry: dense_check, the extra pointers, nq > 0, a workspace of dense_search_ws_bytes<V>)
 template <typename V>
 static int dense_search_route(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q,
-                              int nq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores,
-                              int64_t* ids, int* status, int* qstatus, char* w, hipStream_t s) {
-    if (dense_exact_route(N)) return V::exact(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s);
+                              int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack,
+                              float* scores, int64_t* ids, int* status, int* qstatus, char* w, hipStream_t s) {
+    if (dense_exact_route(N)) return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s);
     const dense_fast_layout L = dense_fast_ws(N, nq);
     float* sample = (float*)(w + L.sample);
     float* thr = (float*)(w + L.thr);
@@ -196,23 +241,56 @@ static int dense_search_route(rc_handle_t h, const typename V::T* x, int64_t ldx
     const typename V::Q* qs;
     int rc = V::prepass(h, q, nq, D, w + L.total, &qs, s);
     if (rc != RC_OK) return rc;
-    rc = V::template launch_gemm<DENSE_STORE>(h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
+    rc = V::template launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
     if (rc != RC_OK) return rc;
     rc = rc_adc_launch_threshold(h, sample, L.S, nq, rc_adc_sample_rank(N, L.S, k, sel_slack), thr, s);
     if (rc != RC_OK) return rc;
     RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
-    rc = V::template launch_gemm<DENSE_FILTER>(h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
+    rc = V::template launch_gemm<DENSE_FILTER>(xsq, h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
     if (rc != RC_OK) return rc;
     if constexpr (V::approximate) {
-        rc = dense_launch_rescore(h, x, ldx, D, q, nq, cnt, cand, s);
+        rc = dense_launch_rescore<V::l2>(h, x, ldx, D, q, nq, cnt, cand, s);
         if (rc != RC_OK) return rc;
     }
     rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, scores, ids, status, s, qstatus);
+    if (rc != RC_OK) return rc;
     if constexpr (V::approximate) {
-        if (rc != RC_OK) return rc;
         hipLaunchKernelGGL(dense_certify_kernel<V>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, thr, xnorm_max, scores,
                            status, qstatus);
         RC_LAUNCH_CHECK(h);
     }
-    return rc;
+    return V::finish(h, scores, (int64_t)nq * k, s);
 }
+
+// ---- the entries ------------------------------------------------------------------------------------------------------------
+// The bodies of rc_dense*_search_exact and rc_dense*_search_q.  The order of the checks is part of the C ABI: shapes before
+// pointers (dense_check), a missing status / xnorm_max / xsq before the nq == 0 success, the workspace last.
+template <typename V>
+static int dense_exact_entry(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q, int nq,
+                             int k, int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes,
+                             rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
+    if (crc != RC_OK) return crc;
+    if (nq == 0) return RC_OK;
+    const dense_exact_layout L = dense_exact_ws(N, nq);
+    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
+    return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
+}
+
+// xsq is read if V::l2, xnorm_max if V::approximate
+template <typename V>
+static int dense_search_entry(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q,
+                              int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack,
+                              float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                              rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
+    if (crc != RC_OK) return crc;
+    if (!status || (V::l2 && !xsq) || (V::approximate && !xnorm_max)) return RC_EINVAL;
+    if (nq == 0) return RC_OK;
+    if (!ws || ((uintptr_t)ws & (V::ws_align - 1)) || ws_bytes < dense_search_ws_bytes<V>(N, D, nq, k)) return RC_EWORKSPACE;
+    return dense_search_route<V>(h, x, ldx, N, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, scores, ids, status, qstatus,
+                                 (char*)ws, (hipStream_t)stream);
+}
+

@@ -16,24 +16,21 @@
 //
 // The route of a search (sample -> threshold -> FILTER -> select, or the exact route for small N) is dense_search_route
 // (dense_screen.h) with this unit's variant: the fp32 GEMM is sample screen, FILTER screen and exact route at once, its scores
-// are the chain, so nothing is rescored or certified.  The GEMM kernel, the workspace layouts and the exact route are in
-// dense_gemm.h.
+// are the chain, so nothing is rescored or certified.  The GEMM kernel and the workspace layouts are in dense_gemm.h.
 #include "dense_screen.h"
 
-int dense_exact_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
-                    int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s) {
-    return dense_exact<float>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, L, s);
+int dense_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
+                         hipStream_t s) {
+    return dense_launch_gemm<DENSE_STORE, float>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
 }
 
-struct dense_f32_variant {
+struct dense_f32_variant : dense_variant_defaults {
     typedef float T;
     typedef float Q;
     static constexpr bool approximate = false;
-    static size_t extra_ws_bytes(int, int) { return 0; }
-    static int prepass(rc_handle_t, const float* q, int, int, char*, const float** qs, hipStream_t) { *qs = q; return RC_OK; }
     template <int MODE, typename... A>
-    static int launch_gemm(A... a) { return dense_launch_gemm<MODE, float>(a...); }
-    static constexpr auto* exact = &dense_exact_f32;
+    static int launch_gemm(const float*, A... a) { return dense_launch_gemm<MODE, float>(a...); }
+    static constexpr auto* exact_rows = &dense_exact_rows_f32;
 };
 
 extern "C" size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
@@ -45,24 +42,12 @@ extern "C" size_t rc_dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
 extern "C" int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                      int k, int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes,
                                      rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
-    if (crc != RC_OK) return crc;
-    if (nq == 0) return RC_OK;
-    const dense_exact_layout L = dense_exact_ws(N, nq);
-    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
-    return dense_exact_f32(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
+    return dense_exact_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
                                  int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus,
                                  void* ws, size_t ws_bytes, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
-    if (crc != RC_OK) return crc;
-    if (!status) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ws_bytes < rc_dense_search_ws_bytes(N, D, nq, k)) return RC_EWORKSPACE;
-    return dense_search_route<dense_f32_variant>(h, x, ldx, N, D, q, nq, nullptr, k, id_offset, sel_slack, scores, ids, status,
-                                                 qstatus, (char*)ws, (hipStream_t)stream);
+    return dense_search_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, nullptr, nullptr, k, id_offset, sel_slack, scores, ids,
+                                                 status, qstatus, ws, ws_bytes, stream);
 }

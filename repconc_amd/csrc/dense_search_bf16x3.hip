@@ -2,7 +2,7 @@
 // dense_search.hip (ids AND score bits of rc_dense_search_q), the corpus stays fp32, only the screen leaves the fp32 matrix
 // cores.  The route is dense_search_route (dense_screen.h) with this unit's variant: dense_bf16x3_split_kernel is its query
 // pre-pass, dense_bf16x3_gemm_kernel screens, the candidates are rescored by the chain and every answer carries a certificate
-// with the E_q derived below.  Exact route: dense_exact_f32 (dense_search.hip), i.e. rc_dense_search_exact.
+// with the E_q derived below.  Exact route: the rows of dense_exact_rows_f32 (dense_search.hip), i.e. rc_dense_search_exact.
 //
 // Score (unchanged): s(q, n) = fp32 fmaf chain over d = 0 .. D-1 ascending from +0.0f on the fp32 values.
 //
@@ -224,18 +224,19 @@ static int dense_b3_launch_gemm(rc_handle_t h, const float* x, int64_t ldx, int6
 }
 
 // The certificate refuses a query value whose bf16 rounding is infinite (|v| >= 2^128 - 2^119; inf and NaN with it) and D > 65536.
-struct dense_b3_variant {
+struct dense_b3_variant : dense_variant_defaults {
     typedef float T;
     typedef __bf16 Q;
     static constexpr bool approximate = true;
+    static constexpr unsigned ws_align = 16;             // the planes are read with 16-byte loads
     static size_t extra_ws_bytes(int nq, int D) { return dense_b3_split_bytes(nq, D); }
     static int prepass(rc_handle_t h, const float* q, int nq, int D, char* tail, const Q** qs, hipStream_t s) {
         *qs = (const __bf16*)tail;                       // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
         return dense_b3_launch_split(h, q, nq, D, (__bf16*)tail, s);
     }
     template <int MODE, typename... A>
-    static int launch_gemm(A... a) { return dense_b3_launch_gemm<MODE>(a...); }
-    static constexpr auto* exact = &dense_exact_f32;
+    static int launch_gemm(const float*, A... a) { return dense_b3_launch_gemm<MODE>(a...); }
+    static constexpr auto* exact_rows = &dense_exact_rows_f32;
     __device__ static bool refuse(float v, int D) {
         return (__float_as_uint(v) & 0x7FFFFFFFu) >= 0x7F7F8000u || D > DENSE_B3_MAX_D;
     }
@@ -279,12 +280,6 @@ extern "C" int rc_dense_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx
 extern "C" int rc_dense_bf16x3_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                         const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores,
                                         int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
-    if (crc != RC_OK) return crc;
-    if (!status || !xnorm_max) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ((uintptr_t)ws & 15u) || ws_bytes < rc_dense_bf16x3_search_ws_bytes(N, D, nq, k)) return RC_EWORKSPACE;
-    return dense_search_route<dense_b3_variant>(h, x, ldx, N, D, q, nq, xnorm_max, k, id_offset, sel_slack, scores, ids, status,
-                                                qstatus, (char*)ws, (hipStream_t)stream);
+    return dense_search_entry<dense_b3_variant>(h, x, ldx, N, D, q, nq, nullptr, xnorm_max, k, id_offset, sel_slack, scores, ids,
+                                                status, qstatus, ws, ws_bytes, stream);
 }

@@ -141,15 +141,15 @@ static int dense_f16_launch_gemm(rc_handle_t h, const _Float16* x, int64_t ldx, 
     return RC_OK;
 }
 
-struct dense_f16_variant {
+struct dense_f16_variant : dense_variant_defaults {
     typedef _Float16 T;
     typedef _Float16 Q;
     static constexpr bool approximate = true;
-    static size_t extra_ws_bytes(int, int) { return 0; }
-    static int prepass(rc_handle_t, const T* q, int, int, char*, const Q** qs, hipStream_t) { *qs = q; return RC_OK; }
     template <int MODE, typename... A>
-    static int launch_gemm(A... a) { return dense_f16_launch_gemm<MODE>(a...); }
-    static constexpr auto* exact = &dense_exact<_Float16>;
+    static int launch_gemm(const float*, A... a) { return dense_f16_launch_gemm<MODE>(a...); }
+    static int exact_rows(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, float* out, hipStream_t s) {
+        return dense_launch_gemm<DENSE_STORE, T>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
+    }
     __device__ static bool refuse(float, int) { return false; }
     __device__ static double eq(int D, double ss, double xnorm) {
         const double up = 1.0 + 0x1p-30;
@@ -170,15 +170,9 @@ extern "C" size_t rc_dense_f16_search_ws_bytes(int64_t N, int D, int nq, int k) 
 extern "C" int rc_dense_f16_search_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
                                          int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
                                          size_t ws_bytes, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    const _Float16* xh = reinterpret_cast<const _Float16*>(x);
-    const _Float16* qh = reinterpret_cast<const _Float16*>(q);
-    const int crc = dense_check(h, xh, ldx, N, D, qh, nq, k, scores, ids);
-    if (crc != RC_OK) return crc;
-    if (nq == 0) return RC_OK;
-    const dense_exact_layout L = dense_exact_ws(N, nq);
-    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
-    return dense_exact(h, xh, ldx, N, D, qh, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
+    return dense_exact_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
+                                                reinterpret_cast<const _Float16*>(q), nq, k, id_offset, scores, ids, ws, ws_bytes,
+                                                stream);
 }
 
 extern "C" int rc_dense_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
@@ -195,14 +189,7 @@ extern "C" int rc_dense_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx
 extern "C" int rc_dense_f16_search_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
                                      const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores,
                                      int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    const _Float16* xh = reinterpret_cast<const _Float16*>(x);
-    const _Float16* qh = reinterpret_cast<const _Float16*>(q);
-    const int crc = dense_check(h, xh, ldx, N, D, qh, nq, k, scores, ids);
-    if (crc != RC_OK) return crc;
-    if (!status || !xnorm_max) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ws_bytes < rc_dense_f16_search_ws_bytes(N, D, nq, k)) return RC_EWORKSPACE;
-    return dense_search_route<dense_f16_variant>(h, xh, ldx, N, D, qh, nq, xnorm_max, k, id_offset, sel_slack, scores, ids, status,
-                                                 qstatus, (char*)ws, (hipStream_t)stream);
+    return dense_search_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
+                                                 reinterpret_cast<const _Float16*>(q), nq, nullptr, xnorm_max, k, id_offset,
+                                                 sel_slack, scores, ids, status, qstatus, ws, ws_bytes, stream);
 }

@@ -7,11 +7,12 @@
 // works on s = -d with the keys of topk.h (negation is exact, every zero is -0.0f, "largest s, lowest row" is "smallest d,
 // lowest row"); the entries negate the k output values once at the end: d ascending, +0.0f for a zero, +inf / -1 past N.
 //
-// Route (dense_l2_route, the sequence of dense_search_route in dense_screen.h with this unit's kernels):
+// Route: dense_search_route (dense_screen.h) with this unit's variant.
 //   N <= DENSE_EXACT_MAX_N, and the queries the fast route gives up on: dense_l2_exact_kernel writes the full rows of -d of a
-//   chunk of queries (the layout and the chunking of dense_exact, dense_gemm.h), then the radix select (topk_exact_select).
-//   Above:  1. screen<STORE> over the strided sample  2. threshold  3. screen<FILTER> over all rows  4. dense_l2_rescore_kernel
-//   replaces the score half of every candidate key by -d  5. select  6. dense_certify_kernel  7. negate.
+//   chunk of queries (dense_exact), then the radix select (topk_exact_select), then the sign.
+//   Above:  1. screen<STORE> over the strided sample  2. threshold  3. screen<FILTER> over all rows, xsq passed to both
+//   4. dense_rescore_kernel<.., L2 = true> replaces the score half of every candidate key by -d  5. select
+//   6. dense_certify_kernel  7. dense_l2_negate_kernel (the variant's finish).
 //
 // Screen.  sigma(q, n) = fmaf(2, dot(q, x_n), -xsq[n]): dot is the fp32 MFMA accumulator of the GEMM of dense_gemm.h
 // (dense_gemm_body<.., L2 = true>), xsq[n] the caller's fp32 squared norm of row n (an fp64 sum rounded to nearest,
@@ -61,8 +62,8 @@ __global__ __launch_bounds__(256) void dense_l2_gemm_kernel(const float* __restr
 }
 
 template <int MODE>
-static int dense_l2_launch_gemm(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
-                                const float* q, int nq, int D, const float* xsq, const float* thr, float* out, unsigned* cnt,
+static int dense_l2_launch_gemm(const float* xsq, rc_handle_t h, const float* x, int64_t ldx, int64_t N, int64_t nrows,
+                                int64_t smap, const float* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
                                 unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (D % DENSE_KC == 0)
@@ -71,63 +72,6 @@ static int dense_l2_launch_gemm(rc_handle_t h, const float* x, int64_t ldx, int6
     else
         hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, true>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr, out,
                            cnt, cand, xsq);
-    RC_LAUNCH_CHECK(h);
-    return RC_OK;
-}
-
-// ---- rescoring ---------------------------------------------------------------------------------------------------------------
-// dense_rescore_kernel<VEC, float> (dense_screen.h: grid, candidate walk, staged query, row loads) with the L2 chain: a literal
-// subtraction, then fmaf(t, t, s), d ascending; the key's score half becomes -d.
-template <bool VEC>
-__global__ __launch_bounds__(256) void dense_l2_rescore_kernel(const float* __restrict__ x, int64_t ldx, int D,
-                                                               const float* __restrict__ q, const unsigned* __restrict__ cnt,
-                                                               unsigned long long* __restrict__ cand) {
-    __shared__ float sq[DENSE_RESCORE_QCHUNK];
-    const int qi = blockIdx.x, tid = threadIdx.x;
-    const unsigned raw = cnt[qi];
-    const unsigned n = raw > ADC_CAND_CAP ? ADC_CAND_CAP : raw;
-    if (blockIdx.y * 256u >= n) return;                                // block-uniform
-    const unsigned i = blockIdx.y * 256u + tid;
-    const bool mine = i < n;
-    unsigned long long* kp = cand + (size_t)qi * ADC_CAND_CAP + i;
-    const unsigned row = mine ? 0xFFFFFFFFu - (unsigned)(*kp & 0xFFFFFFFFull) : 0u;
-    const float* xp = x + (int64_t)row * ldx;
-    const float* qp = q + (int64_t)qi * D;
-    float s = 0.f;
-    for (int d0 = 0; d0 < D; d0 += DENSE_RESCORE_QCHUNK) {
-        const int dn = D - d0 < DENSE_RESCORE_QCHUNK ? D - d0 : DENSE_RESCORE_QCHUNK;
-        __syncthreads();
-        for (int d = tid; d < dn; d += 256) sq[d] = qp[d0 + d];
-        __syncthreads();
-        if (mine) {
-            int d = 0;
-            if constexpr (VEC) {
-                for (; d + 8 <= dn; d += 8) {
-                    float v[8];
-                    dense_load8(xp + d0 + d, v);
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const float t = sq[d + e] - v[e];
-                        s = __builtin_fmaf(t, t, s);
-                    }
-                }
-            }
-            for (; d < dn; ++d) {
-                const float t = sq[d] - xp[d0 + d];
-                s = __builtin_fmaf(t, t, s);
-            }
-        }
-    }
-    if (mine) *kp = adc_exact_key(-s, (int64_t)row);
-}
-
-static int dense_l2_launch_rescore(rc_handle_t h, const float* x, int64_t ldx, int D, const float* q, int nq,
-                                   const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
-    const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
-    if (ldx % 4 == 0 && !((uintptr_t)x & 15u))
-        hipLaunchKernelGGL(dense_l2_rescore_kernel<true>, grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
-    else
-        hipLaunchKernelGGL(dense_l2_rescore_kernel<false>, grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -249,25 +193,16 @@ static int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_
     return RC_OK;
 }
 
-// the exact route: dense_exact (dense_gemm.h) with the rows of -d from dense_l2_exact_kernel, then the sign
-static int dense_l2_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
-                          int64_t id_offset, float* dist, int64_t* ids, char* w, const dense_exact_layout& L, hipStream_t s) {
-    float* sc = (float*)(w + L.sc);
-    for (int q0 = 0; q0 < nq; q0 += L.qx) {
-        const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
-        int rc = dense_l2_launch_exact_rows(h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
-        if (rc != RC_OK) return rc;
-        rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, dist + (size_t)q0 * k, ids + (size_t)q0 * k, s);
-        if (rc != RC_OK) return rc;
-    }
-    return dense_l2_launch_negate(h, dist, (int64_t)nq * k, s);
-}
-
-// ---- certificate and route ---------------------------------------------------------------------------------------------------
-// What dense_certify_kernel needs of a variant.  The route itself is a sibling of dense_search_route, not an instance: xsq goes
-// into both screen launches, the rescorer is this unit's, and the output is negated after the certificate has read it.
-struct dense_l2_variant {
+// ---- the variant -------------------------------------------------------------------------------------------------------------
+struct dense_l2_variant : dense_variant_defaults {
     typedef float T;
+    typedef float Q;
+    static constexpr bool approximate = true;
+    static constexpr bool l2 = true;
+    template <int MODE, typename... A>
+    static int launch_gemm(A... a) { return dense_l2_launch_gemm<MODE>(a...); }
+    static constexpr auto* exact_rows = &dense_l2_launch_exact_rows;
+    static constexpr auto* finish = &dense_l2_launch_negate;
     __device__ static bool refuse(float v, int D) { return !(v - v == 0.f) || D > DENSE_L2_MAX_D; }
     // E_q - ss_down: what is added to thr~ (header).  +inf (never certified) unless (||q|| + X)^2 < 2^126.
     __device__ static double eq(int D, double ss, double xnorm) {
@@ -280,38 +215,6 @@ struct dense_l2_variant {
     }
 };
 
-static size_t dense_l2_ws_bytes(int64_t N, int D, int nq, int k) {
-    if (!dense_shape_ok(N, D, nq, k)) return 0;
-    return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total;
-}
-
-// checked arguments (dense_check, status, xsq, xnorm_max, nq > 0, a workspace of dense_l2_ws_bytes)
-static int dense_l2_route(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, const float* xsq,
-                          const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* dist, int64_t* ids,
-                          int* status, int* qstatus, char* w, hipStream_t s) {
-    if (dense_exact_route(N)) return dense_l2_exact(h, x, ldx, N, D, q, nq, k, id_offset, dist, ids, w, dense_exact_ws(N, nq), s);
-    const dense_fast_layout L = dense_fast_ws(N, nq);
-    float* sample = (float*)(w + L.sample);
-    float* thr = (float*)(w + L.thr);
-    unsigned* cnt = (unsigned*)(w + L.cnt);
-    unsigned long long* cand = (unsigned long long*)(w + L.cand);
-    int rc = dense_l2_launch_gemm<DENSE_STORE>(h, x, ldx, N, L.S, L.S, q, nq, D, xsq, nullptr, sample, nullptr, nullptr, s);
-    if (rc != RC_OK) return rc;
-    rc = rc_adc_launch_threshold(h, sample, L.S, nq, rc_adc_sample_rank(N, L.S, k, sel_slack), thr, s);
-    if (rc != RC_OK) return rc;
-    RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
-    rc = dense_l2_launch_gemm<DENSE_FILTER>(h, x, ldx, N, N, 0, q, nq, D, xsq, thr, nullptr, cnt, cand, s);
-    if (rc != RC_OK) return rc;
-    rc = dense_l2_launch_rescore(h, x, ldx, D, q, nq, cnt, cand, s);
-    if (rc != RC_OK) return rc;
-    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, dist, ids, status, s, qstatus);
-    if (rc != RC_OK) return rc;
-    hipLaunchKernelGGL(dense_certify_kernel<dense_l2_variant>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, thr, xnorm_max, dist,
-                       status, qstatus);
-    RC_LAUNCH_CHECK(h);
-    return dense_l2_launch_negate(h, dist, (int64_t)nq * k, s);
-}
-
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------
 extern "C" void rc_dense_l2_error_constants(double* c) {
     c[0] = DENSE_L2_C_REL;
@@ -321,32 +224,22 @@ extern "C" void rc_dense_l2_error_constants(double* c) {
 
 extern "C" size_t rc_dense_l2_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
 
-extern "C" size_t rc_dense_l2_search_ws_bytes(int64_t N, int D, int nq, int k) { return dense_l2_ws_bytes(N, D, nq, k); }
+extern "C" size_t rc_dense_l2_search_ws_bytes(int64_t N, int D, int nq, int k) {
+    return dense_search_ws_bytes<dense_l2_variant>(N, D, nq, k);
+}
 
 extern "C" int rc_dense_l2_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                         int k, int64_t id_offset, float* dist, int64_t* ids, void* ws, size_t ws_bytes,
                                         rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, dist, ids);
-    if (crc != RC_OK) return crc;
-    if (nq == 0) return RC_OK;
-    const dense_exact_layout L = dense_exact_ws(N, nq);
-    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
-    return dense_l2_exact(h, x, ldx, N, D, q, nq, k, id_offset, dist, ids, (char*)ws, L, (hipStream_t)stream);
+    return dense_exact_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, k, id_offset, dist, ids, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_l2_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                     const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack,
                                     float* dist, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
                                     rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, dist, ids);
-    if (crc != RC_OK) return crc;
-    if (!status || !xsq || !xnorm_max) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ws_bytes < dense_l2_ws_bytes(N, D, nq, k)) return RC_EWORKSPACE;
-    return dense_l2_route(h, x, ldx, N, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, dist, ids, status, qstatus, (char*)ws,
-                          (hipStream_t)stream);
+    return dense_search_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, dist, ids, status,
+                                                qstatus, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_l2_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
@@ -356,6 +249,6 @@ extern "C" int rc_dense_l2_scores(rc_handle_t h, const float* x, int64_t ldx, in
     if (!h || !x || !q || !xsq || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
     if (D % DENSE_KC == 0 && (ldx % 4 != 0 || ((uintptr_t)x & 15u) || ((uintptr_t)q & 15u))) return RC_EINVAL;
     if (nq == 0) return RC_OK;
-    return dense_l2_launch_gemm<DENSE_STORE>(h, x, ldx, N, N, 0, q, nq, D, xsq, nullptr, out, nullptr, nullptr,
+    return dense_l2_launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr,
                                              (hipStream_t)stream);
 }

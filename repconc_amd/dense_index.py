@@ -27,7 +27,8 @@ from .index import METRIC_INNER_PRODUCT, METRIC_L2
 
 class _FlatIndex:
     """What the flat indexes share: the device, ONE [capacity, d] tensor of vectors appended to in place (the first `add`
-    allocates exactly, later growth is 1.5x), and `search` / `search_async` around the subclass's `_enqueue`."""
+    allocates exactly, later growth is 1.5x), the front end of `add` (`_rows`), `reset`, and `search` / `search_async` around
+    the subclass's `_enqueue`."""
     PAD = float("-inf")          # the value of the slots past ntotal
 
     def _init_store(self, d: int, device, dtype) -> None:
@@ -42,6 +43,8 @@ class _FlatIndex:
         self.sel_slack = ops.DENSE_SEL_SLACK
         self.last_search = None
         self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
+        # screened searches: device fp32 [1] >= the largest row norm held (the search's certificate)
+        self._xnorm_max = None
 
     @property
     def xb(self) -> torch.Tensor:
@@ -58,6 +61,24 @@ class _FlatIndex:
     def _grow_for(self, need: int) -> None:
         if need > self._x.shape[0]:
             self.reserve(need if self.ntotal == 0 else max(need, int(self._x.shape[0] * 1.5)))
+
+    def _rows(self, x) -> torch.Tensor:
+        """The argument of `add` as a tensor (numpy -> fp32), checked to be [n, d]."""
+        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        if xt.dim() != 2 or xt.shape[1] != self.d:
+            raise ValueError(f"add: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
+        return xt
+
+    def reset(self) -> None:
+        self.ntotal = 0
+        self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
+        self._xnorm_max = None
+
+    def search(self, x, k: int):
+        """(scores or distances [nq, k], ids [nq, k]); numpy in -> numpy out (evaluate_dense.py:74), CUDA tensors in -> CUDA
+        tensors out (faiss.contrib.torch_utils).  float16 storage rounds the queries to fp16 without a range check: a query
+        value of magnitude >= 65520 becomes inf (`ops.dense_search_f16`)."""
+        return self.search_async(x, k)()
 
     def search_async(self, x, k: int):
         """Enqueue the search and return a callable that yields what `search` returns; nothing synchronises with the host
@@ -104,15 +125,11 @@ class FlatIPIndex(_FlatIndex):
         self.screen = screen
         self._init_store(d, device, self.STORAGE[storage])
         self.metric_type = METRIC_INNER_PRODUCT
-        # float16 storage / bf16x3 screen: device fp32 [1] >= the largest row norm held (the search's certificate)
-        self._xnorm_max = None
         self._search = ops.dense_search_f16 if storage == "float16" else ops.dense_search_bf16x3 if screen == "bf16x3" \
             else ops.dense_search
 
     def add(self, x) -> None:
-        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        if xt.dim() != 2 or xt.shape[1] != self.d:
-            raise ValueError(f"add: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
+        xt = self._rows(x)
         n = xt.shape[0]
         need = self.ntotal + n
         xnorm = None
@@ -136,17 +153,6 @@ class FlatIPIndex(_FlatIndex):
         if xnorm is not None:
             self._xnorm_max = xnorm if self._xnorm_max is None else torch.maximum(self._xnorm_max, xnorm)
 
-    def reset(self) -> None:
-        self.ntotal = 0
-        self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
-        self._xnorm_max = None
-
-    def search(self, x, k: int):
-        """(scores [nq, k], ids [nq, k]); numpy in -> numpy out (evaluate_dense.py:74), CUDA tensors in -> CUDA tensors
-        out (faiss.contrib.torch_utils).  float16 storage rounds the queries to fp16 without a range check: a query value of
-        magnitude >= 65520 becomes inf (`ops.dense_search_f16`)."""
-        return self.search_async(x, k)()
-
     def _enqueue(self, q, k: int):
         norm = {} if self._search is ops.dense_search else {"xnorm_max": self._xnorm_max}
         return self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True, **norm)
@@ -166,7 +172,6 @@ class FlatL2Index(_FlatIndex):
         self._init_store(d, device, torch.float32)
         self.metric_type = METRIC_L2
         self._xsq = torch.empty((0,), dtype=torch.float32, device=self.device)
-        self._xnorm_max = None
 
     def reserve(self, n: int) -> None:
         """Capacity for `n` rows in total (the rows and norms held so far are kept)."""
@@ -177,9 +182,7 @@ class FlatL2Index(_FlatIndex):
             self._xsq = grown
 
     def add(self, x) -> None:
-        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        if xt.dim() != 2 or xt.shape[1] != self.d:
-            raise ValueError(f"add: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
+        xt = self._rows(x)
         n = xt.shape[0]
         if n == 0:
             return
@@ -194,15 +197,8 @@ class FlatL2Index(_FlatIndex):
         self.ntotal = need
 
     def reset(self) -> None:
-        self.ntotal = 0
-        self._x = torch.empty((0, self.d), dtype=torch.float32, device=self.device)
+        super().reset()
         self._xsq = torch.empty((0,), dtype=torch.float32, device=self.device)
-        self._xnorm_max = None
-
-    def search(self, x, k: int):
-        """(distances [nq, k], ids [nq, k]); numpy in -> numpy out, CUDA tensors in -> CUDA tensors out
-        (faiss.contrib.torch_utils)."""
-        return self.search_async(x, k)()
 
     def _enqueue(self, q, k: int):
         return ops.dense_search_l2(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,

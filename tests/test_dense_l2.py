@@ -301,6 +301,36 @@ def test_l2_screen_error_stays_inside_the_certificate_bound(D):
     print(f"D={D}: largest screen-error ratio {worst:.5f}")
 
 
+_CHUNK_SEEDS = {"l2": 7000, "bf16x3": 7100, "f16": 7200}      # of the corpus; the queries' is one more
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("D", [1040, 1029])
+@pytest.mark.parametrize("search", ["l2", "bf16x3", "f16"])
+def test_rescoring_walks_a_second_query_chunk_in_every_screened_search(search, D):
+    """One rescoring kernel body serves the three screened searches and stages the query in chunks of 1024 values.  D = 1040:
+    an aligned second chunk of two 8-wide steps on the 16-byte loads; D = 1029: unaligned rows, element-wise loads and a tail
+    that crosses the chunk boundary.  A query handed to the exact route never met the rescorer: none may be."""
+    from repconc_amd import ops
+    from test_dense_flat import oracle_topk
+    N, nq, k = 140001, 5, 10
+    x = _randn((N, D), _CHUNK_SEEDS[search] + D)
+    q = _randn((nq, D), _CHUNK_SEEDS[search] + D + 1)
+    if search == "l2":
+        want = oracle_topk_l2(x, q, k)
+        pending = ops.dense_search_l2(x, q, k, defer=True)
+    elif search == "bf16x3":
+        want = oracle_topk(x, q, k)
+        pending = ops.dense_search_bf16x3(x, q, k, defer=True)
+    else:
+        x16 = x.half()
+        want = oracle_topk(x16.float(), q.half().float(), k)     # the rounded values: what the fp16 search scores
+        pending = ops.dense_search_f16(x16, q, k, defer=True)
+    assert_matches(pending.result(), want)
+    print(f"{search} D={D}: {pending.stats}")
+    assert pending.stats["exact_queries"] == 0, pending.stats
+
+
 @pytest.mark.gpu
 def test_l2_self_matches_are_plus_zero_and_ties_take_the_lower_id():
     import torch
