@@ -521,6 +521,39 @@ int rc_dense_l2_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, in
                        float* out, rc_stream_t stream);
 void rc_dense_l2_error_constants(double* c);
 
+/* ------------------------------------------------------------------ dense flat search, L2 metric, fp16 storage
+ * The L2 search over a corpus stored as IEEE fp16 (faiss.IndexFlatL2 with useFloat16): x [N, ldx] and q [nq, D] are fp16 bit
+ * patterns (uint16_t), finite.  Distance d(q, n) = the chain above over the widened values, t = (float)q[j] - (float)x[n][j],
+ * acc = fmaf(t, t, acc): ids AND distance bits equal rc_dense_l2_search_q on the widened arrays.  Order, padding (+inf / -1),
+ * id_offset and the limits (any D >= 1, N < 2^32, 1 <= k <= 8192, else RC_ESHAPE) as there; alignment rules of
+ * rc_dense_f16_search_q (D % 16 == 0 requires x and q 16-byte aligned and ldx % 8 == 0, else RC_EINVAL; rows are read with
+ * 16-byte loads when D % 8 == 0, ldx % 8 == 0 and both pointers are 16-byte aligned, element by element otherwise).
+ * rc_dense_l2_f16_search_q: N <= 131072 takes the exact route below.  Above: the f16 matrix cores screen with sigma =
+ *   fmaf(2, dot(q, x_n), -xsq[n]); threshold, candidates, rescoring by the chain and sorting as rc_dense_l2_search_q.  xsq:
+ *   DEVICE fp32 [N], the squared norm of every stored (rounded) row, an fp64 sum rounded to nearest; xnorm_max: DEVICE pointer
+ *   to one float X >= the largest Euclidean row norm; NULL for either is RC_EINVAL.  With D_pad = D rounded up to 16 and c[0] of
+ *   rc_dense_l2_f16_error_constants,
+ *     E_q = c0 D_pad 2^-24 (||q||_2 + X)^2                                        (every |sigma - ||q||^2 + d| <= E_q),
+ *   -t >= thr~ - ||q||^2 + E_q for t = the query's k-th distance, all rounded to the safe side, proves the answer.  status /
+ *   qstatus as rc_dense_l2_search_q: bit0, bit1, bit2 = not certified (also: a non-finite query value, D > 65536): repeat those
+ *   queries with another sel_slack or answer them by rc_dense_l2_f16_search_exact.  ws: rc_dense_l2_f16_search_ws_bytes.
+ * rc_dense_l2_f16_search_exact: the vector-ALU kernel of rc_dense_l2_search_exact over rows widened on load, then the radix
+ *   select; takes no norms, no status.  ws: rc_dense_l2_f16_search_exact_ws_bytes(N, D, nq, k).
+ * rc_dense_l2_f16_scores (test hook): the screen's raw sigma, out [nq][N] fp32.
+ * rc_dense_l2_f16_error_constants: c[2] = {2.5, 65536}: the factor of E_q as the certificate kernel was compiled with it and
+ *   the largest D it is proven for (no GPU needed). */
+size_t rc_dense_l2_f16_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_l2_f16_search_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                             const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* dist,
+                             int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_dense_l2_f16_search_exact_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_l2_f16_search_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                                 int k, int64_t id_offset, float* dist, int64_t* ids, void* ws, size_t ws_bytes,
+                                 rc_stream_t stream);
+int rc_dense_l2_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                           const float* xsq, float* out, rc_stream_t stream);
+void rc_dense_l2_f16_error_constants(double* c);
+
 /* ------------------------------------------------------------------ a-9 … a-11, stateful form
  * The index object the reference keeps inside Faiss (initialize_index / add_docs / index.search,
  * models/repconc/evaluate_repconc.py:78-98,182; JPQ's per-step synchronize_model_index, models/jpq/finetune_jpq.py:209-214),

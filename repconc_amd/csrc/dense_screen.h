@@ -1,8 +1,8 @@
-// What the four dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
+// What the five dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
 // dense_search_f16.hip: fp16 corpus and f16 screen, dense_search_bf16x3.hip: fp32 corpus and bf16x3 screen,
-// dense_search_l2.hip: fp32 corpus, squared Euclidean distance): the route of a search and the bodies of its entries, the
-// pieces common to the two 16x16x32 screen GEMMs, the rescoring kernel and the certificate kernel.  Device code: every
-// translation unit compiles its own copy, no -fgpu-rdc.
+// dense_search_l2.hip: fp32 corpus, squared Euclidean distance, dense_search_l2_f16.hip: the same over an fp16 corpus): the
+// route of a search and the bodies of its entries, the pieces common to the two 16x16x32 screen GEMMs, the rescoring kernel
+// and the certificate kernel.  Device code: every translation unit compiles its own copy, no -fgpu-rdc.
 //
 // The route (dense_search_route).  A variant V supplies the storage type, its screen GEMM, an optional query pre-pass and,
 // if its screen only approximates the score (V::approximate), the bound E_q of its certificate.  The L2 variant (V::l2) scores
@@ -54,12 +54,26 @@ __device__ __forceinline__ const float* dense_screen_stage_thr(unsigned char* sa
     return s_thr;
 }
 
-// the epilogue of a wave's 4 x 4 result tiles: dense_emit on every element
-template <int MODE>
+// this lane's side operand of the L2 epilogue: nxs[b] = minus the stored squared norm of its corpus row of column tile b,
+// read at the mapped corpus row of the strided sample (smap != 0) as the screen's loader reads the row itself; once per block
+__device__ __forceinline__ void dense_screen_load_nxs(const float* __restrict__ xsq, int64_t j0, int wc, int col, int64_t N,
+                                                      int64_t nrows, int64_t smap, float (&nxs)[4]) {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        const int64_t j = j0 + wc * 64 + b * 16 + col;
+        const int64_t jc = j < nrows ? j : nrows - 1;
+        nxs[b] = -xsq[smap ? (int64_t)((uint64_t)jc * (uint64_t)N / (uint64_t)smap) : jc];
+    }
+}
+
+// the epilogue of a wave's 4 x 4 result tiles: dense_emit on every element; L2: on sigma = fmaf(2, dot, nxs[b]) as
+// dense_gemm_body<.., L2 = true> emits it (nxs: dense_screen_load_nxs)
+template <int MODE, bool L2 = false>
 __device__ __forceinline__ void dense_screen_epilogue(const dense_f32x4 (&acc)[4][4], int64_t j0, int wr, int wc, int col,
                                                       int grp, int qt, int nq, const float* s_thr, int64_t nrows,
                                                       float* __restrict__ out, unsigned* __restrict__ cnt,
-                                                      unsigned long long* __restrict__ cand, int l) {
+                                                      unsigned long long* __restrict__ cand, int l,
+                                                      const float* nxs = nullptr) {
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         const int64_t j = j0 + wc * 64 + b * 16 + col;
@@ -69,8 +83,9 @@ __device__ __forceinline__ void dense_screen_epilogue(const dense_f32x4 (&acc)[4
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int qo = wr * 64 + a * 16 + 4 * grp + r;
-                dense_emit<MODE, 16>(acc[a][b][r], j, jv, qt + qo, nq, MODE == DENSE_FILTER ? s_thr[qo] : 0.f, nrows, out, cnt,
-                                     cand, l);
+                float sc = acc[a][b][r];
+                if constexpr (L2) sc = __builtin_fmaf(2.f, sc, nxs[b]);
+                dense_emit<MODE, 16>(sc, j, jv, qt + qo, nq, MODE == DENSE_FILTER ? s_thr[qo] : 0.f, nrows, out, cnt, cand, l);
             }
     }
 }

@@ -8,8 +8,8 @@
 // lowest row"); the entries negate the k output values once at the end: d ascending, +0.0f for a zero, +inf / -1 past N.
 //
 // Route: dense_search_route (dense_screen.h) with this unit's variant.
-//   N <= DENSE_EXACT_MAX_N, and the queries the fast route gives up on: dense_l2_exact_kernel writes the full rows of -d of a
-//   chunk of queries (dense_exact), then the radix select (topk_exact_select), then the sign.
+//   N <= DENSE_EXACT_MAX_N, and the queries the fast route gives up on: dense_l2_exact_kernel (dense_l2.h) writes the full
+//   rows of -d of a chunk of queries (dense_exact), then the radix select (topk_exact_select), then the sign.
 //   Above:  1. screen<STORE> over the strided sample  2. threshold  3. screen<FILTER> over all rows, xsq passed to both
 //   4. dense_rescore_kernel<.., L2 = true> replaces the score half of every candidate key by -d  5. select
 //   6. dense_certify_kernel  7. dense_l2_negate_kernel (the variant's finish).
@@ -42,7 +42,7 @@
 // Certificate.  A row outside the list has sigma < thr~, hence -d < thr~ - ||q||^2 + E_q: with t = the k-th best -d of the list,
 // t >= thr~ - ss_down + E_q proves that no such row enters the top-k or ties with its last member.  dense_certify_kernel adds
 // V::eq to thr~: here E_q (pushed upwards) minus the query's squared norm (pushed downwards), all in fp64.
-#include "dense_screen.h"
+#include "dense_l2.h"
 
 #define DENSE_L2_C_REL 2.0                               // E_rel   = C_REL D_pad 2^-24 (||q|| + X)^2
 #define DENSE_L2_C_FLUSH 0x1p-124                        // E_flush = C_FLUSH sqrt(D_pad) (||q|| + X)        (4 * 2^-126)
@@ -76,118 +76,14 @@ static int dense_l2_launch_gemm(const float* xsq, rc_handle_t h, const float* x,
     return RC_OK;
 }
 
-// ---- the exact route's kernel ------------------------------------------------------------------------------------------------
-// The matrix cores cannot compute a chain of squared differences: this is vector-ALU work, two lane-operations per (q, n, d),
-// the subtraction and the fmaf.  grid: ceil(N / 128) blocks of 256 threads, two per CU.  A block owns 128 corpus rows and walks
-// every tile of 64 queries (the corpus is read from HBM once per launch), K in chunks of 16 through LDS, double buffered, both
-// tiles stored k-major: thread (tx = tid % 32, ty = tid / 32) owns rows 4 tx .. + 3 and queries 8 ty .. + 7 of the tiles, 32
-// accumulators that each walk d ascending, and reads per k one 16-byte vector of corpus values (32 lanes: 512 contiguous bytes)
-// and two of query values (broadcast) for 64 vector operations.  out [nq][N] = -d, the score rows topk_exact_select reads.
-// !PAD: D % 16 == 0 and 16-byte aligned rows (dense_check); PAD reads element by element and pads K with zeros.
-// (-O3 pairs the 32 independent subtractions and fmas of a k step into v_pk_add_f32 / v_pk_fma_f32: two IEEE operations per
-// instruction with the roundings of the plain forms.  Forcing v_sub_f32 + v_fmac_f32 one by one was measured slower)
-#define DENSE_L2_QT 64
-#define DENSE_L2_XLD (DENSE_TILE + 4)                    // words per k of the corpus tile: 8 k apart is 32 banks apart
-#define DENSE_L2_QLD (DENSE_L2_QT + 4)                   // words per k of the query tile: 4 k apart is 16 banks apart
-
-template <bool PAD>
-__global__ __launch_bounds__(256, 2) void dense_l2_exact_kernel(const float* __restrict__ x, int64_t ldx, int64_t N,
-                                                                const float* __restrict__ q, int nq, int D,
-                                                                float* __restrict__ out) {
-    __shared__ __attribute__((aligned(16))) float sx[2][DENSE_KC * DENSE_L2_XLD];
-    __shared__ __attribute__((aligned(16))) float sq[2][DENSE_KC * DENSE_L2_QLD];
-    const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
-    const int64_t j0 = (int64_t)blockIdx.x * DENSE_TILE;
-    // loader mapping: corpus thread -> (row tid / 2, 8 consecutive k), query thread -> (row tid / 4, 4 consecutive k)
-    const int xr = tid >> 1, xk = (tid & 1) * 8, qr = tid >> 2, qk = (tid & 3) * 4;
-    const float* xp = x + ((j0 + xr < N) ? j0 + xr : N - 1) * ldx;
-    const int nkc = (D + DENSE_KC - 1) / DENSE_KC;
-    for (int qt = 0; qt < nq; qt += DENSE_L2_QT) {
-        const float* qp = q + (int64_t)((qt + qr < nq) ? qt + qr : nq - 1) * D;
-        float acc[8][4];
-#pragma unroll
-        for (int a = 0; a < 8; ++a)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[a][r] = 0.f;
-        float rx[8], rq[4];
-        auto gload = [&](int kc) {
-            const int k0 = kc * DENSE_KC;
-            if constexpr (PAD) {
-#pragma unroll
-                for (int i = 0; i < 8; ++i) rx[i] = (k0 + xk + i < D) ? xp[k0 + xk + i] : 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) rq[i] = (k0 + qk + i < D) ? qp[k0 + qk + i] : 0.f;
-            } else {
-                dense_load8(xp + k0 + xk, rx);
-                const float4 v = *reinterpret_cast<const float4*>(qp + k0 + qk);
-                rq[0] = v.x; rq[1] = v.y; rq[2] = v.z; rq[3] = v.w;
-            }
-        };
-        auto sstore = [&](int buf) {
-#pragma unroll
-            for (int i = 0; i < 8; ++i) sx[buf][(xk + i) * DENSE_L2_XLD + xr] = rx[i];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) sq[buf][(qk + i) * DENSE_L2_QLD + qr] = rq[i];
-        };
-        const bool act = qt + 8 * ty < nq;                           // this thread's 8 queries are not all padding
-        gload(0);
-        sstore(0);
-        __syncthreads();
-        for (int kc = 0; kc < nkc; ++kc) {
-            const int buf = kc & 1;
-            if (kc + 1 < nkc) gload(kc + 1);
-            if (act) {
-#pragma unroll
-                for (int k = 0; k < DENSE_KC; ++k) {
-                    const float4 xv = *reinterpret_cast<const float4*>(&sx[buf][k * DENSE_L2_XLD + 4 * tx]);
-                    const float4 qa = *reinterpret_cast<const float4*>(&sq[buf][k * DENSE_L2_QLD + 8 * ty]);
-                    const float4 qb = *reinterpret_cast<const float4*>(&sq[buf][k * DENSE_L2_QLD + 8 * ty + 4]);
-                    const float xs[4] = {xv.x, xv.y, xv.z, xv.w};
-                    const float qv[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
-#pragma unroll
-                    for (int a = 0; a < 8; ++a)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float t = qv[a] - xs[r];
-                            acc[a][r] = __builtin_fmaf(t, t, acc[a][r]);
-                        }
-                }
-            }
-            if (kc + 1 < nkc) sstore(buf ^ 1);
-            __syncthreads();
-        }
-#pragma unroll
-        for (int a = 0; a < 8; ++a) {
-            const int qi = qt + 8 * ty + a;
-            if (qi < nq) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int64_t j = j0 + 4 * tx + r;
-                    if (j < N) out[(int64_t)qi * N + j] = -acc[a][r];
-                }
-            }
-        }
-    }
-}
-
-static int dense_l2_launch_exact_rows(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
-                                      float* out, hipStream_t s) {
-    const dim3 grid((unsigned)((N + DENSE_TILE - 1) / DENSE_TILE));
-    if (D % DENSE_KC == 0)
-        hipLaunchKernelGGL(dense_l2_exact_kernel<false>, grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out);
-    else
-        hipLaunchKernelGGL(dense_l2_exact_kernel<true>, grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out);
-    RC_LAUNCH_CHECK(h);
-    return RC_OK;
-}
-
+// ---- the sign at the end (declared in dense_l2.h, the finish of both L2 units) ------------------------------------------------
 // -d -> d in place over the n output values: -0.0f -> +0.0f, the -inf of the padding -> +inf
 __global__ __launch_bounds__(256) void dense_l2_negate_kernel(float* __restrict__ v, int64_t n) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i < n) v[i] = -v[i];
 }
 
-static int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_t s) {
+int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_t s) {
     hipLaunchKernelGGL(dense_l2_negate_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, v, n);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
@@ -201,7 +97,7 @@ struct dense_l2_variant : dense_variant_defaults {
     static constexpr bool l2 = true;
     template <int MODE, typename... A>
     static int launch_gemm(A... a) { return dense_l2_launch_gemm<MODE>(a...); }
-    static constexpr auto* exact_rows = &dense_l2_launch_exact_rows;
+    static constexpr auto* exact_rows = &dense_l2_launch_exact_rows<float>;
     static constexpr auto* finish = &dense_l2_launch_negate;
     __device__ static bool refuse(float v, int D) { return !(v - v == 0.f) || D > DENSE_L2_MAX_D; }
     // E_q - ss_down: what is added to thr~ (header).  +inf (never certified) unless (||q|| + X)^2 < 2^126.

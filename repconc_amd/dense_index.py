@@ -13,6 +13,9 @@ fmaf chain over the rounded values, bit for bit what the fp32 index returns for 
 `screen="bf16x3"` (float32 storage only): the vectors stay fp32 and `search` returns the same ids and score bits as the default
 index, but the candidates are chosen on the bf16 matrix cores by `ops.dense_search_bf16x3` (csrc/dense_search_bf16x3.hip).
 `add` then refuses values whose bf16 rounding is not finite (magnitude >= 2^128 - 2^119, inf, NaN).
+
+`FlatL2Index` / `FlatL2F16Index`: the squared-Euclidean indexes (`faiss.IndexFlatL2`, fp32 and fp16 storage), classes of
+their own beside `FlatIPIndex`.
 """
 from __future__ import annotations
 
@@ -67,6 +70,13 @@ class _FlatIndex:
         xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
         if xt.dim() != 2 or xt.shape[1] != self.d:
             raise ValueError(f"add: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
+        return xt
+
+    def _rounded_f16(self, xt: torch.Tensor) -> torch.Tensor:
+        """The rows of an `add` on the device, rounded to fp16 and checked before anything is stored or grown; one host read."""
+        xt = xt.to(self.device).to(torch.float16)
+        if xt.shape[0] and not bool(torch.isfinite(xt).all()):
+            raise ValueError("add: float16 storage needs finite values of magnitude < 65520 (fp16 rounds the rest to inf)")
         return xt
 
     def reset(self) -> None:
@@ -134,10 +144,7 @@ class FlatIPIndex(_FlatIndex):
         need = self.ntotal + n
         xnorm = None
         if self.storage == "float16":
-            # rounded and checked before anything is stored or grown; one host read per add
-            xt = xt.to(self.device).to(torch.float16)
-            if n and not bool(torch.isfinite(xt).all()):
-                raise ValueError("add: float16 storage needs finite values of magnitude < 65520 (fp16 rounds the rest to inf)")
+            xt = self._rounded_f16(xt)
             if n:
                 xnorm = ops.dense_f16_xnorm_max(xt)
         elif self.screen == "bf16x3":
@@ -158,18 +165,14 @@ class FlatIPIndex(_FlatIndex):
         return self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True, **norm)
 
 
-class FlatL2Index(_FlatIndex):
-    """Exact squared-Euclidean index resident in HBM: the GPU `faiss.IndexFlatL2` the reference names at
-    models/repconc/evaluate_repconc.py:102 and train/run_warmup.py:102,107.  Duck-typed like `FlatIPIndex`, fp32 storage and
-    the fp32 screen only (no `storage` / `screen` options).  `search` answers with `ops.dense_search_l2`
-    (csrc/dense_search_l2.hip): a distance is the fp32 chain t = q_j - x_j, acc = fmaf(t, t, acc) over j ascending, bit for
-    bit, never negative; results are sorted (distance asc, id asc), +inf / -1 past ntotal.  Beside the vectors the index keeps
-    their fp32 squared norms in a capacity-sized tensor and a bound of the largest norm, both updated by `add` without a host
-    read: the screen's second operand and its certificate's X."""
+class _FlatL2(_FlatIndex):
+    """What the two L2 indexes share: beside the vectors, their fp32 squared norms in a capacity-sized tensor and a bound of the
+    largest norm, both updated by `add` without a host read: the screen's second operand and its certificate's X.  A subclass
+    says how `add` stores a row (`_stored`) and which search answers (`_search`)."""
     PAD = float("inf")
 
-    def __init__(self, d: int, device: Optional[torch.device] = None):
-        self._init_store(d, device, torch.float32)
+    def _init_l2(self, d: int, device, dtype) -> None:
+        self._init_store(d, device, dtype)
         self.metric_type = METRIC_L2
         self._xsq = torch.empty((0,), dtype=torch.float32, device=self.device)
 
@@ -187,7 +190,7 @@ class FlatL2Index(_FlatIndex):
         if n == 0:
             return
         need = self.ntotal + n
-        xt = xt.to(self.device, torch.float32)
+        xt = self._stored(xt)
         self._grow_for(need)
         self._x[self.ntotal:need] = xt
         xsq = ops.dense_row_sqnorms(xt)
@@ -201,5 +204,38 @@ class FlatL2Index(_FlatIndex):
         self._xsq = torch.empty((0,), dtype=torch.float32, device=self.device)
 
     def _enqueue(self, q, k: int):
-        return ops.dense_search_l2(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
-                                   xsq=self._xsq[: self.ntotal], xnorm_max=self._xnorm_max)
+        return self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
+                            xsq=self._xsq[: self.ntotal], xnorm_max=self._xnorm_max)
+
+
+class FlatL2Index(_FlatL2):
+    """Exact squared-Euclidean index resident in HBM: the GPU `faiss.IndexFlatL2` the reference names at
+    models/repconc/evaluate_repconc.py:102 and train/run_warmup.py:102,107.  Duck-typed like `FlatIPIndex`, fp32 storage and
+    the fp32 screen only (no `storage` / `screen` options; fp16 storage is `FlatL2F16Index`).  `search` answers with
+    `ops.dense_search_l2` (csrc/dense_search_l2.hip): a distance is the fp32 chain t = q_j - x_j, acc = fmaf(t, t, acc) over j
+    ascending, bit for bit, never negative; results are sorted (distance asc, id asc), +inf / -1 past ntotal.  Beside the
+    vectors the index keeps their fp32 squared norms in a capacity-sized tensor and a bound of the largest norm, both updated
+    by `add` without a host read: the screen's second operand and its certificate's X."""
+    _search = staticmethod(ops.dense_search_l2)
+
+    def __init__(self, d: int, device: Optional[torch.device] = None):
+        self._init_l2(d, device, torch.float32)
+
+    def _stored(self, xt: torch.Tensor) -> torch.Tensor:
+        return xt.to(self.device, torch.float32)
+
+
+class FlatL2F16Index(_FlatL2):
+    """`FlatL2Index` with the vectors stored as IEEE fp16 (`faiss.IndexFlatL2` with useFloat16), half the bytes.  `add` rounds
+    every value to fp16 (round to nearest even) and refuses a non-finite value or a magnitude >= 65520 before anything is
+    stored (the one host read of an `add`, as `FlatIPIndex(storage="float16")`); `search` rounds the queries the same way,
+    without a range check, and answers with `ops.dense_search_l2_f16` (csrc/dense_search_l2_f16.hip): ids and distance bits are
+    what `FlatL2Index` returns for `x.half().float()`, `q.half().float()`.  The squared norms kept are those of the rounded
+    rows."""
+    _search = staticmethod(ops.dense_search_l2_f16)
+
+    def __init__(self, d: int, device: Optional[torch.device] = None):
+        self._init_l2(d, device, torch.float16)
+
+    def _stored(self, xt: torch.Tensor) -> torch.Tensor:
+        return self._rounded_f16(xt)

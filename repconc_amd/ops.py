@@ -1144,7 +1144,7 @@ def _dense_f16_args(x16: torch.Tensor, q: torch.Tensor, k: int):
     return x16, q16
 
 
-# One dense search in three variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
+# One dense search in five variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
 # library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes; exact: rc_<exact>_search_exact / ..._ws_bytes, the route that
 # cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate);
 # rownorms: it also takes xsq, the squared norm of every row, before xnorm_max; pad: the value of the slots past N.
@@ -1154,6 +1154,7 @@ _DENSE_F32 = _DenseVariant(_dense_args, "dense", "dense", False)
 _DENSE_F16 = _DenseVariant(_dense_f16_args, "dense_f16", "dense_f16", True)
 _DENSE_BF16X3 = _DenseVariant(_dense_args, "dense_bf16x3", "dense", True)
 _DENSE_L2 = _DenseVariant(_dense_args, "dense_l2", "dense_l2", True, True, float("inf"))
+_DENSE_L2_F16 = _DenseVariant(_dense_f16_args, "dense_l2_f16", "dense_l2_f16", True, True, float("inf"))
 
 
 def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int):
@@ -1433,10 +1434,74 @@ def dense_search_l2(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0
     be given: such queries are repeated, then answered by `dense_search_l2_exact`; `.stats` of the `PendingSearch`).
     xsq: device fp32 [N], the rows' squared norms (`dense_row_sqnorms`); xnorm_max: device fp32 [1] >= the largest row norm;
     both computed here when None, and neither is read up to DENSE_EXACT_MAX_N rows.  Everything else as `dense_search`."""
+    return _dense_search_l2(_DENSE_L2, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)
+
+
+def _dense_search_l2(v: _DenseVariant, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max):
+    """The front of both L2 searches: a missing xnorm_max comes from the squared norms, which are then computed once."""
     if not 1 <= int(k) <= DENSE_MAX_K:
         raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
     if xnorm_max is None and x.dim() == 2 and x.shape[0] > DENSE_EXACT_MAX_N and method == "auto" and x.is_cuda:
         if xsq is None:
             xsq = dense_row_sqnorms(x)
         xnorm_max = _dense_l2_xnorm_max(xsq)
-    return _dense_search(_DENSE_L2, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, xsq)
+    return _dense_search(v, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, xsq)
+
+
+# ---------------------------------------------------------------------------------------- dense, L2 metric, fp16 storage
+def dense_l2_f16_error_constants():
+    """(c_rel, max_d) of E_q as the certificate kernel was compiled with them (csrc/dense_search_l2_f16.hip)."""
+    c = (C.c_double * 2)()
+    _lib.load().rc_dense_l2_f16_error_constants(c)
+    return tuple(float(v) for v in c)
+
+
+def dense_l2_f16_error_bound(D: int, qnorm, xmax):
+    """E = 2.5 D_pad 2^-24 (||q|| + X)^2, D_pad = D rounded up to 16: the bound on |sigma - ||q||^2 + d| between the fp16 L2
+    screen sigma = fmaf(2, dot, -xsq), dot ANY fp32 accumulation of the D exact products of finite fp16 values, and the chain d
+    that the certificate of `dense_search_l2_f16` uses, for D <= 65536; derivation in the header comment of
+    csrc/dense_search_l2_f16.hip.  The constant is the library's.  Plain float / numpy arithmetic: scalars or arrays."""
+    c_rel, _ = dense_l2_f16_error_constants()
+    dpad = (int(D) + 15) // 16 * 16
+    r = qnorm + xmax
+    return c_rel * dpad * 2.0 ** -24 * r * r
+
+
+def dense_l2_f16_scores(x16: torch.Tensor, q16: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw screen values sigma [nq, N] = fmaf(2, dot(q, x_n), -xsq[n]) of the fp16 L2 search (rc_dense_l2_f16_scores): a
+    test hook, never a result."""
+    x16, q16 = _dense_f16_args(x16, q16, 1)
+    lib, h, s, _ = _ctx(q16)
+    if xsq is None:
+        xsq = dense_row_sqnorms(x16)
+    _need_cuda(xsq)
+    xsq = xsq.to(torch.float32).contiguous()
+    if xsq.shape != (x16.shape[0],):
+        raise ValueError("dense_l2_f16_scores: xsq must hold one squared norm per row, [N]")
+    out = torch.empty((q16.shape[0], x16.shape[0]), dtype=torch.float32, device=q16.device)
+    if out.numel():
+        _lib.check(lib.rc_dense_l2_f16_scores(h, _p(x16), x16.stride(0), x16.shape[0], x16.shape[1], _p(q16), q16.shape[0],
+                                              _p(xsq), _p(out), s), "rc_dense_l2_f16_scores", h)
+    return out
+
+
+def dense_search_l2_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+    """The same answer as `dense_search_l2_f16` by the route that cannot fail (rc_dense_l2_f16_search_exact)."""
+    return _dense_search_exact(_DENSE_L2_F16, x16, q, k, id_offset)
+
+
+def dense_search_l2_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
+                        defer: bool = False, method: str = "auto", max_retries: int = 2, xsq: Optional[torch.Tensor] = None,
+                        xnorm_max: Optional[torch.Tensor] = None):
+    """Exact top-k squared-Euclidean search of `q` [nq, D] against the FINITE fp16 corpus `x16` [N, D] (faiss.IndexFlatL2 with
+    useFloat16).  The queries are rounded to fp16 as `dense_search_f16` rounds them (to nearest even, no range check: a value of
+    magnitude >= 65520 becomes inf, such a query gets no certificate and the exact route gives it the chain's inf / NaN
+    distances).  A distance is the chain of `dense_search_l2` over the widened values: ids and distance bits equal
+    `dense_search_l2(x16.float(), q.half().float(), k)`.  The f16 matrix cores only screen; candidates are rescored by the chain
+    and every answer of the fast route carries a certificate (qstatus bit2 when it cannot be given: such queries are repeated,
+    then answered by `dense_search_l2_f16_exact`; `.stats` of the `PendingSearch`).  xsq: device fp32 [N], the squared norms of
+    the fp16 rows (`dense_row_sqnorms`); xnorm_max: device fp32 [1] >= the largest row norm; both computed here from the fp16
+    corpus when None, and neither is read up to DENSE_EXACT_MAX_N rows.  Everything else as `dense_search_l2`."""
+    if x16.dtype != torch.float16:       # before any norm is computed from it
+        raise ValueError("dense_search_l2_f16: the corpus must be float16 (FlatL2F16Index rounds and checks it)")
+    return _dense_search_l2(_DENSE_L2_F16, x16, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)

@@ -10,7 +10,13 @@ of every pass and its spread, the repeated / exact-route query counts, a sample 
 of tests/test_dense_l2.py, the same work as a chunked expanded torch.mm + torch.topk composition (ids compared where the
 distance margin exceeds the chain's bound), the exact-route kernel alone at 1 200 x 131 072 x 768 against its vector-ALU
 issue bound, and 1 / 32 / 128 queries at k = 100 beside the inner-product times.  --quick: one pass at k = 1000, no torch
-leg, no small query sets."""
+leg, no small query sets.
+
+    python tools/dense_l2_bench.py --storage float16 [--out profiles/dense_l2_f16_bench.json] [--quick] [--l2-only]
+
+--storage float16: the fp16 L2 index (csrc/dense_search_l2_f16.hip, FlatL2F16Index) beside the fp32 L2 index and the fp16
+inner-product index of the same process, the same alternating passes and small query sets, the fp16 L2 / fp32 L2 and fp16 L2 /
+fp16 IP time ratios of every pass, a sample of queries checked against the chain oracle on the widened values."""
 import argparse
 import json
 import os
@@ -93,8 +99,102 @@ def exact_kernel_alone(x, q, say):
     return row
 
 
+def storage_f16(a, say, res):
+    """--storage float16: the fp16 L2 index beside the fp32 L2 index (the same vectors before rounding) and the fp16
+    inner-product index (the same fp16 tensor) of this process, alternating passes; then 1 / 32 / 128 queries at k = 100."""
+    import numpy as np
+    import torch
+    from repconc_amd import ops
+    from repconc_amd.dense_index import FlatIPIndex, FlatL2F16Index, FlatL2Index
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    h = FlatL2F16Index(a.d, device=dev)
+    h.reserve(a.n)
+    l2 = None if a.l2_only else FlatL2Index(a.d, device=dev)
+    if l2 is not None:
+        l2.reserve(a.n)
+    for r0 in range(0, a.n, 1 << 20):
+        part = torch.randn((min(1 << 20, a.n - r0), a.d), generator=g, device=dev)
+        h.add(part)
+        if l2 is not None:
+            l2.add(part)
+    q = torch.randn((a.nq, a.d), generator=g, device=dev)
+    ip = None
+    if not a.l2_only:
+        ip = FlatIPIndex(a.d, device=dev, storage="float16")
+        ip._x, ip.ntotal, ip._xnorm_max = h._x, h.ntotal, h._xnorm_max      # the same fp16 vectors (measurement only)
+    legs = [("l2_f16", h), ("l2_f32", l2), ("ip_f16", ip)]
+    legs = [(n, ix) for n, ix in legs if ix is not None]
+    qn = q.cpu().numpy()
+    nb = -(-a.nq // a.batch)
+    ks = [1000] if a.quick else [int(v) for v in a.ks.split(",")]
+    passes = 1 if a.quick else a.passes
+    last = {}
+    for k in ks:
+        for _, index in legs:
+            index.search(qn[:a.batch], k)                    # warm-up
+        rows = []
+        for p in range(passes):
+            row = {"k": k, "pass": p, "batches": nb}
+            for name, index in legs:
+                t, sc, ids, retried, exact = timed_batches(index, qn, k, nb)
+                row.update({f"{name}_ms_per_batch": 1e3 * t / nb, f"{name}_queries_per_s": a.nq / t,
+                            f"{name}_retried_queries": retried, f"{name}_exact_queries": exact})
+                if name == "l2_f16":
+                    last[k] = (sc, ids)
+            if len(legs) == 3:
+                row["l2_f16_over_l2_f32_time"] = row["l2_f16_ms_per_batch"] / row["l2_f32_ms_per_batch"]
+                row["l2_f16_over_ip_f16_time"] = row["l2_f16_ms_per_batch"] / row["ip_f16_ms_per_batch"]
+            rows.append(row)
+            say(row)
+        summary = {"k": k}
+        for name, _ in legs:
+            summary[f"{name}_ms_per_batch_median"] = float(np.median([r[f"{name}_ms_per_batch"] for r in rows]))
+            summary[f"{name}_queries_per_s_median"] = float(np.median([r[f"{name}_queries_per_s"] for r in rows]))
+            summary[f"{name}_retried_queries"] = sum(r[f"{name}_retried_queries"] for r in rows)
+            summary[f"{name}_exact_queries"] = sum(r[f"{name}_exact_queries"] for r in rows)
+        for key in ("l2_f16_over_l2_f32_time", "l2_f16_over_ip_f16_time"):
+            if key in rows[0]:
+                v = [r[key] for r in rows]
+                summary.update({key + "_median": float(np.median(v)), key + "_min": min(v), key + "_max": max(v)})
+        say(summary)
+        res["runs"].append({"passes": rows, "summary": summary})
+    if a.verify:
+        from test_dense_l2 import oracle_topk_l2
+        k = ks[-1]
+        sel = np.linspace(0, a.nq - 1, a.verify).astype(int)
+        ws, wi = oracle_topk_l2(h.xb, q[sel].half().float(), k, qblock=16, rblock=1 << 20)    # the oracle widens block by block
+        gs, gi = last[k][0][sel], last[k][1][sel]
+        res["verified_queries"] = int(len(sel))
+        res["verified_equal"] = bool(np.array_equal(gi, wi) and np.array_equal(gs.view(np.uint32), ws.view(np.uint32)))
+        say({"oracle_check_queries": int(len(sel)), "equal": res["verified_equal"]})
+    if not a.quick:
+        res["small"] = []
+        for nq in [int(v) for v in a.small.split(",")]:
+            qq = q[:nq].contiguous()
+            row = {"nq": nq, "k": 100}
+            fns = {"l2_f16": lambda: ops.dense_search_l2_f16(h.xb, qq, 100, xsq=h._xsq[: h.ntotal], xnorm_max=h._xnorm_max)}
+            if l2 is not None:
+                fns["l2_f32"] = lambda: ops.dense_search_l2(l2.xb, qq, 100, xsq=l2._xsq[: l2.ntotal], xnorm_max=l2._xnorm_max)
+                fns["ip_f16"] = lambda: ops.dense_search_f16(h.xb, qq, 100, xnorm_max=h._xnorm_max)
+            for name, fn in fns.items():
+                for _ in range(2):
+                    fn()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    fn()
+                torch.cuda.synchronize()
+                row[name + "_ms"] = 1e3 * (time.perf_counter() - t0) / 10
+            res["small"].append(row)
+            say(row)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--storage", default="float32", choices=["float32", "float16"],
+                    help="float16: the fp16 L2 index beside the fp32 L2 index and the fp16 inner-product index")
     ap.add_argument("--n", type=int, default=8841823)
     ap.add_argument("--d", type=int, default=768)
     ap.add_argument("--nq", type=int, default=6980)
@@ -120,6 +220,13 @@ def main():
     def say(row):
         print(json.dumps(row), flush=True)
 
+    if a.storage == "float16":
+        res["storage"] = "float16"
+        storage_f16(a, say, res)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            json.dump(res, open(a.out, "w"), indent=1)
+        return
     if a.exact_only:
         x = torch.randn((131072, a.d), generator=g, device=dev)
         res["exact_kernel"] = exact_kernel_alone(x, torch.randn((1200, a.d), generator=g, device=dev), say)
