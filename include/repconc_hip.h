@@ -105,8 +105,13 @@ int rc_pq_assign_nearest(rc_handle_t h, const float* x, int64_t ldx, const float
  * ws: rc_pq_assign_nearest_fast_ws_bytes(B, M) bytes (one doubt-list slot per pair: the list cannot overflow; plus the
  * staged bf16 image of the centroids, written once per call by assign_prep_kernel and fetched by every block).
  * Asynchronous and complete — no follow-up call is needed.  rc_pq_assign_nearest_fast_overflow (synchronises) only
- * reports the number of doubtful pairs in *doubtful and returns 0. */
+ * reports the number of doubtful pairs in *doubtful and returns 0.
+ * The rounding bound: a pair is doubtful unless its best screened value leads the second best by more than
+ * margin * (||x_m||^2 + max_k ||c_mk||^2), margin = 2 E = 2 [3.63e-5 + (3 KP + 7) 3.6e-7 + (2 dsub + 4) 1.2e-7], KP = dsub
+ * rounded up to 16 (1.21e-4 at dsub 16; the terms are derived in the header of csrc/pq_assign_mfma.hip).
+ * rc_pq_assign_nearest_fast_margin(dsub) returns the compiled margin, negative for a width without a screen; no GPU. */
 size_t rc_pq_assign_nearest_fast_ws_bytes(int64_t B, int M);
+float rc_pq_assign_nearest_fast_margin(int dsub);
 int rc_pq_assign_nearest_fast(rc_handle_t h, const float* x, int64_t ldx, const float* C, int64_t B,
                               int D, int M, int K, uint8_t* codes_u8, int64_t* codes_i64, void* ws,
                               size_t ws_bytes, rc_stream_t stream);

@@ -131,15 +131,16 @@ void orc_centre(float* d, const float* minmax, int64_t B, int M) {
     }
 }
 
-/* codes[b][m] = argmin_k d[m][b][k], first minimum.  :52,:66 */
+/* codes[b][m] = argmin_k d[m][b][k], first minimum.  :52,:66.  A NaN distance never wins, wherever it stands (the scan
+ * starts from +inf, not from d[0]: a NaN at k = 0 used to win by standing first); code 0 when no distance is below +inf. */
 void orc_argmin(const float* d, int64_t B, int M, uint8_t* codes) {
 #pragma omp parallel for collapse(2) schedule(static)
     for (int m = 0; m < M; ++m)
         for (int64_t b = 0; b < B; ++b) {
             const float* p = d + ((int64_t)m * B + b) * K;
             int bi = 0;
-            float best = p[0];
-            for (int k = 1; k < K; ++k)
+            float best = INFINITY;
+            for (int k = 0; k < K; ++k)
                 if (p[k] < best) { best = p[k]; bi = k; }
             codes[b * M + m] = (uint8_t)bi;
         }

@@ -162,7 +162,8 @@ def quantize(x, centroids, use_constraint: bool, epsilon: float = 0.003, iters: 
     B = x.shape[0]
     d = dist_table(x, centroids)
     if not use_constraint:
-        codes = np.argmin(d, axis=-1)                                   # :52 first-min
+        # :52 first-min; a NaN distance never wins (np.argmin alone would return the first NaN), code 0 if none is below +inf
+        codes = np.argmin(np.where(np.isnan(d), F32(np.inf), d), axis=-1)
         return (codes.T.copy(), {"dist": d}) if return_intermediates else codes.T.copy()
     mx, mn = minmax_per_m(d)                                            # global == max over ranks
     dc = centre(d, mx, mn)                                              # :54

@@ -34,6 +34,7 @@ PROTOTYPES = {
     "rc_profile_collect": (_i, [_vp, _i, C.POINTER(_i), C.POINTER(_d)]),
     "rc_pq_assign_nearest": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp]),
     "rc_pq_assign_nearest_fast_ws_bytes": (_sz, [_i64, _i]),
+    "rc_pq_assign_nearest_fast_margin": (C.c_float, [_i]),
     "rc_pq_assign_nearest_fast": (_i, [_vp, _vp, _i64, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     "rc_pq_assign_nearest_fast_overflow": (_i, [_vp, _vp, _i64, _i, C.POINTER(_i)]),
     "rc_pq_dist_table_ws_bytes": (_sz, [_i64, _i]),

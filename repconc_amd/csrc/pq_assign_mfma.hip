@@ -6,20 +6,32 @@
 //     S[k,b] = ||c_k||^2 - 2 <c_k, x_b>            ( = d[k,b] - ||x_b||^2 up to rounding )
 // is within a provable distance E of the reference's d (both measured from the real-number distance), so the
 // reference's argmin is among the centroids with S <= S_min + 2E.  The MFMA pass keeps, per (row, sub-quantiser), the
-// best and second-best S: when the gap exceeds the margin the best IS the reference's code; otherwise (~2e-3 of the
+// best and second-best S: when the gap exceeds the margin the best IS the reference's code; otherwise (~3e-3 of the
 // pairs, and every exact tie) the pair is appended to a list and assign_redo_kernel recomputes it with the exact
 // arithmetic and the first-minimum rule.  Output = reference codes, bit for bit (tests compare with the exact kernel
 // and the oracle).
 //
 // Which MFMA.  v_mfma_f32_32x32x2_f32 runs at the fp32 VECTOR rate (64 cycles / instruction, sharing the pipe with the
 // VALU epilogue: measured 19 ms per 4 M rows, 2.4x the exact kernel).  The bf16 XDL pipe is 16x faster and co-issues
-// with the VALU, so the screen splits every fp32 operand in two bf16 pieces, v = vh + vl + (|rest| <= 2^-18 |v|), and
-// takes three products  wh.xh + wh.xl + wl.xh  (w = -2c) accumulated in fp32:
-//     dropped terms  <= 3.1 * 2^-18 * sum|w_j x_j|  <= 1.2e-5 (||x||^2 + ||c||^2)
+// with the VALU, so the screen splits every fp32 operand in two bf16 pieces (round to nearest even, 8 significant bits
+// each), v = vh + vl + rest, and takes three products  wh.xh + wh.xl + wl.xh  (w = -2c) accumulated in fp32.
+// The split.  |v - vh| <= half a bf16 ulp of v <= 2^-8 |v|, so |vl| <= 2^-8 |v| (measured over a whole binade:
+// 1.992 * 2^-9); the remainder v - vh is exact in fp32 and lies in a binade at most 2^-8 of v's, so
+// |rest| <= half a bf16 ulp of it <= 2^-17 |v| (measured: 1.996 * 2^-18, e.g. at 0x3f8040c0).  The terms of E, each as
+// a multiple of (||x||^2 + ||c||^2) >= 2 sum|c_j x_j| = sum|w_j x_j|:
+//     dropped products  wl.xl + (wh + wl).xr + wr.x :  (2^-16 + 2^-17 + 2^-17) sum|w_j x_j| = 8 * 2^-18     3.052e-5
+//       (tests/test_assign_screen.py builds rows and centroids whose dropped terms all have one sign: 3.01e-5)
+//     the 4 tag bits (below) replace the low mantissa bits of a screened value <= 3 (||x||^2 + ||c||^2):
+//       < 16 ulp = 2^-19 of it                                                                                5.73e-6
 //     fp32 accumulation of 3*KP+6 terms (||c||^2 and the document offset below enter as 3 exact bf16 pieces each), each
-//       <= 1 ulp of a partial sum <= 3 (||x||^2+||c||^2):  (3 KP + 7) 3.6e-7
-//     ||c||^2 and the reference's own d: (dsub+2) 1.2e-7 each; the 4 tag bits (below): 5.7e-6
-// => E = [1.8e-5 + (3 KP + 7) 3.6e-7 + (2 dsub + 4) 1.2e-7] (||x||^2 + max_k ||c_k||^2),  margin = 2 E.
+//       <= 1 ulp of a partial sum <= 3 (||x||^2+||c||^2) (the rounding inside a bf16 MFMA is not documented: one ulp
+//       per term, not half):                                                                    (3 KP + 7) 3.6e-7
+//     ||c||^2 (fma chain) and the reference's own d: (dsub+2) 1.2e-7 each                       (2 dsub + 4) 1.2e-7
+// => E = [3.63e-5 + (3 KP + 7) 3.6e-7 + (2 dsub + 4) 1.2e-7] (||x||^2 + max_k ||c_k||^2),  margin = 2 E
+// (3.052e-5 + 5.73e-6 = 3.625e-5, rounded up; mf_margin below, rc_pq_assign_nearest_fast_margin returns it).  Until
+// the split bound was corrected the first line read 3.1 * 2^-18 (unit round-off 2^-9 instead of 2^-8) and the constant
+// 1.8e-5: the built inputs above used 71-75 % of that E with this one term at dsub 8 / 16, and the codes held only
+// through the slack of the accumulation allowance.
 //
 // Mapping (v_mfma_f32_32x32x16_bf16, 32 cycles): D = A*B + C with A[i][kk] = piece of -2 c_{32 kt + i}[kk] (LDS, 16 B
 // per lane), B[kk][j] = piece of x_{b0 + j}[kk] (registers); one more MFMA adds ||c||^2 (three pieces against 1.0) and a
@@ -121,6 +133,12 @@ __device__ __forceinline__ void mf_split2(float v0, float v1, unsigned& hi, unsi
     hi = __builtin_bit_cast(unsigned, __builtin_convertvector(v, mf_bf16x2));
     const mf_f32x2 r = {v0 - __uint_as_float(hi << 16), v1 - __uint_as_float(hi & 0xFFFF0000u)};
     lo = __builtin_bit_cast(unsigned, __builtin_convertvector(r, mf_bf16x2));
+}
+
+// rounding bound of the screen (file header): margin = 2 E, as a multiple of ||x||^2 + max_k ||c_k||^2
+constexpr float mf_margin(int dsub) {
+    const int kp = (dsub + 15) / 16 * 16;
+    return 2.0f * (3.63e-5f + (float)(3 * kp + 7) * 3.6e-7f + (float)(2 * dsub + 4) * 1.2e-7f);
 }
 
 template <int DSUB>
@@ -291,8 +309,7 @@ __global__ __launch_bounds__(256, (DSUB <= 16 ? 3 : (DSUB <= 32 ? 2 : 1))) void 
             }
             xn[s] = nrm + __shfl_xor(nrm, 32);
         }
-        // rounding bound of the screen (file header): margin = 2 E
-        constexpr float MARGIN = 2.0f * (1.8e-5f + (float)(3 * KP + 7) * 3.6e-7f + (float)(2 * DSUB + 4) * 1.2e-7f);
+        constexpr float MARGIN = mf_margin(DSUB);                   // rounding bound of the screen (file header)
         // B operand of the ||c||^2 MFMA: 1.0 in k-slots 0-2, and in k-slots 3-5 the three bf16 pieces of the document's
         // offset ||x||^2 + margin: every screened value becomes (distance^2 + margin) > 0, so the float bits order like
         // signed integers and the epilogue can use v_min3_i32 / v_min_i32 next to v_med3_f32
@@ -610,6 +627,16 @@ extern "C" int rc_pq_assign_nearest_fast(rc_handle_t h, const float* x, int64_t 
     rc_prof_mark(h, RC_PROF_ASSIGN_NEAREST, s);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
+}
+
+// The compiled margin of the screen for a sub-vector width (negative: no screen for that width).  Needs no GPU.
+extern "C" float rc_pq_assign_nearest_fast_margin(int dsub) {
+    switch (dsub) {
+#define MF_CASE(DS) case DS: return mf_margin(DS);
+        MF_CASE(8) MF_CASE(12) MF_CASE(16) MF_CASE(24) MF_CASE(32) MF_CASE(48) MF_CASE(64) MF_CASE(96)
+#undef MF_CASE
+        default: return -1.0f;
+    }
 }
 
 // After the stream has drained: did the doubt list overflow?  (1 = yes: rerun with rc_pq_assign_nearest.)

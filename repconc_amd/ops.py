@@ -122,6 +122,15 @@ def assign_nearest(x: torch.Tensor, centroids: torch.Tensor, dtype=torch.int64, 
     return codes
 
 
+def assign_margin(dsub: int) -> float:
+    """The compiled margin of the matrix-core screen of assign_nearest: a (row, sub-quantiser) pair is re-judged exactly
+    unless its best screened value leads the second best by more than margin * (||x_m||^2 + max_k ||c_mk||^2).  Needs no GPU."""
+    v = float(_lib.load().rc_pq_assign_nearest_fast_margin(int(dsub)))
+    if v < 0:
+        raise ValueError(f"no matrix-core screen for dsub = {dsub}")
+    return v
+
+
 # --------------------------------------------------------------------------- distance table
 def dist_table(x: torch.Tensor, centroids: torch.Tensor, with_minmax: bool = True):
     """d [M,B,K] fp32 (+ minmax [2M]: max then min per m).  modeling_repconc.py:50,76-77."""

@@ -41,6 +41,14 @@ def test_size_helpers_need_no_gpu():
     assert w_lists > 0 and w_probes >= w_lists + 4 * (2 * pairs + 4 * 5000 + 3 * 1200)
     assert lib.rc_ivf_search_probes_ws_bytes(24, 1200, 32, 5000, 8192) == 0      # no conflict-free screen for M = 24
     assert lib.rc_ivf_search_probes_ws_bytes(96, 1200, 0, 5000, 8192) == 0
+    # the compiled margin of the assignment screen: the header's sum, in the kernel's fp32 order; no screen, no margin
+    import numpy as np
+    f = np.float32
+    for dsub in (8, 12, 16, 24, 32, 48, 64, 96):
+        kp = (dsub + 15) // 16 * 16
+        want = f(2) * ((f(3.63e-5) + f(3 * kp + 7) * f(3.6e-7)) + f(2 * dsub + 4) * f(1.2e-7))
+        assert f(lib.rc_pq_assign_nearest_fast_margin(dsub)) == want
+    assert lib.rc_pq_assign_nearest_fast_margin(20) < 0 and lib.rc_pq_assign_nearest_fast_margin(0) < 0
 
 
 def test_cpu_tensors_are_rejected_loudly():
