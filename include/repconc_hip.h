@@ -559,6 +559,36 @@ int rc_dense_l2_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_
                            const float* xsq, float* out, rc_stream_t stream);
 void rc_dense_l2_f16_error_constants(double* c);
 
+/* ------------------------------------------------------------------ dense flat search, L2 metric, fp32 corpus, bf16x3 screen
+ * rc_dense_l2_search_q with the screen on the bf16 matrix cores: the corpus stays fp32 and ids AND distance bits are those of
+ * rc_dense_l2_search_q (the chain t = q[j] - x[n][j], acc = fmaf(t, t, acc); distance asc, row asc; +0.0f for a zero;
+ * +inf / -1 past min(k, N)).  Arguments, alignment rules and limits of rc_dense_l2_search_q; the corpus must round to finite
+ * bf16 (every |x| < 2^128 - 2^119).
+ * rc_dense_l2_bf16x3_search_q: N <= 131072 takes the route of rc_dense_l2_search_exact.  Above: the screen is sigma~ =
+ *   fmaf(2, s~(q, x_n), -xsq[n]) with s~ the three-product bf16 split sum of rc_dense_bf16x3_search_q; threshold, candidates,
+ *   rescoring by the chain and sorting as rc_dense_l2_search_q.  xsq: DEVICE fp32 [N], the squared norm of every row (an fp64
+ *   sum rounded to nearest); xnorm_max: DEVICE pointer to one float X >= the largest Euclidean row norm; NULL for either is
+ *   RC_EINVAL.  With D_pad = D rounded up to 16, R = (||q||_2 + X)^2 and the constants c[0..3] of
+ *   rc_dense_l2_bf16x3_error_constants,
+ *     E_q = (c0 D_pad 2^-24 + c1 2^-16) R + c2 sqrt(D_pad) (||q||_2 + X) + c3 D_pad   (every |sigma~ - ||q||^2 + d| <= E_q),
+ *   -t >= thr~ - ||q||^2 + E_q for t = the query's k-th distance, all rounded to the safe side, proves the answer.  status /
+ *   qstatus as rc_dense_l2_search_q: bit0, bit1, bit2 = not certified (also: a query value that is not finite or whose bf16
+ *   rounding is not, D > 65536, R >= 2^126): repeat those queries with another sel_slack or answer them by
+ *   rc_dense_l2_search_exact; there is no exact entry of its own.  ws (16-byte aligned, it holds the queries' bf16 planes):
+ *   rc_dense_l2_bf16x3_search_ws_bytes(N, D, nq, k).
+ * rc_dense_l2_bf16x3_scores (test hook): the screen's raw sigma~, out [nq][N] fp32; ws (16-byte aligned):
+ *   rc_dense_l2_bf16x3_scores_ws_bytes(D, nq).
+ * rc_dense_l2_bf16x3_error_constants: c[4] = {5, 2, 4 * 2^-126, 8 * 2^-149} as the certificate kernel was compiled (no GPU
+ *   needed). */
+size_t rc_dense_l2_bf16x3_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_l2_bf16x3_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* dist,
+                                int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_dense_l2_bf16x3_scores_ws_bytes(int D, int nq);
+int rc_dense_l2_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                              const float* xsq, float* out, void* ws, size_t ws_bytes, rc_stream_t stream);
+void rc_dense_l2_bf16x3_error_constants(double* c);
+
 /* ------------------------------------------------------------------ a-9 … a-11, stateful form
  * The index object the reference keeps inside Faiss (initialize_index / add_docs / index.search,
  * models/repconc/evaluate_repconc.py:78-98,182; JPQ's per-step synchronize_model_index, models/jpq/finetune_jpq.py:209-214),

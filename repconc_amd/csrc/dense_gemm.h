@@ -1,5 +1,5 @@
-// What the five dense flat searches share (dense_search.hip, dense_search_f16.hip, dense_search_bf16x3.hip,
-// dense_search_l2.hip, dense_search_l2_f16.hip): the GEMM on the fp32 matrix cores whose result IS the inner-product score (the fp32 fmaf chain over d
+// What the six dense flat searches share (dense_search.hip, dense_search_f16.hip, dense_search_bf16x3.hip,
+// dense_search_l2.hip, dense_search_l2_f16.hip, dense_search_l2_bf16x3.hip): the GEMM on the fp32 matrix cores whose result IS the inner-product score (the fp32 fmaf chain over d
 // ascending) and, with one more operand, the L2 screen; the workspace layouts and the argument checks.  T is the storage
 // type of x and q: float, or _Float16 widened to fp32 on load (exact).  Device code: every translation unit that uses it
 // compiles its own copy, no -fgpu-rdc.  The route of a search, exact route included, and what the screened searches share

@@ -1,6 +1,7 @@
-// What the two dense L2 searches share beyond dense_screen.h (dense_search_l2.hip: fp32 corpus, dense_search_l2_f16.hip: fp16
-// corpus): the exact route's kernel over either storage type and the sign flip at the end.  Device code: each unit instantiates
-// the storage type it searches, no -fgpu-rdc.
+// What the three dense L2 searches share beyond dense_screen.h (dense_search_l2.hip: fp32 corpus, dense_search_l2_f16.hip: fp16
+// corpus, dense_search_l2_bf16x3.hip: fp32 corpus, bf16x3 screen): the exact route's kernel over either storage type and the
+// sign flip at the end.  Device code: each unit instantiates the storage type it searches, no -fgpu-rdc; the fp32 form is
+// instantiated in dense_search_l2.hip alone and reached from the bf16x3 unit through dense_l2_exact_rows_f32.
 #pragma once
 #include "dense_screen.h"
 
@@ -137,6 +138,11 @@ static int dense_l2_launch_exact_rows(rc_handle_t h, const T* x, int64_t ldx, in
     return RC_OK;
 }
 
-// -d -> d in place over the n output values: -0.0f -> +0.0f, the -inf of the padding -> +inf.  The finish of both L2 variants,
+// -d -> d in place over the n output values: -0.0f -> +0.0f, the -inf of the padding -> +inf.  The finish of every L2 variant,
 // defined once in dense_search_l2.hip.
 int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_t s);
+
+// dense_l2_launch_exact_rows<float>, the rows of rc_dense_l2_search_exact, for the other unit that searches an fp32 corpus;
+// defined in dense_search_l2.hip.
+int dense_l2_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
+                            hipStream_t s);

@@ -1,6 +1,7 @@
-// What the five dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
+// What the six dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
 // dense_search_f16.hip: fp16 corpus and f16 screen, dense_search_bf16x3.hip: fp32 corpus and bf16x3 screen,
-// dense_search_l2.hip: fp32 corpus, squared Euclidean distance, dense_search_l2_f16.hip: the same over an fp16 corpus): the
+// dense_search_l2.hip: fp32 corpus, squared Euclidean distance, dense_search_l2_f16.hip: the same over an fp16 corpus,
+// dense_search_l2_bf16x3.hip: the fp32 L2 corpus under the bf16x3 screen): the
 // route of a search and the bodies of its entries, the pieces common to the two 16x16x32 screen GEMMs, the rescoring kernel
 // and the certificate kernel.  Device code: every translation unit compiles its own copy, no -fgpu-rdc.
 //
@@ -13,7 +14,7 @@
 //   over rows widened on load; L2: dense_l2_exact_kernel), then the 8-pass radix select over the 64-bit keys
 //   (topk_exact_select), then V::finish.  It terminates with the same answer for any content (all rows identical, k >= N, ...).
 //   Fast route (N > 4 S, S = min(N, 32768)):
-//   0. V::prepass: bf16x3 splits the queries into two bf16 planes in the tail of the workspace; nothing for the others
+//   0. V::prepass: the bf16x3 screens split the queries into two bf16 planes in the tail of the workspace; nothing for the others
 //   1. screen<STORE> over the strided sample j -> row j N / S: s~ of the sample (fp32 screen: s~ = s, the chain)
 //   2. adc_threshold_kernel (topk.hip): thr~[q] = the r-th best s~ of the sample, r by the ADC formula (rc_adc_sample_rank)
 //   3. screen<FILTER> over all N rows: the key (s~, row) of every s~ >= thr~[q] -> q's candidate list

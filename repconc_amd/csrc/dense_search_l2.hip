@@ -89,6 +89,12 @@ int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_t s) {
     return RC_OK;
 }
 
+// the exact route's rows for dense_search_l2_bf16x3.hip (declared in dense_l2.h)
+int dense_l2_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
+                            hipStream_t s) {
+    return dense_l2_launch_exact_rows<float>(h, x, ldx, N, D, q, nq, out, s);
+}
+
 // ---- the variant -------------------------------------------------------------------------------------------------------------
 struct dense_l2_variant : dense_variant_defaults {
     typedef float T;

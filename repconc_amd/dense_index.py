@@ -14,8 +14,8 @@ fmaf chain over the rounded values, bit for bit what the fp32 index returns for 
 index, but the candidates are chosen on the bf16 matrix cores by `ops.dense_search_bf16x3` (csrc/dense_search_bf16x3.hip).
 `add` then refuses values whose bf16 rounding is not finite (magnitude >= 2^128 - 2^119, inf, NaN).
 
-`FlatL2Index` / `FlatL2F16Index`: the squared-Euclidean indexes (`faiss.IndexFlatL2`, fp32 and fp16 storage), classes of
-their own beside `FlatIPIndex`.
+`FlatL2Index` / `FlatL2F16Index` / `FlatL2Bf16x3Index`: the squared-Euclidean indexes (`faiss.IndexFlatL2`: fp32 storage, fp16
+storage, fp32 storage with the bf16x3 screen), classes of their own beside `FlatIPIndex`.
 """
 from __future__ import annotations
 
@@ -77,6 +77,14 @@ class _FlatIndex:
         xt = xt.to(self.device).to(torch.float16)
         if xt.shape[0] and not bool(torch.isfinite(xt).all()):
             raise ValueError("add: float16 storage needs finite values of magnitude < 65520 (fp16 rounds the rest to inf)")
+        return xt
+
+    def _finite_bf16(self, xt: torch.Tensor) -> torch.Tensor:
+        """The rows of an `add` on the device in fp32, checked to round to finite bf16 before anything is stored or grown; one
+        host read."""
+        xt = xt.to(self.device, torch.float32)
+        if xt.shape[0] and not bool(torch.isfinite(xt.to(torch.bfloat16)).all()):
+            raise ValueError("add: the bf16x3 screen needs finite values of magnitude < 2^128 - 2^119 (bf16 rounds the rest to inf)")
         return xt
 
     def reset(self) -> None:
@@ -148,10 +156,7 @@ class FlatIPIndex(_FlatIndex):
             if n:
                 xnorm = ops.dense_f16_xnorm_max(xt)
         elif self.screen == "bf16x3":
-            # checked before anything is stored or grown; one host read per add
-            xt = xt.to(self.device, torch.float32)
-            if n and not bool(torch.isfinite(xt.to(torch.bfloat16)).all()):
-                raise ValueError("add: the bf16x3 screen needs finite values of magnitude < 2^128 - 2^119 (bf16 rounds the rest to inf)")
+            xt = self._finite_bf16(xt)
             if n:
                 xnorm = ops.dense_xnorm_max(xt)
         self._grow_for(need)
@@ -166,7 +171,7 @@ class FlatIPIndex(_FlatIndex):
 
 
 class _FlatL2(_FlatIndex):
-    """What the two L2 indexes share: beside the vectors, their fp32 squared norms in a capacity-sized tensor and a bound of the
+    """What the L2 indexes share: beside the vectors, their fp32 squared norms in a capacity-sized tensor and a bound of the
     largest norm, both updated by `add` without a host read: the screen's second operand and its certificate's X.  A subclass
     says how `add` stores a row (`_stored`) and which search answers (`_search`)."""
     PAD = float("inf")
@@ -211,7 +216,8 @@ class _FlatL2(_FlatIndex):
 class FlatL2Index(_FlatL2):
     """Exact squared-Euclidean index resident in HBM: the GPU `faiss.IndexFlatL2` the reference names at
     models/repconc/evaluate_repconc.py:102 and train/run_warmup.py:102,107.  Duck-typed like `FlatIPIndex`, fp32 storage and
-    the fp32 screen only (no `storage` / `screen` options; fp16 storage is `FlatL2F16Index`).  `search` answers with
+    the fp32 screen only (no `storage` / `screen` options; fp16 storage is `FlatL2F16Index`, the bf16x3 screen
+    `FlatL2Bf16x3Index`).  `search` answers with
     `ops.dense_search_l2` (csrc/dense_search_l2.hip): a distance is the fp32 chain t = q_j - x_j, acc = fmaf(t, t, acc) over j
     ascending, bit for bit, never negative; results are sorted (distance asc, id asc), +inf / -1 past ntotal.  Beside the
     vectors the index keeps their fp32 squared norms in a capacity-sized tensor and a bound of the largest norm, both updated
@@ -239,3 +245,17 @@ class FlatL2F16Index(_FlatL2):
 
     def _stored(self, xt: torch.Tensor) -> torch.Tensor:
         return self._rounded_f16(xt)
+
+
+class FlatL2Bf16x3Index(_FlatL2):
+    """`FlatL2Index` with the candidates chosen on the bf16 matrix cores: the vectors stay fp32 and `search` returns the same
+    ids and distance bits, answered by `ops.dense_search_l2_bf16x3` (csrc/dense_search_l2_bf16x3.hip).  `add` refuses values
+    whose bf16 rounding is not finite (magnitude >= 2^128 - 2^119, inf, NaN) before anything is stored (the one host read of an
+    `add`, as `FlatIPIndex(screen="bf16x3")`)."""
+    _search = staticmethod(ops.dense_search_l2_bf16x3)
+
+    def __init__(self, d: int, device: Optional[torch.device] = None):
+        self._init_l2(d, device, torch.float32)
+
+    def _stored(self, xt: torch.Tensor) -> torch.Tensor:
+        return self._finite_bf16(xt)

@@ -5,7 +5,8 @@ recipe step 3) — same arguments, same module-level names and positional signat
 Pipeline: corpus and queries encoded by the dense model (or read from corpus_embeds.npy / corpus_ids.npy and
 query_embeds.npy / qids.npy, written only with --save_corpus_embed / --save_query_embed); `create_index` +
 `batch_dense_search` (exact fp32 inner product, `rc_dense_search_q`) -> <out_query_dir>/run.tsv -> `pytrec_evaluate` ->
-metric.json.  An existing metric.json skips the search.  Only the main process reads caches, searches and writes files.
+metric.json.  `--index_metric l2` searches by squared Euclidean distance instead and writes the scores -d.  An existing
+metric.json skips the search.  Only the main process reads caches, searches and writes files.
 `--search_threads` is accepted with no effect (no OpenMP pool).
 """
 import json
@@ -20,9 +21,9 @@ import transformers
 from transformers import AutoConfig, AutoTokenizer, HfArgumentParser, TrainingArguments, set_seed
 from transformers.trainer_utils import is_main_process
 
-from ..dense_index import FlatIPIndex
 from ..models.dense import AutoDense
-from ..models.dense.evaluate_dense import batch_dense_search, create_index, encode_dense_corpus, encode_dense_query
+from ..models.dense.evaluate_dense import (INDEX_METRICS, batch_dense_search, check_index_options, create_index,
+                                           encode_dense_corpus, encode_dense_query)
 from ..utils.eval_utils import load_corpus, load_queries, pytrec_evaluate, write_run
 
 logger = logging.getLogger(__name__)
@@ -60,6 +61,9 @@ class EvalArguments(TrainingArguments):
                                                                   "queries are rounded to fp16, the search stays exact)"})
     index_screen: str = field(default="fp32", metadata={"help": "fp32, or bf16x3: the fp32 index with its candidates chosen on "
                                                                 "the bf16 matrix cores (same results; not with index_float16)"})
+    index_metric: str = field(default="ip", metadata={"help": "ip: inner product; l2: squared Euclidean distance, smallest first "
+                                                              "(run.tsv then holds the scores -d)",
+                                                      "choices": list(INDEX_METRICS)})
     remove_unused_columns: Optional[bool] = field(default=False)
 
 
@@ -103,11 +107,15 @@ def load_or_encode_corpus(model, tokenizer, model_args, data_args, eval_args):
 
 def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_ids, out_metric_path, out_query_dir,
                                qrel_path, eval_args):
-    """Exact search on the GPU, run.tsv, and with a qrels file metric.json.  run_dense_eval.py:111-127."""
+    """Exact search on the GPU, run.tsv, and with a qrels file metric.json.  run_dense_eval.py:111-127.  index_metric "l2":
+    the scores written are -d, exactly: run.tsv and trec_eval rank by descending score."""
+    metric = getattr(eval_args, "index_metric", "ip")
     index = create_index(corpus_embeds, use_float16=getattr(eval_args, "index_float16", False),
-                         screen=getattr(eval_args, "index_screen", "fp32"))
+                         screen=getattr(eval_args, "index_screen", "fp32"), metric=metric)
     all_topk_scores, all_topk_ids = batch_dense_search(query_ids, query_embeds, corpus_ids, index, eval_args.topk,
                                                        batch_size=eval_args.search_batch)
+    if metric == "l2":
+        all_topk_scores = -all_topk_scores
     out_run_path = os.path.join(out_query_dir, "run.tsv")
     write_run(out_run_path, query_ids, all_topk_scores, all_topk_ids)
     if qrel_path is None:
@@ -123,7 +131,7 @@ def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_id
 def main(argv=None):
     parser = HfArgumentParser((ModelArguments, DataArguments, EvalArguments))
     model_args, data_args, eval_args = parser.parse_args_into_dataclasses(argv)
-    FlatIPIndex.check_options("float16" if eval_args.index_float16 else "float32", eval_args.index_screen)   # before encoding
+    check_index_options(eval_args.index_metric, eval_args.index_float16, eval_args.index_screen)            # before encoding
     main_process = is_main_process(eval_args.local_rank)
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s -   %(message)s", datefmt="%m/%d/%Y %H:%M:%S",
                         level=logging.INFO if main_process else logging.WARN)

@@ -1,7 +1,8 @@
 """Everything evaluate/run_dense_eval.py imports from the reference's models/dense/evaluate_dense.py, under the same names:
 `DenseEvaluater`, `encode_dense_corpus`, `encode_dense_query`, `dense_search`, `batch_dense_search`, `create_index`.
 No Faiss import: the index is repconc_amd.dense_index.FlatIPIndex, the exact fp32 inner-product search of a GPU
-faiss.IndexFlatIP with useFloat16 = False (evaluate_dense.py:84-129) on the matrix cores (csrc/dense_search.hip).
+faiss.IndexFlatIP with useFloat16 = False (evaluate_dense.py:84-129) on the matrix cores (csrc/dense_search.hip);
+`create_index(metric="l2")` builds the squared-Euclidean indexes of the same module instead (faiss.IndexFlatL2).
 
 `DenseEvaluater` keeps the reference's constructor and `.predict(dataset).predictions` contract (evaluate_dense.py:18-33)
 but is a plain batched loop, not an HF-Trainer subclass, like RepCONCEvaluater (evaluate_repconc.py here).  It runs on one
@@ -18,7 +19,7 @@ from typing import Dict, Union
 import numpy as np
 import torch
 
-from ...dense_index import FlatIPIndex
+from ...dense_index import FlatIPIndex, FlatL2Bf16x3Index, FlatL2F16Index, FlatL2Index
 from ...utils.eval_utils import TextDataset, get_collator_func
 
 logger = logging.getLogger(__name__)
@@ -120,13 +121,29 @@ def batch_dense_search(query_ids: np.ndarray, query_embeds, corpus_ids: np.ndarr
     return np.concatenate(all_scores, axis=0), np.concatenate(all_ids, axis=0)
 
 
-def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="fp32") -> FlatIPIndex:
-    """An exact inner-product index holding `corpus_embeds`, on device `single_gpu_id` or the current device.
+INDEX_METRICS = ("ip", "l2")
+
+
+def check_index_options(metric: str, use_float16: bool, screen: str) -> None:
+    """ValueError for an unknown metric, storage or screen, or a combination that does not exist (fp16 storage with the bf16x3
+    screen, under either metric); touches no device.  The one rule of `create_index` and of run_dense_eval's arguments."""
+    if metric not in INDEX_METRICS:
+        raise ValueError(f"metric must be one of {list(INDEX_METRICS)}, got {metric!r}")
+    FlatIPIndex.check_options("float16" if use_float16 else "float32", screen)
+
+
+def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="fp32", metric="ip"):
+    """An exact index holding `corpus_embeds`, on device `single_gpu_id` or the current device.
     use_float16: store the vectors as fp16 (GpuClonerOptions.useFloat16, which the reference leaves False).
     screen="bf16x3" (fp32 storage only): the same results, candidates chosen on the bf16 matrix cores.
-    evaluate_dense.py:115-129."""
-    FlatIPIndex.check_options("float16" if use_float16 else "float32", screen)                # before a device is looked at
+    metric="ip": `FlatIPIndex` (evaluate_dense.py:115-129); metric="l2": squared Euclidean distance, smallest first,
+    `FlatL2Index`, `FlatL2F16Index` (use_float16) or `FlatL2Bf16x3Index` (screen="bf16x3")."""
+    check_index_options(metric, use_float16, screen)                                           # before a device is looked at
     dev = torch.device("cuda", single_gpu_id if single_gpu_id is not None else torch.cuda.current_device())
-    index = FlatIPIndex(corpus_embeds.shape[1], device=dev, storage="float16" if use_float16 else "float32", screen=screen)
+    d = corpus_embeds.shape[1]
+    if metric == "l2":
+        index = (FlatL2F16Index if use_float16 else FlatL2Bf16x3Index if screen == "bf16x3" else FlatL2Index)(d, device=dev)
+    else:
+        index = FlatIPIndex(d, device=dev, storage="float16" if use_float16 else "float32", screen=screen)
     index.add(corpus_embeds)
     return index

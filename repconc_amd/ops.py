@@ -1153,7 +1153,7 @@ def _dense_f16_args(x16: torch.Tensor, q: torch.Tensor, k: int):
     return x16, q16
 
 
-# One dense search in five variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
+# One dense search in six variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
 # library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes; exact: rc_<exact>_search_exact / ..._ws_bytes, the route that
 # cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate);
 # rownorms: it also takes xsq, the squared norm of every row, before xnorm_max; pad: the value of the slots past N.
@@ -1164,6 +1164,7 @@ _DENSE_F16 = _DenseVariant(_dense_f16_args, "dense_f16", "dense_f16", True)
 _DENSE_BF16X3 = _DenseVariant(_dense_args, "dense_bf16x3", "dense", True)
 _DENSE_L2 = _DenseVariant(_dense_args, "dense_l2", "dense_l2", True, True, float("inf"))
 _DENSE_L2_F16 = _DenseVariant(_dense_f16_args, "dense_l2_f16", "dense_l2_f16", True, True, float("inf"))
+_DENSE_L2_BF16X3 = _DenseVariant(_dense_args, "dense_l2_bf16x3", "dense_l2", True, True, float("inf"))
 
 
 def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int):
@@ -1447,7 +1448,7 @@ def dense_search_l2(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0
 
 
 def _dense_search_l2(v: _DenseVariant, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max):
-    """The front of both L2 searches: a missing xnorm_max comes from the squared norms, which are then computed once."""
+    """The front of the three L2 searches: a missing xnorm_max comes from the squared norms, which are then computed once."""
     if not 1 <= int(k) <= DENSE_MAX_K:
         raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
     if xnorm_max is None and x.dim() == 2 and x.shape[0] > DENSE_EXACT_MAX_N and method == "auto" and x.is_cuda:
@@ -1514,3 +1515,56 @@ def dense_search_l2_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: i
     if x16.dtype != torch.float16:       # before any norm is computed from it
         raise ValueError("dense_search_l2_f16: the corpus must be float16 (FlatL2F16Index rounds and checks it)")
     return _dense_search_l2(_DENSE_L2_F16, x16, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)
+
+
+# ------------------------------------------------------------------------ dense, L2 metric, fp32 corpus, bf16x3 screen
+def dense_l2_bf16x3_error_constants():
+    """(c_sum, c_split, c_flush, c_under) of E_q as the certificate kernel was compiled with them
+    (csrc/dense_search_l2_bf16x3.hip)."""
+    c = (C.c_double * 4)()
+    _lib.load().rc_dense_l2_bf16x3_error_constants(c)
+    return tuple(float(v) for v in c)
+
+
+def dense_l2_bf16x3_error_bound(D: int, qnorm, xmax):
+    """E = (5 D_pad 2^-24 + 2 * 2^-16) (||q|| + X)^2 + 4 * 2^-126 sqrt(D_pad) (||q|| + X) + 8 D_pad 2^-149, D_pad = D rounded
+    up to 16: the bound on |sigma~ - ||q||^2 + d| between the bf16x3 L2 screen sigma~ = fmaf(2, s~, -xsq) (s~ any fp32
+    accumulation of the 3 D products of the round-to-nearest-even bf16 splits) and the chain d that the certificate of
+    `dense_search_l2_bf16x3` uses, for D <= 65536; derivation in the header comment of csrc/dense_search_l2_bf16x3.hip.  The
+    constants are the library's.  Plain float / numpy arithmetic: `qnorm`, `xmax` scalars or arrays."""
+    c_sum, c_split, c_flush, c_under = dense_l2_bf16x3_error_constants()
+    dpad = (int(D) + 15) // 16 * 16
+    r = qnorm + xmax
+    return (c_sum * dpad * 2.0 ** -24 + c_split * 2.0 ** -16) * r * r + c_flush * dpad ** 0.5 * r + c_under * dpad
+
+
+def dense_l2_bf16x3_scores(x: torch.Tensor, q: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw screen values sigma~ [nq, N] = fmaf(2, s~(q, x_n), -xsq[n]) of the bf16x3 L2 search
+    (rc_dense_l2_bf16x3_scores): a test hook, never a result."""
+    x, q = _dense_args(x, q, 1)
+    lib, h, s, _ = _ctx(q)
+    if xsq is None:
+        xsq = dense_row_sqnorms(x)
+    _need_cuda(xsq)
+    xsq = xsq.to(torch.float32).contiguous()
+    if xsq.shape != (x.shape[0],):
+        raise ValueError("dense_l2_bf16x3_scores: xsq must hold one squared norm per row, [N]")
+    out = torch.empty((q.shape[0], x.shape[0]), dtype=torch.float32, device=q.device)
+    if out.numel():
+        wsb = lib.rc_dense_l2_bf16x3_scores_ws_bytes(x.shape[1], q.shape[0])
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        _lib.check(lib.rc_dense_l2_bf16x3_scores(h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], _p(xsq),
+                                                 _p(out), _p(ws), wsb, s), "rc_dense_l2_bf16x3_scores", h)
+    return out
+
+
+def dense_search_l2_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
+                           defer: bool = False, method: str = "auto", max_retries: int = 2,
+                           xsq: Optional[torch.Tensor] = None, xnorm_max: Optional[torch.Tensor] = None):
+    """`dense_search_l2` with the screen on the bf16 matrix cores: the same ids and distance bits for a FINITE fp32 corpus `x`
+    whose values round to finite bf16 (magnitude < 2^128 - 2^119; `FlatL2Bf16x3Index` checks it) and any queries.  Nothing is
+    rounded in the result: the screen's three-term bf16 split only chooses candidates, which are rescored by the chain of
+    `dense_search_l2`, and every answer of the fast route carries a certificate (qstatus bit2 when it cannot be given, also
+    for a query with a non-finite value or one that rounds to a bf16 inf: such queries are repeated, then answered by
+    `dense_search_l2_exact`; `.stats` of the `PendingSearch`).  xsq, xnorm_max and everything else as `dense_search_l2`."""
+    return _dense_search_l2(_DENSE_L2_BF16X3, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)

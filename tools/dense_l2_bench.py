@@ -16,7 +16,13 @@ leg, no small query sets.
 
 --storage float16: the fp16 L2 index (csrc/dense_search_l2_f16.hip, FlatL2F16Index) beside the fp32 L2 index and the fp16
 inner-product index of the same process, the same alternating passes and small query sets, the fp16 L2 / fp32 L2 and fp16 L2 /
-fp16 IP time ratios of every pass, a sample of queries checked against the chain oracle on the widened values."""
+fp16 IP time ratios of every pass, a sample of queries checked against the chain oracle on the widened values.
+
+    python tools/dense_l2_bench.py --screen bf16x3 [--out profiles/dense_l2_bf16x3_bench.json] [--quick] [--l2-only]
+
+--screen bf16x3: the fp32 L2 index with the bf16x3 screen (csrc/dense_search_l2_bf16x3.hip, FlatL2Bf16x3Index) beside the fp32
+L2 index and the bf16x3 inner-product index over the same fp32 tensor, the same alternating passes and small query sets, the
+time ratios of every pass, a sample of queries checked against the chain oracle."""
 import argparse
 import json
 import os
@@ -191,8 +197,99 @@ def storage_f16(a, say, res):
             say(row)
 
 
+def screen_bf16x3(a, say, res):
+    """--screen bf16x3: the bf16x3 L2 index beside the fp32 L2 index and the bf16x3 inner-product index, all three over the one
+    fp32 tensor (and, for the two L2 indexes, the one tensor of squared norms), alternating passes; then 1 / 32 / 128 queries at
+    k = 100."""
+    import numpy as np
+    import torch
+    from repconc_amd import ops
+    from repconc_amd.dense_index import FlatIPIndex, FlatL2Bf16x3Index, FlatL2Index
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device=dev)
+    g.manual_seed(1234)
+    b3 = FlatL2Bf16x3Index(a.d, device=dev)
+    b3.reserve(a.n)
+    for r0 in range(0, a.n, 1 << 20):
+        b3.add(torch.randn((min(1 << 20, a.n - r0), a.d), generator=g, device=dev))
+    q = torch.randn((a.nq, a.d), generator=g, device=dev)
+    l2 = ip = None
+    if not a.l2_only:                                        # the same vectors and norms, not a second copy (measurement only)
+        l2 = FlatL2Index(a.d, device=dev)
+        l2._x, l2._xsq, l2.ntotal, l2._xnorm_max = b3._x, b3._xsq, b3.ntotal, b3._xnorm_max
+        ip = FlatIPIndex(a.d, device=dev, screen="bf16x3")
+        ip._x, ip.ntotal, ip._xnorm_max = b3._x, b3.ntotal, b3._xnorm_max
+    legs = [(n, ix) for n, ix in (("l2_bf16x3", b3), ("l2_f32", l2), ("ip_bf16x3", ip)) if ix is not None]
+    qn = q.cpu().numpy()
+    nb = -(-a.nq // a.batch)
+    ks = [1000] if a.quick else [int(v) for v in a.ks.split(",")]
+    passes = 1 if a.quick else a.passes
+    last = {}
+    for k in ks:
+        for _, index in legs:
+            index.search(qn[:a.batch], k)                    # warm-up
+        rows = []
+        for p in range(passes):
+            row = {"k": k, "pass": p, "batches": nb}
+            for name, index in legs:
+                t, sc, ids, retried, exact = timed_batches(index, qn, k, nb)
+                row.update({f"{name}_ms_per_batch": 1e3 * t / nb, f"{name}_queries_per_s": a.nq / t,
+                            f"{name}_retried_queries": retried, f"{name}_exact_queries": exact})
+                if name == "l2_bf16x3":
+                    last[k] = (sc, ids)
+            if len(legs) == 3:
+                row["l2_f32_over_l2_bf16x3_time"] = row["l2_f32_ms_per_batch"] / row["l2_bf16x3_ms_per_batch"]
+                row["l2_bf16x3_over_ip_bf16x3_time"] = row["l2_bf16x3_ms_per_batch"] / row["ip_bf16x3_ms_per_batch"]
+            rows.append(row)
+            say(row)
+        summary = {"k": k}
+        for name, _ in legs:
+            summary[f"{name}_ms_per_batch_median"] = float(np.median([r[f"{name}_ms_per_batch"] for r in rows]))
+            summary[f"{name}_queries_per_s_median"] = float(np.median([r[f"{name}_queries_per_s"] for r in rows]))
+            summary[f"{name}_retried_queries"] = sum(r[f"{name}_retried_queries"] for r in rows)
+            summary[f"{name}_exact_queries"] = sum(r[f"{name}_exact_queries"] for r in rows)
+        for key in ("l2_f32_over_l2_bf16x3_time", "l2_bf16x3_over_ip_bf16x3_time"):
+            if key in rows[0]:
+                v = [r[key] for r in rows]
+                summary.update({key + "_median": float(np.median(v)), key + "_min": min(v), key + "_max": max(v)})
+        say(summary)
+        res["runs"].append({"passes": rows, "summary": summary})
+    if a.verify:
+        from test_dense_l2 import oracle_topk_l2
+        k = ks[-1]
+        sel = np.linspace(0, a.nq - 1, a.verify).astype(int)
+        ws, wi = oracle_topk_l2(b3.xb, q[sel], k, qblock=16, rblock=1 << 20)
+        gs, gi = last[k][0][sel], last[k][1][sel]
+        res["verified_queries"] = int(len(sel))
+        res["verified_equal"] = bool(np.array_equal(gi, wi) and np.array_equal(gs.view(np.uint32), ws.view(np.uint32)))
+        say({"oracle_check_queries": int(len(sel)), "equal": res["verified_equal"]})
+    if not a.quick:
+        res["small"] = []
+        xsq = b3._xsq[: b3.ntotal]
+        for nq in [int(v) for v in a.small.split(",")]:
+            qq = q[:nq].contiguous()
+            row = {"nq": nq, "k": 100}
+            fns = {"l2_bf16x3": lambda: ops.dense_search_l2_bf16x3(b3.xb, qq, 100, xsq=xsq, xnorm_max=b3._xnorm_max)}
+            if l2 is not None:
+                fns["l2_f32"] = lambda: ops.dense_search_l2(b3.xb, qq, 100, xsq=xsq, xnorm_max=b3._xnorm_max)
+                fns["ip_bf16x3"] = lambda: ops.dense_search_bf16x3(b3.xb, qq, 100, xnorm_max=b3._xnorm_max)
+            for name, fn in fns.items():
+                for _ in range(2):
+                    fn()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(10):
+                    fn()
+                torch.cuda.synchronize()
+                row[name + "_ms"] = 1e3 * (time.perf_counter() - t0) / 10
+            res["small"].append(row)
+            say(row)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--screen", default="fp32", choices=["fp32", "bf16x3"],
+                    help="bf16x3: the bf16x3 L2 index beside the fp32 L2 index and the bf16x3 inner-product index (fp32 storage)")
     ap.add_argument("--storage", default="float32", choices=["float32", "float16"],
                     help="float16: the fp16 L2 index beside the fp32 L2 index and the fp16 inner-product index")
     ap.add_argument("--n", type=int, default=8841823)
@@ -220,9 +317,15 @@ def main():
     def say(row):
         print(json.dumps(row), flush=True)
 
-    if a.storage == "float16":
-        res["storage"] = "float16"
-        storage_f16(a, say, res)
+    if a.screen == "bf16x3" and a.storage != "float32":
+        ap.error("--screen bf16x3 needs --storage float32")
+    if a.storage == "float16" or a.screen == "bf16x3":
+        if a.screen == "bf16x3":
+            res["screen"] = "bf16x3"
+            screen_bf16x3(a, say, res)
+        else:
+            res["storage"] = "float16"
+            storage_f16(a, say, res)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             json.dump(res, open(a.out, "w"), indent=1)
