@@ -461,11 +461,53 @@ def mrr_at_k(ranked_ids: np.ndarray, positives, k: int = 10) -> float:
 
 
 # --------------------------------------------------------------------------- IVF extension
-def ivf_search(q, centroids, codes, list_ids, coarse, k, nprobe):
+def adc_lut_l2(q: np.ndarray, centroids: np.ndarray) -> np.ndarray:
+    """L2 look-up tables in the library's internal sign (include/repconc_hip.h "L2 metric"): S[nq,M,K] = float32(0) - T,
+    T[q,m,c] the fp32 chain acc = +0.0f, t = q[m dsub + j] - C[m][c][j], acc = acc + t * t for j ascending — numpy rounds
+    the subtraction, the product and the sum separately (no FMA).  Every entry is -x, +0.0f or -inf, never -0.0f."""
+    nq, D = q.shape
+    M, K, dsub = centroids.shape
+    qs = q.reshape(nq, M, dsub).astype(F32)
+    C = centroids.astype(F32)
+    T = np.zeros((nq, M, K), F32)
+    for j in range(dsub):
+        t = qs[:, :, None, j] - C[None, :, :, j]
+        T = T + t * t
+    return F32(0) - T
+
+
+def ivf_probe_l2(q, coarse, nprobe):
+    """[nq, nprobe] cells of smallest fp64 ||q - c_l||^2, nearest first, ties to the lower cell; also the fp64 distances
+    [nq, nlist]."""
+    d = ((q.astype(F64)[:, None, :] - coarse.astype(F64)[None, :, :]) ** 2).sum(2)
+    order = np.lexsort((np.broadcast_to(np.arange(d.shape[1]), d.shape), d), axis=1)[:, :nprobe]
+    return order, d
+
+
+def ivf_search(q, centroids, codes, list_ids, coarse, k, nprobe, metric=0):
     """Brute-force restatement of repconc_amd.ivf.IVFPQIndex.search (a build-side extension with no reference
     counterpart): probe the nprobe cells with the largest <q, coarse centroid> (ties: lower cell),
-    score the rows of those cells with the flat ADC arithmetic, top-k by (score desc, id asc); -1 / -inf padding."""
+    score the rows of those cells with the flat ADC arithmetic, top-k by (score desc, id asc); -1 / -inf padding.
+    metric=1 (METRIC_L2): probe the nprobe cells of smallest fp64 ||q - c_l||^2 (ties: lower cell), score the probed rows
+    with S = `adc_lut_l2` (m ascending, fp32), order by (distance asc, corpus id asc), return d = float32(0) - s with
+    +inf / -1 in the unfilled slots."""
     nq = q.shape[0]
+    if metric == 1:
+        order, _ = ivf_probe_l2(q, coarse, nprobe)
+        lut = adc_lut_l2(q, centroids)
+        out_d = np.full((nq, k), np.inf, F32)
+        out_i = np.full((nq, k), -1, np.int64)
+        for qi in range(nq):
+            rows = np.nonzero(np.isin(list_ids, order[qi]))[0]
+            if len(rows) == 0:
+                continue
+            s = adc_scores(lut[qi:qi + 1], codes[rows])[0]
+            o = np.lexsort((rows, -s.astype(F64)))[:k]
+            out_d[qi, :len(o)] = F32(0) - s[o]
+            out_i[qi, :len(o)] = rows[o]
+        return out_d, out_i
+    if metric != 0:
+        raise ValueError("metric must be 0 (inner product) or 1 (L2)")
     cs = q.astype(F32) @ coarse.astype(F32).T
     order = np.lexsort((np.broadcast_to(np.arange(cs.shape[1]), cs.shape), -cs.astype(F64)), axis=1)[:, :nprobe]
     lut = adc_lut(q, centroids)

@@ -254,11 +254,16 @@ class IVFPQIndex:
                      for i in range(0, nq, self.MAX_QUERY_BATCH)]
             return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
         nprobe = min(int(nprobe), self.nlist)
-        probes = self.probe(q, nprobe, ordered=False)
         if method not in ("auto", "lists", "lists8", "lists16", "lists_host_plan", "scan"):
             raise ValueError("method must be auto|lists|lists8|lists16|lists_host_plan|scan")
-        if method in ("lists", "lists8", "lists16", "lists_host_plan") and self.image is None:
+        if method in ("lists", "lists8", "lists16", "lists_host_plan") and not ops.adc_image_supported(self.M):
             raise _lib.RepconcHipError(f"the list-centric search needs M in (16, 32, 48, 64, 96), not {self.M}")
+        if nq == 0 or self.ntotal == 0:
+            # no query or no row: every slot is unfilled, whatever the method (an empty index has no image, and the
+            # per-query scan would size its workspace from the maximum of an empty tensor)
+            return (torch.full((nq, int(k)), float("-inf"), dtype=torch.float32, device=self.device),
+                    torch.full((nq, int(k)), -1, dtype=torch.int64, device=self.device))
+        probes = self.probe(q, nprobe, ordered=False)
         if method == "auto" and self.image is not None:
             # few probed rows per query: the per-query scan has less fixed work (task list, per-query byte tables)
             method = "lists" if self.ntotal * nprobe / max(self.nlist, 1) * self.M >= self.LISTS_MIN_BYTES else "scan"

@@ -209,6 +209,7 @@ class ReplicatedIVFPQIndex:
             same = index.device.index == d and not any(p is index for p in self.parts)
             self.parts.append(index if same else index.to(torch.device("cuda", d)))
         self.device, self.d, self.M, self.nlist = index.device, index.d, index.M, index.nlist
+        self.metric_type = index.metric_type              # as the flat multi-indexes: `sharded_search` merges by it
         self.nprobe = getattr(index, "nprobe", 8)         # Faiss's attribute: cells probed when search() is not told
         self.whole_query_set = True                       # batch_search: every query in one call (each replica takes its slice)
         self._pool = ThreadPoolExecutor(max_workers=len(self.parts))

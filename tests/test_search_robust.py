@@ -172,8 +172,14 @@ def test_ivf_search_never_raises_on_degenerate_cells(method):
         assert np.array_equal(s.cpu().numpy().view(np.uint32), ws.view(np.uint32))
 
 
-@pytest.mark.parametrize("M", [32, 48, 96])
-def test_ivf_pipelined_screen_on_cells_of_several_rounds(M):
+def _l2_probes_are_decided(q, coarse, nprobe):
+    """The L2 oracle probes by fp64, the library by fp32: the case must not hang on a near-tie of two cells (the rounding bound
+    of tests/test_ivf_l2.py)."""
+    from test_ivf_l2 import _assert_decisive
+    _assert_decisive(q, coarse, nprobe)
+
+
+def _several_rounds(M, metric):
     """Cells far larger than the 1920 rows (12 waves x 10 chunks x 16) a block screens per round (several rounds per task, ragged last chunk, first row
     of a cell in the middle of a chunk), cells smaller than one chunk, empty cells, fewer queries than a task holds and
     queries that keep every row: the list-centric search (persistent pipelined screen, survivor streams, bucket pass)
@@ -186,17 +192,30 @@ def test_ivf_pipelined_screen_on_cells_of_several_rounds(M):
     cells = rng.choice(nlist, N, p=[0.45, 0.3, 0.15, 0.05, 0.03, 0.0199, 0.0001, 0, 0, 0, 0, 0])   # 31 k-row cell ... 7 rows, empty
     C = synth.gaussian(4102 + M, (M, 256, 768 // M))
     coarse = synth.gaussian(4103 + M, (nlist, 768))
-    ivf = IVFPQIndex(768, M, nlist, device=DEV)
+    ivf = IVFPQIndex(768, M, nlist, device=DEV, metric=metric)
     ivf.set_centroids(_t(C))
     ivf.coarse = _t(coarse)
     ivf.set_lists(_t(codes), _t(cells))
     for nq, nprobe in ((3, 2), (19, 5), (70, nlist)):
         q = synth.gaussian(4104 + M + nq, (nq, 768))
-        ws, wi = pq_oracle.ivf_search(q, C, codes, cells, coarse, k, nprobe)
+        if metric == 1:
+            _l2_probes_are_decided(q, coarse, nprobe)
+        ws, wi = pq_oracle.ivf_search(q, C, codes, cells, coarse, k, nprobe, metric)
         for method in ("lists8", "lists16"):                 # both widths of the screen (round 6)
             s, i = ivf.search(_t(q), k, nprobe, method=method)
             assert np.array_equal(i.cpu().numpy(), wi), (M, nq, nprobe, method)
             assert np.array_equal(s.cpu().numpy().view(np.uint32), ws.view(np.uint32))
+
+
+@pytest.mark.parametrize("M", [32, 48, 96])
+def test_ivf_pipelined_screen_on_cells_of_several_rounds(M):
+    _several_rounds(M, 0)
+
+
+def test_ivf_pipelined_screen_on_cells_of_several_rounds_l2():
+    """The same cells under METRIC_L2 (tables of one sign, zeros at the top of the range), against the L2 oracle: nearest
+    cells by fp64, distances ascending, +inf / -1 past the probed rows."""
+    _several_rounds(48, 1)
 
 
 _EDGE_CELLS = (5, 0, 16, 17, 1919, 1920, 1921, 1, 3841, 15, 31, 4000, 0, 7)       # rows per cell, in cell order
@@ -206,13 +225,14 @@ _EDGE_WEIGHTS = (40.0, 32.0, 24.0)                                              
 
 
 @functools.lru_cache(maxsize=None)
-def _edge_case(M):
+def _edge_case(M, metric=0):
     """Index, queries and the oracle's three answers of test_ivf_screens_on_cell_and_task_edges, constructed rather than drawn: rows dealt to the cells
     so that set_lists yields exactly _EDGE_CELLS, coarse centroids = scaled orthonormal directions, a query = its three
     cells' directions (weights 40 / 32 / 24 over the centroid's scale: those are its coarse scores) + N(0, 0.25) noise, whose
     coarse scores stay below ~3.  The triples: every query takes the three cells with the most probes left (ties: lower
     cell), which meets any _EDGE_SHARE whose largest entry is at most a third of its sum.  Computed once per M and shared by
-    the two screen widths: nobody writes to it."""
+    the two screen widths: nobody writes to it.  metric = 1 (METRIC_L2): the coarse centroids all have norm 1, so that the
+    nearest cells are the cells of the largest inner product and the same triples come out; the answers are the L2 oracle's."""
     from oracle import pq_oracle
     sizes = np.array(_EDGE_CELLS)
     nlist, N = len(sizes), int(sizes.sum())
@@ -221,7 +241,7 @@ def _edge_case(M):
     codes = synth.uniform_codes(5201 + M, N, M)
     C = synth.gaussian(5202 + M, (M, 256, 768 // M))
     basis = np.linalg.qr(synth.gaussian(5203, (768, nlist)).astype(np.float64))[0].T           # [nlist, 768], orthonormal rows
-    scale = np.linspace(0.8, 1.25, nlist)
+    scale = np.linspace(0.8, 1.25, nlist) if metric == 0 else np.ones(nlist)
     coarse = (basis * scale[:, None]).astype(np.float32)
     left = np.array(_EDGE_SHARE)
     assert left.sum() % 3 == 0 and 3 * left.max() <= left.sum()
@@ -237,17 +257,18 @@ def _edge_case(M):
         q += (wgt / scale[triples[:, j]])[:, None] * basis[triples[:, j]]
     q = q.astype(np.float32)
     two = [0, int(np.nonzero(triples[:, 0] != triples[0, 0])[0][0])]               # two queries with different first cells
-    want = {"k4096": pq_oracle.ivf_search(q, C, codes, cells, coarse, 4096, 3),
-            "k10": pq_oracle.ivf_search(q, C, codes, cells, coarse, 10, 3),
-            "two": pq_oracle.ivf_search(q[two], C, codes, cells, coarse, 10, 1)}
+    if metric == 1:
+        _l2_probes_are_decided(q, coarse, 3)
+        _l2_probes_are_decided(q[two], coarse, 1)
+    want = {"k4096": pq_oracle.ivf_search(q, C, codes, cells, coarse, 4096, 3, metric),
+            "k10": pq_oracle.ivf_search(q, C, codes, cells, coarse, 10, 3, metric),
+            "two": pq_oracle.ivf_search(q[two], C, codes, cells, coarse, 10, 1, metric)}
     for a in (C, codes, cells, coarse, q, triples, *[x for w in want.values() for x in w]):
         a.setflags(write=False)
     return C, codes, cells, coarse, q, triples, two, want
 
 
-@pytest.mark.parametrize("method", ["lists8", "lists16"])
-@pytest.mark.parametrize("M", [16, 48, 96])
-def test_ivf_screens_on_cell_and_task_edges(M, method):
+def _cell_and_task_edges(M, method, metric):
     """What the two pipelined screens share (csrc/ivfs_common.h: the block's share of the tasks, a task's cell range, a wave's
     chunks of a round, the survivor stream), where an off-by-one would hide behind random cell sizes.  Cells of 5, 0, 16, 17,
     1919, 1920, 1921, 1, 3841, 15, 31, 4000, 0 and 7 rows: most start off a 16-row boundary, the lengths sit on either side of
@@ -259,15 +280,16 @@ def test_ivf_screens_on_cell_and_task_edges(M, method):
         the answer; and the list-centric pass itself must have answered those queries (the per-query scan that repairs a
         flagged query would hide a dropped row);
       * k = 10: the thresholded path, with queries probing the 3841-, 4000- and 1921-row cells (round boundaries);
-      * two queries, nprobe = 1: fewer tasks than XCDs, most blocks have none."""
+      * two queries, nprobe = 1: fewer tasks than XCDs, most blocks have none.
+    metric = 1 (METRIC_L2): the same construction with coarse centroids of one norm, distances and +inf for scores and -inf."""
     from repconc_amd.ivf import IVFPQIndex
 
     def dev(a):                                     # (the shared case is read-only: the device gets a copy)
         return _t(a.copy())
 
-    C, codes, cells, coarse, q, triples, two, want = _edge_case(M)
+    C, codes, cells, coarse, q, triples, two, want = _edge_case(M, metric)
     sizes, nlist = np.array(_EDGE_CELLS), len(_EDGE_CELLS)
-    ivf = IVFPQIndex(768, M, nlist, device=DEV)
+    ivf = IVFPQIndex(768, M, nlist, device=DEV, metric=metric)
     ivf.set_centroids(dev(C))
     ivf.coarse = dev(coarse)
     ivf.set_lists(dev(codes), dev(cells))
@@ -297,7 +319,7 @@ def test_ivf_screens_on_cell_and_task_edges(M, method):
     for j in np.nonzero(keep_all)[0]:                                                # (the oracle itself: exactly the probed rows)
         n = int(probed_rows[j])
         assert np.array_equal(np.sort(wi[j, :n]), np.nonzero(np.isin(cells, probes[j]))[0]) and (wi[j, n:] == -1).all()
-        assert np.isneginf(ws[j, n:]).all()
+        assert (np.isposinf if metric else np.isneginf)(ws[j, n:]).all()
     s, i = spy(dev(q), 4096, 3, method)
     _same(s, i, ws, wi)
     repaired = [x for kk, x in scanned if kk == 4096]
@@ -313,6 +335,18 @@ def test_ivf_screens_on_cell_and_task_edges(M, method):
     assert (wi[:, 0] >= 0).all() and (cells[wi[:, 0]] == triples[two, 0]).all()
     s, i = spy(dev(q[two]), 10, 1, method)
     _same(s, i, ws, wi)
+
+
+@pytest.mark.parametrize("method", ["lists8", "lists16"])
+@pytest.mark.parametrize("M", [16, 48, 96])
+def test_ivf_screens_on_cell_and_task_edges(M, method):
+    _cell_and_task_edges(M, method, 0)
+
+
+@pytest.mark.parametrize("method", ["lists8", "lists16"])
+@pytest.mark.parametrize("M", [16, 48, 96])
+def test_ivf_screens_on_cell_and_task_edges_l2(M, method):
+    _cell_and_task_edges(M, method, 1)
 
 
 def test_ivf_survivor_stream_overflow_is_answered_not_raised(monkeypatch):
