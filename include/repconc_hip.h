@@ -589,6 +589,34 @@ int rc_dense_l2_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx, int64_
                               const float* xsq, float* out, void* ws, size_t ws_bytes, rc_stream_t stream);
 void rc_dense_l2_bf16x3_error_constants(double* c);
 
+/* ------------------------------------------------------------------ dense stores: exact re-ranking of candidate lists
+ * The second stage of faiss.IndexRefineFlat: cand [nq, ldc] int64 holds kc candidate ids per query (from a PQ or IVF search),
+ * x [N, ldx] is the dense store (fp32; rc_dense_f16_rerank: fp16 bit patterns, x and q both), q [nq, D] the queries.  Only the
+ * candidates' rows are read: nq * kc rows instead of nq * N.
+ * metric: 0 = inner product, 1 = squared L2; anything else is RC_ESHAPE before any launch.
+ * Limits: 1 <= k <= 8192, 1 <= kc <= 16384, N < 2^32 (else RC_ESHAPE); any D >= 1, any row pitch ldx >= D, any ldc >= kc,
+ *   finite inputs, one device.  nq == 0 returns RC_OK and touches nothing; N == 0 pads every output slot.  Rows are staged with
+ *   16-byte loads when x is 16-byte aligned and the pitch is a multiple of 16 bytes, read element by element otherwise.
+ * Valid candidates: candidate c of query i is valid iff 0 <= c - id_offset < N.  Everything else is skipped silently: the -1
+ *   holes of an IVF search, ids outside the store.  A list is a multiset: an id given twice is scored twice and may appear
+ *   twice in the output.
+ * Score of a valid candidate: bit for bit what rc_dense_search_exact / rc_dense_l2_search_exact (rc_dense_f16_search_exact /
+ *   rc_dense_l2_f16_search_exact) produce for that (query, row): one fp32 accumulator from +0.0f, d ascending, over the values
+ *   widened to fp32; inner product s = fmaf(q[d], x[n][d], s); L2 t = q[d] - x[n][d], s = fmaf(t, t, s).
+ * Output scores / ids [nq, k]: the min(k, valid_i) best by the 64-bit key of the searches, then padding.  Inner product: score
+ *   descending, ties by the lower id, padding (-inf, -1).  L2: distance ascending, ties by the lower id, padding (+inf, -1);
+ *   a zero distance is +0.0f, an overflowed distance is +inf and sorts last, ahead of the padding.  Ids are emitted as given,
+ *   id_offset included.
+ * Runs on `stream`; no host synchronisation, no atomics on values, results bit-identical from run to run.
+ * ws: rc_dense_rerank_ws_bytes(nq, kc), a multiple of 256 (128 KiB of keys per query); 0 for nq <= 0 or kc outside [1, 16384]. */
+size_t rc_dense_rerank_ws_bytes(int nq, int kc);
+int rc_dense_rerank(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, const int64_t* cand,
+                    int64_t ldc, int kc, int k, int64_t id_offset, int metric, float* scores, int64_t* ids, void* ws,
+                    size_t ws_bytes, rc_stream_t stream);
+int rc_dense_f16_rerank(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                        const int64_t* cand, int64_t ldc, int kc, int k, int64_t id_offset, int metric, float* scores,
+                        int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream);
+
 /* ------------------------------------------------------------------ a-9 … a-11, stateful form
  * The index object the reference keeps inside Faiss (initialize_index / add_docs / index.search,
  * models/repconc/evaluate_repconc.py:78-98,182; JPQ's per-step synchronize_model_index, models/jpq/finetune_jpq.py:209-214),

@@ -141,7 +141,10 @@ PROTOTYPES = {
     "rc_dense_l2_bf16x3_scores_ws_bytes": (_sz, [_i, _i]),
     "rc_dense_l2_bf16x3_scores": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_l2_bf16x3_error_constants": (None, [C.POINTER(_d)]),
-    "rc_index_create": (_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
+    "rc_dense_rerank_ws_bytes": (_sz, [_i, _i]),
+    "rc_dense_rerank": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_f16_rerank": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
+    "rc_index_create":(_i, [_vp, _i, _i, _i, C.POINTER(_vp)]),
     "rc_index_destroy": (_i, [_vp]),
     "rc_index_set_centroids": (_i, [_vp, _vp, _vp]),
     "rc_index_reserve": (_i, [_vp, _i64, _vp]),

@@ -122,6 +122,32 @@ class _FlatIndex:
             return scores, ids
         return finish
 
+    def rerank(self, x, cand_ids, k: int):
+        """Exact re-ranking of candidate lists (`ops.dense_rerank`, the second stage of faiss.IndexRefineFlat): the `k` best of
+        the ids `cand_ids` [nq, kc] of every query by this index's own metric and storage, scored against the stored vectors
+        with the bits `search` gives them.  Ids outside [id_offset, id_offset + ntotal) — the -1 holes of an IVF search — are
+        skipped; what is missing after them is padded like `search` pads.  numpy in -> numpy out, tensors in -> tensors out."""
+        as_numpy = not isinstance(x, torch.Tensor)
+        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
+        c = cand_ids if isinstance(cand_ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cand_ids))
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"rerank: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
+        if c.dim() != 2 or c.shape[0] != q.shape[0] or c.dtype != torch.int64:
+            raise ValueError(f"rerank: expected int64 [{q.shape[0]}, kc] candidate ids, got {c.dtype} {tuple(c.shape)}")
+        k = int(k)
+        q = q.to(self.device, torch.float32, non_blocking=True)
+        c = c.to(self.device, non_blocking=True)
+        if self.ntotal == 0 or q.shape[0] == 0:
+            if not 1 <= k <= ops.DENSE_MAX_K:
+                raise ValueError(f"rerank: k must be in [1, {ops.DENSE_MAX_K}]")
+            scores = torch.full((q.shape[0], k), self.PAD, dtype=torch.float32, device=self.device)
+            ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
+        else:
+            scores, ids = ops.dense_rerank(self.xb, q, c, k, metric=self.metric_type, id_offset=self.id_offset)
+        if as_numpy:
+            return scores.cpu().numpy(), ids.cpu().numpy()
+        return scores, ids
+
 
 class FlatIPIndex(_FlatIndex):
     STORAGE = {"float32": torch.float32, "float16": torch.float16}

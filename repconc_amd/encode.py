@@ -18,10 +18,12 @@ from .index import PQIndex
 
 @torch.no_grad()
 def encode_corpus_to_index(model, batches: Iterable[Tuple[torch.Tensor, torch.Tensor]], id_offset: int = 0,
-                           index: Optional[PQIndex] = None) -> PQIndex:
+                           index: Optional[PQIndex] = None, refine=None) -> PQIndex:
     """`batches` yields (input_ids, attention_mask) on the model's device, in corpus order for this rank.
     Equivalent to `model(..., return_code=True)` + `add_docs` per batch (modeling_repconc.py:87-110 with
-    use_constraint=False; evaluate_repconc.py:69,89-98), minus the int64 -> uint8 -> numpy -> Faiss hops."""
+    use_constraint=False; evaluate_repconc.py:69,89-98), minus the int64 -> uint8 -> numpy -> Faiss hops.
+    refine: a flat index (`dense_index.FlatIPIndex`, ...) that also receives every batch's continuous embeddings — the
+    re-ranking vectors of a `RefineIndex`, in the same rotated space as the queries the model produces."""
     dev = model.centroids.device
     if index is None:
         index = PQIndex(model.config.hidden_size, model.config.MCQ_M, 8, device=dev)
@@ -30,4 +32,6 @@ def encode_corpus_to_index(model, batches: Iterable[Tuple[torch.Tensor, torch.Te
     for input_ids, attention_mask in batches:
         out = model(input_ids=input_ids, attention_mask=attention_mask)          # continuous (rotated) embeddings only
         index.add_codes(ops.assign_nearest(out.continuous_embeds, model.centroids, torch.uint8))
+        if refine is not None:
+            refine.add(out.continuous_embeds)
     return index

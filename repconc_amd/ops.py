@@ -1250,6 +1250,67 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
     return pending if defer else pending.result()
 
 
+DENSE_RERANK_MAX_KC = 16384         # candidates per query of dense_rerank (ADC_CAND_CAP, csrc/topk.h)
+
+
+def dense_rerank_ws_bytes(nq: int, kc: int) -> int:
+    """Workspace of one rc_dense_rerank / rc_dense_f16_rerank call: a multiple of 256; 0 for a shape outside the limits."""
+    return int(_lib.load().rc_dense_rerank_ws_bytes(int(nq), int(kc)))
+
+
+def dense_rerank(x: torch.Tensor, q: torch.Tensor, cand_ids: torch.Tensor, k: int, metric: int = METRIC_INNER_PRODUCT,
+                 id_offset: int = 0):
+    """Exact re-ranking of candidate lists (the second stage of faiss.IndexRefineFlat): `cand_ids` [nq, kc] int64 are scored
+    against their rows of the dense store `x` [N, D] and the `k` best per query returned as (scores [nq, k] fp32, ids [nq, k]
+    int64) — csrc/dense_rerank.hip.  x is fp32, or fp16 (then the queries are rounded to fp16 as `dense_search_f16` rounds
+    them).  A candidate c is valid iff 0 <= c - id_offset < N; everything else (the -1 holes of an IVF search, foreign ids) is
+    skipped, an id given twice is scored twice.  The score of a valid candidate is bit for bit the one `dense_search_exact` /
+    `dense_search_l2_exact` (or their f16 forms) give that (query, row).  METRIC_INNER_PRODUCT: score descending, ties by the
+    lower id, (-inf, -1) after the valid ones; METRIC_L2: squared distance ascending, ties by the lower id, (+inf, -1).
+    1 <= k <= 8192, 1 <= kc <= 16384, N < 2^32; argument errors are ValueError before any device work."""
+    l2 = _adc_metric(metric)
+    if x.dim() != 2 or q.dim() != 2 or x.shape[1] != q.shape[1] or x.shape[1] < 1:
+        raise ValueError("dense_rerank: x [N, D] and q [nq, D] with the same D >= 1")
+    if x.dtype not in (torch.float32, torch.float16):
+        raise ValueError("dense_rerank: the store must be float32 or float16")
+    if cand_ids.dim() != 2 or cand_ids.dtype != torch.int64:
+        raise ValueError("dense_rerank: cand_ids must be an int64 [nq, kc] matrix")
+    if cand_ids.shape[0] != q.shape[0]:
+        raise ValueError(f"dense_rerank: {cand_ids.shape[0]} candidate lists for {q.shape[0]} queries")
+    k, kc = int(k), int(cand_ids.shape[1])
+    if not 1 <= k <= DENSE_MAX_K:
+        raise ValueError(f"dense_rerank: k must be in [1, {DENSE_MAX_K}]")
+    if not 1 <= kc <= DENSE_RERANK_MAX_KC:
+        raise ValueError(f"dense_rerank: kc must be in [1, {DENSE_RERANK_MAX_KC}]")
+    if x.shape[0] >= 1 << 32:
+        raise ValueError("dense_rerank: N must be < 2^32")
+    _need_cuda(x, q, cand_ids)
+    f16 = x.dtype == torch.float16
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < x.shape[1]):
+        x = x.contiguous()
+    q = q.to(x.device).to(x.dtype).contiguous()             # fp16: round to nearest even, as the corpus was
+    cand_ids = cand_ids.to(x.device)
+    if cand_ids.stride(1) != 1 or cand_ids.stride(0) < kc:
+        cand_ids = cand_ids.contiguous()
+    N, D = x.shape
+    nq = q.shape[0]
+    scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
+    ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
+    if nq == 0:
+        return scores, ids
+    lib, h, s, _ = _ctx(q)
+    name = "rc_dense_f16_rerank" if f16 else "rc_dense_rerank"
+    ldx = x.stride(0) if N > 1 else D
+    for c0 in range(0, nq, DENSE_QCHUNK):
+        n = min(DENSE_QCHUNK, nq - c0)
+        wsb = lib.rc_dense_rerank_ws_bytes(n, kc)
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)         # released in stream order
+        _lib.check(getattr(lib, name)(h, _p(x), ldx, N, D, _p(q[c0:c0 + n]), n, _p(cand_ids[c0:c0 + n]), cand_ids.stride(0), kc,
+                                      k, int(id_offset), int(l2), _p(scores[c0:c0 + n]), _p(ids[c0:c0 + n]), _p(ws), wsb, s),
+                   name, h)
+    return scores, ids
+
+
 def dense_xnorm_max(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
     """Device fp32 scalar [1] >= the largest Euclidean row norm of the floating-point matrix `x` of any dtype (fp64 sums,
     rounded upwards; +inf if the norm exceeds fp32): the `xnorm_max` of `dense_search_bf16x3` and `dense_search_f16`.  No host
