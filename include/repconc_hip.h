@@ -731,6 +731,45 @@ int rc_ivf_search(rc_handle_t h, const uint8_t* codes, const int64_t* list_off, 
                   int nprobe, int64_t stride, int k, float* scores, int64_t* out_ids, int* status, void* ws,
                   size_t ws_bytes, rc_stream_t stream);
 
+/* ------------------------------------------------------------------ IVF over dense rows (csrc/ivf_flat.hip; faiss.IndexIVFFlat)
+ * The exact scan of the part of a dense store that a coarse quantiser selects.  x [N, ldx] holds the rows list-major (sorted by
+ * coarse cell; fp32, rc_ivf_flat_f16_search: fp16 bit patterns, x and q both), list_off [nlist + 1] int64 the first row of
+ * every cell, ids [N] int64 the corpus position of every row, q [nq, D] the queries, probes [nq, nprobe] int32 the probed
+ * cells of every query: distinct, in ascending order, as rc_ivf_select_probes writes them.
+ * metric: 0 = inner product, 1 = squared L2.
+ * Score of a (query, row) pair: bit for bit the chain of the flat dense searches (rc_dense_search_exact /
+ *   rc_dense_l2_search_exact and their f16 forms): one fp32 accumulator from +0.0f, d ascending, values widened to fp32; inner
+ *   product s = fmaf(q[d], x[n][d], s); L2 t = q[d] - x[n][d], s = fmaf(t, t, s).
+ * Output scores / ids [nq, k]: inner product: score descending; L2: distance ascending; ties by the lower CORPUS id (ids[row],
+ *   not the row); (-inf, -1) / (+inf, -1) when the probed cells hold fewer than k rows; a zero L2 distance is +0.0f, an
+ *   overflowed one +inf ahead of the padding.  Probing every cell gives exactly what the flat search gives over the same vectors.
+ * The scan is list-centric: the plan (cells, the queries of every cell, tasks of up to 8 queries of one cell) is made on the
+ *   device from `probes` and `list_off`, a cell's rows are read once per task, every pair's score goes to the query's dense
+ *   score row (stride floats per query, stride >= the largest number of rows nprobe cells can hold), then the exact k-th
+ *   largest score per query, the keys at or above it and the select of the other searches.  No sampling, no slack.
+ * status (one device int, zeroed by the caller) / qstatus [nq] (zeroed by the caller, may be NULL): bit 1 (value 2) = more than
+ *   16384 probed rows tie at the query's k-th score, its output is not valid (answer it by an exact search over its probed
+ *   rows); the other queries' results stand.  status bit 2 (value 4) = a caller's error the device found: a probe outside
+ *   [0, nlist) or more probed rows than `stride`; nothing is written out of bounds, the results are not valid.
+ * Limits: 1 <= k <= 8192, N < 2^32, nlist <= 16384, metric in {0, 1} (else RC_ESHAPE); any D >= 1, ldx >= D; probed rows per
+ *   query < 2^31; finite inputs; one device.  Rows are read with 16-byte loads when x is 16-byte aligned and D and ldx are
+ *   multiples of 16 bytes, element by element otherwise — the same arithmetic.  Null or non-positive arguments (nprobe >
+ *   nlist, ldx < D included) are RC_EINVAL; nq == 0 returns RC_OK and touches nothing.
+ * Runs on `stream`; no host synchronisation, no atomics on values, results bit-identical from run to run.
+ * ws: rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, stride), a multiple of 256 (8 bytes per probed row and 128 KiB of keys per
+ *   query, plus the plan); 0 for nq <= 0, nprobe <= 0, nprobe > nlist or stride <= 0.  RC_EWORKSPACE for a short one. */
+size_t rc_ivf_flat_search_ws_bytes(int nq, int nprobe, int nlist, int64_t stride);
+/* queries of one cell that share a task of the scan (8): what tests and tools need to hit the group boundary; no GPU involved */
+int rc_ivf_flat_query_group(void);
+int rc_ivf_flat_search(rc_handle_t h, const float* x, int64_t ldx, const int64_t* list_off, const int64_t* ids, int64_t N,
+                       int nlist, int D, const float* q, int nq, const int* probes, int nprobe, int64_t stride, int k,
+                       int metric, float* scores, int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                       rc_stream_t stream);
+int rc_ivf_flat_f16_search(rc_handle_t h, const uint16_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                           int64_t N, int nlist, int D, const uint16_t* q, int nq, const int* probes, int nprobe,
+                           int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status, int* qstatus,
+                           void* ws, size_t ws_bytes, rc_stream_t stream);
+
 /* ------------------------------------------------------------------ JPQ scoring head (csrc/jpq_head.hip)
  * Scores of (query, document id) pairs straight from the resident codes, and their gradients (stage 2 of the recipe,
  * models/jpq/finetune_jpq.py:176-189, without the decoded embeddings and without atomics on values).

@@ -104,6 +104,12 @@ PROTOTYPES = {
                                       _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rc_ivf_search_ws_bytes": (_sz, [_i, _i64]),
     "rc_ivf_search": (_i, [_vp, _vp, _vp, _vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i64, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rc_ivf_flat_search_ws_bytes": (_sz, [_i, _i, _i, _i64]),
+    "rc_ivf_flat_query_group": (_i, []),
+    "rc_ivf_flat_search": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                _sz, _vp]),
+    "rc_ivf_flat_f16_search": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp,
+                                    _vp, _sz, _vp]),
     "rc_adc_lut": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "rc_adc_lut_l2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "rc_adc_search_l2_q": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -4,6 +4,7 @@
 // ivfs_screen_kernel) and ivfs_screen16.h (16, ivfs_screen16_kernel), with what they share in ivfs_common.h; the caller
 // (IVFPQIndex.search) picks the width per call.  Split from adc_search.hip in round 4; shares adc_common.h with the flat search.
 #include "adc_common.h"
+#include "ivf_plan.h"
 #include <stdio.h>
 #include <string.h>
 #include <vector>
@@ -493,8 +494,7 @@ struct ivfp_ws {
 ivfp_ws ivfp_layout(size_t base, int nq, int nprobe, int nlist) {
     ivfp_ws P;
     const size_t pairs = (size_t)nq * nprobe;
-    size_t ub = (size_t)nlist + pairs / 8 + 1;                // tasks: at most one partly filled group per probed cell
-    if (ub > pairs) ub = pairs;
+    const size_t ub = ivf_plan_task_bound(nq, nprobe, nlist, 8);      // sized for the 8-query tasks: the 16-query form has fewer
     P.ub = (int64_t)ub;
     size_t o = base;
     auto take = [&](size_t n) { const size_t at = o; o += rc_align_up(n * sizeof(int), 256); return at; };
@@ -507,25 +507,7 @@ ivfp_ws ivfp_layout(size_t base, int nq, int nprobe, int nlist) {
 }
 }  // namespace
 
-// exclusive scan of one int per thread over a 256-thread block; returns the block total through `total`
-__device__ __forceinline__ int ivfp_block_scan256(int v, int* s_wave, int& total) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    int before = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) before += (j < wv) ? s_wave[j] : 0;
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-    return before + inc - v;
-}
-
+// (ivfp_block_scan256 and the cell / scatter / task kernels of the plan: ivf_plan.h, shared with ivf_flat.hip)
 // One block per query: sample layout of its probes, totals, threshold rank; counts the queries probing every cell.
 __global__ __launch_bounds__(256) void ivf_plan_query_kernel(const int64_t* __restrict__ list_off, const int* __restrict__ probes,
                                                              int nprobe, int ss, int k, double slack, int keep_all_rows,
@@ -574,61 +556,6 @@ __global__ __launch_bounds__(256) void ivf_plan_query_kernel(const int64_t* __re
         if (rk < 0.0) rk = 0.0;
         rank[qi] = (r <= keep_all_rows) ? 0 : (int)rk;
     }
-}
-
-// One block: exclusive prefix sums over the cells of (queries probing the cell) and of (tasks of the cell).
-__global__ __launch_bounds__(256) void ivf_plan_cells_kernel(const int* __restrict__ per_cell, int nlist,
-                                                             int* __restrict__ cell_start, int* __restrict__ first_task,
-                                                             int* __restrict__ ntasks, int tw) {
-    __shared__ int s_wave[4];
-    int cq = 0, ct = 0;
-    for (int b0 = 0; b0 < nlist; b0 += 256) {
-        const int c = b0 + (int)threadIdx.x;
-        const int n = c < nlist ? per_cell[c] : 0, t = (n + tw - 1) / tw;     // tw = queries per task (8 | 16)
-        int tq, tt;
-        const int eq = ivfp_block_scan256(n, s_wave, tq);
-        const int et = ivfp_block_scan256(t, s_wave, tt);
-        if (c < nlist) { cell_start[c] = cq + eq; first_task[c] = ct + et; }
-        cq += tq;
-        ct += tt;
-    }
-    if (threadIdx.x == 0) *ntasks = ct;
-}
-
-// (query, probe) pairs bucketed by cell; the order inside a cell is whatever the atomics give — it only decides which
-// queries share a task, never a result.
-__global__ __launch_bounds__(256) void ivf_plan_scatter_kernel(const int* __restrict__ probes, int64_t pairs, int nprobe,
-                                                               const int* __restrict__ cell_start, int* __restrict__ cursor,
-                                                               int* __restrict__ sorted_q) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= pairs) return;
-    const int c = probes[i];
-    sorted_q[cell_start[c] + atomicAdd(cursor + c, 1)] = (int)(i / nprobe);
-}
-
-// task t -> (cell, first entry in sorted_q, number of queries); tasks past the device-side count get 0 queries
-__global__ __launch_bounds__(256) void ivf_plan_tasks_kernel(const int* __restrict__ per_cell, const int* __restrict__ cell_start,
-                                                             const int* __restrict__ first_task, const int* __restrict__ ntasks,
-                                                             int nlist, int64_t ub, int* __restrict__ task_list,
-                                                             int* __restrict__ task_qstart, int* __restrict__ task_qcnt, int tw) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= ub) return;
-    int cell = 0, qs = 0, qc = 0;
-    if (t < *ntasks) {
-        int lo = 0, hi = nlist;                               // last cell with first_task <= t (the non-empty one of a plateau)
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (first_task[mid] <= (int)t) lo = mid; else hi = mid;
-        }
-        cell = lo;
-        const int within = (int)t - first_task[cell];
-        qs = cell_start[cell] + tw * within;
-        qc = per_cell[cell] - tw * within;
-        qc = qc > tw ? tw : qc;
-    }
-    task_list[t] = cell;
-    task_qstart[t] = qs;
-    task_qcnt[t] = qc;
 }
 
 // Probe selection: the nprobe cells with the largest coarse score of every query (ties at the boundary: lower cell id),
@@ -764,7 +691,7 @@ static int ivf_search_probes_w(rc_handle_t h, const uint8_t* codes, const uint8_
     hipLaunchKernelGGL(ivf_plan_cells_kernel, dim3(1), dim3(256), 0, s, (const int*)I(P.per_cell), nlist, I(P.cell_start),
                        I(P.first_task), I(P.ntasks), width);
     RC_LAUNCH_CHECK(h);
-    hipLaunchKernelGGL(ivf_plan_scatter_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, probes, pairs, nprobe,
+    hipLaunchKernelGGL(ivf_plan_scatter_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, s, probes, pairs, nprobe, nlist,
                        (const int*)I(P.cell_start), I(P.cursor), I(P.sorted_q));
     RC_LAUNCH_CHECK(h);
     hipLaunchKernelGGL(ivf_plan_tasks_kernel, dim3((unsigned)((P.ub + 255) / 256)), dim3(256), 0, s, (const int*)I(P.per_cell),

@@ -64,6 +64,11 @@ class EvalArguments(TrainingArguments):
     index_metric: str = field(default="ip", metadata={"help": "ip: inner product; l2: squared Euclidean distance, smallest first "
                                                               "(run.tsv then holds the scores -d)",
                                                       "choices": list(INDEX_METRICS)})
+    index_nlist: int = field(default=0, metadata={"help": "0: the flat index (every row is scored); > 0: an exact IVF index of that "
+                                                          "many cells (IVFFlatIndex: only the rows of the probed cells are scored; "
+                                                          "not with index_screen bf16x3)"})
+    index_nprobe: int = field(default=8, metadata={"help": "cells probed per query when index_nlist > 0 (they should hold at "
+                                                           "least topk rows)"})
     remove_unused_columns: Optional[bool] = field(default=False)
 
 
@@ -111,7 +116,8 @@ def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_id
     the scores written are -d, exactly: run.tsv and trec_eval rank by descending score."""
     metric = getattr(eval_args, "index_metric", "ip")
     index = create_index(corpus_embeds, use_float16=getattr(eval_args, "index_float16", False),
-                         screen=getattr(eval_args, "index_screen", "fp32"), metric=metric)
+                         screen=getattr(eval_args, "index_screen", "fp32"), metric=metric,
+                         nlist=getattr(eval_args, "index_nlist", 0), nprobe=getattr(eval_args, "index_nprobe", 8))
     all_topk_scores, all_topk_ids = batch_dense_search(query_ids, query_embeds, corpus_ids, index, eval_args.topk,
                                                        batch_size=eval_args.search_batch)
     if metric == "l2":
@@ -131,7 +137,8 @@ def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_id
 def main(argv=None):
     parser = HfArgumentParser((ModelArguments, DataArguments, EvalArguments))
     model_args, data_args, eval_args = parser.parse_args_into_dataclasses(argv)
-    check_index_options(eval_args.index_metric, eval_args.index_float16, eval_args.index_screen)            # before encoding
+    check_index_options(eval_args.index_metric, eval_args.index_float16, eval_args.index_screen,
+                        eval_args.index_nlist)                                                              # before encoding
     main_process = is_main_process(eval_args.local_rank)
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s -   %(message)s", datefmt="%m/%d/%Y %H:%M:%S",
                         level=logging.INFO if main_process else logging.WARN)

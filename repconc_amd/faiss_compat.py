@@ -11,6 +11,9 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
                                                                         useFloat16: FlatIPIndex(d, storage="float16"))
     faiss.IndexFlatL2(d)                                                evaluate_repconc.py:102, run_warmup.py:102,107 (exact
                                                                         fp32 squared distances, dense_index.FlatL2Index)
+    faiss.IndexIVFFlat(quantizer, d, nlist[, metric])                   not in the reference; what a Faiss user expects beside
+                                                                        IndexFlat* and IndexIVFPQ (exact scan of the probed cells,
+                                                                        ivf_flat.IVFFlatIndex)
     faiss.write_index(index, path) / faiss.read_index(path)             run_warmup.py:187, run_repconc_eval.py:42
     faiss.omp_set_num_threads(n)                                        run_repconc_eval.py:149 (no-op: the scan runs on the GPU)
 
@@ -25,6 +28,7 @@ import torch
 from .dense_index import FlatIPIndex, FlatL2Index
 from .faiss_io import read_index, write_index  # noqa: F401  (re-exported)
 from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex  # noqa: F401  (METRIC_L2 re-exported)
+from .ivf_flat import IVFFlatIndex
 
 
 def IndexPQ(d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT) -> PQIndex:
@@ -33,6 +37,28 @@ def IndexPQ(d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT) -> PQIn
 
 IndexFlatIP = FlatIPIndex      # faiss.IndexFlatIP(d): exact inner product over fp32 vectors resident on the device
 IndexFlatL2 = FlatL2Index      # faiss.IndexFlatL2(d): exact squared Euclidean distance over the same storage
+
+
+class IndexIVFFlat(IVFFlatIndex):
+    """faiss.IndexIVFFlat(quantizer, d, nlist, metric=METRIC_L2): `IVFFlatIndex` with Faiss's argument order and default
+    metric.  `quantizer` is a flat index (IndexFlatL2 / IndexFlatIP) or None: one that already holds `nlist` vectors provides the
+    coarse centroids and the index is trained; otherwise `train` fits them and, as Faiss does, adds them to an empty quantizer.
+    The index lives on the quantizer's device."""
+
+    def __init__(self, quantizer, d: int, nlist: int, metric=METRIC_L2):
+        if quantizer is not None and getattr(quantizer, "d", d) != d:
+            raise ValueError(f"IndexIVFFlat: the quantizer holds vectors of width {quantizer.d}, the index {d}")
+        super().__init__(d, nlist, device=getattr(quantizer, "device", None), metric=metric)
+        self.quantizer = quantizer
+        if quantizer is not None and getattr(quantizer, "ntotal", 0) == self.nlist:
+            self.set_coarse(quantizer.xb.float())
+
+    def train(self, x, iters: int = 10, seed: int = 1234) -> None:
+        if self.is_trained:                             # Faiss: training a trained index is a no-op
+            return
+        super().train(x, iters, seed)
+        if self.quantizer is not None and getattr(self.quantizer, "ntotal", None) == 0 and hasattr(self.quantizer, "add"):
+            self.quantizer.add(self.coarse)
 
 
 def copy_array_to_vector(array, vector: torch.Tensor) -> None:

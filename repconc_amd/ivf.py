@@ -90,7 +90,44 @@ def coarse_assign(x: torch.Tensor, cent: torch.Tensor, chunk: int = 1 << 20, as_
     return out if as_int32 else out.to(torch.int64)
 
 
-class IVFPQIndex:
+class CoarseProbe:
+    """What the IVF indexes share on the query side (`IVFPQIndex` here, `ivf_flat.IVFFlatIndex`): the probe rule over the
+    coarse table.  The owner has `coarse` [nlist, d], `nlist`, `metric_type` and `_coarse_sq = (None, None, None)`."""
+
+    def _coarse_sqnorms(self) -> torch.Tensor:
+        """||c_l||^2 [nlist] fp32, kept with the coarse table it was made from (`coarse` is a plain attribute: a new tensor or an
+        in-place write makes it anew)."""
+        c = self.coarse
+        held, version, sq = self._coarse_sq
+        if held is not c or version != c._version:
+            sq = (c.float() * c.float()).sum(1)
+            self._coarse_sq = (c, c._version, sq)
+        return sq
+
+    def probe(self, q: torch.Tensor, nprobe: int, ordered: bool = True) -> torch.Tensor:
+        """[nq, nprobe] int32: the nprobe cells with the largest <q, centroid> (ties at the boundary: lower cell id) — under
+        METRIC_L2 the largest 2 <q, c_l> - ||c_l||^2, i.e. the nearest cells (||q||^2 is the same for every cell), same tie rule.
+        ordered=True ranks them by decreasing score (ties: lower cell id); ordered=False — what the searches use — returns
+        the same set in ascending cell order from one HIP kernel (rc_ivf_select_probes) after the library GEMM."""
+        s = q.float() @ self.coarse.T
+        if self.metric_type == METRIC_L2:
+            s = 2.0 * s - self._coarse_sqnorms()[None, :]
+        if not ordered and self.nlist <= 16384 and q.shape[0] > 0:
+            s = s.contiguous()
+            out = torch.empty((q.shape[0], nprobe), dtype=torch.int32, device=s.device)
+            lib, h, st, _ = ops._ctx(s)
+            _lib.check(lib.rc_ivf_select_probes(h, C.c_void_p(s.data_ptr()), s.shape[0], self.nlist, int(nprobe),
+                                                C.c_void_p(out.data_ptr()), st), "rc_ivf_select_probes", h)
+            return out
+        # a stable sort of the whole row.  A torch.topk shortcut selects by the bits (-0.0 below +0.0) and promises nothing
+        # about WHICH of several equal scores it returns, so it does not keep "ties at the boundary: lower cell id"
+        # (tests/test_ivf_build.py).  The searches use the kernel above (nlist <= 16384); this path is the readable statement of
+        # the rule and the kernel's cross-check.
+        order = torch.argsort(s, dim=1, descending=True, stable=True)[:, :nprobe]
+        return order.to(torch.int32).contiguous()
+
+
+class IVFPQIndex(CoarseProbe):
     def __init__(self, d: int, M: int, nlist: int, device: Optional[torch.device] = None, metric=METRIC_INNER_PRODUCT):
         if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
             raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
@@ -187,39 +224,7 @@ class IVFPQIndex:
             out.coarse = None if out.coarse is None else out.coarse.clone()
         return out
 
-    # ---- search
-    def _coarse_sqnorms(self) -> torch.Tensor:
-        """||c_l||^2 [nlist] fp32, kept with the coarse table it was made from (`coarse` is a plain attribute: a new tensor or an
-        in-place write makes it anew)."""
-        c = self.coarse
-        held, version, sq = self._coarse_sq
-        if held is not c or version != c._version:
-            sq = (c.float() * c.float()).sum(1)
-            self._coarse_sq = (c, c._version, sq)
-        return sq
-
-    def probe(self, q: torch.Tensor, nprobe: int, ordered: bool = True) -> torch.Tensor:
-        """[nq, nprobe] int32: the nprobe cells with the largest <q, centroid> (ties at the boundary: lower cell id) — under
-        METRIC_L2 the largest 2 <q, c_l> - ||c_l||^2, i.e. the nearest cells (||q||^2 is the same for every cell), same tie rule.
-        ordered=True ranks them by decreasing score (ties: lower cell id); ordered=False — what the searches use — returns
-        the same set in ascending cell order from one HIP kernel (rc_ivf_select_probes) after the library GEMM."""
-        s = q.float() @ self.coarse.T
-        if self.metric_type == METRIC_L2:
-            s = 2.0 * s - self._coarse_sqnorms()[None, :]
-        if not ordered and self.nlist <= 16384 and q.shape[0] > 0:
-            s = s.contiguous()
-            out = torch.empty((q.shape[0], nprobe), dtype=torch.int32, device=s.device)
-            lib, h, st, _ = ops._ctx(s)
-            _lib.check(lib.rc_ivf_select_probes(h, C.c_void_p(s.data_ptr()), s.shape[0], self.nlist, int(nprobe),
-                                                C.c_void_p(out.data_ptr()), st), "rc_ivf_select_probes", h)
-            return out
-        # a stable sort of the whole row.  A torch.topk shortcut selects by the bits (-0.0 below +0.0) and promises nothing
-        # about WHICH of several equal scores it returns, so it does not keep "ties at the boundary: lower cell id"
-        # (tests/test_ivf_build.py).  The searches use the kernel above (nlist <= 16384); this path is the readable statement of
-        # the rule and the kernel's cross-check.
-        order = torch.argsort(s, dim=1, descending=True, stable=True)[:, :nprobe]
-        return order.to(torch.int32).contiguous()
-
+    # ---- search (probe, _coarse_sqnorms: CoarseProbe)
     def search(self, x, k: int, nprobe: Optional[int] = None, method: str = "auto"):
         """nprobe: cells probed per query (default: the index's `nprobe` attribute, as with a Faiss IVF index).
         method: "lists" = list-centric 8-bit screen (rc_ivf_search_probes_q / _q16: the queries probing a cell share its read,

@@ -1,0 +1,256 @@
+"""Exact IVF index over dense vectors: the GPU `faiss.IndexIVFFlat`, between the flat indexes of `dense_index` (every row, exactly)
+and `IVFPQIndex` (the probed cells, lossy codes).  A query is scored exactly against the rows of its `nprobe` best cells only.
+The semantics are fixed here, as `ivf.py` fixes them for the PQ index:
+
+  * store: the rows are kept list-major — `xb` [N, d] sorted by coarse cell (fp32, or fp16 with `storage="float16"`),
+    `list_off` [nlist + 1], `ids` [N] corpus positions, ascending inside a cell (stable sort).  A document goes to its L2-nearest
+    coarse centroid (`coarse_assign`, first minimum) under either metric, the rule of `IVFPQIndex`;
+  * probing: `IVFPQIndex.probe`'s rule (`ivf.CoarseProbe`): the `nprobe` cells with the largest <q, c> (METRIC_L2: the largest
+    2 <q, c> - ||c||^2), ties at the boundary to the lower cell id, `nprobe` clipped to `nlist`;
+  * score: the chain of the flat searches, bit for bit — one fp32 accumulator from +0.0f, d ascending, values widened to fp32,
+    s = fmaf(q_d, x_d, s), or t = q_d - x_d, s = fmaf(t, t, s) for L2.  float16 storage rounds rows and queries to fp16 first, as
+    `FlatIPIndex(storage="float16")` / `FlatL2F16Index` do, and `add` refuses magnitudes >= 65520;
+  * result [nq, k]: inner product: score descending; L2: distance ascending; ties go to the lower CORPUS id; -inf / +inf and -1
+    when the probed cells hold fewer than k rows.  Probing every cell returns exactly what the flat index over the same vectors
+    returns: ids and score bits.
+
+`search` runs `ops.ivf_flat_search` (csrc/ivf_flat.hip: a list-centric scan, then an exact k-th-score selection — no sampling,
+no slack) in chunks of queries whose workspace stays under `MAX_WS_BYTES`.  The one query that route cannot answer is one with
+more than 16384 probed rows tied at its k-th score (status bit 1): those queries alone are answered by `_search_exact_probed`,
+the exact dense search over their probed rows gathered in corpus-id order (the mirror of `IVFPQIndex._search_exact_probed`).
+
+`add` may be called repeatedly; ids continue from `ntotal`.  Every `add` rebuilds the list-major store from the rows held and the
+new ones: while it runs, a second copy of the whole store exists on the device.
+"""
+from __future__ import annotations
+
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import ops
+from .index import METRIC_INNER_PRODUCT, METRIC_L2
+from .ivf import CoarseProbe, coarse_assign, coarse_kmeans
+
+
+class IVFFlatIndex(CoarseProbe):
+    STORAGE = {"float32": torch.float32, "float16": torch.float16}
+    MAX_NLIST = ops.IVF_FLAT_MAX_NLIST
+    MAX_WS_BYTES = 4 << 30            # workspace of one library call: a search is cut into chunks of queries that stay below it
+
+    def __init__(self, d: int, nlist: int, device: Optional[torch.device] = None, metric=METRIC_INNER_PRODUCT,
+                 storage: str = "float32"):
+        if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
+            raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
+        if storage not in self.STORAGE:
+            raise ValueError(f"storage must be one of {sorted(self.STORAGE)}, got {storage!r}")
+        if int(d) < 1 or not 1 <= int(nlist) <= self.MAX_NLIST:
+            raise ValueError(f"d must be >= 1 and nlist in [1, {self.MAX_NLIST}]")
+        self.metric_type = metric
+        self.storage = storage
+        self._dtype = self.STORAGE[storage]
+        self._coarse_sq = (None, None, None)                                # CoarseProbe: (coarse, its version, ||c_l||^2)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.d, self.nlist = int(d), int(nlist)
+        self.coarse = None                                                  # [nlist, d] fp32
+        self.nprobe = 8                                                     # Faiss's attribute: cells probed when search() is not told
+        self.last_search_stats = {"queries": 0, "fallback_queries": 0, "chunks": 0}
+        self.reset()
+
+    # ---- build
+    @property
+    def is_trained(self) -> bool:
+        return self.coarse is not None
+
+    def reset(self) -> None:
+        """Empties the index; the coarse centroids stay."""
+        self.xb = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
+        self.ids = torch.empty((0,), dtype=torch.int64, device=self.device)
+        self.list_off = torch.zeros((self.nlist + 1,), dtype=torch.int64, device=self.device)
+        self.ntotal = 0
+        self._sizes_desc = np.zeros(0, np.int64)      # cell sizes, descending (host copy): bounds a query's score row
+
+    def _rows(self, x, what: str) -> torch.Tensor:
+        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        if xt.dim() != 2 or xt.shape[1] != self.d:
+            raise ValueError(f"{what}: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
+        return xt
+
+    def train(self, x, iters: int = 10, seed: int = 1234) -> None:
+        """Fits the `nlist` coarse centroids by `coarse_kmeans` on x [n >= nlist, d]."""
+        xt = self._rows(x, "train")
+        if xt.shape[0] < self.nlist:
+            raise ValueError(f"train: {xt.shape[0]} vectors for {self.nlist} cells")
+        self.coarse = coarse_kmeans(xt.to(self.device, torch.float32), self.nlist, iters, seed)
+
+    def set_coarse(self, centroids) -> None:
+        """Installs given coarse centroids [nlist, d]."""
+        c = centroids.detach() if isinstance(centroids, torch.Tensor) else torch.from_numpy(np.asarray(centroids, dtype=np.float32))
+        if c.dim() != 2 or tuple(c.shape) != (self.nlist, self.d):
+            raise ValueError(f"set_coarse: expected [{self.nlist}, {self.d}] centroids, got {tuple(c.shape)}")
+        self.coarse = c.to(self.device, torch.float32).contiguous().clone()
+
+    def _stored(self, xt: torch.Tensor) -> torch.Tensor:
+        """The rows of an `add` in the storage type, checked before anything is stored; one host read."""
+        xs = xt.to(self.device).to(self._dtype)
+        if xs.shape[0] and not bool(torch.isfinite(xs).all()):
+            raise ValueError("add: finite values only" if self.storage == "float32" else
+                             "add: float16 storage needs finite values of magnitude < 65520 (fp16 rounds the rest to inf)")
+        return xs
+
+    def _corpus_order(self) -> tuple:
+        """(rows [ntotal, d] in corpus order, their cells [ntotal]) from the list-major store."""
+        x = torch.empty_like(self.xb)
+        x[self.ids] = self.xb
+        sizes = self.list_off[1:] - self.list_off[:-1]
+        cells = torch.empty((self.ntotal,), dtype=torch.int64, device=self.device)
+        cells[self.ids] = torch.repeat_interleave(torch.arange(self.nlist, device=self.device), sizes)
+        return x, cells
+
+    def _store(self, xs: torch.Tensor, cells: torch.Tensor) -> None:
+        """xs [N, d] in the storage type and corpus order, cells [N] int64 in [0, nlist): the list-major store (stable sort)."""
+        if xs.shape[0] >= 1 << 32:
+            raise ValueError("the index holds fewer than 2^32 rows")
+        order = torch.argsort(cells, stable=True)
+        self.xb = xs[order].contiguous()
+        self.ids = order.to(torch.int64).contiguous()
+        cnt = torch.bincount(cells, minlength=self.nlist)
+        self.list_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(cnt, 0)]).contiguous()
+        self.ntotal = int(xs.shape[0])
+        self._sizes_desc = np.sort(cnt.cpu().numpy())[::-1].astype(np.int64)
+
+    def set_lists(self, x, list_ids) -> None:
+        """Replaces the content by the rows x [N, d] (corpus order: row i has id i) stored under the given cells list_ids [N]."""
+        xt = self._rows(x, "set_lists")
+        li = list_ids if isinstance(list_ids, torch.Tensor) else torch.from_numpy(np.asarray(list_ids))
+        if li.dim() != 1 or li.shape[0] != xt.shape[0] or li.dtype.is_floating_point:
+            raise ValueError(f"set_lists: expected {xt.shape[0]} integer cells, got {li.dtype} {tuple(li.shape)}")
+        if li.numel() and (int(li.min()) < 0 or int(li.max()) >= self.nlist):
+            raise ValueError(f"set_lists: cells must lie in [0, {self.nlist})")
+        self._store(self._stored(xt), li.to(self.device, torch.int64))
+
+    def add(self, x) -> None:
+        """Appends x [n, d]: ids ntotal .. ntotal + n - 1, every row under its L2-nearest coarse centroid (of the values given,
+        before any rounding to the storage type).  Rebuilds the list-major store: a transient second copy of it exists meanwhile."""
+        if self.coarse is None:
+            raise ValueError("add: train() or set_coarse() the coarse quantiser first")
+        xt = self._rows(x, "add")
+        if xt.shape[0] == 0:
+            return
+        xs = self._stored(xt)
+        cells = coarse_assign(xt.to(self.device, torch.float32), self.coarse)
+        if self.ntotal:
+            old_x, old_cells = self._corpus_order()
+            xs, cells = torch.cat([old_x, xs], 0), torch.cat([old_cells, cells], 0)
+        self._store(xs, cells)
+
+    # ---- search
+    def _queries(self, x, k: int):
+        as_numpy = not isinstance(x, torch.Tensor)
+        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
+        if not 1 <= int(k) <= ops.DENSE_MAX_K:
+            raise ValueError(f"search: k must be in [1, {ops.DENSE_MAX_K}]")
+        return q, as_numpy
+
+    def _padding(self, nq: int, k: int):
+        pad = float("inf") if self.metric_type == METRIC_L2 else float("-inf")
+        return (torch.full((nq, k), pad, dtype=torch.float32, device=self.device),
+                torch.full((nq, k), -1, dtype=torch.int64, device=self.device))
+
+    def search(self, x, k: int, nprobe: Optional[int] = None):
+        """(scores or distances [nq, k], ids [nq, k]) over the `nprobe` best cells of every query (default: the index's `nprobe`
+        attribute, as with a Faiss IVF index).  numpy in -> numpy out, tensors in -> tensors out."""
+        q, as_numpy = self._queries(x, k)
+        if self.coarse is None:
+            raise ValueError("search: train() or set_coarse() the coarse quantiser first")
+        nprobe = min(max(int(self.nprobe if nprobe is None else nprobe), 1), self.nlist)
+        return self._answer(q, lambda qd: self.probe(qd, nprobe, ordered=False), int(k), as_numpy)
+
+    def _answer(self, q: torch.Tensor, probes_of, k: int, as_numpy: bool):
+        """The common end of `search` and `_search_probes`: the queries on the device, all padding without a launch for an empty
+        index or no query, `_run` on probes_of(queries on the device) otherwise, numpy out for numpy in."""
+        q = q.to(self.device, torch.float32).contiguous()
+        if q.shape[0] == 0 or self.ntotal == 0:
+            self.last_search_stats = {"queries": int(q.shape[0]), "fallback_queries": 0, "chunks": 0}
+            scores, ids = self._padding(q.shape[0], k)
+        else:
+            scores, ids = self._run(q, probes_of(q), k)
+        return (scores.cpu().numpy(), ids.cpu().numpy()) if as_numpy else (scores, ids)
+
+    def _search_probes(self, x, probes, k: int):
+        """`search` with explicit probes [nq, nprobe] (distinct cells of [0, nlist) per query, any order)."""
+        q, as_numpy = self._queries(x, k)
+        pr = probes if isinstance(probes, torch.Tensor) else torch.from_numpy(np.asarray(probes))
+        if pr.dim() != 2 or pr.shape[0] != q.shape[0] or not 1 <= pr.shape[1] <= self.nlist or pr.dtype.is_floating_point:
+            raise ValueError(f"_search_probes: expected integer probes [{q.shape[0]}, 1 .. {self.nlist}], got {tuple(pr.shape)}")
+        pr = torch.sort(pr.to(torch.int32), dim=1).values
+        if pr.numel() and (int(pr.min()) < 0 or int(pr.max()) >= self.nlist or bool((pr[:, 1:] == pr[:, :-1]).any())):
+            raise ValueError(f"_search_probes: a query's probes must be distinct cells of [0, {self.nlist})")
+        return self._answer(q, lambda qd: pr.to(self.device).contiguous(), int(k), as_numpy)
+
+    def _chunk_queries(self, nq: int, nprobe: int, stride: int) -> int:
+        """The most queries (>= 1) whose workspace stays under MAX_WS_BYTES."""
+        if ops.ivf_flat_search_ws_bytes(nq, nprobe, self.nlist, stride) <= self.MAX_WS_BYTES:
+            return nq
+        lo, hi = 1, nq                                  # ws(lo) fits (or lo == 1), ws(hi) does not
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if ops.ivf_flat_search_ws_bytes(mid, nprobe, self.nlist, stride) <= self.MAX_WS_BYTES:
+                lo = mid
+            else:
+                hi = mid
+        return lo
+
+    def _run(self, q: torch.Tensor, probes: torch.Tensor, k: int):
+        """q [nq, d] fp32 on the device, probes [nq, nprobe] int32 ascending per query; nq > 0, ntotal > 0."""
+        nq, nprobe = probes.shape
+        stride = (max(4, int(self._sizes_desc[:nprobe].sum())) + 3) // 4 * 4      # the nprobe largest cells bound a score row
+        step = self._chunk_queries(nq, nprobe, stride)
+        parts, fallback, chunks = [], 0, 0
+        for c0 in range(0, nq, step):
+            qc, pc = q[c0:c0 + step], probes[c0:c0 + step]
+            scores, ids, status, qstatus = ops.ivf_flat_search(self.xb, self.list_off, self.ids, qc, pc, stride, k,
+                                                               metric=self.metric_type)
+            chunks += 1
+            st = int(status.item())
+            if st & 4:
+                raise RuntimeError("ivf_flat_search: a probe outside the index or a score row too short (status bit 2)")
+            if st & 2:
+                # more than 16384 probed rows tie at these queries' k-th score: the exact dense search over their probed rows
+                bad = torch.nonzero(qstatus & 2).flatten()
+                scores[bad], ids[bad] = self._search_exact_probed(qc[bad], pc[bad], k)
+                fallback += int(bad.numel())
+            parts.append((scores, ids))
+        self.last_search_stats = {"queries": int(nq), "fallback_queries": fallback, "chunks": chunks}
+        if len(parts) == 1:
+            return parts[0]
+        return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+
+    def _search_exact_probed(self, q: torch.Tensor, probes: torch.Tensor, k: int):
+        """The answer for ANY content of the probed cells, query by query: the probed rows gathered in corpus-id order (the
+        search's tie rule becomes the exact entry's "lower row"), then the exact route of the flat search of this metric and
+        storage.  Slow — one gather of the probed rows per query — and only reached for queries the selection could not decide."""
+        exact = {(METRIC_INNER_PRODUCT, "float32"): ops.dense_search_exact, (METRIC_INNER_PRODUCT, "float16"): ops.dense_search_f16_exact,
+                 (METRIC_L2, "float32"): ops.dense_search_l2_exact, (METRIC_L2, "float16"): ops.dense_search_l2_f16_exact}
+        exact = exact[(self.metric_type, self.storage)]
+        scores, ids = self._padding(q.shape[0], k)
+        off = self.list_off
+        for j in range(q.shape[0]):
+            cells = probes[j].long()
+            a, b = off[cells].tolist(), off[cells + 1].tolist()
+            rows = torch.cat([torch.arange(lo, hi, device=self.device) for lo, hi in zip(a, b)])
+            if rows.numel() == 0:
+                continue
+            corpus = self.ids[rows]
+            order = torch.argsort(corpus)
+            rows, corpus = rows[order], corpus[order]
+            s, i = exact(self.xb[rows].contiguous(), q[j:j + 1], k)
+            valid = i[0] >= 0
+            scores[j] = s[0]
+            ids[j, valid] = corpus[i[0][valid]]
+        return scores, ids

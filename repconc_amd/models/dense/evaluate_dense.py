@@ -20,6 +20,8 @@ import numpy as np
 import torch
 
 from ...dense_index import FlatIPIndex, FlatL2Bf16x3Index, FlatL2F16Index, FlatL2Index
+from ...index import METRIC_INNER_PRODUCT, METRIC_L2
+from ...ivf_flat import IVFFlatIndex
 from ...utils.eval_utils import TextDataset, get_collator_func
 
 logger = logging.getLogger(__name__)
@@ -124,23 +126,43 @@ def batch_dense_search(query_ids: np.ndarray, query_embeds, corpus_ids: np.ndarr
 INDEX_METRICS = ("ip", "l2")
 
 
-def check_index_options(metric: str, use_float16: bool, screen: str) -> None:
+def check_index_options(metric: str, use_float16: bool, screen: str, nlist: int = 0) -> None:
     """ValueError for an unknown metric, storage or screen, or a combination that does not exist (fp16 storage with the bf16x3
-    screen, under either metric); touches no device.  The one rule of `create_index` and of run_dense_eval's arguments."""
+    screen, under either metric; the bf16x3 screen with an IVF index, nlist > 0); touches no device.  The one rule of
+    `create_index` and of run_dense_eval's arguments."""
     if metric not in INDEX_METRICS:
         raise ValueError(f"metric must be one of {list(INDEX_METRICS)}, got {metric!r}")
     FlatIPIndex.check_options("float16" if use_float16 else "float32", screen)
+    if int(nlist) < 0 or int(nlist) > IVFFlatIndex.MAX_NLIST:
+        raise ValueError(f"nlist must be in [0, {IVFFlatIndex.MAX_NLIST}], got {nlist!r}")
+    if int(nlist) > 0 and screen == "bf16x3":
+        raise ValueError("screen='bf16x3' belongs to the flat indexes: it cannot be combined with nlist > 0")
 
 
-def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="fp32", metric="ip"):
+IVF_TRAIN_ROWS = 1 << 18       # rows of the seeded sample the coarse centroids are fitted on (IVFPQIndex.from_flat's)
+
+
+def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="fp32", metric="ip", nlist=0, nprobe=8):
     """An exact index holding `corpus_embeds`, on device `single_gpu_id` or the current device.
     use_float16: store the vectors as fp16 (GpuClonerOptions.useFloat16, which the reference leaves False).
     screen="bf16x3" (fp32 storage only): the same results, candidates chosen on the bf16 matrix cores.
     metric="ip": `FlatIPIndex` (evaluate_dense.py:115-129); metric="l2": squared Euclidean distance, smallest first,
-    `FlatL2Index`, `FlatL2F16Index` (use_float16) or `FlatL2Bf16x3Index` (screen="bf16x3")."""
-    check_index_options(metric, use_float16, screen)                                           # before a device is looked at
+    `FlatL2Index`, `FlatL2F16Index` (use_float16) or `FlatL2Bf16x3Index` (screen="bf16x3").
+    nlist > 0: an `IVFFlatIndex` of that many cells instead (faiss.IndexIVFFlat; not in the reference): the coarse centroids are
+    fitted on a seeded sample of at most 2^18 rows, as `IVFPQIndex.from_flat` fits them, and a search scores exactly the rows of
+    the `nprobe` best cells of every query — the flat index's scores for the rows it reaches, not every row."""
+    check_index_options(metric, use_float16, screen, nlist)                                    # before a device is looked at
     dev = torch.device("cuda", single_gpu_id if single_gpu_id is not None else torch.cuda.current_device())
     d = corpus_embeds.shape[1]
+    if int(nlist) > 0:
+        index = IVFFlatIndex(d, int(nlist), device=dev, metric=METRIC_L2 if metric == "l2" else METRIC_INNER_PRODUCT,
+                             storage="float16" if use_float16 else "float32")
+        index.nprobe = int(nprobe)
+        n = corpus_embeds.shape[0]
+        sel = np.sort(np.random.default_rng(1234).permutation(n)[:IVF_TRAIN_ROWS])
+        index.train(corpus_embeds[torch.from_numpy(sel)] if isinstance(corpus_embeds, torch.Tensor) else corpus_embeds[sel])
+        index.add(corpus_embeds)
+        return index
     if metric == "l2":
         index = (FlatL2F16Index if use_float16 else FlatL2Bf16x3Index if screen == "bf16x3" else FlatL2Index)(d, device=dev)
     else:

@@ -1311,6 +1311,71 @@ def dense_rerank(x: torch.Tensor, q: torch.Tensor, cand_ids: torch.Tensor, k: in
     return scores, ids
 
 
+IVF_FLAT_MAX_NLIST = 16384          # cells of the dense IVF search (csrc/ivf_flat.hip)
+
+
+def ivf_flat_query_group() -> int:
+    """Queries of one cell that share a task of the dense IVF scan (IVFF_QG of csrc/ivf_flat.hip, read from the library)."""
+    return int(_lib.load().rc_ivf_flat_query_group())
+
+
+def ivf_flat_search_ws_bytes(nq: int, nprobe: int, nlist: int, stride: int) -> int:
+    """Workspace of one rc_ivf_flat_search / rc_ivf_flat_f16_search call: a multiple of 256; 0 for nq <= 0, nprobe <= 0,
+    nprobe > nlist or stride <= 0.  No GPU involved."""
+    return int(_lib.load().rc_ivf_flat_search_ws_bytes(int(nq), int(nprobe), int(nlist), int(stride)))
+
+
+def ivf_flat_search(xb: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor, q: torch.Tensor, probes: torch.Tensor,
+                    stride: int, k: int, metric: int = METRIC_INNER_PRODUCT):
+    """One call of the exact IVF search over dense rows (csrc/ivf_flat.hip): `xb` [N, D] fp32 or fp16, list-major; `list_off`
+    [nlist + 1] int64; `ids` [N] int64 corpus positions; `q` [nq, D] (rounded to fp16 for an fp16 store, as `dense_search_f16`
+    rounds it); `probes` [nq, nprobe] int32, distinct cells per query in ascending order (rc_ivf_select_probes); `stride` >= the
+    rows any nprobe cells hold.  Returns (scores or distances [nq, k], ids [nq, k], status [1] int32, qstatus [nq] int32) without
+    synchronising: bit 1 of a query's status = more than 16384 of its probed rows tie at its k-th score and its row of the
+    output is not valid (`IVFFlatIndex` answers those queries by the exact search over their probed rows); bit 2 of `status` =
+    a probe outside [0, nlist) or a `stride` too small.  Argument errors are ValueError before any device work."""
+    l2 = _adc_metric(metric)
+    if xb.dim() != 2 or q.dim() != 2 or xb.shape[1] != q.shape[1] or xb.shape[1] < 1:
+        raise ValueError("ivf_flat_search: xb [N, D] and q [nq, D] with the same D >= 1")
+    if xb.dtype not in (torch.float32, torch.float16):
+        raise ValueError("ivf_flat_search: the store must be float32 or float16")
+    if not 1 <= int(k) <= DENSE_MAX_K:
+        raise ValueError(f"ivf_flat_search: k must be in [1, {DENSE_MAX_K}]")
+    N, D = xb.shape
+    nlist = list_off.numel() - 1
+    if list_off.dtype != torch.int64 or list_off.dim() != 1 or not 1 <= nlist <= IVF_FLAT_MAX_NLIST:
+        raise ValueError(f"ivf_flat_search: list_off must be int64 [nlist + 1], 1 <= nlist <= {IVF_FLAT_MAX_NLIST}")
+    if ids.dtype != torch.int64 or ids.shape != (N,):
+        raise ValueError("ivf_flat_search: ids must be int64 [N]")
+    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != q.shape[0] or not 1 <= probes.shape[1] <= nlist:
+        raise ValueError("ivf_flat_search: probes must be int32 [nq, nprobe], 1 <= nprobe <= nlist")
+    if not 1 <= N < 1 << 32:
+        raise ValueError("ivf_flat_search: 1 <= N < 2^32")
+    if int(stride) < 1:
+        raise ValueError("ivf_flat_search: stride must be >= 1")
+    _need_cuda(xb, list_off, ids, q, probes)
+    f16 = xb.dtype == torch.float16
+    if xb.stride(1) != 1 or (N > 1 and xb.stride(0) < D):
+        xb = xb.contiguous()
+    q = q.to(xb.device).to(xb.dtype).contiguous()           # fp16: round to nearest even, as the corpus was
+    list_off, ids, probes = list_off.contiguous(), ids.contiguous(), probes.contiguous()
+    nq, nprobe = probes.shape
+    scores = torch.empty((nq, int(k)), dtype=torch.float32, device=q.device)
+    out_ids = torch.empty((nq, int(k)), dtype=torch.int64, device=q.device)
+    flags = torch.zeros((1 + nq,), dtype=torch.int32, device=q.device)       # [status | per-query status]: one fill
+    status, qstatus = flags[:1], flags[1:]
+    if nq == 0:
+        return scores, out_ids, status, qstatus
+    lib, h, s, _ = _ctx(q)
+    name = "rc_ivf_flat_f16_search" if f16 else "rc_ivf_flat_search"
+    wsb = lib.rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, int(stride))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)             # released in stream order
+    _lib.check(getattr(lib, name)(h, _p(xb), xb.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q), nq,
+                                  _p(probes), nprobe, int(stride), int(k), int(l2), _p(scores), _p(out_ids), _p(status),
+                                  _p(qstatus), _p(ws), wsb, s), name, h)
+    return scores, out_ids, status, qstatus
+
+
 def dense_xnorm_max(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
     """Device fp32 scalar [1] >= the largest Euclidean row norm of the floating-point matrix `x` of any dtype (fp64 sums,
     rounded upwards; +inf if the norm exceeds fp32): the `xnorm_max` of `dense_search_bf16x3` and `dense_search_f16`.  No host
