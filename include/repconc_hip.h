@@ -490,6 +490,55 @@ int rc_dense_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N
                            void* ws, size_t ws_bytes, rc_stream_t stream);
 void rc_dense_bf16x3_error_constants(double* c);
 
+/* ------------------------------------------------------------------ dense flat search, 8-bit scalar-quantised storage
+ * The same search over a corpus of 8-bit scalar-quantiser codes (faiss.IndexScalarQuantizer, QT_8bit): x [N, ldx] int8 holds
+ * c' = c - 128 for the code c in 0 .. 255 of every dimension; dec [2][D] fp32 = step (row 0) and mid (row 1); q [nq, D] fp32,
+ * finite.  A row decodes to x^[d] = fmaf((float)c'[d], step[d], mid[d]) and the score is s(q, n) = fp32 fmaf chain over
+ * d = 0 .. D-1 ascending from +0.0f of q[d] * x^[n][d]: ids AND score bits equal rc_dense_search_q over the decoded corpus
+ * (rc_dense_sq8_decode).  Order, padding (-inf / -1), id_offset and the limits (N < 2^32, 1 <= k <= 8192, else RC_ESHAPE) as
+ * above; 1 <= D <= 65536 (else RC_ESHAPE: the screen's int32 accumulators hold 128 * 128 * D).  Any row pitch ldx >= D and
+ * any alignment: rows are read with 16-byte loads when D % 16 == 0, ldx % 16 == 0 and x is 16-byte aligned, byte by byte
+ * otherwise.
+ * rc_dense_sq8_search_q: N <= 131072 takes the exact route below.  Above: a pre-pass turns every query into w[d] = q[d] step[d],
+ *   bias = sum_d q[d] mid[d] (fp64, rounded once), alpha = max_d |w[d]| / 32639 and two int8 planes h, l with
+ *   rint(w[d] / alpha) = 256 h[d] + l[d]; the int8 matrix cores accumulate A_h = sum_d h[d] c'[d], A_l = sum_d l[d] c'[d] in
+ *   exact int32 and s~ = fmaf(alpha, fmaf(256, A_h, A_l), bias).  Threshold, candidates, rescoring by the chain and the sort as
+ *   rc_dense_f16_search_q.  cstat: DEVICE pointer to two floats, C1 >= the largest sum_d |c'[d]| of a row and X >= the largest
+ *   Euclidean norm of a decoded row.  With W1 = sum_d |w[d]|, B1 = sum_d |q[d] mid[d]|, u = 2^-24, D_pad = D rounded up to 16
+ *   and the constants c[0..6] of rc_dense_sq8_error_constants,
+ *     E_q = (c0 alpha C1 + u (c1 W1 + c2 alpha D + c3 alpha C1 + c4 B1 + c5 (D_pad + 1) ||q||_2 X)
+ *            + c6 2^-149 (D_pad + sqrt(D_pad) ||q||_2 + C1 + 1)) (1 + 2^-20)                  (every |s~ - s| <= E_q),
+ *   t >= thr~ + E_q for t = the query's k-th exact score proves the answer.  status / qstatus as rc_dense_f16_search_q: bit0,
+ *   bit1, bit2 = not certified (also: a query value, w[d] or |q[d] mid[d]| not below 2^100, a NaN anywhere, alpha below 2^-100
+ *   with a nonzero w): repeat those queries with another sel_slack or answer them by rc_dense_sq8_search_exact.
+ *   ws (16-byte aligned): rc_dense_sq8_search_ws_bytes.
+ * rc_dense_sq8_search_exact: the chain of every (query, row) pair over rows decoded on the fly, then the radix select; no
+ *   status.  ws: rc_dense_sq8_search_exact_ws_bytes(N, D, nq, k).
+ * rc_dense_sq8_search_ws_counts (measurement): *cnt_off = the byte offset in the workspace of rc_dense_sq8_search_q where, after
+ *   the call, nq unsigned ints hold the rows of every query that passed the screen (more than 16384: the list overflowed); 0
+ *   where the exact route answers (N <= 131072).  No GPU needed.
+ * rc_dense_sq8_scores (test hook): the screen's raw s~, out [nq][N] fp32; ws: rc_dense_sq8_scores_ws_bytes(D, nq).
+ * rc_dense_sq8_decode: out [N][D] fp32 = the decoded rows (N = 0: nothing).
+ * rc_dense_sq8_error_constants: c[7] = {0.5, 520, 194, 515, 2.1, 1.02, 1}; rc_dense_sq8_qmax: 32639 = 127 * 256 + 127, the
+ *   largest |256 h + l|; rc_dense_sq8_max_d: 65536 (none needs a GPU). */
+size_t rc_dense_sq8_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_sq8_search_q(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                          const float* dec, const float* cstat, int k, int64_t id_offset, double sel_slack, float* scores,
+                          int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+size_t rc_dense_sq8_search_exact_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_sq8_search_exact(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                              const float* dec, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                              size_t ws_bytes, rc_stream_t stream);
+int rc_dense_sq8_search_ws_counts(int64_t N, int D, int nq, int k, size_t* cnt_off);
+size_t rc_dense_sq8_scores_ws_bytes(int D, int nq);
+int rc_dense_sq8_scores(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq, const float* dec,
+                        float* out, void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_sq8_decode(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* dec, float* out,
+                        rc_stream_t stream);
+void rc_dense_sq8_error_constants(double* c);
+int rc_dense_sq8_qmax(void);
+int rc_dense_sq8_max_d(void);
+
 /* ------------------------------------------------------------------ dense flat search, L2 metric
  * Exact squared-Euclidean top-k over an fp32 corpus: faiss.IndexFlatL2, the flat index the reference names at
  * models/repconc/evaluate_repconc.py:102 and train/run_warmup.py:102,107.  Arguments, alignment rules and limits of

@@ -1,5 +1,5 @@
-// What the six dense flat searches share (dense_search.hip, dense_search_f16.hip, dense_search_bf16x3.hip,
-// dense_search_l2.hip, dense_search_l2_f16.hip, dense_search_l2_bf16x3.hip): the GEMM on the fp32 matrix cores whose result IS the inner-product score (the fp32 fmaf chain over d
+// What the seven dense flat searches share (dense_search.hip, dense_search_f16.hip, dense_search_bf16x3.hip,
+// dense_search_l2.hip, dense_search_l2_f16.hip, dense_search_l2_bf16x3.hip, dense_search_sq8.hip): the GEMM on the fp32 matrix cores whose result IS the inner-product score (the fp32 fmaf chain over d
 // ascending) and, with one more operand, the L2 screen; the workspace layouts and the argument checks.  T is the storage
 // type of x and q: float, or _Float16 widened to fp32 on load (exact).  Device code: every translation unit that uses it
 // compiles its own copy, no -fgpu-rdc.  The route of a search, exact route included, and what the screened searches share
@@ -226,13 +226,14 @@ static inline dense_fast_layout dense_fast_ws(int64_t N, int nq) {
 }
 
 // argument checks shared by all entries: shapes first (pure arithmetic), then pointers.  Rows of D % 16 == 0 elements are
-// read with 16-byte loads: x, q and the row pitch must be 16-byte aligned
-template <typename T>
-static int dense_check(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, int k,
-                       const float* scores, const int64_t* ids) {
+// read with 16-byte loads: x, q and the row pitch must be 16-byte aligned (aligned = false: the variant has a form for the rest)
+template <typename X, typename T>
+static int dense_check(rc_handle_t h, const X* x, int64_t ldx, int64_t N, int D, const T* q, int nq, int k,
+                       const float* scores, const int64_t* ids, bool aligned = true) {
     if (N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2) return RC_ESHAPE;
     if (!h || !x || !q || !scores || !ids || N <= 0 || D <= 0 || nq < 0 || k <= 0 || ldx < D) return RC_EINVAL;
-    if (D % DENSE_KC == 0 && (ldx % (16 / (int)sizeof(T)) != 0 || ((uintptr_t)x & 15u) || ((uintptr_t)q & 15u))) return RC_EINVAL;
+    if (aligned && D % DENSE_KC == 0 &&
+        (ldx % (16 / (int)sizeof(X)) != 0 || ((uintptr_t)x & 15u) || ((uintptr_t)q & 15u))) return RC_EINVAL;
     return RC_OK;
 }
 

@@ -1,7 +1,8 @@
-// What the six dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
+// What the seven dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
 // dense_search_f16.hip: fp16 corpus and f16 screen, dense_search_bf16x3.hip: fp32 corpus and bf16x3 screen,
 // dense_search_l2.hip: fp32 corpus, squared Euclidean distance, dense_search_l2_f16.hip: the same over an fp16 corpus,
-// dense_search_l2_bf16x3.hip: the fp32 L2 corpus under the bf16x3 screen): the
+// dense_search_l2_bf16x3.hip: the fp32 L2 corpus under the bf16x3 screen, dense_search_sq8.hip: int8 scalar-quantiser codes,
+// fp32 queries and the int8 screen): the
 // route of a search and the bodies of its entries, the pieces common to the two 16x16x32 screen GEMMs, the rescoring kernel
 // and the certificate kernel.  Device code: every translation unit compiles its own copy, no -fgpu-rdc.
 //
@@ -14,19 +15,22 @@
 //   over rows widened on load; L2: dense_l2_exact_kernel), then the 8-pass radix select over the 64-bit keys
 //   (topk_exact_select), then V::finish.  It terminates with the same answer for any content (all rows identical, k >= N, ...).
 //   Fast route (N > 4 S, S = min(N, 32768)):
-//   0. V::prepass: the bf16x3 screens split the queries into two bf16 planes in the tail of the workspace; nothing for the others
+//   0. V::prepass: the bf16x3 screens split the queries into two bf16 planes in the tail of the workspace, the int8 screen
+//      quantises them to two int8 planes there; nothing for the others
 //   1. screen<STORE> over the strided sample j -> row j N / S: s~ of the sample (fp32 screen: s~ = s, the chain)
 //   2. adc_threshold_kernel (topk.hip): thr~[q] = the r-th best s~ of the sample, r by the ADC formula (rc_adc_sample_rank)
 //   3. screen<FILTER> over all N rows: the key (s~, row) of every s~ >= thr~[q] -> q's candidate list
-//   4. approximate only: dense_rescore_kernel replaces the score half of every candidate key by the chain
+//   4. approximate only: dense_rescore_kernel (coded: V::rescore) replaces the score half of every candidate key by the chain
 //   5. adc_select_kernel (rc_adc_launch_select): sort + emit; qstatus bit0 = fewer than min(k, N) candidates, bit1 = overflow
-//   6. approximate only: dense_certify_kernel.  With t = the query's k-th exact score and |s~ - s| <= E_q for every row, a
-//      row outside the list has s~ < thr~, hence s < thr~ + E_q: if t >= thr~ + E_q (everything in fp64, rounded upwards) no
+//   6. approximate only: dense_certify_kernel (coded: V::certify).  With t = the query's k-th exact score and |s~ - s| <= E_q
+//      for every row, a row outside the list has s~ < thr~, hence s < thr~ + E_q: if t >= thr~ + E_q (everything in fp64, rounded upwards) no
 //      such row can enter the top-k or tie with its last member and the answer is proven equal to the exact route's.
 //      Otherwise qstatus bit2, "not certified": the caller repeats the query with another slack or takes the exact route.
 //   7. V::finish, after the certificate has read the scores
 #pragma once
 #include "dense_gemm.h"
+
+#include <type_traits>
 
 typedef float dense_f32x4 __attribute__((ext_vector_type(4)));
 
@@ -196,7 +200,8 @@ __global__ __launch_bounds__(64) void dense_certify_kernel(const typename V::T* 
 
 // ---- the route --------------------------------------------------------------------------------------------------------------
 // A variant V (dense_variant_defaults holds what most of them say):
-//   typedef T                      storage type of x and q
+//   typedef T                      type of q, and of x unless V says otherwise
+//   typedef X                      optional: the storage type of x where it is not T (dense_storage<V>)
 //   typedef Q                      what its screen reads as the query operand (T, or the bf16 planes of the pre-pass)
 //   static constexpr bool approximate
 //   static constexpr bool l2                              scores are -d: the entry takes xsq [N], the squared norm of every
@@ -209,14 +214,26 @@ __global__ __launch_bounds__(64) void dense_certify_kernel(const typename V::T* 
 //   static int exact_rows(h, x, ldx, N, D, q, nq, out, s) out [nq][N] = the chain of every pair
 //   static int finish(h, scores, n, s)                    the last step over the n output values; empty: launches nothing
 //   approximate: eq / refuse of dense_certify_kernel
+//   static constexpr bool coded                           x holds codes that per-dimension vectors decode (dense_search_sq8.hip).
+//                                                         `side` (xsq of the L2 variants) then points at those vectors, and
+//                                                         prepass and exact_rows take it as their FIRST argument; the variant
+//                                                         brings the rescorer and the certificate of its own:
+//     static int rescore(side, h, x, ldx, D, q, nq, cnt, cand, s)
+//     static int certify(side, h, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s)
 struct dense_variant_defaults {
     static constexpr bool l2 = false;
+    static constexpr bool coded = false;
     static constexpr unsigned ws_align = 1;
     static size_t extra_ws_bytes(int, int) { return 0; }
     template <typename T>
     static int prepass(rc_handle_t, const T* q, int, int, char*, const T** qs, hipStream_t) { *qs = q; return RC_OK; }
     static int finish(rc_handle_t, float*, int64_t, hipStream_t) { return RC_OK; }
 };
+
+template <typename V, typename = void>
+struct dense_storage { typedef typename V::T type; };
+template <typename V>
+struct dense_storage<V, std::void_t<typename V::X>> { typedef typename V::X type; };
 
 static inline size_t dense_exact_ws_bytes(int64_t N, int D, int nq, int k) {
     return dense_shape_ok(N, D, nq, k) ? dense_exact_ws(N, nq).sel.total : 0;
@@ -229,13 +246,15 @@ static size_t dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
 
 // the exact route: full score rows of L.qx queries at a time, then the radix select
 template <typename V>
-static int dense_exact(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q, int nq,
-                       int k, int64_t id_offset, float* scores, int64_t* ids, char* w, const dense_exact_layout& L,
-                       hipStream_t s) {
+static int dense_exact(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                       const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, char* w,
+                       const dense_exact_layout& L, hipStream_t s, const float* side = nullptr) {
     float* sc = (float*)(w + L.sc);             // (the select's status word is never set: exactly min(k, N) keys are collected)
     for (int q0 = 0; q0 < nq; q0 += L.qx) {
         const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
-        int rc = V::exact_rows(h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
+        int rc;
+        if constexpr (V::coded) rc = V::exact_rows(side, h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
+        else rc = V::exact_rows(h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
         if (rc != RC_OK) return rc;
         rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
         if (rc != RC_OK) return rc;
@@ -245,17 +264,20 @@ static int dense_exact(rc_handle_t h, const typename V::T* x, int64_t ldx, int64
 
 // checked arguments (dense_search_entry: dense_check, the extra pointers, nq > 0, a workspace of dense_search_ws_bytes<V>)
 template <typename V>
-static int dense_search_route(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q,
-                              int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack,
-                              float* scores, int64_t* ids, int* status, int* qstatus, char* w, hipStream_t s) {
-    if (dense_exact_route(N)) return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s);
+static int dense_search_route(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                              const typename V::T* q, int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset,
+                              double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, char* w, hipStream_t s) {
+    if (dense_exact_route(N))
+        return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s, xsq);
     const dense_fast_layout L = dense_fast_ws(N, nq);
     float* sample = (float*)(w + L.sample);
     float* thr = (float*)(w + L.thr);
     unsigned* cnt = (unsigned*)(w + L.cnt);
     unsigned long long* cand = (unsigned long long*)(w + L.cand);
     const typename V::Q* qs;
-    int rc = V::prepass(h, q, nq, D, w + L.total, &qs, s);
+    int rc;
+    if constexpr (V::coded) rc = V::prepass(xsq, h, q, nq, D, w + L.total, &qs, s);
+    else rc = V::prepass(h, q, nq, D, w + L.total, &qs, s);
     if (rc != RC_OK) return rc;
     rc = V::template launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
     if (rc != RC_OK) return rc;
@@ -265,12 +287,16 @@ static int dense_search_route(rc_handle_t h, const typename V::T* x, int64_t ldx
     rc = V::template launch_gemm<DENSE_FILTER>(xsq, h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
     if (rc != RC_OK) return rc;
     if constexpr (V::approximate) {
-        rc = dense_launch_rescore<V::l2>(h, x, ldx, D, q, nq, cnt, cand, s);
+        if constexpr (V::coded) rc = V::rescore(xsq, h, x, ldx, D, q, nq, cnt, cand, s);
+        else rc = dense_launch_rescore<V::l2>(h, x, ldx, D, q, nq, cnt, cand, s);
         if (rc != RC_OK) return rc;
     }
     rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, scores, ids, status, s, qstatus);
     if (rc != RC_OK) return rc;
-    if constexpr (V::approximate) {
+    if constexpr (V::coded) {
+        rc = V::certify(xsq, h, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s);
+        if (rc != RC_OK) return rc;
+    } else if constexpr (V::approximate) {
         hipLaunchKernelGGL(dense_certify_kernel<V>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, thr, xnorm_max, scores,
                            status, qstatus);
         RC_LAUNCH_CHECK(h);
@@ -280,30 +306,32 @@ static int dense_search_route(rc_handle_t h, const typename V::T* x, int64_t ldx
 
 // ---- the entries ------------------------------------------------------------------------------------------------------------
 // The bodies of rc_dense*_search_exact and rc_dense*_search_q.  The order of the checks is part of the C ABI: shapes before
-// pointers (dense_check), a missing status / xnorm_max / xsq before the nq == 0 success, the workspace last.
+// pointers (dense_check), a missing status / xnorm_max / xsq before the nq == 0 success, the workspace last.  A coded
+// variant reads `side` on every route and its screen has a form for any row pitch: nothing is asked of the alignment.
 template <typename V>
-static int dense_exact_entry(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q, int nq,
-                             int k, int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes,
-                             rc_stream_t stream) {
+static int dense_exact_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                             const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                             size_t ws_bytes, rc_stream_t stream, const float* side = nullptr) {
     rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids, !V::coded);
     if (crc != RC_OK) return crc;
+    if (V::coded && !side) return RC_EINVAL;
     if (nq == 0) return RC_OK;
     const dense_exact_layout L = dense_exact_ws(N, nq);
     if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
-    return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
+    return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream, side);
 }
 
-// xsq is read if V::l2, xnorm_max if V::approximate
+// xsq is read if V::l2 or V::coded, xnorm_max if V::approximate
 template <typename V>
-static int dense_search_entry(rc_handle_t h, const typename V::T* x, int64_t ldx, int64_t N, int D, const typename V::T* q,
-                              int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack,
-                              float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+static int dense_search_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                              const typename V::T* q, int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset,
+                              double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
                               rc_stream_t stream) {
     rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids, !V::coded);
     if (crc != RC_OK) return crc;
-    if (!status || (V::l2 && !xsq) || (V::approximate && !xnorm_max)) return RC_EINVAL;
+    if (!status || ((V::l2 || V::coded) && !xsq) || (V::approximate && !xnorm_max)) return RC_EINVAL;
     if (nq == 0) return RC_OK;
     if (!ws || ((uintptr_t)ws & (V::ws_align - 1)) || ws_bytes < dense_search_ws_bytes<V>(N, D, nq, k)) return RC_EWORKSPACE;
     return dense_search_route<V>(h, x, ldx, N, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, scores, ids, status, qstatus,

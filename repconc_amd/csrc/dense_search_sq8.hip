@@ -1,0 +1,321 @@
+// Exact dense inner-product top-k search over a corpus of 8-bit scalar-quantiser codes (Faiss IndexScalarQuantizer, QT_8bit):
+// one byte per dimension, a quarter of dense_search.hip's bytes, and the screen runs on the int8 matrix cores.
+//
+// Store and score.  x holds c'_d = c_d - 128 as int8, c_d in 0 .. 255 the code of dimension d; dec = [step | mid], two fp32
+// vectors of D values.  A row decodes to x^_d = fmaf((float)c'_d, step_d, mid_d) and
+//   s(q, n) = fp32 fmaf chain over d = 0 .. D-1 ascending from +0.0f of q_d * x^_d
+// — the definition of dense_search.hip applied to the decoded corpus (rc_dense_sq8_decode writes it out).
+//
+// The route is dense_search_route (dense_screen.h) with this unit's coded variant: dense_i8_prepass_kernel quantises the
+// queries, dense_i8_gemm_kernel (dense_i8_gemm.h) screens, the candidates are rescored by the chain over rows decoded on the
+// fly (dense_sq8_rescore_kernel) and every answer carries a certificate (dense_sq8_certify_kernel).  Exact route: the chain of
+// every pair (dense_sq8_rows_kernel).
+//
+// The bound |s~ - s| <= E_q.  u = 2^-24; every value below is finite and, until the last paragraph, normal.  Per query:
+//   w_d = fl(q_d step_d), W1 = sum_d |w_d|, B1 = sum_d |q_d mid_d|, alpha = alpha_q, v_d = 256 h_d + l_d (dense_i8_gemm.h);
+// per corpus: C1 >= the largest sum_d |c'_d| of a row, X >= the largest Euclidean norm of a decoded row.
+//   chain     s is D roundings away from R = sum_d q_d x^_d: |s - R| <= D u / (1 - D u) * sum_d |q_d x^_d| <= 1.004 D u P,
+//             P = ||q||_2 X (Cauchy-Schwarz), while D <= 65536.
+//   decode    x^_d = (c'_d step_d + mid_d)(1 + e), |e| <= u: |R - sum_d q_d c'_d step_d - sum_d q_d mid_d| <= 1.001 u P.
+//   w         |q_d step_d - w_d| <= u |w_d| (1 + 2u) and |c'_d| <= 128: |sum_d (q_d step_d - w_d) c'_d| <= 1.001 * 128 u W1.
+//   quantise  |w_d - alpha v_d| <= alpha (1/2 + 2^-37): the fp64 quotient is within 2^-53 of the ratio, itself below 2^15.
+//             |sum_d (w_d - alpha v_d) c'_d| <= alpha (1/2 + 2^-37) C1.                    <- the only term that is not a rounding
+//   combine   T = 256 A_h + A_l = sum_d v_d c'_d exactly.  The epilogue rounds A_h, A_l to fp32 and their fmaf:
+//             |t - T| <= u (256 |A_h| + |A_l| + |T| (1 + 3u)) <= 2.001 u sum_d (|256 h_d| + |l_d|) |c'_d|, and
+//             |256 h_d| + |l_d| <= |v_d| + 256, alpha |v_d| <= |w_d| + 0.501 alpha:
+//             alpha |t - T| <= 2.001 u (128 W1 + 64.2 alpha D + 256 alpha C1).
+//   bias      fp64 sum of D products, rounded once: |bias - sum_d q_d mid_d| <= 1.001 u B1.
+//   epilogue  s~ = fl(alpha t + bias): <= u |s~| <= 1.001 u (alpha |T| + alpha |t - T| + 1.001 B1)
+//             <= 1.002 u (128 W1 + 64.2 alpha D + B1).
+//   together  E_rel = C_Q alpha C1 + u (C_W W1 + C_AD alpha D + C_AC alpha C1 + C_B B1 + C_CH (D_pad + 1) ||q||_2 X),
+//             C_Q = 0.5, C_W = 520 >= (1.001 + 2.001 + 1.002) 128, C_AD = 194 >= 3.003 * 64.2, C_AC = 515 >= 2.001 * 256,
+//             C_B = 2.1, C_CH = 1.02; D_pad = D rounded up to 16.
+//   underflow the relative steps fail for subnormal results, whose absolute error is <= 2^-150 instead: a decoded value
+//             (times |q_d|: in total <= 2^-150 sqrt(D) ||q||_2), a chain step (D of them), a w_d (times |c'_d|: <= 2^-150 C1)
+//             and the epilogue's result:  E_abs = C_ABS 2^-149 (D_pad + sqrt(D_pad) ||q||_2 + C1 + 1), C_ABS = 1.
+//   E_q = (E_rel + E_abs)(1 + 2^-20), evaluated in fp64; the factor covers the 2^-37 above and the evaluation's own roundings.
+// The certificate refuses (qstatus bit2: the caller repeats, then takes the exact route) a query with a value, a w_d or a
+// |q_d mid_d| that is not below 2^100, and one whose alpha is below 2^-100 although some w_d is not zero: up to there no
+// intermediate overflows and alpha is normal.  An all-zero w has alpha = 0 and zero limbs: s~ = bias, inside the bound.
+// The constants are exported (rc_dense_sq8_error_constants) and are what ops.dense_sq8_error_bound evaluates.
+#include "dense_i8_gemm.h"
+
+#define DENSE_SQ8_C_Q 0.5
+#define DENSE_SQ8_C_W 520.0
+#define DENSE_SQ8_C_AD 194.0
+#define DENSE_SQ8_C_AC 515.0
+#define DENSE_SQ8_C_B 2.1
+#define DENSE_SQ8_C_CH 1.02
+#define DENSE_SQ8_C_ABS 1.0
+#define DENSE_SQ8_BIG 0x1p100f                           // the certificate's range: |values| below it, alpha above its inverse
+
+typedef signed char dense_i8x16 __attribute__((ext_vector_type(16)));
+
+__device__ __forceinline__ float dense_sq8_decode(signed char c, float step, float mid) {
+    return __builtin_fmaf((float)c, step, mid);
+}
+
+// ---- rescoring --------------------------------------------------------------------------------------------------------------
+// dense_rescore_kernel (dense_screen.h) over coded rows: grid (nq, ADC_CAND_CAP / 256) blocks of 256 threads, one lane per
+// candidate key of query blockIdx.x; step, mid and the query are staged in LDS chunk by chunk.  VEC: 16-byte aligned rows.
+template <bool VEC>
+__global__ __launch_bounds__(256) void dense_sq8_rescore_kernel(const signed char* __restrict__ x, int64_t ldx, int D,
+                                                                const float* __restrict__ dec, const float* __restrict__ q,
+                                                                const unsigned* __restrict__ cnt,
+                                                                unsigned long long* __restrict__ cand) {
+    __shared__ float sq[DENSE_RESCORE_QCHUNK], ss[DENSE_RESCORE_QCHUNK], sm[DENSE_RESCORE_QCHUNK];
+    const int qi = blockIdx.x, tid = threadIdx.x;
+    const unsigned raw = cnt[qi];
+    const unsigned n = raw > ADC_CAND_CAP ? ADC_CAND_CAP : raw;
+    if (blockIdx.y * 256u >= n) return;                                // block-uniform
+    const unsigned i = blockIdx.y * 256u + tid;
+    const bool mine = i < n;
+    unsigned long long* kp = cand + (size_t)qi * ADC_CAND_CAP + i;
+    const unsigned row = mine ? 0xFFFFFFFFu - (unsigned)(*kp & 0xFFFFFFFFull) : 0u;
+    const signed char* xp = x + (int64_t)row * ldx;
+    const float* qp = q + (int64_t)qi * D;
+    float s = 0.f;
+    for (int d0 = 0; d0 < D; d0 += DENSE_RESCORE_QCHUNK) {
+        const int dn = D - d0 < DENSE_RESCORE_QCHUNK ? D - d0 : DENSE_RESCORE_QCHUNK;
+        __syncthreads();
+        for (int d = tid; d < dn; d += 256) { sq[d] = qp[d0 + d]; ss[d] = dec[d0 + d]; sm[d] = dec[D + d0 + d]; }
+        __syncthreads();
+        if (mine) {
+            int d = 0;
+            if constexpr (VEC) {
+                for (; d + 16 <= dn; d += 16) {
+                    const dense_i8x16 v = *reinterpret_cast<const dense_i8x16*>(xp + d0 + d);
+#pragma unroll
+                    for (int e = 0; e < 16; ++e)
+                        s = dense_chain_step<false>(sq[d + e], dense_sq8_decode(v[e], ss[d + e], sm[d + e]), s);
+                }
+            }
+            for (; d < dn; ++d) s = dense_chain_step<false>(sq[d], dense_sq8_decode(xp[d0 + d], ss[d], sm[d]), s);
+        }
+    }
+    if (mine) *kp = adc_exact_key(s, (int64_t)row);
+}
+
+// ---- the exact route's score rows -------------------------------------------------------------------------------------------
+#define DENSE_SQ8_ROWS_QB 4                              // queries that share a decoded value
+// grid: (ceil(N / 256), ceil(nq / 4)) blocks of 256 threads; thread -> one corpus row and four queries: out [nq][N] = the chain
+// of every pair.  A value is decoded once and feeds four chains.  Plain fp32: the exact route serves small corpora and the few
+// queries the fast route gives up on.
+__global__ __launch_bounds__(256) void dense_sq8_rows_kernel(const signed char* __restrict__ x, int64_t ldx, int64_t N, int D,
+                                                             const float* __restrict__ dec, const float* __restrict__ q, int nq,
+                                                             float* __restrict__ out) {
+    __shared__ float sq[DENSE_SQ8_ROWS_QB][DENSE_RESCORE_QCHUNK], ss[DENSE_RESCORE_QCHUNK], sm[DENSE_RESCORE_QCHUNK];
+    const int tid = threadIdx.x;
+    const int q0 = blockIdx.y * DENSE_SQ8_ROWS_QB;
+    const int64_t j = (int64_t)blockIdx.x * 256 + tid;
+    const bool mine = j < N;
+    const signed char* xp = x + (mine ? j : N - 1) * ldx;
+    float s[DENSE_SQ8_ROWS_QB];
+#pragma unroll
+    for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b) s[b] = 0.f;
+    for (int d0 = 0; d0 < D; d0 += DENSE_RESCORE_QCHUNK) {
+        const int dn = D - d0 < DENSE_RESCORE_QCHUNK ? D - d0 : DENSE_RESCORE_QCHUNK;
+        __syncthreads();
+        for (int d = tid; d < dn; d += 256) {
+            ss[d] = dec[d0 + d];
+            sm[d] = dec[D + d0 + d];
+#pragma unroll
+            for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b) sq[b][d] = q[(int64_t)(q0 + b < nq ? q0 + b : nq - 1) * D + d0 + d];
+        }
+        __syncthreads();
+        for (int d = 0; d < dn; ++d) {
+            const float v = dense_sq8_decode(xp[d0 + d], ss[d], sm[d]);
+#pragma unroll
+            for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b) s[b] = dense_chain_step<false>(sq[b][d], v, s[b]);
+        }
+    }
+    if (mine)
+#pragma unroll
+        for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b)
+            if (q0 + b < nq) out[(int64_t)(q0 + b) * N + j] = s[b];
+}
+
+static int dense_sq8_exact_rows(const float* dec, rc_handle_t h, const signed char* x, int64_t ldx, int64_t N, int D,
+                                const float* q, int nq, float* out, hipStream_t s) {
+    const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((nq + DENSE_SQ8_ROWS_QB - 1) / DENSE_SQ8_ROWS_QB));
+    hipLaunchKernelGGL(dense_sq8_rows_kernel, grid, dim3(256), 0, s, x, ldx, N, D, dec, q, nq, out);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+// grid: ceil(N D / 256) blocks of 256 threads: out [N][D] = the decoded corpus
+__global__ __launch_bounds__(256) void dense_sq8_decode_kernel(const signed char* __restrict__ x, int64_t ldx, int64_t N, int D,
+                                                               const float* __restrict__ dec, float* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= N * D) return;
+    const int64_t r = i / D;
+    const int d = (int)(i - r * D);
+    out[i] = dense_sq8_decode(x[r * ldx + d], dec[d], dec[D + d]);
+}
+
+// ---- certificate ------------------------------------------------------------------------------------------------------------
+__host__ __device__ static inline double dense_sq8_eq(int D, double alpha, double w1, double b1, double qn, double c1, double X) {
+    const double dpad = (double)((D + 15) / 16 * 16);
+    const double rel = DENSE_SQ8_C_Q * alpha * c1 +
+                       0x1p-24 * (DENSE_SQ8_C_W * w1 + DENSE_SQ8_C_AD * alpha * (double)D + DENSE_SQ8_C_AC * alpha * c1 +
+                                  DENSE_SQ8_C_B * b1 + DENSE_SQ8_C_CH * (dpad + 1.0) * qn * X);
+    const double abs_ = DENSE_SQ8_C_ABS * 0x1p-149 * (dpad + sqrt(dpad) * qn + c1 + 1.0);
+    return (rel + abs_) * (1.0 + 0x1p-20);
+}
+
+// grid: nq blocks of 64 threads, as dense_certify_kernel.  cstat: [2] fp32 = C1, X.  Sets bit2 of status / qstatus[q] unless
+// t >= thr~ + E_q is proven; a NaN anywhere is "not certified".
+__global__ __launch_bounds__(64) void dense_sq8_certify_kernel(const float* __restrict__ q, int D, int k,
+                                                               const float* __restrict__ dec, const float* __restrict__ alpha,
+                                                               const float* __restrict__ thr, const float* __restrict__ cstat,
+                                                               const float* __restrict__ scores, int* __restrict__ status,
+                                                               int* __restrict__ qstatus) {
+    const int qi = blockIdx.x, lane = threadIdx.x;
+    const float* qp = q + (int64_t)qi * D;
+    double ss = 0.0, w1 = 0.0, b1 = 0.0;
+    int refused = 0, nonzero = 0;
+    for (int d = lane; d < D; d += 64) {
+        const float f = qp[d];
+        const float w = fabsf(f * dec[d]);
+        const double b = fabs((double)f * (double)dec[D + d]);
+        refused |= !(fabsf(f) < DENSE_SQ8_BIG) || !(w < DENSE_SQ8_BIG) || !(b < (double)DENSE_SQ8_BIG);
+        nonzero |= w > 0.f;
+        ss += (double)f * (double)f;
+        w1 += (double)w;
+        b1 += b;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        ss += __shfl_xor(ss, o);
+        w1 += __shfl_xor(w1, o);
+        b1 += __shfl_xor(b1, o);
+        refused |= __shfl_xor(refused, o);
+        nonzero |= __shfl_xor(nonzero, o);
+    }
+    if (lane != 0) return;
+    const float a = alpha[qi];
+    refused |= D > DENSE_I8_MAX_D || (nonzero && !(a >= 1.f / DENSE_SQ8_BIG));
+    const double up = 1.0 + 0x1p-30;
+    const double sum = (double)thr[qi] + dense_sq8_eq(D, (double)a, w1 * up, b1 * up, sqrt(ss) * up, (double)cstat[0], (double)cstat[1]);
+    const double bound = sum + fabs(sum) * 0x1p-30;
+    const double t = (double)scores[(size_t)qi * k + (k - 1)];
+    if (refused || !(t >= bound)) {
+        atomicOr(status, 4);
+        if (qstatus) atomicOr(qstatus + qi, 4);
+    }
+}
+
+// ---- the variant ------------------------------------------------------------------------------------------------------------
+struct dense_sq8_variant : dense_variant_defaults {
+    typedef float T;
+    typedef signed char X;
+    typedef char Q;                                      // the pre-pass's part of the workspace (dense_i8_query_ws)
+    static constexpr bool approximate = true;
+    static constexpr bool coded = true;
+    static constexpr unsigned ws_align = 16;             // the planes are read with 16-byte loads
+    static size_t extra_ws_bytes(int nq, int D) { return dense_i8_query_ws(nq, D).total; }
+    static int prepass(const float* dec, rc_handle_t h, const float* q, int nq, int D, char* tail, const Q** qs, hipStream_t s) {
+        *qs = tail;                                      // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
+        return dense_i8_launch_prepass(h, q, nq, D, dec, tail, s);
+    }
+    template <int MODE>
+    static int launch_gemm(const float*, rc_handle_t h, const X* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
+                           const Q* qs, int nq, int D, const float* thr, float* out, unsigned* cnt, unsigned long long* cand,
+                           hipStream_t s) {
+        return dense_i8_launch_gemm<MODE>(h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s);
+    }
+    static constexpr auto* exact_rows = &dense_sq8_exact_rows;
+    static int rescore(const float* dec, rc_handle_t h, const X* x, int64_t ldx, int D, const float* q, int nq,
+                       const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
+        const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
+        if (ldx % 16 == 0 && !((uintptr_t)x & 15u))
+            hipLaunchKernelGGL(dense_sq8_rescore_kernel<true>, grid, dim3(256), 0, s, x, ldx, D, dec, q, cnt, cand);
+        else
+            hipLaunchKernelGGL(dense_sq8_rescore_kernel<false>, grid, dim3(256), 0, s, x, ldx, D, dec, q, cnt, cand);
+        RC_LAUNCH_CHECK(h);
+        return RC_OK;
+    }
+    static int certify(const float* dec, rc_handle_t h, const float* q, const Q* qs, int nq, int D, int k, const float* thr,
+                       const float* cstat, const float* scores, int* status, int* qstatus, hipStream_t s) {
+        const float* alpha = (const float*)(qs + dense_i8_query_ws(nq, D).alpha);
+        hipLaunchKernelGGL(dense_sq8_certify_kernel, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, dec, alpha, thr, cstat, scores,
+                           status, qstatus);
+        RC_LAUNCH_CHECK(h);
+        return RC_OK;
+    }
+};
+
+static bool dense_sq8_shape_ok(int64_t N, int D, int nq, int k) { return dense_shape_ok(N, D, nq, k) && D <= DENSE_I8_MAX_D; }
+
+extern "C" void rc_dense_sq8_error_constants(double* c) {
+    c[0] = DENSE_SQ8_C_Q;
+    c[1] = DENSE_SQ8_C_W;
+    c[2] = DENSE_SQ8_C_AD;
+    c[3] = DENSE_SQ8_C_AC;
+    c[4] = DENSE_SQ8_C_B;
+    c[5] = DENSE_SQ8_C_CH;
+    c[6] = DENSE_SQ8_C_ABS;
+}
+extern "C" int rc_dense_sq8_qmax(void) { return DENSE_I8_QMAX; }
+extern "C" int rc_dense_sq8_max_d(void) { return DENSE_I8_MAX_D; }
+
+extern "C" size_t rc_dense_sq8_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
+    return dense_sq8_shape_ok(N, D, nq, k) ? dense_exact_ws_bytes(N, D, nq, k) : 0;
+}
+
+extern "C" size_t rc_dense_sq8_search_ws_bytes(int64_t N, int D, int nq, int k) {
+    return dense_sq8_shape_ok(N, D, nq, k) ? dense_search_ws_bytes<dense_sq8_variant>(N, D, nq, k) : 0;
+}
+
+extern "C" int rc_dense_sq8_search_ws_counts(int64_t N, int D, int nq, int k, size_t* cnt_off) {
+    if (!cnt_off) return RC_EINVAL;
+    *cnt_off = 0;
+    if (!dense_sq8_shape_ok(N, D, nq, k)) return RC_ESHAPE;
+    if (!dense_exact_route(N)) *cnt_off = dense_fast_ws(N, nq).cnt;
+    return RC_OK;
+}
+
+extern "C" size_t rc_dense_sq8_scores_ws_bytes(int D, int nq) {
+    return D > 0 && D <= DENSE_I8_MAX_D && nq > 0 ? dense_i8_query_ws(nq, D).total : 0;
+}
+
+extern "C" int rc_dense_sq8_search_exact(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                         const float* dec, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                                         size_t ws_bytes, rc_stream_t stream) {
+    if (D > DENSE_I8_MAX_D) return RC_ESHAPE;
+    return dense_exact_entry<dense_sq8_variant>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, ws, ws_bytes, stream, dec);
+}
+
+extern "C" int rc_dense_sq8_scores(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                   const float* dec, float* out, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (N > 0xFFFFFFFFll || D > DENSE_I8_MAX_D) return RC_ESHAPE;
+    if (!h || !x || !q || !dec || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
+    if (nq == 0) return RC_OK;
+    if (!ws || ((uintptr_t)ws & 15u) || ws_bytes < dense_i8_query_ws(nq, D).total) return RC_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const int rc = dense_i8_launch_prepass(h, q, nq, D, dec, (char*)ws, s);
+    if (rc != RC_OK) return rc;
+    return dense_i8_launch_gemm<DENSE_STORE>(h, x, ldx, N, N, 0, (const char*)ws, nq, D, nullptr, out, nullptr, nullptr, s);
+}
+
+extern "C" int rc_dense_sq8_decode(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* dec, float* out,
+                                   rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (N > 0xFFFFFFFFll || D > DENSE_I8_MAX_D) return RC_ESHAPE;
+    if (!h || !x || !dec || !out || N < 0 || D <= 0 || ldx < D) return RC_EINVAL;
+    if (N == 0) return RC_OK;
+    hipLaunchKernelGGL(dense_sq8_decode_kernel, dim3((unsigned)((N * D + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, ldx,
+                       N, D, dec, out);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+extern "C" int rc_dense_sq8_search_q(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                     const float* dec, const float* cstat, int k, int64_t id_offset, double sel_slack,
+                                     float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                                     rc_stream_t stream) {
+    if (D > DENSE_I8_MAX_D) return RC_ESHAPE;
+    return dense_search_entry<dense_sq8_variant>(h, x, ldx, N, D, q, nq, dec, cstat, k, id_offset, sel_slack, scores, ids, status,
+                                                 qstatus, ws, ws_bytes, stream);
+}

@@ -285,3 +285,106 @@ class FlatL2Bf16x3Index(_FlatL2):
 
     def _stored(self, xt: torch.Tensor) -> torch.Tensor:
         return self._finite_bf16(xt)
+
+
+class FlatSQ8Index(_FlatIndex):
+    """Exact inner-product index over 8-bit scalar-quantiser codes resident in HBM: `faiss.IndexScalarQuantizer(d, QT_8bit,
+    METRIC_INNER_PRODUCT)`, one byte per dimension.  Duck-typed like `FlatIPIndex`, plus `train`.
+
+    `train(x)`: per dimension vmin and vmax over the training rows (Faiss's RS_minmax with argument 0), step = fp32((vmax -
+    vmin) / 255) and mid = fp32(vmin + 128.5 step), evaluated in fp64 and rounded once.  `add` encodes c = clamp(floor((x -
+    vmin) / step), 0, 255) in fp32 (0 where step = 0; values outside the trained range clamp) and stores c - 128 as int8; a
+    non-finite value is refused before anything is stored (the one host read of an `add`).  A stored row IS its decoded value
+    x^ = fmaf(c - 128, step, mid), the centre of its bin (`reconstruct_n`), and `search` answers with `ops.dense_search_sq8`
+    (csrc/dense_search_sq8.hip): ids and score bits are what `FlatIPIndex` returns over `reconstruct_n(0, ntotal)`.  `reset`
+    drops the rows and keeps the training.  Beside the codes the index keeps the two statistics of the search's certificate
+    (`ops.dense_sq8_cstat`), updated by `add` without a host read.  METRIC_L2 is not served."""
+
+    def __init__(self, d: int, device: Optional[torch.device] = None, metric: int = METRIC_INNER_PRODUCT):
+        if metric != METRIC_INNER_PRODUCT:
+            raise ValueError("FlatSQ8Index: METRIC_INNER_PRODUCT only (L2 over int8 codes is not served)")
+        if not 1 <= int(d) <= ops.DENSE_SQ8_MAX_D:
+            raise ValueError(f"FlatSQ8Index: d must be in [1, {ops.DENSE_SQ8_MAX_D}]")
+        self._init_store(d, device, torch.int8)
+        self.metric_type = METRIC_INNER_PRODUCT
+        self.is_trained = False
+        self.vmin = self.step = self.mid = None
+        self._dec = None            # [2, d] fp32: step, mid
+        self._cstat = None          # [2] fp32: the largest row L1 norm of the codes, a bound of the largest decoded row norm
+
+    ROWS_PER_STEP = 1 << 18     # rows that `train` and `add` move and encode at a time
+
+    def train(self, x) -> None:
+        xt = self._rows(x)
+        if xt.shape[0] == 0:
+            raise ValueError("train: no rows")
+        vmin = torch.full((self.d,), float("inf"), device=self.device)
+        vmax = -vmin
+        for r0 in range(0, xt.shape[0], self.ROWS_PER_STEP):
+            part = xt[r0:r0 + self.ROWS_PER_STEP].to(self.device, torch.float32)
+            vmin, vmax = torch.minimum(vmin, part.amin(0)), torch.maximum(vmax, part.amax(0))     # a NaN propagates
+        if not bool((torch.isfinite(vmin) & torch.isfinite(vmax)).all()):
+            raise ValueError("train: finite values only")
+        step = ((vmax.double() - vmin.double()) / 255.0).float()
+        mid = (vmin.double() + 128.5 * step.double()).float()
+        if not bool((torch.isfinite(step) & torch.isfinite(mid)).all()):
+            raise ValueError("train: the range of a dimension exceeds fp32")
+        self.vmin = vmin
+        self._dec = torch.stack([step, mid]).contiguous()
+        self.step, self.mid = self._dec[0], self._dec[1]
+        self.is_trained = True
+
+    def _need_trained(self, what: str) -> None:
+        if not self.is_trained:
+            raise ValueError(f"{what}: the index is not trained (train(x) sets the per-dimension ranges)")
+
+    def encode(self, xt: torch.Tensor) -> torch.Tensor:
+        """The int8 codes c - 128 of fp32 rows on the index's device."""
+        c = torch.floor((xt - self.vmin) / self.step).clamp_(0.0, 255.0)
+        c = torch.where(self.step == 0, torch.zeros_like(c), c)
+        return (c - 128.0).to(torch.int8)
+
+    def add(self, x) -> None:
+        xt = self._rows(x)
+        self._need_trained("add")
+        n = xt.shape[0]
+        if n == 0:
+            return
+        need = self.ntotal + n
+        self._grow_for(need)
+        # the codes are written past ntotal and count only once every value has been seen to be finite (one host read)
+        finite = torch.ones((), dtype=torch.bool, device=self.device)
+        cstat = torch.zeros((2,), dtype=torch.float32, device=self.device)
+        for r0 in range(0, n, self.ROWS_PER_STEP):
+            part = xt[r0:r0 + self.ROWS_PER_STEP].to(self.device, torch.float32)
+            finite &= torch.isfinite(part).all()
+            codes = self.encode(torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0))
+            self._x[self.ntotal + r0:self.ntotal + r0 + codes.shape[0]] = codes
+            cstat = torch.maximum(cstat, ops.dense_sq8_cstat(codes, self._dec))
+        if not bool(finite):
+            raise ValueError("add: int8 storage needs finite values")
+        self.ntotal = need
+        self._cstat = cstat if self._cstat is None else torch.maximum(self._cstat, cstat)
+
+    def reset(self) -> None:
+        super().reset()
+        self._cstat = None
+
+    def reconstruct_n(self, i0: int = 0, ni: int = -1) -> torch.Tensor:
+        """fp32 [ni, d]: the decoded rows i0 .. i0 + ni - 1 (ni = -1: up to ntotal), as the search scores them."""
+        self._need_trained("reconstruct_n")
+        ni = self.ntotal - int(i0) if ni < 0 else int(ni)
+        if not (0 <= int(i0) and ni >= 0 and int(i0) + ni <= self.ntotal):
+            raise ValueError(f"reconstruct_n: rows [{i0}, {int(i0) + ni}) outside [0, {self.ntotal})")
+        return ops.dense_sq8_decode(self._x[int(i0):int(i0) + ni], self._dec)
+
+    def search_async(self, x, k: int):
+        self._need_trained("search")
+        return super().search_async(x, k)
+
+    def rerank(self, x, cand_ids, k: int):
+        raise ValueError("FlatSQ8Index: rerank over an int8 store is not served")
+
+    def _enqueue(self, q, k: int):
+        return ops.dense_search_sq8(self.xb, self._dec, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
+                                    cstat=self._cstat)

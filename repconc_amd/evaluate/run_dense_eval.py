@@ -59,6 +59,9 @@ class EvalArguments(TrainingArguments):
     search_batch: int = field(default=1200)
     index_float16: bool = field(default=False, metadata={"help": "store the corpus as fp16 (half the memory; vectors and "
                                                                   "queries are rounded to fp16, the search stays exact)"})
+    index_int8: bool = field(default=False, metadata={"help": "store the corpus as 8-bit scalar-quantiser codes (a quarter of the "
+                                                               "memory; flat inner-product index only, trained on the corpus; "
+                                                               "scores are exact for the decoded vectors)"})
     index_screen: str = field(default="fp32", metadata={"help": "fp32, or bf16x3: the fp32 index with its candidates chosen on "
                                                                 "the bf16 matrix cores (same results; not with index_float16)"})
     index_metric: str = field(default="ip", metadata={"help": "ip: inner product; l2: squared Euclidean distance, smallest first "
@@ -117,7 +120,8 @@ def search_and_compute_metrics(corpus_embeds, corpus_ids, query_embeds, query_id
     metric = getattr(eval_args, "index_metric", "ip")
     index = create_index(corpus_embeds, use_float16=getattr(eval_args, "index_float16", False),
                          screen=getattr(eval_args, "index_screen", "fp32"), metric=metric,
-                         nlist=getattr(eval_args, "index_nlist", 0), nprobe=getattr(eval_args, "index_nprobe", 8))
+                         nlist=getattr(eval_args, "index_nlist", 0), nprobe=getattr(eval_args, "index_nprobe", 8),
+                         storage="int8" if getattr(eval_args, "index_int8", False) else None)
     all_topk_scores, all_topk_ids = batch_dense_search(query_ids, query_embeds, corpus_ids, index, eval_args.topk,
                                                        batch_size=eval_args.search_batch)
     if metric == "l2":
@@ -138,7 +142,7 @@ def main(argv=None):
     parser = HfArgumentParser((ModelArguments, DataArguments, EvalArguments))
     model_args, data_args, eval_args = parser.parse_args_into_dataclasses(argv)
     check_index_options(eval_args.index_metric, eval_args.index_float16, eval_args.index_screen,
-                        eval_args.index_nlist)                                                              # before encoding
+                        eval_args.index_nlist, "int8" if eval_args.index_int8 else None)                   # before encoding
     main_process = is_main_process(eval_args.local_rank)
     logging.basicConfig(format="%(asctime)s - %(levelname)s - %(name)s -   %(message)s", datefmt="%m/%d/%Y %H:%M:%S",
                         level=logging.INFO if main_process else logging.WARN)

@@ -11,6 +11,8 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
                                                                         useFloat16: FlatIPIndex(d, storage="float16"))
     faiss.IndexFlatL2(d)                                                evaluate_repconc.py:102, run_warmup.py:102,107 (exact
                                                                         fp32 squared distances, dense_index.FlatL2Index)
+    faiss.IndexScalarQuantizer(d, faiss.ScalarQuantizer.QT_8bit,        not in the reference; the flat format between fp16 and PQ
+                               faiss.METRIC_INNER_PRODUCT)              (one byte per dimension, dense_index.FlatSQ8Index)
     faiss.IndexIVFFlat(quantizer, d, nlist[, metric])                   not in the reference; what a Faiss user expects beside
                                                                         IndexFlat* and IndexIVFPQ (exact scan of the probed cells,
                                                                         ivf_flat.IVFFlatIndex)
@@ -25,7 +27,7 @@ from __future__ import annotations
 import numpy as np
 import torch
 
-from .dense_index import FlatIPIndex, FlatL2Index
+from .dense_index import FlatIPIndex, FlatL2Index, FlatSQ8Index
 from .faiss_io import read_index, write_index  # noqa: F401  (re-exported)
 from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex  # noqa: F401  (METRIC_L2 re-exported)
 from .ivf_flat import IVFFlatIndex
@@ -37,6 +39,25 @@ def IndexPQ(d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT) -> PQIn
 
 IndexFlatIP = FlatIPIndex      # faiss.IndexFlatIP(d): exact inner product over fp32 vectors resident on the device
 IndexFlatL2 = FlatL2Index      # faiss.IndexFlatL2(d): exact squared Euclidean distance over the same storage
+
+
+class ScalarQuantizer:
+    """faiss.ScalarQuantizer's quantiser types, Faiss's numbering.  QT_8bit is the one that is served."""
+    QT_8bit, QT_4bit, QT_8bit_uniform, QT_4bit_uniform, QT_fp16, QT_8bit_direct, QT_6bit = range(7)
+
+
+class IndexScalarQuantizer(FlatSQ8Index):
+    """faiss.IndexScalarQuantizer(d, qtype, metric): `FlatSQ8Index` with Faiss's argument order.  Faiss's default metric is
+    METRIC_L2, which is not served over int8 codes: the metric has to be given as METRIC_INNER_PRODUCT, and any qtype but
+    ScalarQuantizer.QT_8bit is refused."""
+
+    def __init__(self, d: int, qtype: int = ScalarQuantizer.QT_8bit, metric=METRIC_L2, device=None):
+        if qtype != ScalarQuantizer.QT_8bit:
+            raise ValueError("IndexScalarQuantizer: only ScalarQuantizer.QT_8bit is served")
+        if metric != METRIC_INNER_PRODUCT:
+            raise ValueError("IndexScalarQuantizer: only METRIC_INNER_PRODUCT is served (pass it: Faiss's default is METRIC_L2)")
+        super().__init__(d, device=device, metric=metric)
+        self.qtype = qtype
 
 
 class IndexIVFFlat(IVFFlatIndex):

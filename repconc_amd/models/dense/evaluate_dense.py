@@ -19,7 +19,7 @@ from typing import Dict, Union
 import numpy as np
 import torch
 
-from ...dense_index import FlatIPIndex, FlatL2Bf16x3Index, FlatL2F16Index, FlatL2Index
+from ...dense_index import FlatIPIndex, FlatL2Bf16x3Index, FlatL2F16Index, FlatL2Index, FlatSQ8Index
 from ...index import METRIC_INNER_PRODUCT, METRIC_L2
 from ...ivf_flat import IVFFlatIndex
 from ...utils.eval_utils import TextDataset, get_collator_func
@@ -124,14 +124,20 @@ def batch_dense_search(query_ids: np.ndarray, query_embeds, corpus_ids: np.ndarr
 
 
 INDEX_METRICS = ("ip", "l2")
+INDEX_STORAGES = (None, "int8")
 
 
-def check_index_options(metric: str, use_float16: bool, screen: str, nlist: int = 0) -> None:
+def check_index_options(metric: str, use_float16: bool, screen: str, nlist: int = 0, storage=None) -> None:
     """ValueError for an unknown metric, storage or screen, or a combination that does not exist (fp16 storage with the bf16x3
-    screen, under either metric; the bf16x3 screen with an IVF index, nlist > 0); touches no device.  The one rule of
-    `create_index` and of run_dense_eval's arguments."""
+    screen, under either metric; the bf16x3 screen with an IVF index, nlist > 0; storage="int8" with fp16 storage, the bf16x3
+    screen, nlist > 0 or the L2 metric); touches no device.  The one rule of `create_index` and of run_dense_eval's arguments."""
     if metric not in INDEX_METRICS:
         raise ValueError(f"metric must be one of {list(INDEX_METRICS)}, got {metric!r}")
+    if storage not in INDEX_STORAGES:
+        raise ValueError(f"storage must be one of {list(INDEX_STORAGES)}, got {storage!r}")
+    if storage == "int8" and (use_float16 or screen != "fp32" or int(nlist) > 0 or metric != "ip"):
+        raise ValueError("storage='int8' is the flat inner-product index over 8-bit codes: it cannot be combined with "
+                         "use_float16, screen='bf16x3', nlist > 0 or metric='l2'")
     FlatIPIndex.check_options("float16" if use_float16 else "float32", screen)
     if int(nlist) < 0 or int(nlist) > IVFFlatIndex.MAX_NLIST:
         raise ValueError(f"nlist must be in [0, {IVFFlatIndex.MAX_NLIST}], got {nlist!r}")
@@ -142,7 +148,8 @@ def check_index_options(metric: str, use_float16: bool, screen: str, nlist: int 
 IVF_TRAIN_ROWS = 1 << 18       # rows of the seeded sample the coarse centroids are fitted on (IVFPQIndex.from_flat's)
 
 
-def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="fp32", metric="ip", nlist=0, nprobe=8):
+def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="fp32", metric="ip", nlist=0, nprobe=8,
+                 storage=None):
     """An exact index holding `corpus_embeds`, on device `single_gpu_id` or the current device.
     use_float16: store the vectors as fp16 (GpuClonerOptions.useFloat16, which the reference leaves False).
     screen="bf16x3" (fp32 storage only): the same results, candidates chosen on the bf16 matrix cores.
@@ -150,10 +157,17 @@ def create_index(corpus_embeds, single_gpu_id=None, use_float16=False, screen="f
     `FlatL2Index`, `FlatL2F16Index` (use_float16) or `FlatL2Bf16x3Index` (screen="bf16x3").
     nlist > 0: an `IVFFlatIndex` of that many cells instead (faiss.IndexIVFFlat; not in the reference): the coarse centroids are
     fitted on a seeded sample of at most 2^18 rows, as `IVFPQIndex.from_flat` fits them, and a search scores exactly the rows of
-    the `nprobe` best cells of every query — the flat index's scores for the rows it reaches, not every row."""
-    check_index_options(metric, use_float16, screen, nlist)                                    # before a device is looked at
+    the `nprobe` best cells of every query — the flat index's scores for the rows it reaches, not every row.
+    storage="int8" (metric "ip", flat, alone): a `FlatSQ8Index` (faiss.IndexScalarQuantizer, QT_8bit), one byte per dimension,
+    trained on the batch it is given, `corpus_embeds`; its scores are exact for the DECODED rows, the centres of their bins."""
+    check_index_options(metric, use_float16, screen, nlist, storage)                           # before a device is looked at
     dev = torch.device("cuda", single_gpu_id if single_gpu_id is not None else torch.cuda.current_device())
     d = corpus_embeds.shape[1]
+    if storage == "int8":
+        index = FlatSQ8Index(d, device=dev)
+        index.train(corpus_embeds)
+        index.add(corpus_embeds)
+        return index
     if int(nlist) > 0:
         index = IVFFlatIndex(d, int(nlist), device=dev, metric=METRIC_L2 if metric == "l2" else METRIC_INNER_PRODUCT,
                              storage="float16" if use_float16 else "float32")

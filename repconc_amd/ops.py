@@ -1121,6 +1121,7 @@ DENSE_SEL_SLACK = ADC_SEL_SLACK     # head-room of the dense search's sampled th
 DENSE_MAX_K = 8192                  # the select's cap (ADC_CAND_CAP / 2, csrc/topk.h)
 DENSE_EXACT_MAX_N = 131072          # up to here every dense search takes the exact route (csrc/dense_gemm.h)
 DENSE_QCHUNK = 2048                 # queries per library call: <= 2048 x 256 KiB of sample scores and candidate keys
+DENSE_SQ8_MAX_D = 65536             # widest row of the int8 search (DENSE_I8_MAX_D, csrc/dense_i8_gemm.h)
 
 
 def _dense_args(x: torch.Tensor, q: torch.Tensor, k: int):
@@ -1153,7 +1154,24 @@ def _dense_f16_args(x16: torch.Tensor, q: torch.Tensor, k: int):
     return x16, q16
 
 
-# One dense search in six variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
+def _dense_sq8_args(x8: torch.Tensor, q: torch.Tensor, k: int):
+    if x8.dim() != 2 or q.dim() != 2 or x8.shape[1] != q.shape[1]:
+        raise ValueError("dense search: x [N, D] and q [nq, D] with the same D")
+    if x8.dtype != torch.int8:
+        raise ValueError("dense_search_sq8: the corpus must be int8 codes, c - 128 (FlatSQ8Index encodes them)")
+    if not 1 <= int(k) <= DENSE_MAX_K:
+        raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
+    if x8.shape[1] > DENSE_SQ8_MAX_D:
+        raise ValueError(f"dense_search_sq8: D must be <= {DENSE_SQ8_MAX_D} (the screen's int32 accumulators)")
+    _need_cuda(x8, q)
+    if x8.stride(1) != 1 or (x8.shape[0] > 1 and x8.stride(0) < x8.shape[1]):
+        x8 = x8.contiguous()
+    if x8.shape[0] >= 1 << 32:
+        raise ValueError("dense search: N must be < 2^32")
+    return x8, q.to(x8.device, torch.float32).contiguous()
+
+
+# One dense search in seven variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
 # library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes; exact: rc_<exact>_search_exact / ..._ws_bytes, the route that
 # cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate);
 # rownorms: it also takes xsq, the squared norm of every row, before xnorm_max; pad: the value of the slots past N.
@@ -1165,9 +1183,12 @@ _DENSE_BF16X3 = _DenseVariant(_dense_args, "dense_bf16x3", "dense", True)
 _DENSE_L2 = _DenseVariant(_dense_args, "dense_l2", "dense_l2", True, True, float("inf"))
 _DENSE_L2_F16 = _DenseVariant(_dense_f16_args, "dense_l2_f16", "dense_l2_f16", True, True, float("inf"))
 _DENSE_L2_BF16X3 = _DenseVariant(_dense_args, "dense_l2_bf16x3", "dense_l2", True, True, float("inf"))
+# int8 codes: both entries take the decoding vectors `dec` after the queries, the search also the corpus statistics `cstat`
+_DENSE_SQ8 = _DenseVariant(_dense_sq8_args, "dense_sq8", "dense_sq8", False)
 
 
-def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int):
+def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int,
+                        dec: Optional[torch.Tensor] = None):
     x, q = v.args(x, q, k)
     N, D = x.shape
     nq = q.shape[0]
@@ -1181,14 +1202,16 @@ def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: i
     name = f"rc_{v.exact}_search_exact"
     wsb = getattr(lib, name + "_ws_bytes")(N, D, nq, int(k))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-    _lib.check(getattr(lib, name)(h, _p(x), x.stride(0), N, D, _p(q), nq, int(k), int(id_offset), _p(scores), _p(ids),
+    side = () if dec is None else (_p(dec),)
+    _lib.check(getattr(lib, name)(h, _p(x), x.stride(0), N, D, _p(q), nq, *side, int(k), int(id_offset), _p(scores), _p(ids),
                                   _p(ws), wsb, s), name, h)
     return scores, ids
 
 
 def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int, sel_slack: Optional[float],
                   defer: bool, method: str, max_retries: int, xnorm_max: Optional[torch.Tensor] = None,
-                  xsq: Optional[torch.Tensor] = None):
+                  xsq: Optional[torch.Tensor] = None, dec: Optional[torch.Tensor] = None,
+                  cstat: Optional[torch.Tensor] = None, stats: Optional[dict] = None):
     if method not in ("auto", "exact"):
         raise ValueError("method must be 'auto' or 'exact'")
     x, q = v.args(x, q, k)
@@ -1197,10 +1220,10 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
     N, D = x.shape
     nq = q.shape[0]
     if method == "exact" or nq == 0 or N == 0:
-        got = _dense_search_exact(v, x, q, k, id_offset)
+        got = _dense_search_exact(v, x, q, k, id_offset, dec)
         return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
     lib, h, _, dev = _ctx(q)
-    norm = ()                                 # the tensors behind the entry's extra pointer arguments
+    norm = () if dec is None else (dec, cstat)    # the tensors behind the entry's extra pointer arguments
     if v.normed:
         if xnorm_max is None:
             # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the norm
@@ -1226,11 +1249,16 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
             _lib.check(search_q(h, _p(x), x.stride(0), N, D, _p(qq[c0:c0 + n]), n, *map(_p, norm), int(k), int(id_offset),
                                 float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]), _p(status), _p(qstatus[c0:c0 + n]),
                                 _p(ws), wsb, st), name, h)
+            if stats is not None and len(stats.setdefault("survivors", [])) * DENSE_QCHUNK < nq:
+                off = C.c_size_t(0)          # measurement: the first pass's candidate counts (rc_<entry>_search_ws_counts)
+                _lib.check(getattr(lib, f"rc_{v.entry}_search_ws_counts")(N, D, n, int(k), C.byref(off)), name, h)
+                if off.value:
+                    stats["survivors"].append(ws[off.value:off.value + 4 * n].view(torch.int32).clone())
 
     def rerun(idx, slack, exact):
         qq = q[idx].contiguous()
         if exact:
-            s_, i_ = _dense_search_exact(v, x, qq, k, id_offset)
+            s_, i_ = _dense_search_exact(v, x, qq, k, id_offset, dec)
             return s_, i_, None
         s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q.device)
         i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q.device)
@@ -1497,6 +1525,118 @@ def dense_search_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int
     `dense_search_exact`; `.stats` of the `PendingSearch`).  xnorm_max: device fp32 [1], >= the largest row norm of x
     (`dense_xnorm_max`, computed here when None).  Everything else as `dense_search`."""
     return _dense_search(_DENSE_BF16X3, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max)
+
+
+# ------------------------------------------------------------------------- dense, 8-bit scalar-quantised storage
+def dense_sq8_error_constants():
+    """(c_q, c_w, c_ad, c_ac, c_b, c_ch, c_abs) of E_q as the certificate kernel was compiled with them
+    (csrc/dense_search_sq8.hip).  No GPU needed."""
+    c = (C.c_double * 7)()
+    _lib.load().rc_dense_sq8_error_constants(c)
+    return tuple(float(v) for v in c)
+
+
+def dense_sq8_qmax() -> int:
+    """The largest |256 h + l| of the query pre-pass, 127 * 256 + 127 (DENSE_I8_QMAX, csrc/dense_i8_gemm.h)."""
+    return int(_lib.load().rc_dense_sq8_qmax())
+
+
+def dense_sq8_error_bound(D: int, alpha, w1, b1, qnorm, c1, xmax):
+    """E_q of the certificate of `dense_search_sq8` (include/repconc_hip.h, rc_dense_sq8_search_q; derivation in the header
+    comment of csrc/dense_search_sq8.hip): the bound on |s~ - s| between the int8 screen and the fmaf chain.  alpha: the
+    query's quantisation step, w1 = sum_d |fl(q_d step_d)|, b1 = sum_d |q_d mid_d|, qnorm = ||q||_2, c1 >= the largest
+    sum_d |c'_d| of a row, xmax >= the largest norm of a decoded row.  The constants are the library's.  Plain float / numpy
+    arithmetic: scalars or arrays."""
+    c_q, c_w, c_ad, c_ac, c_b, c_ch, c_abs = dense_sq8_error_constants()
+    dpad = float((int(D) + 15) // 16 * 16)
+    rel = c_q * alpha * c1 + 2.0 ** -24 * (c_w * w1 + c_ad * alpha * D + c_ac * alpha * c1 + c_b * b1
+                                          + c_ch * (dpad + 1.0) * qnorm * xmax)
+    return (rel + c_abs * 2.0 ** -149 * (dpad + dpad ** 0.5 * qnorm + c1 + 1.0)) * (1.0 + 2.0 ** -20)
+
+
+def _dense_sq8_dec(x8: torch.Tensor, dec: torch.Tensor) -> torch.Tensor:
+    if dec.shape != (2, x8.shape[1]):
+        raise ValueError("dense_search_sq8: dec must be [2, D]: the steps, then the mids")
+    _need_cuda(dec)
+    return dec.to(x8.device, torch.float32).contiguous()
+
+
+def dense_sq8_decode(x8: torch.Tensor, dec: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
+    """The decoded corpus, fp32 [N, D]: x^ = fmaf(c', step, mid) with one rounding (rc_dense_sq8_decode) — the rows whose
+    `dense_search` IS `dense_search_sq8`."""
+    x8, _ = _dense_sq8_args(x8, x8.new_zeros((0, x8.shape[1]), dtype=torch.float32), 1)
+    dec = _dense_sq8_dec(x8, dec)
+    N, D = x8.shape
+    out = torch.empty((N, D), dtype=torch.float32, device=x8.device)
+    if N:
+        lib, h, s, _ = _ctx(x8)
+        for r0 in range(0, N, rows_per_step):
+            n = min(rows_per_step, N - r0)
+            _lib.check(lib.rc_dense_sq8_decode(h, _p(x8[r0:]), x8.stride(0), n, D, _p(dec), _p(out[r0:]), s),
+                       "rc_dense_sq8_decode", h)
+    return out
+
+
+def dense_sq8_cstat(x8: torch.Tensor, dec: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
+    """Device fp32 [2]: C1 = the largest sum_d |c'_d| of a row of `x8` (an integer below 2^24: exact) and X >= the largest
+    Euclidean norm of a decoded row (fp64 sums over the fp64 decode, pushed upwards by 2^-20, which covers both the decode's
+    fp32 rounding and the conversion): the `cstat` of `dense_search_sq8`.  No host synchronisation."""
+    step, mid = dec[0].double(), dec[1].double()
+    c1 = torch.zeros((), dtype=torch.float64, device=x8.device)
+    xx = torch.zeros((), dtype=torch.float64, device=x8.device)
+    for r0 in range(0, x8.shape[0], rows_per_step):
+        c = x8[r0:r0 + rows_per_step].double()
+        c1 = torch.maximum(c1, c.abs().sum(1).max())
+        xx = torch.maximum(xx, (c * step + mid).square_().sum(1).max())
+    return torch.stack([c1, xx.sqrt() * (1.0 + 2.0 ** -20)]).float()
+
+
+def dense_search_sq8_exact(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+    """The same answer as `dense_search_sq8` by the route that cannot fail (rc_dense_sq8_search_exact)."""
+    return _dense_search_exact(_DENSE_SQ8, x8, q, k, id_offset, _dense_sq8_dec(x8, dec))
+
+
+def dense_sq8_scores(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """The raw approximate scores s~ [nq, N] of the int8 matrix-core screen (rc_dense_sq8_scores): a test hook, never a
+    result."""
+    x8, q = _dense_sq8_args(x8, q, 1)
+    dec = _dense_sq8_dec(x8, dec)
+    lib, h, s, _ = _ctx(q)
+    out = torch.empty((q.shape[0], x8.shape[0]), dtype=torch.float32, device=q.device)
+    if out.numel():
+        wsb = lib.rc_dense_sq8_scores_ws_bytes(x8.shape[1], q.shape[0])
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        _lib.check(lib.rc_dense_sq8_scores(h, _p(x8), x8.stride(0), x8.shape[0], x8.shape[1], _p(q), q.shape[0], _p(dec),
+                                           _p(out), _p(ws), wsb, s), "rc_dense_sq8_scores", h)
+    return out
+
+
+def dense_search_sq8(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
+                     sel_slack: Optional[float] = None, defer: bool = False, method: str = "auto", max_retries: int = 2,
+                     cstat: Optional[torch.Tensor] = None, stats: Optional[dict] = None):
+    """Exact top-k inner-product search of `q` [nq, D] against a corpus of 8-bit scalar-quantiser codes (faiss
+    IndexScalarQuantizer, QT_8bit): `x8` [N, D] int8 holds c - 128, `dec` [2, D] fp32 the steps and the mids.  A row decodes
+    to fmaf(c', step, mid) and the scores are the fp32 fmaf chain over d ascending over the decoded values: ids and score
+    bits equal `dense_search(dense_sq8_decode(x8, dec), q, k)`.  The int8 matrix cores only screen (two int8 limbs of
+    q * step per query); candidates are rescored by the chain and every answer of the fast route carries a certificate
+    (qstatus bit2 when it cannot be given — also for a non-finite or huge query value: such queries are repeated, then
+    answered by `dense_search_sq8_exact`; `.stats` of the `PendingSearch`).  cstat: device fp32 [2] (`dense_sq8_cstat`,
+    computed here when None).  stats (measurement): receives "survivors", a list of int32 device tensors (one per library
+    call of the FIRST pass) with the rows of every query that passed the screen.  1 <= D <= 65536.  Everything else as
+    `dense_search`."""
+    if x8.dim() == 2 and dec.shape != (2, x8.shape[1]):
+        raise ValueError("dense_search_sq8: dec must be [2, D]: the steps, then the mids")
+    x8, _ = _dense_sq8_args(x8, q, k)
+    dec = _dense_sq8_dec(x8, dec)
+    if cstat is None:
+        # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the statistics
+        cstat = dense_sq8_cstat(x8, dec) if x8.shape[0] > DENSE_EXACT_MAX_N else torch.zeros((2,), device=x8.device)
+    _need_cuda(cstat)
+    if cstat.shape != (2,):
+        raise ValueError("dense_search_sq8: cstat must be [2]: C1 and X (dense_sq8_cstat)")
+    cstat = cstat.to(x8.device, torch.float32).contiguous()
+    return _dense_search(_DENSE_SQ8, x8, q, k, id_offset, sel_slack, defer, method, max_retries, dec=dec, cstat=cstat,
+                         stats=stats)
 
 
 # ---------------------------------------------------------------------------------------------------- dense, L2 metric
