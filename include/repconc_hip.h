@@ -818,6 +818,19 @@ int rc_ivf_flat_f16_search(rc_handle_t h, const uint16_t* x, int64_t ldx, const 
                            int64_t N, int nlist, int D, const uint16_t* q, int nq, const int* probes, int nprobe,
                            int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status, int* qstatus,
                            void* ws, size_t ws_bytes, rc_stream_t stream);
+/* rc_ivf_flat_sq8_search (faiss.IndexIVFScalarQuantizer, QT_8bit, vectors encoded themselves): the same search over a
+ *   list-major store of 8-bit scalar-quantiser codes, x [N, ldx] int8 = c - 128 and dec [2][D] fp32 = step, mid as in
+ *   rc_dense_sq8_search_q; q [nq, D] fp32, not rounded.  A value is decoded once, x^[n][d] = fmaf((float)c'[n][d], step[d],
+ *   mid[d]), and feeds the chain above: scores are bit for bit what rc_ivf_flat_search gives over the decoded rows
+ *   (rc_dense_sq8_decode), under either metric — the scan is the exact chain, no screen and no certificate.  D > rc_dense_sq8_max_d()
+ *   is RC_ESHAPE and is checked first, as the rc_dense_sq8 entries check it; then the checks of rc_ivf_flat_search in their
+ *   order, with dec among the pointers.  16-byte loads when x is
+ *   16-byte aligned and D and ldx are multiples of 16, byte by byte otherwise.  ws: rc_ivf_flat_search_ws_bytes (the layout
+ *   does not depend on the storage type). */
+int rc_ivf_flat_sq8_search(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids, int64_t N,
+                           int nlist, int D, const float* q, int nq, const float* dec, const int* probes, int nprobe,
+                           int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status, int* qstatus,
+                           void* ws, size_t ws_bytes, rc_stream_t stream);
 
 /* ------------------------------------------------------------------ JPQ scoring head (csrc/jpq_head.hip)
  * Scores of (query, document id) pairs straight from the resident codes, and their gradients (stage 2 of the recipe,

@@ -39,6 +39,7 @@
 // intermediate overflows and alpha is normal.  An all-zero w has alpha = 0 and zero limbs: s~ = bias, inside the bound.
 // The constants are exported (rc_dense_sq8_error_constants) and are what ops.dense_sq8_error_bound evaluates.
 #include "dense_i8_gemm.h"
+#include "dense_sq8.h"
 
 #define DENSE_SQ8_C_Q 0.5
 #define DENSE_SQ8_C_W 520.0
@@ -50,10 +51,6 @@
 #define DENSE_SQ8_BIG 0x1p100f                           // the certificate's range: |values| below it, alpha above its inverse
 
 typedef signed char dense_i8x16 __attribute__((ext_vector_type(16)));
-
-__device__ __forceinline__ float dense_sq8_decode(signed char c, float step, float mid) {
-    return __builtin_fmaf((float)c, step, mid);
-}
 
 // ---- rescoring --------------------------------------------------------------------------------------------------------------
 // dense_rescore_kernel (dense_screen.h) over coded rows: grid (nq, ADC_CAND_CAP / 256) blocks of 256 threads, one lane per

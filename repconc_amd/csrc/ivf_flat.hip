@@ -33,9 +33,15 @@
 // PAD: rows that are not 16-byte aligned (or a D that is no multiple of 16 bytes) are read element by element into the same
 // registers; the arithmetic is the same.  Rows past the cell's end in the last chunk repeat its last row and are not written.
 //   LDS: 2 x 16 x 516 x 4 + 2 x 16 x 8 x 4 = 67 072 bytes, two blocks per CU.
+// ivf_flat_sq8_scan_kernel (rc_ivf_flat_sq8_search; faiss.IndexIVFScalarQuantizer, QT_8bit): the same scan over a list-major
+// store of 8-bit scalar-quantiser codes, fp32 queries.  A code is decoded once, fmaf((float)c', step_d, mid_d) (dense_sq8.h), on
+// its way from the staged registers into the same fp32 tile: the chains, and so the score bits, are those of the fp32 scan over
+// the decoded rows under either metric.  Same LDS, same plan, same selection.
 #include "dense_l2.h"
+#include "dense_sq8.h"
 #include "ivf_plan.h"
 #include "ivf_select.h"
+#include <type_traits>
 
 #define IVFF_QG 8                                        // queries per task
 #define IVFF_RT 512                                      // rows per chunk
@@ -83,17 +89,22 @@ __global__ __launch_bounds__(256) void ivf_flat_plan_query_kernel(const int64_t*
     if (bad) atomicOr(status, 4);
 }
 
-// grid (task bound, <= IVFF_Y_MAX).  dense / rowid: [nq][stride].
-template <typename T, bool L2, bool PAD>
-__global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restrict__ x, int64_t ldx,
-                                                               const int64_t* __restrict__ list_off, int D,
-                                                               const T* __restrict__ q, const int* __restrict__ probes,
-                                                               const int* __restrict__ base, int nprobe, int64_t stride,
-                                                               const int* __restrict__ task_list,
-                                                               const int* __restrict__ task_qstart,
-                                                               const int* __restrict__ task_qcnt,
-                                                               const int* __restrict__ sorted_q, float* __restrict__ dense,
-                                                               int* __restrict__ rowid) {
+// The scan's body.  T: the stored type, TQ: the queries' (T itself for the fp32 and fp16 stores).  T = signed char is the coded
+// form: rows of 8-bit scalar-quantiser codes c' = c - 128 (dense_sq8.h), fp32 queries that are not rounded, dec = [step | mid].
+// A value is decoded once per (row, d), on its way from the staged registers into the fp32 tile, so the compute loop and the
+// LDS tile are those of the other stores and the 16 chains see fmaf((float)c', step_d, mid_d).  A row's slice of a stage is
+// ONE 16-byte piece there (P = 1): the 64 lanes of a load touch 64 rows, and the seven later stages of a row's 128-byte line
+// are served by the caches.  Holding the slices of 2 or 4 stages in registers (one wider fetch per lane every 2 or 4 stages)
+// was measured and is slower at every nprobe (profiles/ivf_flat_sq8_form_ab.txt); this form is the one kept.
+template <typename T, typename TQ, bool L2, bool PAD>
+__device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int64_t ldx, const int64_t* __restrict__ list_off,
+                                                   int D, const TQ* __restrict__ q, const float* __restrict__ dec,
+                                                   const int* __restrict__ probes, const int* __restrict__ base, int nprobe,
+                                                   int64_t stride, const int* __restrict__ task_list,
+                                                   const int* __restrict__ task_qstart, const int* __restrict__ task_qcnt,
+                                                   const int* __restrict__ sorted_q, float* __restrict__ dense,
+                                                   int* __restrict__ rowid) {
+    constexpr bool SQ = std::is_same<T, signed char>::value;
     constexpr int EPP = 16 / (int)sizeof(T);                 // values per 16-byte piece
     constexpr int P = IVFF_KC / EPP;                         // pieces of a row's slice
     constexpr int NL = IVFF_RT * P / 256;                    // pieces per loader thread and stage
@@ -123,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restri
     // the query loader: thread (g = tid / 16, kk = tid % 16) of the first 128 stages value k0 + kk of query g
     const int qg = tid >> 4, qk = tid & 15;
     const bool qload = tid < IVFF_QG * IVFF_KC;
-    const T* qp = q + (int64_t)((qload && qg < qc) ? sorted_q[qs + qg] : sorted_q[qs]) * D;
+    const TQ* qp = q + (int64_t)((qload && qg < qc) ? sorted_q[qs + qg] : sorted_q[qs]) * D;
     const int nkc = (D + IVFF_KC - 1) / IVFF_KC;
     for (int64_t ch = blockIdx.y; ch * IVFF_RT < size; ch += gridDim.y) {
         const int64_t r0 = c0 + ch * IVFF_RT;
@@ -135,6 +146,7 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restri
             for (int r = 0; r < 4; ++r) acc[a][r] = 0.f;
         ivff_u4 stg[NL];
         float rq = 0.f;
+        float dstep[SQ ? IVFF_KC : 1], dmid[SQ ? IVFF_KC : 1];      // coded form: step and mid of the staged slice (wave-uniform)
         // piece i = j 256 + tid of the stage: row i / P of the chunk, piece i % P of its slice; whole pieces inside the row with
         // one 16-byte load, nothing past D (PAD: value by value)
         auto gload = [&](int kc) {
@@ -154,6 +166,14 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restri
                     stg[j] = u.v;
                 }
             }
+            if constexpr (SQ) {
+#pragma unroll
+                for (int e = 0; e < IVFF_KC; ++e) {               // past D: the last dimension's, no chain reads the value
+                    const int d = k0 + e < D ? k0 + e : D - 1;
+                    dstep[e] = dec[d];
+                    dmid[e] = dec[D + d];
+                }
+            }
             if (qload) rq = (qg < qc && k0 + qk < D) ? (float)qp[k0 + qk] : 0.f;
         };
         auto sstore = [&](int buf) {
@@ -163,7 +183,12 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restri
                 union { ivff_u4 v; T e[EPP]; } u;
                 u.v = stg[j];
 #pragma unroll
-                for (int e = 0; e < EPP; ++e) sx[buf][(pc * EPP + e) * IVFF_XLD + row] = (float)u.e[e];
+                for (int e = 0; e < EPP; ++e) {
+                    if constexpr (SQ)
+                        sx[buf][(pc * EPP + e) * IVFF_XLD + row] = dense_sq8_decode(u.e[e], dstep[pc * EPP + e], dmid[pc * EPP + e]);
+                    else
+                        sx[buf][(pc * EPP + e) * IVFF_XLD + row] = (float)u.e[e];
+                }
             }
             if (qload) sq[buf][qk * IVFF_QG + qg] = rq;
         };
@@ -211,6 +236,36 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restri
     }
 }
 
+// grid (task bound, <= IVFF_Y_MAX).  dense / rowid: [nq][stride].
+template <typename T, bool L2, bool PAD>
+__global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restrict__ x, int64_t ldx,
+                                                               const int64_t* __restrict__ list_off, int D,
+                                                               const T* __restrict__ q, const int* __restrict__ probes,
+                                                               const int* __restrict__ base, int nprobe, int64_t stride,
+                                                               const int* __restrict__ task_list,
+                                                               const int* __restrict__ task_qstart,
+                                                               const int* __restrict__ task_qcnt,
+                                                               const int* __restrict__ sorted_q, float* __restrict__ dense,
+                                                               int* __restrict__ rowid) {
+    ivf_flat_scan_body<T, T, L2, PAD>(x, ldx, list_off, D, q, nullptr, probes, base, nprobe, stride, task_list, task_qstart,
+                                      task_qcnt, sorted_q, dense, rowid);
+}
+
+// The coded form: int8 codes, fp32 queries, dec [2][D].  Same grid.
+template <bool L2, bool PAD>
+__global__ __launch_bounds__(256, 2) void ivf_flat_sq8_scan_kernel(const signed char* __restrict__ x, int64_t ldx,
+                                                                   const int64_t* __restrict__ list_off, int D,
+                                                                   const float* __restrict__ q, const float* __restrict__ dec,
+                                                                   const int* __restrict__ probes, const int* __restrict__ base,
+                                                                   int nprobe, int64_t stride, const int* __restrict__ task_list,
+                                                                   const int* __restrict__ task_qstart,
+                                                                   const int* __restrict__ task_qcnt,
+                                                                   const int* __restrict__ sorted_q, float* __restrict__ dense,
+                                                                   int* __restrict__ rowid) {
+    ivf_flat_scan_body<signed char, float, L2, PAD>(x, ldx, list_off, D, q, dec, probes, base, nprobe, stride, task_list,
+                                                    task_qstart, task_qcnt, sorted_q, dense, rowid);
+}
+
 // ---- host --------------------------------------------------------------------------------------------------------------------
 namespace {
 struct ivff_ws {
@@ -244,9 +299,9 @@ ivff_ws ivff_layout(int nq, int nprobe, int nlist, int64_t stride) {
     return L;
 }
 
-template <typename T, bool L2>
-int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, int D, const T* q, const int* probes,
-                     int nprobe, int64_t stride, char* w, const ivff_ws& L, hipStream_t s) {
+template <typename T, typename TQ, bool L2>
+int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, int D, const TQ* q, const float* dec,
+                     const int* probes, int nprobe, int64_t stride, char* w, const ivff_ws& L, hipStream_t s) {
     auto I = [&](size_t off) { return (const int*)(w + off); };
     int64_t y = (stride + IVFF_RT - 1) / IVFF_RT;
     if (y > IVFF_Y_MAX) y = IVFF_Y_MAX;
@@ -254,7 +309,16 @@ int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list
     const bool vec = (D * (int64_t)sizeof(T)) % 16 == 0 && (ldx * (int64_t)sizeof(T)) % 16 == 0 && !((uintptr_t)x & 15u);
     float* dense = (float*)(w + L.dense);
     int* rowid = (int*)(w + L.rowid);
-    if (vec)
+    if constexpr (std::is_same<T, signed char>::value) {
+        if (vec)
+            hipLaunchKernelGGL((ivf_flat_sq8_scan_kernel<L2, false>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, probes,
+                               I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense,
+                               rowid);
+        else
+            hipLaunchKernelGGL((ivf_flat_sq8_scan_kernel<L2, true>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, probes,
+                               I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense,
+                               rowid);
+    } else if (vec)
         hipLaunchKernelGGL((ivf_flat_scan_kernel<T, L2, false>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, probes, I(L.base),
                            nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense, rowid);
     else
@@ -264,13 +328,15 @@ int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list
     return RC_OK;
 }
 
-// The body of both entries.  Order of the checks: pointers and signs, shapes, the nq == 0 success, the workspace.
-template <typename T>
+// The body of the three entries.  Order of the checks: pointers and signs, shapes, the nq == 0 success, the workspace.
+// dec: the coded store's [step | mid] (T = signed char), not looked at otherwise.
+template <typename T, typename TQ>
 int ivff_entry(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, const int64_t* ids, int64_t N, int nlist, int D,
-               const T* q, int nq, const int* probes, int nprobe, int64_t stride, int k, int metric, float* scores,
-               int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+               const TQ* q, const float* dec, int nq, const int* probes, int nprobe, int64_t stride, int k, int metric,
+               float* scores, int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    constexpr bool SQ = std::is_same<T, signed char>::value;
     rc_device_guard device_guard_(h);
-    if (!h || !x || !list_off || !ids || !q || !probes || !scores || !out_ids || !status || N <= 0 || nlist <= 0 || D <= 0 ||
+    if (!h || !x || (SQ && !dec) || !list_off || !ids || !q || !probes || !scores || !out_ids || !status || N <= 0 || nlist <= 0 || D <= 0 ||
         ldx < D || nq < 0 || nprobe <= 0 || nprobe > nlist || stride <= 0 || k <= 0)
         return RC_EINVAL;
     if (k > ADC_CAND_CAP / 2 || N > 0xFFFFFFFFll || nlist > IVFF_MAX_NLIST || (metric != 0 && metric != 1)) return RC_ESHAPE;
@@ -296,8 +362,8 @@ int ivff_entry(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, 
                        I(L.task_list), I(L.task_qstart), I(L.task_qcnt), IVFF_QG);
     RC_LAUNCH_CHECK(h);
     rc_prof_mark(h, RC_PROF_ADC_SCAN, s);
-    int rc = metric ? ivff_launch_scan<T, true>(h, x, ldx, list_off, D, q, probes, nprobe, stride, w, L, s)
-                    : ivff_launch_scan<T, false>(h, x, ldx, list_off, D, q, probes, nprobe, stride, w, L, s);
+    int rc = metric ? ivff_launch_scan<T, TQ, true>(h, x, ldx, list_off, D, q, dec, probes, nprobe, stride, w, L, s)
+                    : ivff_launch_scan<T, TQ, false>(h, x, ldx, list_off, D, q, dec, probes, nprobe, stride, w, L, s);
     rc_prof_mark(h, RC_PROF_ADC_SCAN, s);
     if (rc != RC_OK) return rc;
     unsigned* cnt = (unsigned*)(w + L.cnt);
@@ -324,7 +390,7 @@ extern "C" int rc_ivf_flat_search(rc_handle_t h, const float* x, int64_t ldx, co
                                   int64_t N, int nlist, int D, const float* q, int nq, const int* probes, int nprobe,
                                   int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status, int* qstatus,
                                   void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return ivff_entry<float>(h, x, ldx, list_off, ids, N, nlist, D, q, nq, probes, nprobe, stride, k, metric, scores, out_ids,
+    return ivff_entry<float, float>(h, x, ldx, list_off, ids, N, nlist, D, q, nullptr, nq, probes, nprobe, stride, k, metric, scores, out_ids,
                              status, qstatus, ws, ws_bytes, stream);
 }
 
@@ -332,7 +398,18 @@ extern "C" int rc_ivf_flat_f16_search(rc_handle_t h, const uint16_t* x, int64_t 
                                       int64_t N, int nlist, int D, const uint16_t* q, int nq, const int* probes, int nprobe,
                                       int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status,
                                       int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return ivff_entry<_Float16>(h, reinterpret_cast<const _Float16*>(x), ldx, list_off, ids, N, nlist, D,
-                                reinterpret_cast<const _Float16*>(q), nq, probes, nprobe, stride, k, metric, scores, out_ids,
+    return ivff_entry<_Float16, _Float16>(h, reinterpret_cast<const _Float16*>(x), ldx, list_off, ids, N, nlist, D,
+                                reinterpret_cast<const _Float16*>(q), nullptr, nq, probes, nprobe, stride, k, metric, scores, out_ids,
                                 status, qstatus, ws, ws_bytes, stream);
+}
+
+extern "C" int rc_ivf_flat_sq8_search(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                                      int64_t N, int nlist, int D, const float* q, int nq, const float* dec, const int* probes,
+                                      int nprobe, int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status,
+                                      int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    // the codec's width limit first, as the rc_dense_sq8 entries order it (shapes, then pointers); then the shared order
+    if (D > rc_dense_sq8_max_d()) return RC_ESHAPE;
+    return ivff_entry<signed char, float>(h, reinterpret_cast<const signed char*>(x), ldx, list_off, ids, N, nlist, D, q, dec, nq,
+                                          probes, nprobe, stride, k, metric, scores, out_ids, status, qstatus, ws, ws_bytes,
+                                          stream);
 }

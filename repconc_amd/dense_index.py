@@ -287,6 +287,37 @@ class FlatL2Bf16x3Index(_FlatL2):
         return self._finite_bf16(xt)
 
 
+SQ8_ROWS_PER_STEP = 1 << 18     # rows that the scalar quantiser's training and the indexes' `add` move and encode at a time
+
+
+def sq8_train_range(xt: torch.Tensor, device) -> tuple:
+    """The 8-bit scalar quantiser's training, shared by `FlatSQ8Index` and `IVFFlatIndex(storage="int8")`: xt [n >= 1, d] ->
+    (vmin [d], dec [2, d] = step, mid) fp32 on `device`.  vmin / vmax per dimension over the rows (Faiss's RS_minmax with
+    argument 0), step = fp32((vmax - vmin) / 255), mid = fp32(vmin + 128.5 step), evaluated in fp64 and rounded once."""
+    if xt.shape[0] == 0:
+        raise ValueError("train: no rows")
+    vmin = torch.full((xt.shape[1],), float("inf"), device=device)
+    vmax = -vmin
+    for r0 in range(0, xt.shape[0], SQ8_ROWS_PER_STEP):
+        part = xt[r0:r0 + SQ8_ROWS_PER_STEP].to(device, torch.float32)
+        vmin, vmax = torch.minimum(vmin, part.amin(0)), torch.maximum(vmax, part.amax(0))     # a NaN propagates
+    if not bool((torch.isfinite(vmin) & torch.isfinite(vmax)).all()):
+        raise ValueError("train: finite values only")
+    step = ((vmax.double() - vmin.double()) / 255.0).float()
+    mid = (vmin.double() + 128.5 * step.double()).float()
+    if not bool((torch.isfinite(step) & torch.isfinite(mid)).all()):
+        raise ValueError("train: the range of a dimension exceeds fp32")
+    return vmin, torch.stack([step, mid]).contiguous()
+
+
+def sq8_encode(xt: torch.Tensor, vmin: torch.Tensor, step: torch.Tensor) -> torch.Tensor:
+    """The int8 codes c - 128 of fp32 rows on the device of vmin and step: c = clamp(floor((x - vmin) / step), 0, 255) in fp32,
+    0 where step = 0; values outside the trained range clamp."""
+    c = torch.floor((xt - vmin) / step).clamp_(0.0, 255.0)
+    c = torch.where(step == 0, torch.zeros_like(c), c)
+    return (c - 128.0).to(torch.int8)
+
+
 class FlatSQ8Index(_FlatIndex):
     """Exact inner-product index over 8-bit scalar-quantiser codes resident in HBM: `faiss.IndexScalarQuantizer(d, QT_8bit,
     METRIC_INNER_PRODUCT)`, one byte per dimension.  Duck-typed like `FlatIPIndex`, plus `train`.
@@ -312,25 +343,10 @@ class FlatSQ8Index(_FlatIndex):
         self._dec = None            # [2, d] fp32: step, mid
         self._cstat = None          # [2] fp32: the largest row L1 norm of the codes, a bound of the largest decoded row norm
 
-    ROWS_PER_STEP = 1 << 18     # rows that `train` and `add` move and encode at a time
+    ROWS_PER_STEP = SQ8_ROWS_PER_STEP     # rows that `add` moves and encodes at a time
 
     def train(self, x) -> None:
-        xt = self._rows(x)
-        if xt.shape[0] == 0:
-            raise ValueError("train: no rows")
-        vmin = torch.full((self.d,), float("inf"), device=self.device)
-        vmax = -vmin
-        for r0 in range(0, xt.shape[0], self.ROWS_PER_STEP):
-            part = xt[r0:r0 + self.ROWS_PER_STEP].to(self.device, torch.float32)
-            vmin, vmax = torch.minimum(vmin, part.amin(0)), torch.maximum(vmax, part.amax(0))     # a NaN propagates
-        if not bool((torch.isfinite(vmin) & torch.isfinite(vmax)).all()):
-            raise ValueError("train: finite values only")
-        step = ((vmax.double() - vmin.double()) / 255.0).float()
-        mid = (vmin.double() + 128.5 * step.double()).float()
-        if not bool((torch.isfinite(step) & torch.isfinite(mid)).all()):
-            raise ValueError("train: the range of a dimension exceeds fp32")
-        self.vmin = vmin
-        self._dec = torch.stack([step, mid]).contiguous()
+        self.vmin, self._dec = sq8_train_range(self._rows(x), self.device)
         self.step, self.mid = self._dec[0], self._dec[1]
         self.is_trained = True
 
@@ -340,9 +356,7 @@ class FlatSQ8Index(_FlatIndex):
 
     def encode(self, xt: torch.Tensor) -> torch.Tensor:
         """The int8 codes c - 128 of fp32 rows on the index's device."""
-        c = torch.floor((xt - self.vmin) / self.step).clamp_(0.0, 255.0)
-        c = torch.where(self.step == 0, torch.zeros_like(c), c)
-        return (c - 128.0).to(torch.int8)
+        return sq8_encode(xt, self.vmin, self.step)
 
     def add(self, x) -> None:
         xt = self._rows(x)

@@ -16,6 +16,9 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
     faiss.IndexIVFFlat(quantizer, d, nlist[, metric])                   not in the reference; what a Faiss user expects beside
                                                                         IndexFlat* and IndexIVFPQ (exact scan of the probed cells,
                                                                         ivf_flat.IVFFlatIndex)
+    faiss.IndexIVFScalarQuantizer(quantizer, d, nlist,                  not in the reference; the same scan over 8-bit codes
+                                  faiss.ScalarQuantizer.QT_8bit,        (IVFFlatIndex(storage="int8")); by_residual=False has to
+                                  metric, by_residual=False)            be passed: the vectors themselves are encoded
     faiss.write_index(index, path) / faiss.read_index(path)             run_warmup.py:187, run_repconc_eval.py:42
     faiss.omp_set_num_threads(n)                                        run_repconc_eval.py:149 (no-op: the scan runs on the GPU)
 
@@ -66,10 +69,12 @@ class IndexIVFFlat(IVFFlatIndex):
     coarse centroids and the index is trained; otherwise `train` fits them and, as Faiss does, adds them to an empty quantizer.
     The index lives on the quantizer's device."""
 
+    _STORAGE = "float32"
+
     def __init__(self, quantizer, d: int, nlist: int, metric=METRIC_L2):
         if quantizer is not None and getattr(quantizer, "d", d) != d:
-            raise ValueError(f"IndexIVFFlat: the quantizer holds vectors of width {quantizer.d}, the index {d}")
-        super().__init__(d, nlist, device=getattr(quantizer, "device", None), metric=metric)
+            raise ValueError(f"{type(self).__name__}: the quantizer holds vectors of width {quantizer.d}, the index {d}")
+        super().__init__(d, nlist, device=getattr(quantizer, "device", None), metric=metric, storage=self._STORAGE)
         self.quantizer = quantizer
         if quantizer is not None and getattr(quantizer, "ntotal", 0) == self.nlist:
             self.set_coarse(quantizer.xb.float())
@@ -77,9 +82,30 @@ class IndexIVFFlat(IVFFlatIndex):
     def train(self, x, iters: int = 10, seed: int = 1234) -> None:
         if self.is_trained:                             # Faiss: training a trained index is a no-op
             return
+        if self.coarse is not None:                     # int8 storage over a filled quantizer: only the range is missing
+            self.train_sq(x)
+            return
         super().train(x, iters, seed)
         if self.quantizer is not None and getattr(self.quantizer, "ntotal", None) == 0 and hasattr(self.quantizer, "add"):
             self.quantizer.add(self.coarse)
+
+
+class IndexIVFScalarQuantizer(IndexIVFFlat):
+    """faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric=METRIC_L2, by_residual=True): `IVFFlatIndex(storage=
+    "int8")` with Faiss's argument order and default metric; the quantizer is treated as `IndexIVFFlat` treats it.  Any qtype
+    but ScalarQuantizer.QT_8bit is refused, and so is Faiss's default by_residual=True: this index encodes the vectors
+    themselves, so that its scores are the flat int8 index's — pass by_residual=False."""
+    _STORAGE = "int8"
+
+    def __init__(self, quantizer, d: int, nlist: int, qtype: int = ScalarQuantizer.QT_8bit, metric=METRIC_L2,
+                 by_residual: bool = True):
+        if qtype != ScalarQuantizer.QT_8bit:
+            raise ValueError("IndexIVFScalarQuantizer: only ScalarQuantizer.QT_8bit is served")
+        if by_residual:
+            raise ValueError("IndexIVFScalarQuantizer: residual encoding is not served; pass by_residual=False (Faiss's "
+                             "default is True): the vectors themselves are encoded")
+        super().__init__(quantizer, d, nlist, metric)
+        self.qtype, self.by_residual = qtype, False
 
 
 def copy_array_to_vector(array, vector: torch.Tensor) -> None:

@@ -19,6 +19,21 @@ no slack) in chunks of queries whose workspace stays under `MAX_WS_BYTES`.  The 
 more than 16384 probed rows tied at its k-th score (status bit 1): those queries alone are answered by `_search_exact_probed`,
 the exact dense search over their probed rows gathered in corpus-id order (the mirror of `IVFPQIndex._search_exact_probed`).
 
+`storage="int8"` (`faiss.IndexIVFScalarQuantizer`, QT_8bit, the vectors encoded themselves, not their residuals): the store holds
+8-bit scalar-quantiser codes, one byte per dimension, and the codec is `FlatSQ8Index`'s (`dense_index.sq8_train_range`,
+`sq8_encode`): per dimension vmin, step = fp32((vmax - vmin) / 255), mid = fp32(vmin + 128.5 step), c = clamp(floor((x - vmin) /
+step), 0, 255) stored as c - 128, a stored row IS its decoded value x^ = fmaf(c - 128, step, mid).  `train(x)` fits the coarse
+centroids and the range from the same rows, `train_sq(x)` the range alone (beside `set_coarse`); `is_trained` needs both, and
+`add`, `set_lists`, `search` and `reconstruct_n` before the range exists are ValueErrors.  `add` / `set_lists` take fp32 rows,
+assign cells from the values given, refuse non-finite values before anything is stored and clamp values outside the trained
+range; the list-major store holds codes, a repeated `add` re-sorts codes and never re-encodes them; `reset` keeps the centroids
+and the range.  Queries are fp32 and are not rounded.  The contract of this storage:
+  * results equal the flat fp32 index of the same metric (`FlatIPIndex` / `FlatL2Index`) over `reconstruct_n(0, ntotal)`,
+    restricted to the probed cells: ids and score bits (`ops.ivf_flat_sq8_search` decodes a value once and runs the same chain);
+  * ties go to the lower corpus id; padding is -inf / +inf and -1;
+  * under the inner product, probing every cell equals `FlatSQ8Index` trained on the same rows; under L2, probing every cell
+    IS the exact L2 search over int8 codes (the flat int8 index does not serve L2).
+
 `add` may be called repeatedly; ids continue from `ntotal`.  Every `add` rebuilds the list-major store from the rows held and the
 new ones: while it runs, a second copy of the whole store exists on the device.
 """
@@ -30,12 +45,13 @@ import numpy as np
 import torch
 
 from . import ops
+from .dense_index import SQ8_ROWS_PER_STEP, sq8_encode, sq8_train_range
 from .index import METRIC_INNER_PRODUCT, METRIC_L2
 from .ivf import CoarseProbe, coarse_assign, coarse_kmeans
 
 
 class IVFFlatIndex(CoarseProbe):
-    STORAGE = {"float32": torch.float32, "float16": torch.float16}
+    STORAGE = {"float32": torch.float32, "float16": torch.float16, "int8": torch.int8}
     MAX_NLIST = ops.IVF_FLAT_MAX_NLIST
     MAX_WS_BYTES = 4 << 30            # workspace of one library call: a search is cut into chunks of queries that stay below it
 
@@ -47,6 +63,8 @@ class IVFFlatIndex(CoarseProbe):
             raise ValueError(f"storage must be one of {sorted(self.STORAGE)}, got {storage!r}")
         if int(d) < 1 or not 1 <= int(nlist) <= self.MAX_NLIST:
             raise ValueError(f"d must be >= 1 and nlist in [1, {self.MAX_NLIST}]")
+        if storage == "int8" and int(d) > ops.DENSE_SQ8_MAX_D:
+            raise ValueError(f"int8 storage: d must be <= {ops.DENSE_SQ8_MAX_D}")
         self.metric_type = metric
         self.storage = storage
         self._dtype = self.STORAGE[storage]
@@ -56,6 +74,7 @@ class IVFFlatIndex(CoarseProbe):
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.d, self.nlist = int(d), int(nlist)
         self.coarse = None                                                  # [nlist, d] fp32
+        self.vmin = self.step = self.mid = self._dec = None                 # int8 storage: the trained range, _dec [2, d] = step, mid
         self.nprobe = 8                                                     # Faiss's attribute: cells probed when search() is not told
         self.last_search_stats = {"queries": 0, "fallback_queries": 0, "chunks": 0}
         self.reset()
@@ -63,10 +82,10 @@ class IVFFlatIndex(CoarseProbe):
     # ---- build
     @property
     def is_trained(self) -> bool:
-        return self.coarse is not None
+        return self.coarse is not None and (self.storage != "int8" or self._dec is not None)
 
     def reset(self) -> None:
-        """Empties the index; the coarse centroids stay."""
+        """Empties the index; the coarse centroids (and the range of int8 storage) stay."""
         self.xb = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
         self.ids = torch.empty((0,), dtype=torch.int64, device=self.device)
         self.list_off = torch.zeros((self.nlist + 1,), dtype=torch.int64, device=self.device)
@@ -80,11 +99,27 @@ class IVFFlatIndex(CoarseProbe):
         return xt
 
     def train(self, x, iters: int = 10, seed: int = 1234) -> None:
-        """Fits the `nlist` coarse centroids by `coarse_kmeans` on x [n >= nlist, d]."""
+        """Fits the `nlist` coarse centroids by `coarse_kmeans` on x [n >= nlist, d]; int8 storage: also the per-dimension range
+        of the same rows (`train_sq`)."""
         xt = self._rows(x, "train")
         if xt.shape[0] < self.nlist:
             raise ValueError(f"train: {xt.shape[0]} vectors for {self.nlist} cells")
+        if self.storage == "int8":
+            self.train_sq(xt)
         self.coarse = coarse_kmeans(xt.to(self.device, torch.float32), self.nlist, iters, seed)
+
+    def train_sq(self, x) -> None:
+        """int8 storage: sets the scalar quantiser's per-dimension range from x [n >= 1, d] alone (beside `set_coarse`)."""
+        if self.storage != "int8":
+            raise ValueError("train_sq: only int8 storage has a range to train")
+        if self.ntotal:
+            raise ValueError("train_sq: the index holds codes of the current range; reset() first")
+        self.vmin, self._dec = sq8_train_range(self._rows(x, "train_sq"), self.device)
+        self.step, self.mid = self._dec[0], self._dec[1]
+
+    def _need_range(self, what: str) -> None:
+        if self.storage == "int8" and self._dec is None:
+            raise ValueError(f"{what}: int8 storage needs its range first (train(x), or train_sq(x) beside set_coarse)")
 
     def set_coarse(self, centroids) -> None:
         """Installs given coarse centroids [nlist, d]."""
@@ -95,6 +130,18 @@ class IVFFlatIndex(CoarseProbe):
 
     def _stored(self, xt: torch.Tensor) -> torch.Tensor:
         """The rows of an `add` in the storage type, checked before anything is stored; one host read."""
+        if self.storage == "int8":
+            n = xt.shape[0]
+            codes = torch.empty((n, self.d), dtype=torch.int8, device=self.device)
+            finite = torch.ones((), dtype=torch.bool, device=self.device)
+            for r0 in range(0, n, SQ8_ROWS_PER_STEP):
+                part = xt[r0:r0 + SQ8_ROWS_PER_STEP].to(self.device, torch.float32)
+                finite &= torch.isfinite(part).all()
+                part = torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0)      # refused below; int8(NaN) is undefined
+                codes[r0:r0 + part.shape[0]] = sq8_encode(part, self.vmin, self.step)
+            if not bool(finite):
+                raise ValueError("add: int8 storage needs finite values")
+            return codes
         xs = xt.to(self.device).to(self._dtype)
         if xs.shape[0] and not bool(torch.isfinite(xs).all()):
             raise ValueError("add: finite values only" if self.storage == "float32" else
@@ -125,6 +172,7 @@ class IVFFlatIndex(CoarseProbe):
     def set_lists(self, x, list_ids) -> None:
         """Replaces the content by the rows x [N, d] (corpus order: row i has id i) stored under the given cells list_ids [N]."""
         xt = self._rows(x, "set_lists")
+        self._need_range("set_lists")
         li = list_ids if isinstance(list_ids, torch.Tensor) else torch.from_numpy(np.asarray(list_ids))
         if li.dim() != 1 or li.shape[0] != xt.shape[0] or li.dtype.is_floating_point:
             raise ValueError(f"set_lists: expected {xt.shape[0]} integer cells, got {li.dtype} {tuple(li.shape)}")
@@ -137,6 +185,7 @@ class IVFFlatIndex(CoarseProbe):
         before any rounding to the storage type).  Rebuilds the list-major store: a transient second copy of it exists meanwhile."""
         if self.coarse is None:
             raise ValueError("add: train() or set_coarse() the coarse quantiser first")
+        self._need_range("add")
         xt = self._rows(x, "add")
         if xt.shape[0] == 0:
             return
@@ -147,6 +196,18 @@ class IVFFlatIndex(CoarseProbe):
             xs, cells = torch.cat([old_x, xs], 0), torch.cat([old_cells, cells], 0)
         self._store(xs, cells)
 
+    def reconstruct_n(self, i0: int = 0, ni: int = -1) -> torch.Tensor:
+        """fp32 [ni, d]: the stored values of corpus rows i0 .. i0 + ni - 1 (ni = -1: up to ntotal), as the search scores them;
+        int8 storage: the decoded rows (`ops.dense_sq8_decode`)."""
+        self._need_range("reconstruct_n")
+        ni = self.ntotal - int(i0) if ni < 0 else int(ni)
+        if not (0 <= int(i0) and ni >= 0 and int(i0) + ni <= self.ntotal):
+            raise ValueError(f"reconstruct_n: rows [{i0}, {int(i0) + ni}) outside [0, {self.ntotal})")
+        where = torch.empty_like(self.ids)
+        where[self.ids] = torch.arange(self.ntotal, device=self.device)
+        rows = self.xb[where[int(i0):int(i0) + ni]]
+        return ops.dense_sq8_decode(rows, self._dec) if self.storage == "int8" else rows.float()
+
     # ---- search
     def _queries(self, x, k: int):
         as_numpy = not isinstance(x, torch.Tensor)
@@ -155,6 +216,7 @@ class IVFFlatIndex(CoarseProbe):
             raise ValueError(f"search: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
         if not 1 <= int(k) <= ops.DENSE_MAX_K:
             raise ValueError(f"search: k must be in [1, {ops.DENSE_MAX_K}]")
+        self._need_range("search")
         return q, as_numpy
 
     def _padding(self, nq: int, k: int):
@@ -214,8 +276,12 @@ class IVFFlatIndex(CoarseProbe):
         parts, fallback, chunks = [], 0, 0
         for c0 in range(0, nq, step):
             qc, pc = q[c0:c0 + step], probes[c0:c0 + step]
-            scores, ids, status, qstatus = ops.ivf_flat_search(self.xb, self.list_off, self.ids, qc, pc, stride, k,
-                                                               metric=self.metric_type)
+            if self.storage == "int8":
+                scores, ids, status, qstatus = ops.ivf_flat_sq8_search(self.xb, self._dec, self.list_off, self.ids, qc, pc, stride,
+                                                                       k, metric=self.metric_type)
+            else:
+                scores, ids, status, qstatus = ops.ivf_flat_search(self.xb, self.list_off, self.ids, qc, pc, stride, k,
+                                                                   metric=self.metric_type)
             chunks += 1
             st = int(status.item())
             if st & 4:
@@ -234,9 +300,11 @@ class IVFFlatIndex(CoarseProbe):
     def _search_exact_probed(self, q: torch.Tensor, probes: torch.Tensor, k: int):
         """The answer for ANY content of the probed cells, query by query: the probed rows gathered in corpus-id order (the
         search's tie rule becomes the exact entry's "lower row"), then the exact route of the flat search of this metric and
-        storage.  Slow — one gather of the probed rows per query — and only reached for queries the selection could not decide."""
+        storage (int8: the fp32 exact route over the gathered rows, decoded).  Slow — one gather of the probed rows per query —
+        and only reached for queries the selection could not decide."""
         exact = {(METRIC_INNER_PRODUCT, "float32"): ops.dense_search_exact, (METRIC_INNER_PRODUCT, "float16"): ops.dense_search_f16_exact,
-                 (METRIC_L2, "float32"): ops.dense_search_l2_exact, (METRIC_L2, "float16"): ops.dense_search_l2_f16_exact}
+                 (METRIC_L2, "float32"): ops.dense_search_l2_exact, (METRIC_L2, "float16"): ops.dense_search_l2_f16_exact,
+                 (METRIC_INNER_PRODUCT, "int8"): ops.dense_search_exact, (METRIC_L2, "int8"): ops.dense_search_l2_exact}
         exact = exact[(self.metric_type, self.storage)]
         scores, ids = self._padding(q.shape[0], k)
         off = self.list_off
@@ -249,7 +317,10 @@ class IVFFlatIndex(CoarseProbe):
             corpus = self.ids[rows]
             order = torch.argsort(corpus)
             rows, corpus = rows[order], corpus[order]
-            s, i = exact(self.xb[rows].contiguous(), q[j:j + 1], k)
+            gathered = self.xb[rows].contiguous()
+            if self.storage == "int8":
+                gathered = ops.dense_sq8_decode(gathered, self._dec)
+            s, i = exact(gathered, q[j:j + 1], k)
             valid = i[0] >= 0
             scores[j] = s[0]
             ids[j, valid] = corpus[i[0][valid]]

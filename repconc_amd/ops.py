@@ -1404,6 +1404,59 @@ def ivf_flat_search(xb: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor,
     return scores, out_ids, status, qstatus
 
 
+def ivf_flat_sq8_search(xb8: torch.Tensor, dec: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor, q: torch.Tensor,
+                        probes: torch.Tensor, stride: int, k: int, metric: int = METRIC_INNER_PRODUCT):
+    """`ivf_flat_search` over a list-major store of 8-bit scalar-quantiser codes (rc_ivf_flat_sq8_search): `xb8` [N, D] int8 =
+    c - 128, `dec` [2, D] fp32 = the steps, then the mids (`dense_search_sq8`'s), `q` [nq, D] fp32, not rounded; everything
+    else, the returns and the status bits as `ivf_flat_search`.  Scores are bit for bit those of `ivf_flat_search` over
+    `dense_sq8_decode(xb8, dec)`, under either metric.  Any row pitch >= D and any alignment (a column slice of a wider
+    matrix is read in place).  D <= 65536; argument errors are ValueError before any device work."""
+    l2 = _adc_metric(metric)
+    if xb8.dim() != 2 or q.dim() != 2 or xb8.shape[1] != q.shape[1] or xb8.shape[1] < 1:
+        raise ValueError("ivf_flat_sq8_search: xb8 [N, D] and q [nq, D] with the same D >= 1")
+    if xb8.dtype != torch.int8:
+        raise ValueError("ivf_flat_sq8_search: the store must be int8 codes, c - 128")
+    if q.dtype != torch.float32:
+        raise ValueError("ivf_flat_sq8_search: the queries must be float32")
+    N, D = xb8.shape
+    if D > DENSE_SQ8_MAX_D:
+        raise ValueError(f"ivf_flat_sq8_search: D must be <= {DENSE_SQ8_MAX_D}")
+    if dec.dtype != torch.float32 or dec.shape != (2, D):
+        raise ValueError("ivf_flat_sq8_search: dec must be float32 [2, D]: the steps, then the mids")
+    if not 1 <= int(k) <= DENSE_MAX_K:
+        raise ValueError(f"ivf_flat_sq8_search: k must be in [1, {DENSE_MAX_K}]")
+    nlist = list_off.numel() - 1
+    if list_off.dtype != torch.int64 or list_off.dim() != 1 or not 1 <= nlist <= IVF_FLAT_MAX_NLIST:
+        raise ValueError(f"ivf_flat_sq8_search: list_off must be int64 [nlist + 1], 1 <= nlist <= {IVF_FLAT_MAX_NLIST}")
+    if ids.dtype != torch.int64 or ids.shape != (N,):
+        raise ValueError("ivf_flat_sq8_search: ids must be int64 [N]")
+    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != q.shape[0] or not 1 <= probes.shape[1] <= nlist:
+        raise ValueError("ivf_flat_sq8_search: probes must be int32 [nq, nprobe], 1 <= nprobe <= nlist")
+    if not 1 <= N < 1 << 32:
+        raise ValueError("ivf_flat_sq8_search: 1 <= N < 2^32")
+    if int(stride) < 1:
+        raise ValueError("ivf_flat_sq8_search: stride must be >= 1")
+    _need_cuda(xb8, dec, list_off, ids, q, probes)
+    if xb8.stride(1) != 1 or (N > 1 and xb8.stride(0) < D):
+        xb8 = xb8.contiguous()
+    q, dec = q.to(xb8.device).contiguous(), dec.to(xb8.device).contiguous()
+    list_off, ids, probes = list_off.contiguous(), ids.contiguous(), probes.contiguous()
+    nq, nprobe = probes.shape
+    scores = torch.empty((nq, int(k)), dtype=torch.float32, device=q.device)
+    out_ids = torch.empty((nq, int(k)), dtype=torch.int64, device=q.device)
+    flags = torch.zeros((1 + nq,), dtype=torch.int32, device=q.device)       # [status | per-query status]: one fill
+    status, qstatus = flags[:1], flags[1:]
+    if nq == 0:
+        return scores, out_ids, status, qstatus
+    lib, h, s, _ = _ctx(q)
+    wsb = lib.rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, int(stride))
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)             # released in stream order
+    _lib.check(lib.rc_ivf_flat_sq8_search(h, _p(xb8), xb8.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q),
+                                          nq, _p(dec), _p(probes), nprobe, int(stride), int(k), int(l2), _p(scores),
+                                          _p(out_ids), _p(status), _p(qstatus), _p(ws), wsb, s), "rc_ivf_flat_sq8_search", h)
+    return scores, out_ids, status, qstatus
+
+
 def dense_xnorm_max(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
     """Device fp32 scalar [1] >= the largest Euclidean row norm of the floating-point matrix `x` of any dtype (fp64 sums,
     rounded upwards; +inf if the norm exceeds fp32): the `xnorm_max` of `dense_search_bf16x3` and `dense_search_f16`.  No host

@@ -1,18 +1,21 @@
 #!/usr/bin/env python3
 """Exact IVF search over dense rows (csrc/ivf_flat.hip, IVFFlatIndex) at the README's shape (development tool, GPU):
-8 841 823 x 768 rows, nlist 5000 trained, 1200-query batches, k = 100; fp32 and fp16 stores, both metrics.
+8 841 823 x 768 rows, nlist 5000 trained, 1200-query batches, k = 100; fp32, fp16 and int8 stores, both metrics.
 
-    python tools/ivf_flat_bench.py [--n 8841823] [--batches 2] [--passes 4] [--out profiles/ivf_flat_bench.txt]
+    python tools/ivf_flat_bench.py [--n 8841823] [--batches 2] [--passes 4] [--stores fp32,fp16,int8] [--out profiles/ivf_flat_bench.txt]
 
 Data: clustered Gaussian rows as in tools/dense_bench.py (0.7 centre + 0.5 noise, 64 centres), generated on the device in
 chunks; the queries are corpus rows plus 0.3 N(0, 1).  The coarse centroids are fitted once on a seeded sample of 2^18 rows
-(coarse_kmeans) and every row assigned once (coarse_assign); the fp32 and the fp16 index store their own list-major copy.
+(coarse_kmeans) and every row assigned once (coarse_assign); the fp32, the fp16 and the int8 index store their own list-major
+copy.  The int8 store holds the 8-bit scalar-quantiser codes of the same rows (range trained on all of them); its flat
+counterpart is FlatSQ8Index under the inner product, and there is none under L2 (nor a re-ranking flat index over codes: the
+refined IVF-PQ line is left out for this store).  After the legs: the int8 / fp16 time ratio of every IVF run, per pass.
 
 Per storage and metric, on `--passes` alternating passes in one process, ms per batch of
   * IVFFlatIndex at nprobe 8 / 32 / 128,
   * the flat index of the same vectors,
   * RefineIndex(IVFPQIndex, flat) at nprobe 32 (M = 48 codes, k_factor 10),
-with the top-10 overlap of each with the flat result; and for the IVFFlatIndex runs the rows and bytes of the probed cells per
+with the top-10 overlap of each with the flat result of the same store and, beside it, with the fp32 flat result; and for the IVFFlatIndex runs the rows and bytes of the probed cells per
 batch (every (cell, group of 8 queries) task reads its cell once), the chain steps, the scan kernel's own time (the library's
 profiling events around its launch) and the two bounds it is held against: the cells' bytes at the achievable HBM rate
 (6.3 TB/s; 8 TB/s peak) and the chain steps at the fp32 vector rate the guide measures for v_pk_fma_f32 (52 TFLOP/s = 26 T
@@ -28,7 +31,8 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from repconc_amd import _lib, ops  # noqa: E402
-from repconc_amd.dense_index import FlatIPIndex, FlatL2F16Index, FlatL2Index  # noqa: E402
+from repconc_amd.dense_index import (FlatIPIndex, FlatL2F16Index, FlatL2Index, FlatSQ8Index, sq8_encode,  # noqa: E402
+                                     sq8_train_range)
 from repconc_amd.index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex  # noqa: E402
 from repconc_amd.ivf import IVFPQIndex, coarse_assign, coarse_kmeans  # noqa: E402
 from repconc_amd.ivf_flat import IVFFlatIndex  # noqa: E402
@@ -78,6 +82,9 @@ def hang(index, store, metric):
     both storages) and switches `metric_type` on the live indexes, which keep nothing that depends on the metric.  A change of
     those internals has to be followed here."""
     index._x, index.ntotal = store, store.shape[0]
+    if store.dtype == torch.int8:
+        index._cstat = ops.dense_sq8_cstat(store, index._dec)
+        return index
     if metric == METRIC_L2:
         index._xsq = ops.dense_row_sqnorms(store)
         index._xnorm_max = ops._dense_l2_xnorm_max(index._xsq)
@@ -121,6 +128,7 @@ def main():
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--nlist", type=int, default=5000)
     ap.add_argument("--nprobes", default="8,32,128")
+    ap.add_argument("--stores", default="fp32,fp16,int8")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.out:
@@ -158,20 +166,42 @@ def main():
     ivfpq.nprobe = 32
     del pq
 
-    for sname, store in (("fp32", x), ("fp16", x16)):
-        index = IVFFlatIndex(a.d, a.nlist, storage="float16" if sname == "fp16" else "float32")
+    stores = a.stores.split(",")
+    x8 = vmin8 = dec8 = None
+    if "int8" in stores:
+        vmin8, dec8 = sq8_train_range(x, DEV)
+        x8 = torch.empty((a.n, a.d), dtype=torch.int8, device=DEV)
+        for r0 in range(0, a.n, 1 << 20):
+            x8[r0:r0 + (1 << 20)] = sq8_encode(x[r0:r0 + (1 << 20)], vmin8, dec8[0])
+    flat32, allms = {}, {}          # the fp32 flat ids per metric; ms per pass of every (store, metric, path)
+    for sname, store in (("fp32", x), ("fp16", x16), ("int8", x8)):
+        if sname not in stores:
+            continue
+        index = IVFFlatIndex(a.d, a.nlist, storage={"fp32": "float32", "fp16": "float16", "int8": "int8"}[sname])
         index.set_coarse(coarse)
+        if sname == "int8":
+            index.vmin, index._dec = vmin8, dec8
+            index.step, index.mid = dec8[0], dec8[1]
         index._store(store, cells)
         esz = store.element_size()
         for metric in (METRIC_INNER_PRODUCT, METRIC_L2):
             index.metric_type = ivfpq.metric_type = metric
-            if metric == METRIC_L2:
+            flat = None
+            if sname == "int8":
+                if metric == METRIC_INNER_PRODUCT:
+                    flat = FlatSQ8Index(a.d)
+                    flat.vmin, flat._dec, flat.is_trained = vmin8, dec8, True
+                    flat.step, flat.mid = dec8[0], dec8[1]
+                    flat = hang(flat, store, metric)
+            elif metric == METRIC_L2:
                 flat = hang(FlatL2F16Index(a.d) if sname == "fp16" else FlatL2Index(a.d), store, metric)
             else:
                 flat = hang(FlatIPIndex(a.d, storage="float16" if sname == "fp16" else "float32"), store, metric)
             paths = {f"ivf-flat nprobe {p}": (lambda qb, p=p: index.search(qb, a.k, nprobe=p)) for p in nprobes}
-            paths["flat"] = lambda qb: flat.search(qb, a.k)
-            paths["ivf-pq refined nprobe 32"] = lambda qb: RefineIndex(ivfpq, flat, 10).search(qb, a.k)
+            if flat is not None:
+                paths["flat"] = lambda qb: flat.search(qb, a.k)
+            if sname != "int8":
+                paths["ivf-pq refined nprobe 32"] = lambda qb: RefineIndex(ivfpq, flat, 10).search(qb, a.k)
             stats = {}
             for n, fn in paths.items():
                 fn(batches[0])                                          # warm every code object and allocation
@@ -182,14 +212,21 @@ def main():
                 for n, fn in paths.items():
                     t, out[n] = timed(fn, batches)
                     ms[n].append(t)
-            exact = torch.cat([o[1] for o in out["flat"]])
+            exact = torch.cat([o[1] for o in out["flat"]]) if flat is not None else None
+            if sname == "fp32":
+                flat32[metric] = exact
             for n in paths:
                 v = ms[n]
+                allms[(sname, metric, n)] = v
                 ids = torch.cat([o[1] for o in out[n]])
+                own = f"top-10 overlap with the flat result {overlap10(ids, exact):.3f}" if exact is not None else \
+                    "no flat index over this store and metric"
+                if sname != "fp32" and metric in flat32:
+                    own += f", with the fp32 flat result {overlap10(ids, flat32[metric]):.3f}"
                 say(f"e2e {NAMES[metric]} {sname} {n:26s}: {sum(v) / len(v):8.3f} ms per batch (min {min(v):.3f} max {max(v):.3f}) = "
-                    f"{a.batch / (sum(v) / len(v)):7.1f} k queries/s, top-10 overlap with the flat result {overlap10(ids, exact):.3f}")
-            flat_ms = sum(ms["flat"]) / len(ms["flat"])
-            n32 = sum(ms["ivf-flat nprobe 32"]) / len(ms["ivf-flat nprobe 32"]) if 32 in nprobes else None
+                    f"{a.batch / (sum(v) / len(v)):7.1f} k queries/s, {own}")
+            flat_ms = sum(ms["flat"]) / len(ms["flat"]) if flat is not None else None
+            n32 = sum(ms["ivf-flat nprobe 32"]) / len(ms["ivf-flat nprobe 32"]) if 32 in nprobes and flat is not None else None
             if n32 is not None:
                 say(f"  condition {NAMES[metric]} {sname}: nprobe 32 takes {n32:.3f} ms, the flat search of the same store {flat_ms:.3f} ms "
                     f"-> {'met' if n32 < flat_ms else 'NOT MET'}")
@@ -207,6 +244,13 @@ def main():
             del flat
         del index
         torch.cuda.empty_cache()
+    if "int8" in stores and "fp16" in stores:
+        for metric in (METRIC_INNER_PRODUCT, METRIC_L2):
+            for p in nprobes:
+                n = f"ivf-flat nprobe {p}"
+                r = [i8 / f16 for i8, f16 in zip(allms[("int8", metric, n)], allms[("fp16", metric, n)])]
+                say(f"int8 / fp16 time, {NAMES[metric]} nprobe {p:3d}: {sum(r) / len(r):.3f} over {len(r)} passes (min {min(r):.3f} "
+                    f"max {max(r):.3f})")
 
 
 if __name__ == "__main__":
