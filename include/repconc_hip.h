@@ -638,6 +638,44 @@ int rc_dense_l2_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx, int64_
                               const float* xsq, float* out, void* ws, size_t ws_bytes, rc_stream_t stream);
 void rc_dense_l2_bf16x3_error_constants(double* c);
 
+/* ------------------------------------------------------------------ dense flat search, L2 metric, 8-bit scalar-quantised storage
+ * rc_dense_l2_search_q over the store of rc_dense_sq8_search_q (faiss.IndexScalarQuantizer, QT_8bit, METRIC_L2): x [N, ldx]
+ * int8 = c - 128, dec [2][D] = step, mid, q [nq, D] fp32, finite.  Distance d(q, n) = the chain of rc_dense_l2_search_q over
+ * the decoded row x^[d] = fmaf((float)c'[d], step[d], mid[d]): ids AND distance bits equal rc_dense_l2_search_q over the
+ * decoded corpus (rc_dense_sq8_decode).  dist ascending, lower id first among equals, +0.0f for a zero, +inf / -1 past N.
+ * Limits, row pitch and alignment as rc_dense_sq8_search_q (1 <= D <= 65536, N < 2^32, 1 <= k <= 8192, else RC_ESHAPE).
+ * rc_dense_l2_sq8_search_q: N <= 131072 takes the exact route below.  Above: the pre-pass and the int8 screen s~ of
+ *   rc_dense_sq8_search_q, then sigma = fmaf(2, s~, -xsq[n]); xsq: DEVICE fp32 [N], the squared norm of every decoded row, an
+ *   fp64 sum rounded to nearest (rc_dense_sq8_row_sqnorms); cstat as rc_dense_sq8_search_q.  With its W1, B1, alpha, C1, X, u,
+ *   D_pad, R = (||q||_2 + X)^2 and the constants c[0..8] of rc_dense_l2_sq8_error_constants,
+ *     E_q = (c0 alpha C1 + u (c1 W1 + c2 alpha D + c3 alpha C1 + c4 B1 + c5 (D_pad + 5) R)
+ *            + c6 2^-149 (D_pad + sqrt(D_pad) ||q||_2 + C1 + 3)) (1 + 2^-20)        (every |sigma - ||q||^2 + d| <= E_q),
+ *   +inf unless R < c7 and E_q < c8; -d_k >= thr~ - ||q||^2 + E_q for the query's k-th distance d_k proves the answer.
+ *   status / qstatus, the refusals and ws (16-byte aligned, rc_dense_l2_sq8_search_ws_bytes) as rc_dense_sq8_search_q; bit2:
+ *   repeat with another sel_slack or answer by rc_dense_l2_sq8_search_exact.
+ * rc_dense_l2_sq8_search_exact: the chain of every (query, row) pair over rows decoded on the fly, then the radix select; no
+ *   status, no norms.  ws: rc_dense_l2_sq8_search_exact_ws_bytes(N, D, nq, k).
+ * rc_dense_l2_sq8_search_ws_counts (measurement): as rc_dense_sq8_search_ws_counts.
+ * rc_dense_l2_sq8_scores (test hook): the screen's raw sigma, out [nq][N] fp32; ws: rc_dense_l2_sq8_scores_ws_bytes(D, nq).
+ * rc_dense_sq8_row_sqnorms: out [N] fp32 = the squared norms of the decoded rows, computed from the codes (N = 0: nothing).
+ * rc_dense_l2_sq8_error_constants: c[9] = {1, 1040, 388, 1030, 4.2, 1.01, 1, 2^126, 2^124} (no GPU needed). */
+size_t rc_dense_l2_sq8_search_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_l2_sq8_search_q(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                             const float* dec, const float* xsq, const float* cstat, int k, int64_t id_offset, double sel_slack,
+                             float* dist, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                             rc_stream_t stream);
+size_t rc_dense_l2_sq8_search_exact_ws_bytes(int64_t N, int D, int nq, int k);
+int rc_dense_l2_sq8_search_exact(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                 const float* dec, int k, int64_t id_offset, float* dist, int64_t* ids, void* ws,
+                                 size_t ws_bytes, rc_stream_t stream);
+int rc_dense_l2_sq8_search_ws_counts(int64_t N, int D, int nq, int k, size_t* cnt_off);
+size_t rc_dense_l2_sq8_scores_ws_bytes(int D, int nq);
+int rc_dense_l2_sq8_scores(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                           const float* dec, const float* xsq, float* out, void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_sq8_row_sqnorms(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* dec, float* out,
+                             rc_stream_t stream);
+void rc_dense_l2_sq8_error_constants(double* c);
+
 /* ------------------------------------------------------------------ dense stores: exact re-ranking of candidate lists
  * The second stage of faiss.IndexRefineFlat: cand [nq, ldc] int64 holds kc candidate ids per query (from a PQ or IVF search),
  * x [N, ldx] is the dense store (fp32; rc_dense_f16_rerank: fp16 bit patterns, x and q both), q [nq, D] the queries.  Only the

@@ -160,6 +160,16 @@ PROTOTYPES = {
     "rc_dense_l2_bf16x3_scores_ws_bytes": (_sz, [_i, _i]),
     "rc_dense_l2_bf16x3_scores": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_l2_bf16x3_error_constants": (None, [C.POINTER(_d)]),
+    "rc_dense_l2_sq8_search_ws_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rc_dense_l2_sq8_search_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz,
+                                      _vp]),
+    "rc_dense_l2_sq8_search_exact_ws_bytes": (_sz, [_i64, _i, _i, _i]),
+    "rc_dense_l2_sq8_search_exact": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_l2_sq8_search_ws_counts": (_i, [_i64, _i, _i, _i, C.POINTER(_sz)]),
+    "rc_dense_l2_sq8_scores_ws_bytes": (_sz, [_i, _i]),
+    "rc_dense_l2_sq8_scores": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_sq8_row_sqnorms": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _vp, _vp]),
+    "rc_dense_l2_sq8_error_constants": (None, [C.POINTER(_d)]),
     "rc_dense_rerank_ws_bytes": (_sz, [_i, _i]),
     "rc_dense_rerank": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_f16_rerank": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i, _i64, _i, _vp, _vp, _vp, _sz, _vp]),

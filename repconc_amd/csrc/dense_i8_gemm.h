@@ -1,5 +1,5 @@
-// The screen GEMM on the int8 matrix cores over a corpus of 8-bit scalar-quantiser codes (dense_search_sq8.hip), and the
-// query pre-pass that feeds it.  Device code: the unit instantiates the forms it launches, no -fgpu-rdc.
+// The screen GEMM on the int8 matrix cores over a corpus of 8-bit scalar-quantiser codes (dense_search_sq8.hip, and with the L2
+// epilogue dense_search_l2_sq8.hip), and the query pre-pass that feeds it.  Device code: the unit instantiates the forms it launches, no -fgpu-rdc.
 //
 // Screen.  The store holds c'_d = c_d - 128 as int8; a row decodes to x^_d = fmaf(c'_d, step_d, mid_d).  With w_d = q_d step_d
 // and bias_q = sum_d q_d mid_d the score is sum_d w_d c'_d + bias_q up to roundings.  The pre-pass quantises w to integers
@@ -111,14 +111,18 @@ static int dense_i8_launch_prepass(rc_handle_t h, const float* q, int nq, int D,
 // tile of 128 queries; wave (wr, wc) owns 64 queries x 64 rows as 4 x 4 tiles of v_mfma_i32_16x16x64_i8 with two accumulators
 // each (high and low limb); lane l holds k = 16 (l / 16) .. + 15 of row l % 16 of every operand, one 16-byte LDS read per
 // operand tile, limb and K step; result element r of lane l is corpus row l % 16 and query 4 (l / 16) + r of the tile.
-template <int MODE, bool PAD>
+// L2 (dense_search_l2_sq8.hip): the epilogue emits sigma = fmaf(2, s~, -xsq[row]), xsq [N] = the stored fp32 squared norm of
+// every decoded corpus row (a lane holds one corpus row per column tile: four values, loaded once per block by
+// dense_screen_load_nxs, at the mapped row of the strided sample).  !L2: xsq is unused.
+template <int MODE, bool PAD, bool L2 = false>
 __global__ __launch_bounds__(256, 2) void dense_i8_gemm_kernel(const signed char* __restrict__ x, int64_t ldx, int64_t N,
                                                                int64_t nrows, int64_t smap,
                                                                const signed char* __restrict__ planes,
                                                                const float* __restrict__ alpha, const float* __restrict__ bias,
                                                                int nq, int D, int Dp, const float* __restrict__ thr,
                                                                float* __restrict__ out, unsigned* __restrict__ cnt,
-                                                               unsigned long long* __restrict__ cand) {
+                                                               unsigned long long* __restrict__ cand,
+                                                               const float* __restrict__ xsq) {
     constexpr int TM = 16, NT = 4;
     __shared__ __attribute__((aligned(16))) unsigned char dense_i8_smem[DENSE_I8_LDS_BYTES];
     __shared__ float s_thr[DENSE_TILE], s_alpha[DENSE_TILE], s_bias[DENSE_TILE];
@@ -143,6 +147,8 @@ __global__ __launch_bounds__(256, 2) void dense_i8_gemm_kernel(const signed char
     }
 #pragma unroll
     for (int i = 0; i < 4; ++i) soq[i] = dense_screen_lds_off(qrow + 32 * i, qc);
+    float nxs[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (L2) dense_screen_load_nxs(xsq, j0, wc, col, N, nrows, smap, nxs);
     const int nkc = Dp / DENSE_I8_KC;
     for (int qt = 0; qt < nq; qt += DENSE_TILE) {
         const signed char* qp[4];                                          // this thread's limb plane, at its chunk's first k
@@ -236,7 +242,8 @@ __global__ __launch_bounds__(256, 2) void dense_i8_gemm_kernel(const signed char
                 for (int r = 0; r < 4; ++r) {
                     const int qo = wr * 64 + a * TM + 4 * grp + r;
                     const float t = __builtin_fmaf(256.f, (float)acch[a][b][r], (float)accl[a][b][r]);
-                    const float sc = __builtin_fmaf(s_alpha[qo], t, s_bias[qo]);
+                    float sc = __builtin_fmaf(s_alpha[qo], t, s_bias[qo]);
+                    if constexpr (L2) sc = __builtin_fmaf(2.f, sc, nxs[b]);
                     dense_emit<MODE, 16>(sc, j, jv, qt + qo, nq, MODE == DENSE_FILTER ? s_thr[qo] : 0.f, nrows, out, cnt, cand, l);
                 }
         }
@@ -246,22 +253,22 @@ __global__ __launch_bounds__(256, 2) void dense_i8_gemm_kernel(const signed char
 
 static bool dense_i8_aligned(const void* x, int64_t ldx, int D) { return D % 16 == 0 && ldx % 16 == 0 && !((uintptr_t)x & 15u); }
 
-// qs: the pre-pass's part of the workspace (dense_i8_query_ws), 16-byte aligned
-template <int MODE>
+// qs: the pre-pass's part of the workspace (dense_i8_query_ws), 16-byte aligned; xsq is read only if L2
+template <int MODE, bool L2 = false>
 static int dense_i8_launch_gemm(rc_handle_t h, const signed char* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
                                 const char* qs, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                                unsigned long long* cand, hipStream_t s) {
+                                unsigned long long* cand, hipStream_t s, const float* xsq = nullptr) {
     const dense_i8_query_layout L = dense_i8_query_ws(nq, D);
     const signed char* planes = (const signed char*)(qs + L.planes);
     const float* alpha = (const float*)(qs + L.alpha);
     const float* bias = (const float*)(qs + L.bias);
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (dense_i8_aligned(x, ldx, D))
-        hipLaunchKernelGGL((dense_i8_gemm_kernel<MODE, false>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, planes, alpha, bias,
-                           nq, D, L.Dp, thr, out, cnt, cand);
+        hipLaunchKernelGGL((dense_i8_gemm_kernel<MODE, false, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, planes, alpha,
+                           bias, nq, D, L.Dp, thr, out, cnt, cand, xsq);
     else
-        hipLaunchKernelGGL((dense_i8_gemm_kernel<MODE, true>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, planes, alpha, bias,
-                           nq, D, L.Dp, thr, out, cnt, cand);
+        hipLaunchKernelGGL((dense_i8_gemm_kernel<MODE, true, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, planes, alpha,
+                           bias, nq, D, L.Dp, thr, out, cnt, cand, xsq);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }

@@ -1,8 +1,8 @@
-// What the seven dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
+// What the eight dense flat searches share beyond the fp32 GEMM of dense_gemm.h (dense_search.hip: fp32 corpus and screen,
 // dense_search_f16.hip: fp16 corpus and f16 screen, dense_search_bf16x3.hip: fp32 corpus and bf16x3 screen,
 // dense_search_l2.hip: fp32 corpus, squared Euclidean distance, dense_search_l2_f16.hip: the same over an fp16 corpus,
 // dense_search_l2_bf16x3.hip: the fp32 L2 corpus under the bf16x3 screen, dense_search_sq8.hip: int8 scalar-quantiser codes,
-// fp32 queries and the int8 screen): the
+// fp32 queries and the int8 screen, dense_search_l2_sq8.hip: the same codes under the squared Euclidean distance): the
 // route of a search and the bodies of its entries, the pieces common to the two 16x16x32 screen GEMMs, the rescoring kernel
 // and the certificate kernel.  Device code: every translation unit compiles its own copy, no -fgpu-rdc.
 //
@@ -214,6 +214,7 @@ __global__ __launch_bounds__(64) void dense_certify_kernel(const typename V::T* 
 //   static int exact_rows(h, x, ldx, N, D, q, nq, out, s) out [nq][N] = the chain of every pair
 //   static int finish(h, scores, n, s)                    the last step over the n output values; empty: launches nothing
 //   approximate: eq / refuse of dense_certify_kernel
+//   typedef Side                   optional: the side operand where one pointer is not enough (dense_side<V>)
 //   static constexpr bool coded                           x holds codes that per-dimension vectors decode (dense_search_sq8.hip).
 //                                                         `side` (xsq of the L2 variants) then points at those vectors, and
 //                                                         prepass and exact_rows take it as their FIRST argument; the variant
@@ -229,6 +230,14 @@ struct dense_variant_defaults {
     static int prepass(rc_handle_t, const T* q, int, int, char*, const T** qs, hipStream_t) { *qs = q; return RC_OK; }
     static int finish(rc_handle_t, float*, int64_t, hipStream_t) { return RC_OK; }
 };
+
+// the side operand of a variant: one pointer (xsq of the L2 variants, the decoding vectors of the coded one) unless the
+// variant names a small struct of its own, V::Side, for more than one (dense_search_l2_sq8.hip: both); `!side` says that
+// something of it is missing.  The route only hands it on: no variant takes another branch for it.
+template <typename V, typename = void>
+struct dense_side { typedef const float* type; };
+template <typename V>
+struct dense_side<V, std::void_t<typename V::Side>> { typedef typename V::Side type; };
 
 template <typename V, typename = void>
 struct dense_storage { typedef typename V::T type; };
@@ -248,7 +257,7 @@ static size_t dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
 template <typename V>
 static int dense_exact(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
                        const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, char* w,
-                       const dense_exact_layout& L, hipStream_t s, const float* side = nullptr) {
+                       const dense_exact_layout& L, hipStream_t s, typename dense_side<V>::type side = {}) {
     float* sc = (float*)(w + L.sc);             // (the select's status word is never set: exactly min(k, N) keys are collected)
     for (int q0 = 0; q0 < nq; q0 += L.qx) {
         const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
@@ -265,8 +274,9 @@ static int dense_exact(rc_handle_t h, const typename dense_storage<V>::type* x, 
 // checked arguments (dense_search_entry: dense_check, the extra pointers, nq > 0, a workspace of dense_search_ws_bytes<V>)
 template <typename V>
 static int dense_search_route(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                              const typename V::T* q, int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset,
-                              double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, char* w, hipStream_t s) {
+                              const typename V::T* q, int nq, typename dense_side<V>::type xsq, const float* xnorm_max, int k,
+                              int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, char* w,
+                              hipStream_t s) {
     if (dense_exact_route(N))
         return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s, xsq);
     const dense_fast_layout L = dense_fast_ws(N, nq);
@@ -311,7 +321,7 @@ static int dense_search_route(rc_handle_t h, const typename dense_storage<V>::ty
 template <typename V>
 static int dense_exact_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
                              const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
-                             size_t ws_bytes, rc_stream_t stream, const float* side = nullptr) {
+                             size_t ws_bytes, rc_stream_t stream, typename dense_side<V>::type side = {}) {
     rc_device_guard device_guard_(h);
     const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids, !V::coded);
     if (crc != RC_OK) return crc;
@@ -325,9 +335,9 @@ static int dense_exact_entry(rc_handle_t h, const typename dense_storage<V>::typ
 // xsq is read if V::l2 or V::coded, xnorm_max if V::approximate
 template <typename V>
 static int dense_search_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                              const typename V::T* q, int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset,
-                              double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
-                              rc_stream_t stream) {
+                              const typename V::T* q, int nq, typename dense_side<V>::type xsq, const float* xnorm_max, int k,
+                              int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, void* ws,
+                              size_t ws_bytes, rc_stream_t stream) {
     rc_device_guard device_guard_(h);
     const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids, !V::coded);
     if (crc != RC_OK) return crc;

@@ -39,7 +39,7 @@
 // intermediate overflows and alpha is normal.  An all-zero w has alpha = 0 and zero limbs: s~ = bias, inside the bound.
 // The constants are exported (rc_dense_sq8_error_constants) and are what ops.dense_sq8_error_bound evaluates.
 #include "dense_i8_gemm.h"
-#include "dense_sq8.h"
+#include "dense_sq8_chain.h"
 
 #define DENSE_SQ8_C_Q 0.5
 #define DENSE_SQ8_C_W 520.0
@@ -48,97 +48,9 @@
 #define DENSE_SQ8_C_B 2.1
 #define DENSE_SQ8_C_CH 1.02
 #define DENSE_SQ8_C_ABS 1.0
-#define DENSE_SQ8_BIG 0x1p100f                           // the certificate's range: |values| below it, alpha above its inverse
 
-typedef signed char dense_i8x16 __attribute__((ext_vector_type(16)));
-
-// ---- rescoring --------------------------------------------------------------------------------------------------------------
-// dense_rescore_kernel (dense_screen.h) over coded rows: grid (nq, ADC_CAND_CAP / 256) blocks of 256 threads, one lane per
-// candidate key of query blockIdx.x; step, mid and the query are staged in LDS chunk by chunk.  VEC: 16-byte aligned rows.
-template <bool VEC>
-__global__ __launch_bounds__(256) void dense_sq8_rescore_kernel(const signed char* __restrict__ x, int64_t ldx, int D,
-                                                                const float* __restrict__ dec, const float* __restrict__ q,
-                                                                const unsigned* __restrict__ cnt,
-                                                                unsigned long long* __restrict__ cand) {
-    __shared__ float sq[DENSE_RESCORE_QCHUNK], ss[DENSE_RESCORE_QCHUNK], sm[DENSE_RESCORE_QCHUNK];
-    const int qi = blockIdx.x, tid = threadIdx.x;
-    const unsigned raw = cnt[qi];
-    const unsigned n = raw > ADC_CAND_CAP ? ADC_CAND_CAP : raw;
-    if (blockIdx.y * 256u >= n) return;                                // block-uniform
-    const unsigned i = blockIdx.y * 256u + tid;
-    const bool mine = i < n;
-    unsigned long long* kp = cand + (size_t)qi * ADC_CAND_CAP + i;
-    const unsigned row = mine ? 0xFFFFFFFFu - (unsigned)(*kp & 0xFFFFFFFFull) : 0u;
-    const signed char* xp = x + (int64_t)row * ldx;
-    const float* qp = q + (int64_t)qi * D;
-    float s = 0.f;
-    for (int d0 = 0; d0 < D; d0 += DENSE_RESCORE_QCHUNK) {
-        const int dn = D - d0 < DENSE_RESCORE_QCHUNK ? D - d0 : DENSE_RESCORE_QCHUNK;
-        __syncthreads();
-        for (int d = tid; d < dn; d += 256) { sq[d] = qp[d0 + d]; ss[d] = dec[d0 + d]; sm[d] = dec[D + d0 + d]; }
-        __syncthreads();
-        if (mine) {
-            int d = 0;
-            if constexpr (VEC) {
-                for (; d + 16 <= dn; d += 16) {
-                    const dense_i8x16 v = *reinterpret_cast<const dense_i8x16*>(xp + d0 + d);
-#pragma unroll
-                    for (int e = 0; e < 16; ++e)
-                        s = dense_chain_step<false>(sq[d + e], dense_sq8_decode(v[e], ss[d + e], sm[d + e]), s);
-                }
-            }
-            for (; d < dn; ++d) s = dense_chain_step<false>(sq[d], dense_sq8_decode(xp[d0 + d], ss[d], sm[d]), s);
-        }
-    }
-    if (mine) *kp = adc_exact_key(s, (int64_t)row);
-}
-
-// ---- the exact route's score rows -------------------------------------------------------------------------------------------
-#define DENSE_SQ8_ROWS_QB 4                              // queries that share a decoded value
-// grid: (ceil(N / 256), ceil(nq / 4)) blocks of 256 threads; thread -> one corpus row and four queries: out [nq][N] = the chain
-// of every pair.  A value is decoded once and feeds four chains.  Plain fp32: the exact route serves small corpora and the few
-// queries the fast route gives up on.
-__global__ __launch_bounds__(256) void dense_sq8_rows_kernel(const signed char* __restrict__ x, int64_t ldx, int64_t N, int D,
-                                                             const float* __restrict__ dec, const float* __restrict__ q, int nq,
-                                                             float* __restrict__ out) {
-    __shared__ float sq[DENSE_SQ8_ROWS_QB][DENSE_RESCORE_QCHUNK], ss[DENSE_RESCORE_QCHUNK], sm[DENSE_RESCORE_QCHUNK];
-    const int tid = threadIdx.x;
-    const int q0 = blockIdx.y * DENSE_SQ8_ROWS_QB;
-    const int64_t j = (int64_t)blockIdx.x * 256 + tid;
-    const bool mine = j < N;
-    const signed char* xp = x + (mine ? j : N - 1) * ldx;
-    float s[DENSE_SQ8_ROWS_QB];
-#pragma unroll
-    for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b) s[b] = 0.f;
-    for (int d0 = 0; d0 < D; d0 += DENSE_RESCORE_QCHUNK) {
-        const int dn = D - d0 < DENSE_RESCORE_QCHUNK ? D - d0 : DENSE_RESCORE_QCHUNK;
-        __syncthreads();
-        for (int d = tid; d < dn; d += 256) {
-            ss[d] = dec[d0 + d];
-            sm[d] = dec[D + d0 + d];
-#pragma unroll
-            for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b) sq[b][d] = q[(int64_t)(q0 + b < nq ? q0 + b : nq - 1) * D + d0 + d];
-        }
-        __syncthreads();
-        for (int d = 0; d < dn; ++d) {
-            const float v = dense_sq8_decode(xp[d0 + d], ss[d], sm[d]);
-#pragma unroll
-            for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b) s[b] = dense_chain_step<false>(sq[b][d], v, s[b]);
-        }
-    }
-    if (mine)
-#pragma unroll
-        for (int b = 0; b < DENSE_SQ8_ROWS_QB; ++b)
-            if (q0 + b < nq) out[(int64_t)(q0 + b) * N + j] = s[b];
-}
-
-static int dense_sq8_exact_rows(const float* dec, rc_handle_t h, const signed char* x, int64_t ldx, int64_t N, int D,
-                                const float* q, int nq, float* out, hipStream_t s) {
-    const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((nq + DENSE_SQ8_ROWS_QB - 1) / DENSE_SQ8_ROWS_QB));
-    hipLaunchKernelGGL(dense_sq8_rows_kernel, grid, dim3(256), 0, s, x, ldx, N, D, dec, q, nq, out);
-    RC_LAUNCH_CHECK(h);
-    return RC_OK;
-}
+// The chain over coded rows — dense_sq8_rescore_kernel<VEC> for the fast route's candidates, dense_sq8_rows_kernel<> for the
+// exact route — is dense_sq8_chain.h's, shared with the L2 search over the same store.
 
 // grid: ceil(N D / 256) blocks of 256 threads: out [N][D] = the decoded corpus
 __global__ __launch_bounds__(256) void dense_sq8_decode_kernel(const signed char* __restrict__ x, int64_t ldx, int64_t N, int D,
@@ -160,47 +72,13 @@ __host__ __device__ static inline double dense_sq8_eq(int D, double alpha, doubl
     return (rel + abs_) * (1.0 + 0x1p-20);
 }
 
-// grid: nq blocks of 64 threads, as dense_certify_kernel.  cstat: [2] fp32 = C1, X.  Sets bit2 of status / qstatus[q] unless
-// t >= thr~ + E_q is proven; a NaN anywhere is "not certified".
-__global__ __launch_bounds__(64) void dense_sq8_certify_kernel(const float* __restrict__ q, int D, int k,
-                                                               const float* __restrict__ dec, const float* __restrict__ alpha,
-                                                               const float* __restrict__ thr, const float* __restrict__ cstat,
-                                                               const float* __restrict__ scores, int* __restrict__ status,
-                                                               int* __restrict__ qstatus) {
-    const int qi = blockIdx.x, lane = threadIdx.x;
-    const float* qp = q + (int64_t)qi * D;
-    double ss = 0.0, w1 = 0.0, b1 = 0.0;
-    int refused = 0, nonzero = 0;
-    for (int d = lane; d < D; d += 64) {
-        const float f = qp[d];
-        const float w = fabsf(f * dec[d]);
-        const double b = fabs((double)f * (double)dec[D + d]);
-        refused |= !(fabsf(f) < DENSE_SQ8_BIG) || !(w < DENSE_SQ8_BIG) || !(b < (double)DENSE_SQ8_BIG);
-        nonzero |= w > 0.f;
-        ss += (double)f * (double)f;
-        w1 += (double)w;
-        b1 += b;
+// what dense_sq8_certify_kernel (dense_sq8_chain.h) adds to thr~: E_q from the sums it collected, each pushed upwards
+struct dense_sq8_bound {
+    __device__ static double add(int D, double alpha, double w1, double b1, double ss, double c1, double X) {
+        const double up = 1.0 + 0x1p-30;
+        return dense_sq8_eq(D, alpha, w1 * up, b1 * up, sqrt(ss) * up, c1, X);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        ss += __shfl_xor(ss, o);
-        w1 += __shfl_xor(w1, o);
-        b1 += __shfl_xor(b1, o);
-        refused |= __shfl_xor(refused, o);
-        nonzero |= __shfl_xor(nonzero, o);
-    }
-    if (lane != 0) return;
-    const float a = alpha[qi];
-    refused |= D > DENSE_I8_MAX_D || (nonzero && !(a >= 1.f / DENSE_SQ8_BIG));
-    const double up = 1.0 + 0x1p-30;
-    const double sum = (double)thr[qi] + dense_sq8_eq(D, (double)a, w1 * up, b1 * up, sqrt(ss) * up, (double)cstat[0], (double)cstat[1]);
-    const double bound = sum + fabs(sum) * 0x1p-30;
-    const double t = (double)scores[(size_t)qi * k + (k - 1)];
-    if (refused || !(t >= bound)) {
-        atomicOr(status, 4);
-        if (qstatus) atomicOr(qstatus + qi, 4);
-    }
-}
+};
 
 // ---- the variant ------------------------------------------------------------------------------------------------------------
 struct dense_sq8_variant : dense_variant_defaults {
@@ -221,25 +99,9 @@ struct dense_sq8_variant : dense_variant_defaults {
                            hipStream_t s) {
         return dense_i8_launch_gemm<MODE>(h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s);
     }
-    static constexpr auto* exact_rows = &dense_sq8_exact_rows;
-    static int rescore(const float* dec, rc_handle_t h, const X* x, int64_t ldx, int D, const float* q, int nq,
-                       const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
-        const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
-        if (ldx % 16 == 0 && !((uintptr_t)x & 15u))
-            hipLaunchKernelGGL(dense_sq8_rescore_kernel<true>, grid, dim3(256), 0, s, x, ldx, D, dec, q, cnt, cand);
-        else
-            hipLaunchKernelGGL(dense_sq8_rescore_kernel<false>, grid, dim3(256), 0, s, x, ldx, D, dec, q, cnt, cand);
-        RC_LAUNCH_CHECK(h);
-        return RC_OK;
-    }
-    static int certify(const float* dec, rc_handle_t h, const float* q, const Q* qs, int nq, int D, int k, const float* thr,
-                       const float* cstat, const float* scores, int* status, int* qstatus, hipStream_t s) {
-        const float* alpha = (const float*)(qs + dense_i8_query_ws(nq, D).alpha);
-        hipLaunchKernelGGL(dense_sq8_certify_kernel, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, dec, alpha, thr, cstat, scores,
-                           status, qstatus);
-        RC_LAUNCH_CHECK(h);
-        return RC_OK;
-    }
+    static constexpr auto* exact_rows = &dense_sq8_launch_exact_rows<false>;
+    static constexpr auto* rescore = &dense_sq8_launch_rescore<false>;
+    static constexpr auto* certify = &dense_sq8_launch_certify<dense_sq8_bound>;
 };
 
 static bool dense_sq8_shape_ok(int64_t N, int D, int nq, int k) { return dense_shape_ok(N, D, nq, k) && D <= DENSE_I8_MAX_D; }

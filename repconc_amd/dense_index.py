@@ -16,6 +16,9 @@ index, but the candidates are chosen on the bf16 matrix cores by `ops.dense_sear
 
 `FlatL2Index` / `FlatL2F16Index` / `FlatL2Bf16x3Index`: the squared-Euclidean indexes (`faiss.IndexFlatL2`: fp32 storage, fp16
 storage, fp32 storage with the bf16x3 screen), classes of their own beside `FlatIPIndex`.
+
+`FlatSQ8Index` / `FlatL2SQ8Index`: the inner-product and the squared-Euclidean index over 8-bit scalar-quantiser codes
+(`faiss.IndexScalarQuantizer`, QT_8bit), one byte per dimension; they share the store and its training (`_SQ8Store`).
 """
 from __future__ import annotations
 
@@ -318,32 +321,21 @@ def sq8_encode(xt: torch.Tensor, vmin: torch.Tensor, step: torch.Tensor) -> torc
     return (c - 128.0).to(torch.int8)
 
 
-class FlatSQ8Index(_FlatIndex):
-    """Exact inner-product index over 8-bit scalar-quantiser codes resident in HBM: `faiss.IndexScalarQuantizer(d, QT_8bit,
-    METRIC_INNER_PRODUCT)`, one byte per dimension.  Duck-typed like `FlatIPIndex`, plus `train`.
+class _SQ8Store(_FlatIndex):
+    """What the indexes over 8-bit scalar-quantiser codes share: the training, `add` (encode in chunks, refuse non-finite rows
+    before anything counts, the certificate's statistics `ops.dense_sq8_cstat` without a host read), `reconstruct_n`, and a
+    `reset` that keeps the training.  A subclass says which search answers (`_enqueue`) and may keep more per row
+    (`_chunk_added`)."""
+    ROWS_PER_STEP = SQ8_ROWS_PER_STEP     # rows that `add` moves and encodes at a time
 
-    `train(x)`: per dimension vmin and vmax over the training rows (Faiss's RS_minmax with argument 0), step = fp32((vmax -
-    vmin) / 255) and mid = fp32(vmin + 128.5 step), evaluated in fp64 and rounded once.  `add` encodes c = clamp(floor((x -
-    vmin) / step), 0, 255) in fp32 (0 where step = 0; values outside the trained range clamp) and stores c - 128 as int8; a
-    non-finite value is refused before anything is stored (the one host read of an `add`).  A stored row IS its decoded value
-    x^ = fmaf(c - 128, step, mid), the centre of its bin (`reconstruct_n`), and `search` answers with `ops.dense_search_sq8`
-    (csrc/dense_search_sq8.hip): ids and score bits are what `FlatIPIndex` returns over `reconstruct_n(0, ntotal)`.  `reset`
-    drops the rows and keeps the training.  Beside the codes the index keeps the two statistics of the search's certificate
-    (`ops.dense_sq8_cstat`), updated by `add` without a host read.  METRIC_L2 is not served."""
-
-    def __init__(self, d: int, device: Optional[torch.device] = None, metric: int = METRIC_INNER_PRODUCT):
-        if metric != METRIC_INNER_PRODUCT:
-            raise ValueError("FlatSQ8Index: METRIC_INNER_PRODUCT only (L2 over int8 codes is not served)")
+    def _init_sq8(self, d: int, device, init_store) -> None:
         if not 1 <= int(d) <= ops.DENSE_SQ8_MAX_D:
-            raise ValueError(f"FlatSQ8Index: d must be in [1, {ops.DENSE_SQ8_MAX_D}]")
-        self._init_store(d, device, torch.int8)
-        self.metric_type = METRIC_INNER_PRODUCT
+            raise ValueError(f"{type(self).__name__}: d must be in [1, {ops.DENSE_SQ8_MAX_D}]")
+        init_store(d, device, torch.int8)
         self.is_trained = False
         self.vmin = self.step = self.mid = None
         self._dec = None            # [2, d] fp32: step, mid
         self._cstat = None          # [2] fp32: the largest row L1 norm of the codes, a bound of the largest decoded row norm
-
-    ROWS_PER_STEP = SQ8_ROWS_PER_STEP     # rows that `add` moves and encodes at a time
 
     def train(self, x) -> None:
         self.vmin, self._dec = sq8_train_range(self._rows(x), self.device)
@@ -357,6 +349,9 @@ class FlatSQ8Index(_FlatIndex):
     def encode(self, xt: torch.Tensor) -> torch.Tensor:
         """The int8 codes c - 128 of fp32 rows on the index's device."""
         return sq8_encode(xt, self.vmin, self.step)
+
+    def _chunk_added(self, lo: int, codes: torch.Tensor) -> None:
+        """The codes of one chunk of an `add` were written at row `lo` (past ntotal: they do not count yet)."""
 
     def add(self, x) -> None:
         xt = self._rows(x)
@@ -375,6 +370,7 @@ class FlatSQ8Index(_FlatIndex):
             codes = self.encode(torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0))
             self._x[self.ntotal + r0:self.ntotal + r0 + codes.shape[0]] = codes
             cstat = torch.maximum(cstat, ops.dense_sq8_cstat(codes, self._dec))
+            self._chunk_added(self.ntotal + r0, codes)
         if not bool(finite):
             raise ValueError("add: int8 storage needs finite values")
         self.ntotal = need
@@ -397,8 +393,49 @@ class FlatSQ8Index(_FlatIndex):
         return super().search_async(x, k)
 
     def rerank(self, x, cand_ids, k: int):
-        raise ValueError("FlatSQ8Index: rerank over an int8 store is not served")
+        raise ValueError(f"{type(self).__name__}: rerank over an int8 store is not served")
+
+
+class FlatSQ8Index(_SQ8Store):
+    """Exact inner-product index over 8-bit scalar-quantiser codes resident in HBM: `faiss.IndexScalarQuantizer(d, QT_8bit,
+    METRIC_INNER_PRODUCT)`, one byte per dimension.  Duck-typed like `FlatIPIndex`, plus `train`.
+
+    `train(x)`: per dimension vmin and vmax over the training rows (Faiss's RS_minmax with argument 0), step = fp32((vmax -
+    vmin) / 255) and mid = fp32(vmin + 128.5 step), evaluated in fp64 and rounded once.  `add` encodes c = clamp(floor((x -
+    vmin) / step), 0, 255) in fp32 (0 where step = 0; values outside the trained range clamp) and stores c - 128 as int8; a
+    non-finite value is refused before anything is stored (the one host read of an `add`).  A stored row IS its decoded value
+    x^ = fmaf(c - 128, step, mid), the centre of its bin (`reconstruct_n`), and `search` answers with `ops.dense_search_sq8`
+    (csrc/dense_search_sq8.hip): ids and score bits are what `FlatIPIndex` returns over `reconstruct_n(0, ntotal)`.  `reset`
+    drops the rows and keeps the training.  Beside the codes the index keeps the two statistics of the search's certificate
+    (`ops.dense_sq8_cstat`), updated by `add` without a host read.  METRIC_L2 is not served here: `FlatL2SQ8Index` is the
+    squared-Euclidean index over the same store."""
+
+    def __init__(self, d: int, device: Optional[torch.device] = None, metric: int = METRIC_INNER_PRODUCT):
+        if metric != METRIC_INNER_PRODUCT:
+            raise ValueError("FlatSQ8Index: METRIC_INNER_PRODUCT only (the L2 index over int8 codes is FlatL2SQ8Index)")
+        self._init_sq8(d, device, self._init_store)
+        self.metric_type = METRIC_INNER_PRODUCT
 
     def _enqueue(self, q, k: int):
         return ops.dense_search_sq8(self.xb, self._dec, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
                                     cstat=self._cstat)
+
+
+class FlatL2SQ8Index(_SQ8Store, _FlatL2):
+    """Exact squared-Euclidean index over 8-bit scalar-quantiser codes resident in HBM: `faiss.IndexScalarQuantizer(d, QT_8bit)`
+    with Faiss's default metric, a class of its own beside `FlatSQ8Index` as `FlatL2F16Index` is beside `FlatIPIndex`.  The
+    store, `train`, `add`, `reconstruct_n` and `reset` are `FlatSQ8Index`'s; `search` answers with `ops.dense_search_l2_sq8`
+    (csrc/dense_search_l2_sq8.hip): ids and distance bits are what `FlatL2Index` returns over `reconstruct_n(0, ntotal)`,
+    sorted (distance asc, id asc), +inf / -1 past ntotal.  Beside the codes and the certificate's statistics the index keeps the
+    fp32 squared norms of the decoded rows in a capacity-sized tensor, as the other L2 indexes keep theirs
+    (`ops.dense_sq8_row_sqnorms`, computed from the codes chunk by chunk in `add`, no extra host read)."""
+
+    def __init__(self, d: int, device: Optional[torch.device] = None):
+        self._init_sq8(d, device, self._init_l2)
+
+    def _chunk_added(self, lo: int, codes: torch.Tensor) -> None:
+        self._xsq[lo:lo + codes.shape[0]] = ops.dense_sq8_row_sqnorms(codes, self._dec)
+
+    def _enqueue(self, q, k: int):
+        return ops.dense_search_l2_sq8(self.xb, self._dec, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack,
+                                       defer=True, xsq=self._xsq[: self.ntotal], cstat=self._cstat)

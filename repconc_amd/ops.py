@@ -10,6 +10,7 @@ import collections
 import ctypes as C
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -1171,7 +1172,7 @@ def _dense_sq8_args(x8: torch.Tensor, q: torch.Tensor, k: int):
     return x8, q.to(x8.device, torch.float32).contiguous()
 
 
-# One dense search in seven variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
+# One dense search in eight variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
 # library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes; exact: rc_<exact>_search_exact / ..._ws_bytes, the route that
 # cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate);
 # rownorms: it also takes xsq, the squared norm of every row, before xnorm_max; pad: the value of the slots past N.
@@ -1185,6 +1186,8 @@ _DENSE_L2_F16 = _DenseVariant(_dense_f16_args, "dense_l2_f16", "dense_l2_f16", T
 _DENSE_L2_BF16X3 = _DenseVariant(_dense_args, "dense_l2_bf16x3", "dense_l2", True, True, float("inf"))
 # int8 codes: both entries take the decoding vectors `dec` after the queries, the search also the corpus statistics `cstat`
 _DENSE_SQ8 = _DenseVariant(_dense_sq8_args, "dense_sq8", "dense_sq8", False)
+# int8 codes under L2: the search takes dec, the rows' squared norms xsq and cstat, in that order
+_DENSE_L2_SQ8 = _DenseVariant(_dense_sq8_args, "dense_l2_sq8", "dense_l2_sq8", False, True, float("inf"))
 
 
 def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int,
@@ -1236,7 +1239,8 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
         _need_cuda(xsq)
         if xsq.shape != (N,):
             raise ValueError("dense search: xsq must hold one squared norm per row, [N]")
-        norm = (xsq.to(torch.float32).contiguous(),) + norm
+        xsq = xsq.to(torch.float32).contiguous()
+        norm = (xsq,) + norm if dec is None else (dec, xsq, cstat)
     name = f"rc_{v.entry}_search_q"
     search_q, ws_bytes = getattr(lib, name), getattr(lib, f"rc_{v.entry}_search_ws_bytes")
 
@@ -1766,15 +1770,19 @@ def dense_search_l2(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0
     return _dense_search_l2(_DENSE_L2, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)
 
 
-def _dense_search_l2(v: _DenseVariant, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max):
-    """The front of the three L2 searches: a missing xnorm_max comes from the squared norms, which are then computed once."""
+def _dense_search_l2(v: _DenseVariant, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max,
+                     dec=None, cstat=None, stats=None):
+    """The front of the four L2 searches: a missing xnorm_max comes from the squared norms, which are then computed once.
+    Over int8 codes (`dec` given) the norms are those of the decoded rows and the certificate reads `cstat`, not xnorm_max."""
     if not 1 <= int(k) <= DENSE_MAX_K:
         raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
-    if xnorm_max is None and x.dim() == 2 and x.shape[0] > DENSE_EXACT_MAX_N and method == "auto" and x.is_cuda:
+    missing = xnorm_max is None if dec is None else xsq is None
+    if missing and x.dim() == 2 and x.shape[0] > DENSE_EXACT_MAX_N and method == "auto" and x.is_cuda:
         if xsq is None:
-            xsq = dense_row_sqnorms(x)
-        xnorm_max = _dense_l2_xnorm_max(xsq)
-    return _dense_search(v, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, xsq)
+            xsq = dense_row_sqnorms(x) if dec is None else dense_sq8_row_sqnorms(x, dec)
+        if dec is None:
+            xnorm_max = _dense_l2_xnorm_max(xsq)
+    return _dense_search(v, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, xsq, dec, cstat, stats)
 
 
 # ---------------------------------------------------------------------------------------- dense, L2 metric, fp16 storage
@@ -1887,3 +1895,110 @@ def dense_search_l2_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: 
     for a query with a non-finite value or one that rounds to a bf16 inf: such queries are repeated, then answered by
     `dense_search_l2_exact`; `.stats` of the `PendingSearch`).  xsq, xnorm_max and everything else as `dense_search_l2`."""
     return _dense_search_l2(_DENSE_L2_BF16X3, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)
+
+
+# ----------------------------------------------------------------- dense, L2 metric, 8-bit scalar-quantised storage
+def dense_l2_sq8_error_constants():
+    """(c_q, c_w, c_ad, c_ac, c_b, c_r, c_abs, max_r, max_e) of E_q as the certificate kernel was compiled with them
+    (csrc/dense_search_l2_sq8.hip).  No GPU needed."""
+    c = (C.c_double * 9)()
+    _lib.load().rc_dense_l2_sq8_error_constants(c)
+    return tuple(float(v) for v in c)
+
+
+def dense_l2_sq8_error_bound(D: int, alpha, w1, b1, qnorm, c1, xmax):
+    """E_q of the certificate of `dense_search_l2_sq8` (include/repconc_hip.h, rc_dense_l2_sq8_search_q; derivation in the
+    header comment of csrc/dense_search_l2_sq8.hip): the bound on |sigma - ||q||^2 + d| between the int8 L2 screen sigma =
+    fmaf(2, s~, -xsq) and the chain d.  Arguments as `dense_sq8_error_bound`; +inf where (qnorm + xmax)^2 or E_q itself leaves
+    the range in which nothing overflows.  The constants are the library's.  numpy arithmetic: scalars or arrays."""
+    c_q, c_w, c_ad, c_ac, c_b, c_r, c_abs, max_r, max_e = dense_l2_sq8_error_constants()
+    dpad = float((int(D) + 15) // 16 * 16)
+    r = np.asarray(qnorm, dtype=np.float64) + xmax
+    R = r * r
+    rel = c_q * alpha * c1 + 2.0 ** -24 * (c_w * w1 + c_ad * alpha * D + c_ac * alpha * c1 + c_b * b1 + c_r * (dpad + 5.0) * R)
+    e = (rel + c_abs * 2.0 ** -149 * (dpad + dpad ** 0.5 * qnorm + c1 + 3.0)) * (1.0 + 2.0 ** -20)
+    return np.where((R < max_r) & (e < max_e), e, np.where(np.isnan(e), e, np.inf))
+
+
+def dense_sq8_row_sqnorms(x8: torch.Tensor, dec: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
+    """fp32 [N] on the device of `x8`: the squared Euclidean norm of every DECODED row fmaf(c', step, mid), an fp64 sum rounded
+    to nearest (the rule of `dense_row_sqnorms`): the `xsq` of `dense_search_l2_sq8`.  On the GPU a kernel computes it from
+    the codes (rc_dense_sq8_row_sqnorms; the decoded corpus is never written); on the CPU, torch operators (the decode's one
+    rounding through an fp64 sum rounded to odd).  No host synchronisation."""
+    if x8.dim() != 2 or x8.dtype != torch.int8 or dec.shape != (2, x8.shape[1]):
+        raise ValueError("dense_sq8_row_sqnorms: int8 codes [N, D] and dec [2, D]")
+    N, D = x8.shape
+    dec = dec.to(x8.device, torch.float32).contiguous()
+    out = torch.empty((N,), dtype=torch.float32, device=x8.device)
+    if x8.is_cuda:
+        if x8.stride(1) != 1 or (N > 1 and x8.stride(0) < D):
+            x8 = x8.contiguous()
+        if N:
+            lib, h, s, _ = _ctx(x8)
+            _lib.check(lib.rc_dense_sq8_row_sqnorms(h, _p(x8), x8.stride(0), N, D, _p(dec), _p(out), s),
+                       "rc_dense_sq8_row_sqnorms", h)
+        return out
+    step, mid = dec[0].double(), dec[1].double()
+    for r0 in range(0, N, rows_per_step):
+        p = x8[r0:r0 + rows_per_step].double() * step               # exact: 8 + 24 significant bits
+        s = p + mid
+        bb = s - p
+        e = (p - (s - bb)) + (mid - bb)                             # TwoSum: p + mid = s + e exactly
+        odd = torch.where(e > 0, torch.nextafter(s, torch.full_like(s, float("inf"))),
+                          torch.nextafter(s, torch.full_like(s, float("-inf"))))
+        s = torch.where((e != 0) & ((s.view(torch.int64) & 1) == 0), odd, s)       # inexact and even: the odd neighbour
+        out[r0:r0 + rows_per_step] = s.float().double().square_().sum(1)
+    return out
+
+
+def dense_search_l2_sq8_exact(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+    """The same answer as `dense_search_l2_sq8` by the route that cannot fail (rc_dense_l2_sq8_search_exact)."""
+    return _dense_search_exact(_DENSE_L2_SQ8, x8, q, k, id_offset, _dense_sq8_dec(x8, dec))
+
+
+def dense_l2_sq8_scores(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The raw screen values sigma [nq, N] = fmaf(2, s~(q, n), -xsq[n]) of the int8 L2 search (rc_dense_l2_sq8_scores): a test
+    hook, never a result."""
+    x8, q = _dense_sq8_args(x8, q, 1)
+    dec = _dense_sq8_dec(x8, dec)
+    lib, h, s, _ = _ctx(q)
+    if xsq is None:
+        xsq = dense_sq8_row_sqnorms(x8, dec)
+    _need_cuda(xsq)
+    xsq = xsq.to(torch.float32).contiguous()
+    if xsq.shape != (x8.shape[0],):
+        raise ValueError("dense_l2_sq8_scores: xsq must hold one squared norm per row, [N]")
+    out = torch.empty((q.shape[0], x8.shape[0]), dtype=torch.float32, device=q.device)
+    if out.numel():
+        wsb = lib.rc_dense_l2_sq8_scores_ws_bytes(x8.shape[1], q.shape[0])
+        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        _lib.check(lib.rc_dense_l2_sq8_scores(h, _p(x8), x8.stride(0), x8.shape[0], x8.shape[1], _p(q), q.shape[0], _p(dec),
+                                              _p(xsq), _p(out), _p(ws), wsb, s), "rc_dense_l2_sq8_scores", h)
+    return out
+
+
+def dense_search_l2_sq8(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
+                        sel_slack: Optional[float] = None, defer: bool = False, method: str = "auto", max_retries: int = 2,
+                        xsq: Optional[torch.Tensor] = None, cstat: Optional[torch.Tensor] = None,
+                        stats: Optional[dict] = None):
+    """Exact top-k squared-Euclidean search of `q` [nq, D] against a corpus of 8-bit scalar-quantiser codes (faiss
+    IndexScalarQuantizer, QT_8bit, METRIC_L2): the store of `dense_search_sq8` under the distance of `dense_search_l2`.  A
+    distance is the chain t = q_j - x^_j, acc = fmaf(t, t, acc) over the decoded values x^ = fmaf(c', step, mid): ids and
+    distance bits equal `dense_search_l2(dense_sq8_decode(x8, dec), q, k)`; sorted (distance asc, id asc), +inf / -1 past N.
+    The int8 matrix cores only screen with sigma = fmaf(2, s~, -xsq); candidates are rescored by the chain and every answer of
+    the fast route carries a certificate (qstatus bit2 when it cannot be given: such queries are repeated, then answered by
+    `dense_search_l2_sq8_exact`; `.stats` of the `PendingSearch`).  xsq: device fp32 [N], the squared norms of the decoded rows
+    (`dense_sq8_row_sqnorms`); cstat: device fp32 [2] (`dense_sq8_cstat`); both computed here when None, and neither is read up
+    to DENSE_EXACT_MAX_N rows.  stats and everything else as `dense_search_sq8`."""
+    if x8.dim() == 2 and dec.shape != (2, x8.shape[1]):
+        raise ValueError("dense_search_l2_sq8: dec must be [2, D]: the steps, then the mids")
+    x8, _ = _dense_sq8_args(x8, q, k)
+    dec = _dense_sq8_dec(x8, dec)
+    if cstat is None:
+        cstat = dense_sq8_cstat(x8, dec) if x8.shape[0] > DENSE_EXACT_MAX_N else torch.zeros((2,), device=x8.device)
+    _need_cuda(cstat)
+    if cstat.shape != (2,):
+        raise ValueError("dense_search_l2_sq8: cstat must be [2]: C1 and X (dense_sq8_cstat)")
+    cstat = cstat.to(x8.device, torch.float32).contiguous()
+    return _dense_search_l2(_DENSE_L2_SQ8, x8, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, None, dec, cstat,
+                            stats)
