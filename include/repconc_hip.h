@@ -869,6 +869,20 @@ int rc_ivf_flat_sq8_search(rc_handle_t h, const int8_t* x, int64_t ldx, const in
                            int nlist, int D, const float* q, int nq, const float* dec, const int* probes, int nprobe,
                            int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status, int* qstatus,
                            void* ws, size_t ws_bytes, rc_stream_t stream);
+/* rc_ivf_flat_sq8r_search (faiss.IndexIVFScalarQuantizer, QT_8bit, by_residual = true): rc_ivf_flat_sq8_search over codes of
+ *   RESIDUALS.  Row n of cell l holds the codes of fp32(x[n][d] - coarse[l][d]) under one range (step, mid) shared by all cells;
+ *   coarse [nlist, ldc] fp32, ldc >= D, are the centroids the rows were encoded against.  A stored value is
+ *     x^[n][d] = fp32(fmaf((float)c'[n][d], step[d], mid[d]) + coarse[l][d]):
+ *   the decode of rc_ivf_flat_sq8_search, then ONE separate fp32 addition (two roundings, never one fused operation), done once
+ *   per value on its way into the scan's fp32 tile.  x^ feeds the chain above: scores are bit for bit what rc_ivf_flat_search
+ *   gives over those rows, under either metric; plan, selection, ties, padding, status bits, limits and ws
+ *   (rc_ivf_flat_search_ws_bytes) are those of rc_ivf_flat_sq8_search.  Only the centroids of probed cells are read, D values
+ *   of a row each.  Checks in the order of rc_ivf_flat_sq8_search: D > rc_dense_sq8_max_d() is RC_ESHAPE and comes first; then
+ *   dec and coarse among the pointers (a null coarse or ldc < D is RC_EINVAL). */
+int rc_ivf_flat_sq8r_search(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids, int64_t N,
+                            int nlist, int D, const float* q, int nq, const float* dec, const float* coarse, int64_t ldc,
+                            const int* probes, int nprobe, int64_t stride, int k, int metric, float* scores, int64_t* out_ids,
+                            int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
 
 /* ------------------------------------------------------------------ JPQ scoring head (csrc/jpq_head.hip)
  * Scores of (query, document id) pairs straight from the resident codes, and their gradients (stage 2 of the recipe,

@@ -37,6 +37,10 @@
 // store of 8-bit scalar-quantiser codes, fp32 queries.  A code is decoded once, fmaf((float)c', step_d, mid_d) (dense_sq8.h), on
 // its way from the staged registers into the same fp32 tile: the chains, and so the score bits, are those of the fp32 scan over
 // the decoded rows under either metric.  Same LDS, same plan, same selection.
+// RES (rc_ivf_flat_sq8r_search; faiss.IndexIVFScalarQuantizer, QT_8bit, by_residual = true): the codes are those of the row minus
+// the centroid of its cell, and a stored value is x^ = fp32(fmaf((float)c', step_d, mid_d) + coarse[cell][d]): the decode, then
+// ONE separate fp32 addition (two roundings) on the way into the tile.  A task is one cell, so the 16 centroid values of a
+// stage are uniform over the block, as step and mid are.
 #include "dense_l2.h"
 #include "dense_sq8.h"
 #include "ivf_plan.h"
@@ -96,15 +100,18 @@ __global__ __launch_bounds__(256) void ivf_flat_plan_query_kernel(const int64_t*
 // ONE 16-byte piece there (P = 1): the 64 lanes of a load touch 64 rows, and the seven later stages of a row's 128-byte line
 // are served by the caches.  Holding the slices of 2 or 4 stages in registers (one wider fetch per lane every 2 or 4 stages)
 // was measured and is slower at every nprobe (profiles/ivf_flat_sq8_form_ab.txt); this form is the one kept.
-template <typename T, typename TQ, bool L2, bool PAD>
+// RES (coded form only): coarse [nlist][ldc] fp32, the centroid of the task's cell is added to every decoded value.
+template <typename T, typename TQ, bool L2, bool PAD, bool RES = false>
 __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int64_t ldx, const int64_t* __restrict__ list_off,
                                                    int D, const TQ* __restrict__ q, const float* __restrict__ dec,
+                                                   const float* __restrict__ coarse, int64_t ldc,
                                                    const int* __restrict__ probes, const int* __restrict__ base, int nprobe,
                                                    int64_t stride, const int* __restrict__ task_list,
                                                    const int* __restrict__ task_qstart, const int* __restrict__ task_qcnt,
                                                    const int* __restrict__ sorted_q, float* __restrict__ dense,
                                                    int* __restrict__ rowid) {
     constexpr bool SQ = std::is_same<T, signed char>::value;
+    static_assert(SQ || !RES, "the residual form is a form of the coded scan");
     constexpr int EPP = 16 / (int)sizeof(T);                 // values per 16-byte piece
     constexpr int P = IVFF_KC / EPP;                         // pieces of a row's slice
     constexpr int NL = IVFF_RT * P / 256;                    // pieces per loader thread and stage
@@ -136,6 +143,7 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
     const bool qload = tid < IVFF_QG * IVFF_KC;
     const TQ* qp = q + (int64_t)((qload && qg < qc) ? sorted_q[qs + qg] : sorted_q[qs]) * D;
     const int nkc = (D + IVFF_KC - 1) / IVFF_KC;
+    const float* cp = RES ? coarse + (int64_t)cell * ldc : nullptr;      // the cell's centroid (block-uniform)
     for (int64_t ch = blockIdx.y; ch * IVFF_RT < size; ch += gridDim.y) {
         const int64_t r0 = c0 + ch * IVFF_RT;
         const int nrows = size - ch * IVFF_RT < IVFF_RT ? (int)(size - ch * IVFF_RT) : IVFF_RT;
@@ -147,6 +155,7 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
         ivff_u4 stg[NL];
         float rq = 0.f;
         float dstep[SQ ? IVFF_KC : 1], dmid[SQ ? IVFF_KC : 1];      // coded form: step and mid of the staged slice (wave-uniform)
+        float dcen[RES ? IVFF_KC : 1];                              // residual form: the cell's centroid over the slice, likewise
         // piece i = j 256 + tid of the stage: row i / P of the chunk, piece i % P of its slice; whole pieces inside the row with
         // one 16-byte load, nothing past D (PAD: value by value)
         auto gload = [&](int kc) {
@@ -172,6 +181,7 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
                     const int d = k0 + e < D ? k0 + e : D - 1;
                     dstep[e] = dec[d];
                     dmid[e] = dec[D + d];
+                    if constexpr (RES) dcen[e] = cp[d];
                 }
             }
             if (qload) rq = (qg < qc && k0 + qk < D) ? (float)qp[k0 + qk] : 0.f;
@@ -184,7 +194,10 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
                 u.v = stg[j];
 #pragma unroll
                 for (int e = 0; e < EPP; ++e) {
-                    if constexpr (SQ)
+                    if constexpr (RES)          // the decode's rounding, then the addition's: never one fused operation
+                        sx[buf][(pc * EPP + e) * IVFF_XLD + row] =
+                            dense_sq8_decode(u.e[e], dstep[pc * EPP + e], dmid[pc * EPP + e]) + dcen[pc * EPP + e];
+                    else if constexpr (SQ)
                         sx[buf][(pc * EPP + e) * IVFF_XLD + row] = dense_sq8_decode(u.e[e], dstep[pc * EPP + e], dmid[pc * EPP + e]);
                     else
                         sx[buf][(pc * EPP + e) * IVFF_XLD + row] = (float)u.e[e];
@@ -247,8 +260,8 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restri
                                                                const int* __restrict__ task_qcnt,
                                                                const int* __restrict__ sorted_q, float* __restrict__ dense,
                                                                int* __restrict__ rowid) {
-    ivf_flat_scan_body<T, T, L2, PAD>(x, ldx, list_off, D, q, nullptr, probes, base, nprobe, stride, task_list, task_qstart,
-                                      task_qcnt, sorted_q, dense, rowid);
+    ivf_flat_scan_body<T, T, L2, PAD>(x, ldx, list_off, D, q, nullptr, nullptr, 0, probes, base, nprobe, stride, task_list,
+                                      task_qstart, task_qcnt, sorted_q, dense, rowid);
 }
 
 // The coded form: int8 codes, fp32 queries, dec [2][D].  Same grid.
@@ -262,8 +275,24 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_sq8_scan_kernel(const signed 
                                                                    const int* __restrict__ task_qcnt,
                                                                    const int* __restrict__ sorted_q, float* __restrict__ dense,
                                                                    int* __restrict__ rowid) {
-    ivf_flat_scan_body<signed char, float, L2, PAD>(x, ldx, list_off, D, q, dec, probes, base, nprobe, stride, task_list,
-                                                    task_qstart, task_qcnt, sorted_q, dense, rowid);
+    ivf_flat_scan_body<signed char, float, L2, PAD>(x, ldx, list_off, D, q, dec, nullptr, 0, probes, base, nprobe, stride,
+                                                    task_list, task_qstart, task_qcnt, sorted_q, dense, rowid);
+}
+
+// The residual coded form: the codes of x - coarse[cell]; coarse [nlist][ldc] fp32.  Same grid.
+template <bool L2, bool PAD>
+__global__ __launch_bounds__(256, 2) void ivf_flat_sq8r_scan_kernel(const signed char* __restrict__ x, int64_t ldx,
+                                                                    const int64_t* __restrict__ list_off, int D,
+                                                                    const float* __restrict__ q, const float* __restrict__ dec,
+                                                                    const float* __restrict__ coarse, int64_t ldc,
+                                                                    const int* __restrict__ probes, const int* __restrict__ base,
+                                                                    int nprobe, int64_t stride, const int* __restrict__ task_list,
+                                                                    const int* __restrict__ task_qstart,
+                                                                    const int* __restrict__ task_qcnt,
+                                                                    const int* __restrict__ sorted_q, float* __restrict__ dense,
+                                                                    int* __restrict__ rowid) {
+    ivf_flat_scan_body<signed char, float, L2, PAD, true>(x, ldx, list_off, D, q, dec, coarse, ldc, probes, base, nprobe, stride,
+                                                          task_list, task_qstart, task_qcnt, sorted_q, dense, rowid);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -299,9 +328,10 @@ ivff_ws ivff_layout(int nq, int nprobe, int nlist, int64_t stride) {
     return L;
 }
 
-template <typename T, typename TQ, bool L2>
+template <typename T, typename TQ, bool L2, bool RES>
 int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, int D, const TQ* q, const float* dec,
-                     const int* probes, int nprobe, int64_t stride, char* w, const ivff_ws& L, hipStream_t s) {
+                     const float* coarse, int64_t ldc, const int* probes, int nprobe, int64_t stride, char* w, const ivff_ws& L,
+                     hipStream_t s) {
     auto I = [&](size_t off) { return (const int*)(w + off); };
     int64_t y = (stride + IVFF_RT - 1) / IVFF_RT;
     if (y > IVFF_Y_MAX) y = IVFF_Y_MAX;
@@ -309,7 +339,16 @@ int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list
     const bool vec = (D * (int64_t)sizeof(T)) % 16 == 0 && (ldx * (int64_t)sizeof(T)) % 16 == 0 && !((uintptr_t)x & 15u);
     float* dense = (float*)(w + L.dense);
     int* rowid = (int*)(w + L.rowid);
-    if constexpr (std::is_same<T, signed char>::value) {
+    if constexpr (RES) {
+        if (vec)
+            hipLaunchKernelGGL((ivf_flat_sq8r_scan_kernel<L2, false>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, coarse,
+                               ldc, probes, I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt),
+                               I(L.sorted_q), dense, rowid);
+        else
+            hipLaunchKernelGGL((ivf_flat_sq8r_scan_kernel<L2, true>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, coarse,
+                               ldc, probes, I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt),
+                               I(L.sorted_q), dense, rowid);
+    } else if constexpr (std::is_same<T, signed char>::value) {
         if (vec)
             hipLaunchKernelGGL((ivf_flat_sq8_scan_kernel<L2, false>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, probes,
                                I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense,
@@ -328,16 +367,18 @@ int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list
     return RC_OK;
 }
 
-// The body of the three entries.  Order of the checks: pointers and signs, shapes, the nq == 0 success, the workspace.
-// dec: the coded store's [step | mid] (T = signed char), not looked at otherwise.
-template <typename T, typename TQ>
+// The body of the four entries.  Order of the checks: pointers and signs, shapes, the nq == 0 success, the workspace.
+// dec: the coded store's [step | mid] (T = signed char), not looked at otherwise.  RES: the residual coded form, coarse
+// [nlist][ldc >= D] the centroids the codes are residuals of; not looked at otherwise.
+template <typename T, typename TQ, bool RES = false>
 int ivff_entry(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, const int64_t* ids, int64_t N, int nlist, int D,
-               const TQ* q, const float* dec, int nq, const int* probes, int nprobe, int64_t stride, int k, int metric,
+               const TQ* q, const float* dec, const float* coarse, int64_t ldc, int nq, const int* probes, int nprobe,
+               int64_t stride, int k, int metric,
                float* scores, int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
     constexpr bool SQ = std::is_same<T, signed char>::value;
     rc_device_guard device_guard_(h);
-    if (!h || !x || (SQ && !dec) || !list_off || !ids || !q || !probes || !scores || !out_ids || !status || N <= 0 || nlist <= 0 || D <= 0 ||
-        ldx < D || nq < 0 || nprobe <= 0 || nprobe > nlist || stride <= 0 || k <= 0)
+    if (!h || !x || (SQ && !dec) || (RES && (!coarse || ldc < D)) || !list_off || !ids || !q || !probes || !scores || !out_ids ||
+        !status || N <= 0 || nlist <= 0 || D <= 0 || ldx < D || nq < 0 || nprobe <= 0 || nprobe > nlist || stride <= 0 || k <= 0)
         return RC_EINVAL;
     if (k > ADC_CAND_CAP / 2 || N > 0xFFFFFFFFll || nlist > IVFF_MAX_NLIST || (metric != 0 && metric != 1)) return RC_ESHAPE;
     if (nq == 0) return RC_OK;
@@ -362,8 +403,10 @@ int ivff_entry(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, 
                        I(L.task_list), I(L.task_qstart), I(L.task_qcnt), IVFF_QG);
     RC_LAUNCH_CHECK(h);
     rc_prof_mark(h, RC_PROF_ADC_SCAN, s);
-    int rc = metric ? ivff_launch_scan<T, TQ, true>(h, x, ldx, list_off, D, q, dec, probes, nprobe, stride, w, L, s)
-                    : ivff_launch_scan<T, TQ, false>(h, x, ldx, list_off, D, q, dec, probes, nprobe, stride, w, L, s);
+    int rc = metric ? ivff_launch_scan<T, TQ, true, RES>(h, x, ldx, list_off, D, q, dec, coarse, ldc, probes, nprobe, stride, w,
+                                                         L, s)
+                    : ivff_launch_scan<T, TQ, false, RES>(h, x, ldx, list_off, D, q, dec, coarse, ldc, probes, nprobe, stride, w,
+                                                          L, s);
     rc_prof_mark(h, RC_PROF_ADC_SCAN, s);
     if (rc != RC_OK) return rc;
     unsigned* cnt = (unsigned*)(w + L.cnt);
@@ -390,8 +433,8 @@ extern "C" int rc_ivf_flat_search(rc_handle_t h, const float* x, int64_t ldx, co
                                   int64_t N, int nlist, int D, const float* q, int nq, const int* probes, int nprobe,
                                   int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status, int* qstatus,
                                   void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return ivff_entry<float, float>(h, x, ldx, list_off, ids, N, nlist, D, q, nullptr, nq, probes, nprobe, stride, k, metric, scores, out_ids,
-                             status, qstatus, ws, ws_bytes, stream);
+    return ivff_entry<float, float>(h, x, ldx, list_off, ids, N, nlist, D, q, nullptr, nullptr, 0, nq, probes, nprobe, stride, k,
+                                    metric, scores, out_ids, status, qstatus, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_ivf_flat_f16_search(rc_handle_t h, const uint16_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
@@ -399,8 +442,8 @@ extern "C" int rc_ivf_flat_f16_search(rc_handle_t h, const uint16_t* x, int64_t 
                                       int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status,
                                       int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
     return ivff_entry<_Float16, _Float16>(h, reinterpret_cast<const _Float16*>(x), ldx, list_off, ids, N, nlist, D,
-                                reinterpret_cast<const _Float16*>(q), nullptr, nq, probes, nprobe, stride, k, metric, scores, out_ids,
-                                status, qstatus, ws, ws_bytes, stream);
+                                reinterpret_cast<const _Float16*>(q), nullptr, nullptr, 0, nq, probes, nprobe, stride, k, metric,
+                                scores, out_ids, status, qstatus, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_ivf_flat_sq8_search(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
@@ -409,7 +452,18 @@ extern "C" int rc_ivf_flat_sq8_search(rc_handle_t h, const int8_t* x, int64_t ld
                                       int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
     // the codec's width limit first, as the rc_dense_sq8 entries order it (shapes, then pointers); then the shared order
     if (D > rc_dense_sq8_max_d()) return RC_ESHAPE;
-    return ivff_entry<signed char, float>(h, reinterpret_cast<const signed char*>(x), ldx, list_off, ids, N, nlist, D, q, dec, nq,
-                                          probes, nprobe, stride, k, metric, scores, out_ids, status, qstatus, ws, ws_bytes,
-                                          stream);
+    return ivff_entry<signed char, float>(h, reinterpret_cast<const signed char*>(x), ldx, list_off, ids, N, nlist, D, q, dec,
+                                          nullptr, 0, nq, probes, nprobe, stride, k, metric, scores, out_ids, status, qstatus, ws,
+                                          ws_bytes, stream);
+}
+
+extern "C" int rc_ivf_flat_sq8r_search(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                                       int64_t N, int nlist, int D, const float* q, int nq, const float* dec, const float* coarse,
+                                       int64_t ldc, const int* probes, int nprobe, int64_t stride, int k, int metric, float* scores,
+                                       int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    // the order of rc_ivf_flat_sq8_search: the codec's width limit, then the shared order with dec and coarse among the pointers
+    if (D > rc_dense_sq8_max_d()) return RC_ESHAPE;
+    return ivff_entry<signed char, float, true>(h, reinterpret_cast<const signed char*>(x), ldx, list_off, ids, N, nlist, D, q, dec,
+                                                coarse, ldc, nq, probes, nprobe, stride, k, metric, scores, out_ids, status,
+                                                qstatus, ws, ws_bytes, stream);
 }

@@ -293,16 +293,20 @@ class FlatL2Bf16x3Index(_FlatL2):
 SQ8_ROWS_PER_STEP = 1 << 18     # rows that the scalar quantiser's training and the indexes' `add` move and encode at a time
 
 
-def sq8_train_range(xt: torch.Tensor, device) -> tuple:
+def sq8_train_range(xt: torch.Tensor, device, residual=None) -> tuple:
     """The 8-bit scalar quantiser's training, shared by `FlatSQ8Index` and `IVFFlatIndex(storage="int8")`: xt [n >= 1, d] ->
     (vmin [d], dec [2, d] = step, mid) fp32 on `device`.  vmin / vmax per dimension over the rows (Faiss's RS_minmax with
-    argument 0), step = fp32((vmax - vmin) / 255), mid = fp32(vmin + 128.5 step), evaluated in fp64 and rounded once."""
+    argument 0), step = fp32((vmax - vmin) / 255), mid = fp32(vmin + 128.5 step), evaluated in fp64 and rounded once.
+    `residual` (the residual form of the IVF index): a function of a chunk of fp32 rows on `device` giving the rows the range
+    is fitted on in their place."""
     if xt.shape[0] == 0:
         raise ValueError("train: no rows")
     vmin = torch.full((xt.shape[1],), float("inf"), device=device)
     vmax = -vmin
     for r0 in range(0, xt.shape[0], SQ8_ROWS_PER_STEP):
         part = xt[r0:r0 + SQ8_ROWS_PER_STEP].to(device, torch.float32)
+        if residual is not None:
+            part = residual(part)
         vmin, vmax = torch.minimum(vmin, part.amin(0)), torch.maximum(vmax, part.amax(0))     # a NaN propagates
     if not bool((torch.isfinite(vmin) & torch.isfinite(vmax)).all()):
         raise ValueError("train: finite values only")

@@ -94,7 +94,8 @@ class IndexIVFScalarQuantizer(IndexIVFFlat):
     """faiss.IndexIVFScalarQuantizer(quantizer, d, nlist, qtype, metric=METRIC_L2, by_residual=True): `IVFFlatIndex(storage=
     "int8")` with Faiss's argument order and default metric; the quantizer is treated as `IndexIVFFlat` treats it.  Any qtype
     but ScalarQuantizer.QT_8bit is refused, and so is Faiss's default by_residual=True: this index encodes the vectors
-    themselves, so that its scores are the flat int8 index's — pass by_residual=False."""
+    themselves, so that its scores are the flat int8 index's — pass by_residual=False.  (Residual codes exist as
+    `IVFFlatIndex(storage="int8", by_residual=True)`; this class does not turn into them under Faiss's default.)"""
     _STORAGE = "int8"
 
     def __init__(self, quantizer, d: int, nlist: int, qtype: int = ScalarQuantizer.QT_8bit, metric=METRIC_L2,

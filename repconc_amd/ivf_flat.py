@@ -34,6 +34,25 @@ and the range.  Queries are fp32 and are not rounded.  The contract of this stor
   * under the inner product, probing every cell equals `FlatSQ8Index` trained on the same rows; under L2, probing every cell
     IS the exact L2 search over int8 codes (the flat int8 index does not serve L2).
 
+`storage="int8", by_residual=True` (Faiss's default for that index): a row is stored as the code of its RESIDUAL, r = fp32(x -
+coarse[cell]), one fp32 subtraction per value, under the same codec and ONE range (vmin, step, mid) shared by all cells.  The
+residuals of clustered rows span less than the rows do, so the same byte buys a finer step.  What changes against the above:
+  * `train(x)` fits the centroids first, assigns the training rows (`coarse_assign`) and fits the range on their residuals;
+    `train_sq(x)` needs the centroids (ValueError otherwise), assigns x and fits the range on the residuals;
+  * `add` encodes against the centroid of the L2-nearest cell of the values given, `set_lists` against the centroid of the
+    cell GIVEN; both refuse a non-finite row and a non-finite residual before anything is stored; a repeated `add` still
+    re-sorts codes and never re-encodes them (a row's cell never changes);
+  * `set_coarse` over stored rows is a ValueError naming `reset`: new centroids would change what the stored codes mean;
+  * a stored row IS x^ = fp32(fmaf(c - 128, step, mid) + coarse[cell]): the decode above, then one separate fp32 addition (two
+    roundings).  `reconstruct_n` returns exactly x^, and results equal the flat fp32 index of the same metric over
+    `reconstruct_n(0, ntotal)` restricted to the probed cells, in ids and score bits (`ops.ivf_flat_sq8r_search` adds the
+    centroid once per value on its way into the scan's tile); ties, padding, probing and the limits are unchanged.
+Index files, `create_index` / `run_dense_eval` and the Faiss shim do not serve this form.
+
+On the CPU device (`device="cpu"`: the build side with torch operators, for inspection and tests; the searches are GPU only)
+cells are assigned by the same rule, argmin_l (||c_l||^2 - 2 <x, c_l>), first minimum, and codes decode with the same single
+rounding.
+
 `add` may be called repeatedly; ids continue from `ntotal`.  Every `add` rebuilds the list-major store from the rows held and the
 new ones: while it runs, a second copy of the whole store exists on the device.
 """
@@ -50,13 +69,26 @@ from .index import METRIC_INNER_PRODUCT, METRIC_L2
 from .ivf import CoarseProbe, coarse_assign, coarse_kmeans
 
 
+def _sq8_decode_host(codes: torch.Tensor, dec: torch.Tensor) -> torch.Tensor:
+    """fmaf(c', step, mid) with its single rounding, in torch operators (the CPU device): the product is exact in fp64, the sum
+    is rounded to odd there (TwoSum finds whether it was inexact), and fp64 -> fp32 of a value rounded to odd is the correctly
+    rounded fp32 of the exact sum."""
+    p, mid = codes.double() * dec[0].double(), dec[1].double().expand(codes.shape)
+    s = p + mid
+    b = s - p
+    err = (p - (s - b)) + (mid - b)
+    even = (s.view(torch.int64) & 1) == 0
+    odd = torch.nextafter(s, torch.where(err > 0, torch.inf, -torch.inf).to(s.dtype))
+    return torch.where((err != 0) & even, odd, s).float()
+
+
 class IVFFlatIndex(CoarseProbe):
     STORAGE = {"float32": torch.float32, "float16": torch.float16, "int8": torch.int8}
     MAX_NLIST = ops.IVF_FLAT_MAX_NLIST
     MAX_WS_BYTES = 4 << 30            # workspace of one library call: a search is cut into chunks of queries that stay below it
 
     def __init__(self, d: int, nlist: int, device: Optional[torch.device] = None, metric=METRIC_INNER_PRODUCT,
-                 storage: str = "float32"):
+                 storage: str = "float32", *, by_residual: bool = False):
         if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
             raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
         if storage not in self.STORAGE:
@@ -65,8 +97,11 @@ class IVFFlatIndex(CoarseProbe):
             raise ValueError(f"d must be >= 1 and nlist in [1, {self.MAX_NLIST}]")
         if storage == "int8" and int(d) > ops.DENSE_SQ8_MAX_D:
             raise ValueError(f"int8 storage: d must be <= {ops.DENSE_SQ8_MAX_D}")
+        if by_residual and storage != "int8":
+            raise ValueError(f"by_residual=True encodes residuals: it needs storage='int8', not {storage!r}")
         self.metric_type = metric
         self.storage = storage
+        self.by_residual = bool(by_residual)
         self._dtype = self.STORAGE[storage]
         self._coarse_sq = (None, None, None)                                # CoarseProbe: (coarse, its version, ||c_l||^2)
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
@@ -100,21 +135,28 @@ class IVFFlatIndex(CoarseProbe):
 
     def train(self, x, iters: int = 10, seed: int = 1234) -> None:
         """Fits the `nlist` coarse centroids by `coarse_kmeans` on x [n >= nlist, d]; int8 storage: also the per-dimension range
-        of the same rows (`train_sq`)."""
+        of the same rows (`train_sq`); by_residual: the range of their residuals against the centroids just fitted."""
         xt = self._rows(x, "train")
         if xt.shape[0] < self.nlist:
             raise ValueError(f"train: {xt.shape[0]} vectors for {self.nlist} cells")
-        if self.storage == "int8":
+        if self.by_residual and self.ntotal:
+            raise ValueError("train: the index holds residual codes of the current centroids and range; reset() first")
+        if self.storage == "int8" and not self.by_residual:
             self.train_sq(xt)
         self.coarse = coarse_kmeans(xt.to(self.device, torch.float32), self.nlist, iters, seed)
+        if self.by_residual:
+            self.train_sq(xt)
 
     def train_sq(self, x) -> None:
-        """int8 storage: sets the scalar quantiser's per-dimension range from x [n >= 1, d] alone (beside `set_coarse`)."""
+        """int8 storage: sets the scalar quantiser's per-dimension range from x [n >= 1, d] alone (beside `set_coarse`);
+        by_residual: from the residuals of x against the centroids of their L2-nearest cells, which have to exist."""
         if self.storage != "int8":
             raise ValueError("train_sq: only int8 storage has a range to train")
         if self.ntotal:
             raise ValueError("train_sq: the index holds codes of the current range; reset() first")
-        self.vmin, self._dec = sq8_train_range(self._rows(x, "train_sq"), self.device)
+        if self.by_residual and self.coarse is None:
+            raise ValueError("train_sq: residual encoding needs the coarse centroids first (set_coarse, or train)")
+        self.vmin, self._dec = sq8_train_range(self._rows(x, "train_sq"), self.device, self._residual if self.by_residual else None)
         self.step, self.mid = self._dec[0], self._dec[1]
 
     def _need_range(self, what: str) -> None:
@@ -123,13 +165,30 @@ class IVFFlatIndex(CoarseProbe):
 
     def set_coarse(self, centroids) -> None:
         """Installs given coarse centroids [nlist, d]."""
+        if self.by_residual and self.ntotal:
+            raise ValueError("set_coarse: the index holds codes of residuals against the current centroids; reset() first")
         c = centroids.detach() if isinstance(centroids, torch.Tensor) else torch.from_numpy(np.asarray(centroids, dtype=np.float32))
         if c.dim() != 2 or tuple(c.shape) != (self.nlist, self.d):
             raise ValueError(f"set_coarse: expected [{self.nlist}, {self.d}] centroids, got {tuple(c.shape)}")
         self.coarse = c.to(self.device, torch.float32).contiguous().clone()
 
-    def _stored(self, xt: torch.Tensor) -> torch.Tensor:
-        """The rows of an `add` in the storage type, checked before anything is stored; one host read."""
+    def _assign(self, xt: torch.Tensor) -> torch.Tensor:
+        """The L2-nearest cell [n] int64 of fp32 rows on the index's device: `coarse_assign`; the CPU device: its rule in torch
+        operators."""
+        if self.device.type == "cuda":
+            return coarse_assign(xt, self.coarse)
+        c2 = (self.coarse * self.coarse).sum(1)
+        parts = [torch.argmin(c2[None, :] - 2.0 * (xt[i:i + (1 << 16)] @ self.coarse.T), dim=1) for i in range(0, xt.shape[0], 1 << 16)]
+        return torch.cat(parts) if parts else torch.empty((0,), dtype=torch.int64, device=self.device)
+
+    def _residual(self, part: torch.Tensor) -> torch.Tensor:
+        """fp32 rows on the device minus the centroids of their L2-nearest cells; a non-finite row (refused by whoever takes the
+        residuals) is assigned as zeros and stays non-finite."""
+        return part - self.coarse[self._assign(torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0))]
+
+    def _stored(self, xt: torch.Tensor, cells: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The rows of an `add` in the storage type, checked before anything is stored; one host read.  by_residual: `cells` [n]
+        on the device, the codes are those of fp32(x - coarse[cell])."""
         if self.storage == "int8":
             n = xt.shape[0]
             codes = torch.empty((n, self.d), dtype=torch.int8, device=self.device)
@@ -137,10 +196,13 @@ class IVFFlatIndex(CoarseProbe):
             for r0 in range(0, n, SQ8_ROWS_PER_STEP):
                 part = xt[r0:r0 + SQ8_ROWS_PER_STEP].to(self.device, torch.float32)
                 finite &= torch.isfinite(part).all()
+                if self.by_residual:
+                    part = part - self.coarse[cells[r0:r0 + part.shape[0]]]
+                    finite &= torch.isfinite(part).all()                            # finite values whose difference overflows
                 part = torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0)      # refused below; int8(NaN) is undefined
                 codes[r0:r0 + part.shape[0]] = sq8_encode(part, self.vmin, self.step)
             if not bool(finite):
-                raise ValueError("add: int8 storage needs finite values")
+                raise ValueError("add: int8 storage needs finite values" + (" and finite residuals" if self.by_residual else ""))
             return codes
         xs = xt.to(self.device).to(self._dtype)
         if xs.shape[0] and not bool(torch.isfinite(xs).all()):
@@ -178,7 +240,8 @@ class IVFFlatIndex(CoarseProbe):
             raise ValueError(f"set_lists: expected {xt.shape[0]} integer cells, got {li.dtype} {tuple(li.shape)}")
         if li.numel() and (int(li.min()) < 0 or int(li.max()) >= self.nlist):
             raise ValueError(f"set_lists: cells must lie in [0, {self.nlist})")
-        self._store(self._stored(xt), li.to(self.device, torch.int64))
+        li = li.to(self.device, torch.int64)
+        self._store(self._stored(xt, li), li)
 
     def add(self, x) -> None:
         """Appends x [n, d]: ids ntotal .. ntotal + n - 1, every row under its L2-nearest coarse centroid (of the values given,
@@ -189,8 +252,12 @@ class IVFFlatIndex(CoarseProbe):
         xt = self._rows(x, "add")
         if xt.shape[0] == 0:
             return
-        xs = self._stored(xt)
-        cells = coarse_assign(xt.to(self.device, torch.float32), self.coarse)
+        if self.by_residual:      # the codes need the cells first; a non-finite row, which `_stored` refuses, is assigned as zeros
+            cells = self._assign(torch.nan_to_num(xt.to(self.device, torch.float32), nan=0.0, posinf=0.0, neginf=0.0))
+            xs = self._stored(xt, cells)
+        else:
+            xs = self._stored(xt)
+            cells = self._assign(xt.to(self.device, torch.float32))
         if self.ntotal:
             old_x, old_cells = self._corpus_order()
             xs, cells = torch.cat([old_x, xs], 0), torch.cat([old_cells, cells], 0)
@@ -198,15 +265,24 @@ class IVFFlatIndex(CoarseProbe):
 
     def reconstruct_n(self, i0: int = 0, ni: int = -1) -> torch.Tensor:
         """fp32 [ni, d]: the stored values of corpus rows i0 .. i0 + ni - 1 (ni = -1: up to ntotal), as the search scores them;
-        int8 storage: the decoded rows (`ops.dense_sq8_decode`)."""
+        int8 storage: the decoded rows (`ops.dense_sq8_decode`), by_residual: plus the centroid of every row's cell."""
         self._need_range("reconstruct_n")
         ni = self.ntotal - int(i0) if ni < 0 else int(ni)
         if not (0 <= int(i0) and ni >= 0 and int(i0) + ni <= self.ntotal):
             raise ValueError(f"reconstruct_n: rows [{i0}, {int(i0) + ni}) outside [0, {self.ntotal})")
         where = torch.empty_like(self.ids)
         where[self.ids] = torch.arange(self.ntotal, device=self.device)
-        rows = self.xb[where[int(i0):int(i0) + ni]]
-        return ops.dense_sq8_decode(rows, self._dec) if self.storage == "int8" else rows.float()
+        pos = where[int(i0):int(i0) + ni]
+        return self._decoded(pos) if self.storage == "int8" else self.xb[pos].float()
+
+    def _decoded(self, pos: torch.Tensor) -> torch.Tensor:
+        """int8 storage: the stored values fp32 [n, d] of the list-major rows `pos`: the decode with its one rounding, and
+        by_residual one separate fp32 addition of the centroid of the row's cell (the scan's two roundings)."""
+        codes = self.xb[pos].contiguous()
+        rows = ops.dense_sq8_decode(codes, self._dec) if self.device.type == "cuda" else _sq8_decode_host(codes, self._dec)
+        if self.by_residual:
+            rows = rows + self.coarse[torch.searchsorted(self.list_off, pos, right=True) - 1]
+        return rows
 
     # ---- search
     def _queries(self, x, k: int):
@@ -276,7 +352,10 @@ class IVFFlatIndex(CoarseProbe):
         parts, fallback, chunks = [], 0, 0
         for c0 in range(0, nq, step):
             qc, pc = q[c0:c0 + step], probes[c0:c0 + step]
-            if self.storage == "int8":
+            if self.by_residual:
+                scores, ids, status, qstatus = ops.ivf_flat_sq8r_search(self.xb, self._dec, self.coarse, self.list_off, self.ids,
+                                                                        qc, pc, stride, k, metric=self.metric_type)
+            elif self.storage == "int8":
                 scores, ids, status, qstatus = ops.ivf_flat_sq8_search(self.xb, self._dec, self.list_off, self.ids, qc, pc, stride,
                                                                        k, metric=self.metric_type)
             else:
@@ -300,8 +379,8 @@ class IVFFlatIndex(CoarseProbe):
     def _search_exact_probed(self, q: torch.Tensor, probes: torch.Tensor, k: int):
         """The answer for ANY content of the probed cells, query by query: the probed rows gathered in corpus-id order (the
         search's tie rule becomes the exact entry's "lower row"), then the exact route of the flat search of this metric and
-        storage (int8: the fp32 exact route over the gathered rows, decoded).  Slow — one gather of the probed rows per query —
-        and only reached for queries the selection could not decide."""
+        storage (int8: the fp32 exact route over the gathered rows, decoded, by_residual with their centroids added).  Slow —
+        one gather of the probed rows per query — and only reached for queries the selection could not decide."""
         exact = {(METRIC_INNER_PRODUCT, "float32"): ops.dense_search_exact, (METRIC_INNER_PRODUCT, "float16"): ops.dense_search_f16_exact,
                  (METRIC_L2, "float32"): ops.dense_search_l2_exact, (METRIC_L2, "float16"): ops.dense_search_l2_f16_exact,
                  (METRIC_INNER_PRODUCT, "int8"): ops.dense_search_exact, (METRIC_L2, "int8"): ops.dense_search_l2_exact}
@@ -317,9 +396,7 @@ class IVFFlatIndex(CoarseProbe):
             corpus = self.ids[rows]
             order = torch.argsort(corpus)
             rows, corpus = rows[order], corpus[order]
-            gathered = self.xb[rows].contiguous()
-            if self.storage == "int8":
-                gathered = ops.dense_sq8_decode(gathered, self._dec)
+            gathered = self._decoded(rows) if self.storage == "int8" else self.xb[rows].contiguous()
             s, i = exact(gathered, q[j:j + 1], k)
             valid = i[0] >= 0
             scores[j] = s[0]

@@ -1415,32 +1415,53 @@ def ivf_flat_sq8_search(xb8: torch.Tensor, dec: torch.Tensor, list_off: torch.Te
     else, the returns and the status bits as `ivf_flat_search`.  Scores are bit for bit those of `ivf_flat_search` over
     `dense_sq8_decode(xb8, dec)`, under either metric.  Any row pitch >= D and any alignment (a column slice of a wider
     matrix is read in place).  D <= 65536; argument errors are ValueError before any device work."""
+    return _ivf_flat_sq8_search("ivf_flat_sq8_search", xb8, dec, None, list_off, ids, q, probes, stride, k, metric)
+
+
+def ivf_flat_sq8r_search(xb8: torch.Tensor, dec: torch.Tensor, coarse: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor,
+                         q: torch.Tensor, probes: torch.Tensor, stride: int, k: int, metric: int = METRIC_INNER_PRODUCT):
+    """`ivf_flat_sq8_search` over codes of residuals (rc_ivf_flat_sq8r_search): the rows of cell l hold the codes of x -
+    `coarse`[l], `coarse` [nlist, D] fp32 on the device of the store (any row pitch >= D), and a stored value is
+    fp32(fmaf(c', step, mid) + coarse[l][d]) — the decode, then one separate fp32 addition.  Scores are bit for bit those of
+    `ivf_flat_search` over `dense_sq8_decode(xb8, dec)` + the centroid of every row's cell, under either metric.  The checks
+    of `ivf_flat_sq8_search`, and `coarse` must be float32 [nlist, D]."""
+    if not isinstance(coarse, torch.Tensor):
+        raise ValueError("ivf_flat_sq8r_search: coarse must be a float32 tensor [nlist, D]")
+    return _ivf_flat_sq8_search("ivf_flat_sq8r_search", xb8, dec, coarse, list_off, ids, q, probes, stride, k, metric)
+
+
+def _ivf_flat_sq8_search(name, xb8, dec, coarse, list_off, ids, q, probes, stride, k, metric):
+    """The two coded IVF searches: `coarse` None = the vectors themselves are encoded, else their residuals."""
     l2 = _adc_metric(metric)
     if xb8.dim() != 2 or q.dim() != 2 or xb8.shape[1] != q.shape[1] or xb8.shape[1] < 1:
-        raise ValueError("ivf_flat_sq8_search: xb8 [N, D] and q [nq, D] with the same D >= 1")
+        raise ValueError(f"{name}: xb8 [N, D] and q [nq, D] with the same D >= 1")
     if xb8.dtype != torch.int8:
-        raise ValueError("ivf_flat_sq8_search: the store must be int8 codes, c - 128")
+        raise ValueError(f"{name}: the store must be int8 codes, c - 128")
     if q.dtype != torch.float32:
-        raise ValueError("ivf_flat_sq8_search: the queries must be float32")
+        raise ValueError(f"{name}: the queries must be float32")
     N, D = xb8.shape
     if D > DENSE_SQ8_MAX_D:
-        raise ValueError(f"ivf_flat_sq8_search: D must be <= {DENSE_SQ8_MAX_D}")
+        raise ValueError(f"{name}: D must be <= {DENSE_SQ8_MAX_D}")
     if dec.dtype != torch.float32 or dec.shape != (2, D):
-        raise ValueError("ivf_flat_sq8_search: dec must be float32 [2, D]: the steps, then the mids")
+        raise ValueError(f"{name}: dec must be float32 [2, D]: the steps, then the mids")
     if not 1 <= int(k) <= DENSE_MAX_K:
-        raise ValueError(f"ivf_flat_sq8_search: k must be in [1, {DENSE_MAX_K}]")
+        raise ValueError(f"{name}: k must be in [1, {DENSE_MAX_K}]")
     nlist = list_off.numel() - 1
     if list_off.dtype != torch.int64 or list_off.dim() != 1 or not 1 <= nlist <= IVF_FLAT_MAX_NLIST:
-        raise ValueError(f"ivf_flat_sq8_search: list_off must be int64 [nlist + 1], 1 <= nlist <= {IVF_FLAT_MAX_NLIST}")
+        raise ValueError(f"{name}: list_off must be int64 [nlist + 1], 1 <= nlist <= {IVF_FLAT_MAX_NLIST}")
+    if coarse is not None and (coarse.dtype != torch.float32 or coarse.shape != (nlist, D)):
+        raise ValueError(f"{name}: coarse must be float32 [nlist, D]: the centroids the rows were encoded against")
     if ids.dtype != torch.int64 or ids.shape != (N,):
-        raise ValueError("ivf_flat_sq8_search: ids must be int64 [N]")
+        raise ValueError(f"{name}: ids must be int64 [N]")
     if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != q.shape[0] or not 1 <= probes.shape[1] <= nlist:
-        raise ValueError("ivf_flat_sq8_search: probes must be int32 [nq, nprobe], 1 <= nprobe <= nlist")
+        raise ValueError(f"{name}: probes must be int32 [nq, nprobe], 1 <= nprobe <= nlist")
     if not 1 <= N < 1 << 32:
-        raise ValueError("ivf_flat_sq8_search: 1 <= N < 2^32")
+        raise ValueError(f"{name}: 1 <= N < 2^32")
     if int(stride) < 1:
-        raise ValueError("ivf_flat_sq8_search: stride must be >= 1")
-    _need_cuda(xb8, dec, list_off, ids, q, probes)
+        raise ValueError(f"{name}: stride must be >= 1")
+    _need_cuda(xb8, dec, coarse, list_off, ids, q, probes)
+    if coarse is not None and coarse.device != xb8.device:
+        raise ValueError(f"{name}: coarse must be on the device of the store")
     if xb8.stride(1) != 1 or (N > 1 and xb8.stride(0) < D):
         xb8 = xb8.contiguous()
     q, dec = q.to(xb8.device).contiguous(), dec.to(xb8.device).contiguous()
@@ -1455,9 +1476,15 @@ def ivf_flat_sq8_search(xb8: torch.Tensor, dec: torch.Tensor, list_off: torch.Te
     lib, h, s, _ = _ctx(q)
     wsb = lib.rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, int(stride))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)             # released in stream order
-    _lib.check(lib.rc_ivf_flat_sq8_search(h, _p(xb8), xb8.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q),
-                                          nq, _p(dec), _p(probes), nprobe, int(stride), int(k), int(l2), _p(scores),
-                                          _p(out_ids), _p(status), _p(qstatus), _p(ws), wsb, s), "rc_ivf_flat_sq8_search", h)
+    head = (h, _p(xb8), xb8.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q), nq, _p(dec))
+    tail = (_p(probes), nprobe, int(stride), int(k), int(l2), _p(scores), _p(out_ids), _p(status), _p(qstatus), _p(ws), wsb, s)
+    if coarse is None:
+        rc = lib.rc_ivf_flat_sq8_search(*head, *tail)
+    else:
+        if coarse.stride(1) != 1 or (nlist > 1 and coarse.stride(0) < D):
+            coarse = coarse.contiguous()
+        rc = lib.rc_ivf_flat_sq8r_search(*head, _p(coarse), coarse.stride(0) if nlist > 1 else D, *tail)
+    _lib.check(rc, "rc_" + name, h)
     return scores, out_ids, status, qstatus
 
 

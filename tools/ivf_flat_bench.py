@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """Exact IVF search over dense rows (csrc/ivf_flat.hip, IVFFlatIndex) at the README's shape (development tool, GPU):
-8 841 823 x 768 rows, nlist 5000 trained, 1200-query batches, k = 100; fp32, fp16 and int8 stores, both metrics.
+8 841 823 x 768 rows, nlist 5000 trained, 1200-query batches, k = 100; fp32, fp16 and int8 stores, the int8 store also with
+residual encoding, both metrics.
 
-    python tools/ivf_flat_bench.py [--n 8841823] [--batches 2] [--passes 4] [--stores fp32,fp16,int8] [--out profiles/ivf_flat_bench.txt]
+    python tools/ivf_flat_bench.py [--n 8841823] [--batches 2] [--passes 4] [--stores fp32,fp16,int8,int8r] [--out profiles/ivf_flat_bench.txt]
 
 Data: clustered Gaussian rows as in tools/dense_bench.py (0.7 centre + 0.5 noise, 64 centres), generated on the device in
 chunks; the queries are corpus rows plus 0.3 N(0, 1).  The coarse centroids are fitted once on a seeded sample of 2^18 rows
@@ -10,6 +11,10 @@ chunks; the queries are corpus rows plus 0.3 N(0, 1).  The coarse centroids are 
 copy.  The int8 store holds the 8-bit scalar-quantiser codes of the same rows (range trained on all of them); its flat
 counterpart is FlatSQ8Index under the inner product, and there is none under L2 (nor a re-ranking flat index over codes: the
 refined IVF-PQ line is left out for this store).  After the legs: the int8 / fp16 time ratio of every IVF run, per pass.
+`int8r` (needs `int8`): IVFFlatIndex(storage="int8", by_residual=True) over the same rows and cells, the codes of x - coarse[cell]
+under the range of all residuals.  Its searches run INSIDE the int8 leg, pass by pass beside the plain int8 ones (the yardstick of
+its time is the plain leg of the same pass), with their top-10 overlap with the fp32 flat result; after the legs: the residual /
+plain int8 time ratio of every IVF run, per pass.
 
 Per storage and metric, on `--passes` alternating passes in one process, ms per batch of
   * IVFFlatIndex at nprobe 8 / 32 / 128,
@@ -128,7 +133,7 @@ def main():
     ap.add_argument("--k", type=int, default=100)
     ap.add_argument("--nlist", type=int, default=5000)
     ap.add_argument("--nprobes", default="8,32,128")
-    ap.add_argument("--stores", default="fp32,fp16,int8")
+    ap.add_argument("--stores", default="fp32,fp16,int8,int8r")
     ap.add_argument("--out", default="")
     a = ap.parse_args()
     if a.out:
@@ -173,6 +178,23 @@ def main():
         x8 = torch.empty((a.n, a.d), dtype=torch.int8, device=DEV)
         for r0 in range(0, a.n, 1 << 20):
             x8[r0:r0 + (1 << 20)] = sq8_encode(x[r0:r0 + (1 << 20)], vmin8, dec8[0])
+    index_r = None
+    if "int8r" in stores:
+        if "int8" not in stores:
+            raise SystemExit("--stores int8r runs beside the plain int8 leg: name int8 too")
+        index_r = IVFFlatIndex(a.d, a.nlist, storage="int8", by_residual=True)
+        index_r.set_coarse(coarse)
+        resid = lambda r0: x[r0:r0 + (1 << 20)] - coarse[cells[r0:r0 + (1 << 20)]]
+        ends = [torch.stack([r.amin(0), r.amax(0)]) for r in (resid(r0) for r0 in range(0, a.n, 1 << 20))]
+        index_r.vmin, index_r._dec = sq8_train_range(torch.cat(ends), DEV)            # the range is the extremes' alone
+        index_r.step, index_r.mid = index_r._dec[0], index_r._dec[1]
+        x8r = torch.empty((a.n, a.d), dtype=torch.int8, device=DEV)
+        for r0 in range(0, a.n, 1 << 20):
+            x8r[r0:r0 + (1 << 20)] = sq8_encode(resid(r0), index_r.vmin, index_r.step)
+        index_r._store(x8r, cells)
+        del x8r
+        say(f"residual int8 store: largest step {float(index_r.step.max()):.5f} against {float(dec8[0].max()):.5f} of the plain int8 store "
+            f"(mean {float(index_r.step.mean()):.5f} against {float(dec8[0].mean()):.5f})")
     flat32, allms = {}, {}          # the fp32 flat ids per metric; ms per pass of every (store, metric, path)
     for sname, store in (("fp32", x), ("fp16", x16), ("int8", x8)):
         if sname not in stores:
@@ -198,6 +220,11 @@ def main():
             else:
                 flat = hang(FlatIPIndex(a.d, storage="float16" if sname == "fp16" else "float32"), store, metric)
             paths = {f"ivf-flat nprobe {p}": (lambda qb, p=p: index.search(qb, a.k, nprobe=p)) for p in nprobes}
+            legs = [(index, "ivf-flat", sname)]
+            if sname == "int8" and index_r is not None:
+                index_r.metric_type = metric
+                paths.update({f"ivf-flat residual nprobe {p}": (lambda qb, p=p: index_r.search(qb, a.k, nprobe=p)) for p in nprobes})
+                legs.append((index_r, "ivf-flat residual", "int8r"))
             if flat is not None:
                 paths["flat"] = lambda qb: flat.search(qb, a.k)
             if sname != "int8":
@@ -206,7 +233,7 @@ def main():
             for n, fn in paths.items():
                 fn(batches[0])                                          # warm every code object and allocation
                 if n.startswith("ivf-flat"):
-                    stats[n] = dict(index.last_search_stats)
+                    stats[n] = dict((index_r if "residual" in n else index).last_search_stats)
             ms, out = {n: [] for n in paths}, {}
             for _ in range(a.passes):
                 for n, fn in paths.items():
@@ -219,8 +246,8 @@ def main():
                 v = ms[n]
                 allms[(sname, metric, n)] = v
                 ids = torch.cat([o[1] for o in out[n]])
-                own = f"top-10 overlap with the flat result {overlap10(ids, exact):.3f}" if exact is not None else \
-                    "no flat index over this store and metric"
+                own = "no flat index over residual codes" if "residual" in n else "no flat index over this store and metric" \
+                    if exact is None else f"top-10 overlap with the flat result {overlap10(ids, exact):.3f}"
                 if sname != "fp32" and metric in flat32:
                     own += f", with the fp32 flat result {overlap10(ids, flat32[metric]):.3f}"
                 say(f"e2e {NAMES[metric]} {sname} {n:26s}: {sum(v) / len(v):8.3f} ms per batch (min {min(v):.3f} max {max(v):.3f}) = "
@@ -230,17 +257,18 @@ def main():
             if n32 is not None:
                 say(f"  condition {NAMES[metric]} {sname}: nprobe 32 takes {n32:.3f} ms, the flat search of the same store {flat_ms:.3f} ms "
                     f"-> {'met' if n32 < flat_ms else 'NOT MET'}")
-            for p in nprobes:
-                pairs, read_rows, tasks, cell_rows = work(index, batches[0], p)
-                kms, launches = scan_ms(index, batches[0], a.k, p)
-                nbytes, steps = read_rows * a.d * esz, pairs * a.d
-                t_hbm, t_valu = 1e3 * nbytes / HBM_ACHIEVABLE, 1e3 * steps / VALU_STEPS[metric]
-                st = stats[f"ivf-flat nprobe {p}"]
-                say(f"  scan {NAMES[metric]} {sname} nprobe {p:3d}: {pairs / a.batch:9.0f} rows scored per query, {tasks} tasks read "
-                    f"{read_rows} rows = {nbytes / 1e9:.2f} GB per batch ({cell_rows * a.d * esz / 1e9:.2f} GB of distinct cells), "
-                    f"{steps / 1e9:.1f} G chain steps; scan kernel {kms:.3f} ms in {launches} launch(es), bounds: HBM {t_hbm:.3f} ms, "
-                    f"vector ALU {t_valu:.3f} ms -> {kms / max(t_hbm, t_valu):.2f} x the larger bound; chunks {st['chunks']}, "
-                    f"fallback queries {st['fallback_queries']}")
+            for leg, path, lname in legs:
+                for p in nprobes:
+                    pairs, read_rows, tasks, cell_rows = work(leg, batches[0], p)
+                    kms, launches = scan_ms(leg, batches[0], a.k, p)
+                    nbytes, steps = read_rows * a.d * esz, pairs * a.d
+                    t_hbm, t_valu = 1e3 * nbytes / HBM_ACHIEVABLE, 1e3 * steps / VALU_STEPS[metric]
+                    st = stats[f"{path} nprobe {p}"]
+                    say(f"  scan {NAMES[metric]} {lname} nprobe {p:3d}: {pairs / a.batch:9.0f} rows scored per query, {tasks} tasks read "
+                        f"{read_rows} rows = {nbytes / 1e9:.2f} GB per batch ({cell_rows * a.d * esz / 1e9:.2f} GB of distinct cells), "
+                        f"{steps / 1e9:.1f} G chain steps; scan kernel {kms:.3f} ms in {launches} launch(es), bounds: HBM {t_hbm:.3f} ms, "
+                        f"vector ALU {t_valu:.3f} ms -> {kms / max(t_hbm, t_valu):.2f} x the larger bound; chunks {st['chunks']}, "
+                        f"fallback queries {st['fallback_queries']}")
             del flat
         del index
         torch.cuda.empty_cache()
@@ -251,6 +279,14 @@ def main():
                 r = [i8 / f16 for i8, f16 in zip(allms[("int8", metric, n)], allms[("fp16", metric, n)])]
                 say(f"int8 / fp16 time, {NAMES[metric]} nprobe {p:3d}: {sum(r) / len(r):.3f} over {len(r)} passes (min {min(r):.3f} "
                     f"max {max(r):.3f})")
+    if index_r is not None:
+        for metric in (METRIC_INNER_PRODUCT, METRIC_L2):
+            for p in nprobes:
+                res, plain = allms[("int8", metric, f"ivf-flat residual nprobe {p}")], allms[("int8", metric, f"ivf-flat nprobe {p}")]
+                r = [a_ / b_ for a_, b_ in zip(res, plain)]
+                say(f"residual / plain int8 time, {NAMES[metric]} nprobe {p:3d}: {sum(r) / len(r):.3f} over {len(r)} passes (min {min(r):.3f} "
+                    f"max {max(r):.3f}; per pass {' '.join(f'{v:.3f}' for v in r)}; plain ms per pass "
+                    f"{' '.join(f'{v:.3f}' for v in plain)})")
 
 
 if __name__ == "__main__":
