@@ -33,7 +33,7 @@
 // PAD: rows that are not 16-byte aligned (or a D that is no multiple of 16 bytes) are read element by element into the same
 // registers; the arithmetic is the same.  Rows past the cell's end in the last chunk repeat its last row and are not written.
 //   LDS: 2 x 16 x 516 x 4 + 2 x 16 x 8 x 4 = 67 072 bytes, two blocks per CU.
-// ivf_flat_sq8_scan_kernel (rc_ivf_flat_sq8_search; faiss.IndexIVFScalarQuantizer, QT_8bit): the same scan over a list-major
+// T = signed char, TQ = float (rc_ivf_flat_sq8_search; faiss.IndexIVFScalarQuantizer, QT_8bit): the same scan over a list-major
 // store of 8-bit scalar-quantiser codes, fp32 queries.  A code is decoded once, fmaf((float)c', step_d, mid_d) (dense_sq8.h), on
 // its way from the staged registers into the same fp32 tile: the chains, and so the score bits, are those of the fp32 scan over
 // the decoded rows under either metric.  Same LDS, same plan, same selection.
@@ -249,50 +249,21 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
     }
 }
 
-// grid (task bound, <= IVFF_Y_MAX).  dense / rowid: [nq][stride].
-template <typename T, bool L2, bool PAD>
+// grid (task bound, <= IVFF_Y_MAX).  dense / rowid: [nq][stride].  One kernel for every store: dec is the coded store's
+// [2][D], coarse [nlist][ldc] the residual form's centroids; a form that does not take them is handed nullptr / 0.
+template <typename T, typename TQ, bool L2, bool PAD, bool RES>
 __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restrict__ x, int64_t ldx,
                                                                const int64_t* __restrict__ list_off, int D,
-                                                               const T* __restrict__ q, const int* __restrict__ probes,
-                                                               const int* __restrict__ base, int nprobe, int64_t stride,
-                                                               const int* __restrict__ task_list,
+                                                               const TQ* __restrict__ q, const float* __restrict__ dec,
+                                                               const float* __restrict__ coarse, int64_t ldc,
+                                                               const int* __restrict__ probes, const int* __restrict__ base,
+                                                               int nprobe, int64_t stride, const int* __restrict__ task_list,
                                                                const int* __restrict__ task_qstart,
                                                                const int* __restrict__ task_qcnt,
                                                                const int* __restrict__ sorted_q, float* __restrict__ dense,
                                                                int* __restrict__ rowid) {
-    ivf_flat_scan_body<T, T, L2, PAD>(x, ldx, list_off, D, q, nullptr, nullptr, 0, probes, base, nprobe, stride, task_list,
-                                      task_qstart, task_qcnt, sorted_q, dense, rowid);
-}
-
-// The coded form: int8 codes, fp32 queries, dec [2][D].  Same grid.
-template <bool L2, bool PAD>
-__global__ __launch_bounds__(256, 2) void ivf_flat_sq8_scan_kernel(const signed char* __restrict__ x, int64_t ldx,
-                                                                   const int64_t* __restrict__ list_off, int D,
-                                                                   const float* __restrict__ q, const float* __restrict__ dec,
-                                                                   const int* __restrict__ probes, const int* __restrict__ base,
-                                                                   int nprobe, int64_t stride, const int* __restrict__ task_list,
-                                                                   const int* __restrict__ task_qstart,
-                                                                   const int* __restrict__ task_qcnt,
-                                                                   const int* __restrict__ sorted_q, float* __restrict__ dense,
-                                                                   int* __restrict__ rowid) {
-    ivf_flat_scan_body<signed char, float, L2, PAD>(x, ldx, list_off, D, q, dec, nullptr, 0, probes, base, nprobe, stride,
-                                                    task_list, task_qstart, task_qcnt, sorted_q, dense, rowid);
-}
-
-// The residual coded form: the codes of x - coarse[cell]; coarse [nlist][ldc] fp32.  Same grid.
-template <bool L2, bool PAD>
-__global__ __launch_bounds__(256, 2) void ivf_flat_sq8r_scan_kernel(const signed char* __restrict__ x, int64_t ldx,
-                                                                    const int64_t* __restrict__ list_off, int D,
-                                                                    const float* __restrict__ q, const float* __restrict__ dec,
-                                                                    const float* __restrict__ coarse, int64_t ldc,
-                                                                    const int* __restrict__ probes, const int* __restrict__ base,
-                                                                    int nprobe, int64_t stride, const int* __restrict__ task_list,
-                                                                    const int* __restrict__ task_qstart,
-                                                                    const int* __restrict__ task_qcnt,
-                                                                    const int* __restrict__ sorted_q, float* __restrict__ dense,
-                                                                    int* __restrict__ rowid) {
-    ivf_flat_scan_body<signed char, float, L2, PAD, true>(x, ldx, list_off, D, q, dec, coarse, ldc, probes, base, nprobe, stride,
-                                                          task_list, task_qstart, task_qcnt, sorted_q, dense, rowid);
+    ivf_flat_scan_body<T, TQ, L2, PAD, RES>(x, ldx, list_off, D, q, dec, coarse, ldc, probes, base, nprobe, stride, task_list,
+                                            task_qstart, task_qcnt, sorted_q, dense, rowid);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -337,32 +308,10 @@ int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list
     if (y > IVFF_Y_MAX) y = IVFF_Y_MAX;
     const dim3 grid((unsigned)L.ub, (unsigned)(y < 1 ? 1 : y));
     const bool vec = (D * (int64_t)sizeof(T)) % 16 == 0 && (ldx * (int64_t)sizeof(T)) % 16 == 0 && !((uintptr_t)x & 15u);
-    float* dense = (float*)(w + L.dense);
-    int* rowid = (int*)(w + L.rowid);
-    if constexpr (RES) {
-        if (vec)
-            hipLaunchKernelGGL((ivf_flat_sq8r_scan_kernel<L2, false>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, coarse,
-                               ldc, probes, I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt),
-                               I(L.sorted_q), dense, rowid);
-        else
-            hipLaunchKernelGGL((ivf_flat_sq8r_scan_kernel<L2, true>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, coarse,
-                               ldc, probes, I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt),
-                               I(L.sorted_q), dense, rowid);
-    } else if constexpr (std::is_same<T, signed char>::value) {
-        if (vec)
-            hipLaunchKernelGGL((ivf_flat_sq8_scan_kernel<L2, false>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, probes,
-                               I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense,
-                               rowid);
-        else
-            hipLaunchKernelGGL((ivf_flat_sq8_scan_kernel<L2, true>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, probes,
-                               I(L.base), nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense,
-                               rowid);
-    } else if (vec)
-        hipLaunchKernelGGL((ivf_flat_scan_kernel<T, L2, false>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, probes, I(L.base),
-                           nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense, rowid);
-    else
-        hipLaunchKernelGGL((ivf_flat_scan_kernel<T, L2, true>), grid, dim3(256), 0, s, x, ldx, list_off, D, q, probes, I(L.base),
-                           nprobe, stride, I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), dense, rowid);
+    const auto kernel = vec ? ivf_flat_scan_kernel<T, TQ, L2, false, RES> : ivf_flat_scan_kernel<T, TQ, L2, true, RES>;
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, coarse, ldc, probes, I(L.base), nprobe, stride,
+                       I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), (float*)(w + L.dense),
+                       (int*)(w + L.rowid));
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }

@@ -28,7 +28,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .index import METRIC_INNER_PRODUCT, METRIC_L2
+from .index import METRIC_INNER_PRODUCT, METRIC_L2, _as_device, _as_f32_tensor
 
 
 class _FlatIndex:
@@ -39,9 +39,7 @@ class _FlatIndex:
 
     def _init_store(self, d: int, device, dtype) -> None:
         self._dtype = dtype
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _as_device(device)
         self.d = int(d)
         self.is_trained = True
         self.ntotal = 0
@@ -70,7 +68,7 @@ class _FlatIndex:
 
     def _rows(self, x) -> torch.Tensor:
         """The argument of `add` as a tensor (numpy -> fp32), checked to be [n, d]."""
-        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        xt = _as_f32_tensor(x)
         if xt.dim() != 2 or xt.shape[1] != self.d:
             raise ValueError(f"add: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
         return xt
@@ -105,8 +103,7 @@ class _FlatIndex:
         """Enqueue the search and return a callable that yields what `search` returns; nothing synchronises with the host
         until it is called (`batch_dense_search` enqueues every batch first)."""
         as_numpy = not isinstance(x, torch.Tensor)
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
-        q = q.to(self.device, torch.float32, non_blocking=True)
+        q = _as_f32_tensor(x).to(self.device, torch.float32, non_blocking=True)
         if q.dim() != 2 or q.shape[1] != self.d:
             raise ValueError(f"search: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
         k = int(k)
@@ -131,7 +128,7 @@ class _FlatIndex:
         with the bits `search` gives them.  Ids outside [id_offset, id_offset + ntotal) — the -1 holes of an IVF search — are
         skipped; what is missing after them is padded like `search` pads.  numpy in -> numpy out, tensors in -> tensors out."""
         as_numpy = not isinstance(x, torch.Tensor)
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
+        q = _as_f32_tensor(x)
         c = cand_ids if isinstance(cand_ids, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cand_ids))
         if q.dim() != 2 or q.shape[1] != self.d:
             raise ValueError(f"rerank: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
@@ -325,6 +322,21 @@ def sq8_encode(xt: torch.Tensor, vmin: torch.Tensor, step: torch.Tensor) -> torc
     return (c - 128.0).to(torch.int8)
 
 
+def _sq8_encode_chunks(xt: torch.Tensor, vmin: torch.Tensor, step: torch.Tensor, finite: torch.Tensor,
+                      rows_per_step: int = SQ8_ROWS_PER_STEP, shift=None):
+    """The rows of an `add`, `rows_per_step` at a time: yields (r0, the int8 codes of rows r0 ..) on the device of vmin and
+    step, and ANDs into the device flag `finite` whether every value seen was finite, without a host read (the caller refuses
+    the rows after one read; a non-finite value is encoded as 0, int8(NaN) being undefined).  shift(r0, n) (the residual form):
+    the fp32 rows subtracted from rows r0 .. r0 + n - 1 before they are encoded; the differences are checked too."""
+    for r0 in range(0, xt.shape[0], rows_per_step):
+        part = xt[r0:r0 + rows_per_step].to(vmin.device, torch.float32)
+        finite &= torch.isfinite(part).all()
+        if shift is not None:
+            part = part - shift(r0, part.shape[0])
+            finite &= torch.isfinite(part).all()                            # finite values whose difference overflows
+        yield r0, sq8_encode(torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0), vmin, step)
+
+
 class _SQ8Store(_FlatIndex):
     """What the indexes over 8-bit scalar-quantiser codes share: the training, `add` (encode in chunks, refuse non-finite rows
     before anything counts, the certificate's statistics `ops.dense_sq8_cstat` without a host read), `reconstruct_n`, and a
@@ -368,10 +380,7 @@ class _SQ8Store(_FlatIndex):
         # the codes are written past ntotal and count only once every value has been seen to be finite (one host read)
         finite = torch.ones((), dtype=torch.bool, device=self.device)
         cstat = torch.zeros((2,), dtype=torch.float32, device=self.device)
-        for r0 in range(0, n, self.ROWS_PER_STEP):
-            part = xt[r0:r0 + self.ROWS_PER_STEP].to(self.device, torch.float32)
-            finite &= torch.isfinite(part).all()
-            codes = self.encode(torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0))
+        for r0, codes in _sq8_encode_chunks(xt, self.vmin, self.step, finite, self.ROWS_PER_STEP):
             self._x[self.ntotal + r0:self.ntotal + r0 + codes.shape[0]] = codes
             cstat = torch.maximum(cstat, ops.dense_sq8_cstat(codes, self._dec))
             self._chunk_added(self.ntotal + r0, codes)

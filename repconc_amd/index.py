@@ -28,6 +28,17 @@ METRIC_INNER_PRODUCT = ops.METRIC_INNER_PRODUCT  # 0, faiss.METRIC_INNER_PRODUCT
 METRIC_L2 = ops.METRIC_L2                        # 1, faiss.METRIC_L2: PQIndex / IVFPQIndex (ADC distances), dense_index.FlatL2Index
 
 
+def _as_device(device) -> torch.device:
+    """The device of an index: None and "cuda" -> the current device, by index."""
+    device = torch.device("cuda" if device is None else device)
+    return torch.device("cuda", torch.cuda.current_device()) if device.type == "cuda" and device.index is None else device
+
+
+def _as_f32_tensor(x) -> torch.Tensor:
+    """A tensor as it is; anything else (numpy) -> a contiguous fp32 CPU tensor."""
+    return x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+
+
 class PQIndex:
     def __init__(self, d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT,
                  device: Optional[torch.device] = None):
@@ -35,9 +46,7 @@ class PQIndex:
         assert d % M == 0
         if metric not in (METRIC_INNER_PRODUCT, METRIC_L2):
             raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _as_device(device)
         self.metric_type = metric
         self.is_trained = False
         self.ntotal = 0
@@ -95,8 +104,7 @@ class PQIndex:
 
     def add(self, x):
         """IndexPQ.add: encode by L2-nearest sub-centroid and append."""
-        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        self.add_codes(ops.assign_nearest(xt.to(self.device), self._centroids, torch.uint8))
+        self.add_codes(ops.assign_nearest(_as_f32_tensor(x).to(self.device), self._centroids, torch.uint8))
 
     # ---- search
     def search(self, x, k: int):
@@ -109,8 +117,7 @@ class PQIndex:
         host until it is called, so a caller with several query batches (`batch_search`) can enqueue them all first: the
         device then never idles between batches waiting for the host to read a status word and launch the next one."""
         as_numpy = not isinstance(x, torch.Tensor)
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
-        q = q.to(self.device, torch.float32, non_blocking=True)
+        q = _as_f32_tensor(x).to(self.device, torch.float32, non_blocking=True)
         # prefixes of the row-major buffers are contiguous views: nothing is copied
         pending = ops.adc_search(self._codes[: self.ntotal], self._centroids, q, int(k), id_offset=self.id_offset,
                                  scan_image=self._image, defer=True, stats=stats, sel_slack=self.sel_slack,

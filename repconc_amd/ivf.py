@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex
+from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex, _as_device, _as_f32_tensor
 
 
 def coarse_kmeans(x: torch.Tensor, nlist: int, iters: int = 10, seed: int = 1234, chunk: int = 1 << 20) -> torch.Tensor:
@@ -133,9 +133,7 @@ class IVFPQIndex(CoarseProbe):
             raise ValueError(f"metric must be METRIC_INNER_PRODUCT (0) or METRIC_L2 (1), not {metric!r}")
         self.metric_type = metric
         self._coarse_sq = (None, None, None)                                # (coarse tensor, its version, ||c_l||^2): L2 probing
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _as_device(device)
         self.d, self.M, self.nlist = d, M, nlist
         self.coarse = None                                                  # [nlist, d]
         self.pq_centroids = torch.zeros((M, 256, d // M), dtype=torch.float32, device=self.device)
@@ -154,8 +152,7 @@ class IVFPQIndex(CoarseProbe):
 
     # ---- build
     def train(self, x, iters: int = 10, seed: int = 1234):
-        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
-        self.coarse = coarse_kmeans(xt.to(self.device), self.nlist, iters, seed)
+        self.coarse = coarse_kmeans(_as_f32_tensor(x).to(self.device), self.nlist, iters, seed)
 
     def set_centroids(self, centroids):
         c = centroids.detach() if isinstance(centroids, torch.Tensor) else torch.from_numpy(np.asarray(centroids))
@@ -181,7 +178,7 @@ class IVFPQIndex(CoarseProbe):
     def add(self, x, codes: Optional[torch.Tensor] = None):
         """Index (rotated) embeddings x [N,d]: nearest PQ codes (unless the model's `codes` are given) + coarse cell."""
         assert self.coarse is not None, "train() the coarse quantiser first"
-        xt = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))).to(self.device)
+        xt = _as_f32_tensor(x).to(self.device)
         if codes is None:
             codes = ops.assign_nearest(xt, self.pq_centroids, torch.uint8)
         self.set_lists(codes, coarse_assign(xt, self.coarse))
@@ -196,7 +193,7 @@ class IVFPQIndex(CoarseProbe):
             chunks = [flat.reconstruct_n(i, min(1 << 18, flat.ntotal - i)) for i in range(0, flat.ntotal, 1 << 18)]
             xt = torch.cat(chunks, 0)
         else:
-            xt = (x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))).to(flat.device)
+            xt = _as_f32_tensor(x).to(flat.device)
         sel = torch.from_numpy(np.sort(np.random.default_rng(1234).permutation(xt.shape[0])[:train_rows])).to(flat.device)
         ivf.coarse = coarse_kmeans(xt[sel], nlist, iters)
         ivf.set_lists(flat.codes, coarse_assign(xt, ivf.coarse))
@@ -233,8 +230,7 @@ class IVFPQIndex(CoarseProbe):
         where available.
         Both return the same (scores, ids); METRIC_L2: (squared distances ascending, ids), +inf / -1 in unfilled slots."""
         as_numpy = not isinstance(x, torch.Tensor)
-        q = (torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x).to(self.device, torch.float32)
-        q = q.contiguous()
+        q = _as_f32_tensor(x).to(self.device, torch.float32).contiguous()
         if nprobe is None:
             nprobe = self.nprobe
         scores, ids = self._search_scores(q, k, nprobe, method)

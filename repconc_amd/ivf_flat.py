@@ -58,28 +58,17 @@ new ones: while it runs, a second copy of the whole store exists on the device.
 """
 from __future__ import annotations
 
+import functools
 from typing import Optional
 
 import numpy as np
 import torch
 
 from . import ops
-from .dense_index import SQ8_ROWS_PER_STEP, sq8_encode, sq8_train_range
-from .index import METRIC_INNER_PRODUCT, METRIC_L2
+from .dense_index import SQ8_ROWS_PER_STEP, sq8_encode  # noqa: F401  (names this module has always had)
+from .dense_index import _sq8_encode_chunks, sq8_train_range
+from .index import METRIC_INNER_PRODUCT, METRIC_L2, _as_device, _as_f32_tensor
 from .ivf import CoarseProbe, coarse_assign, coarse_kmeans
-
-
-def _sq8_decode_host(codes: torch.Tensor, dec: torch.Tensor) -> torch.Tensor:
-    """fmaf(c', step, mid) with its single rounding, in torch operators (the CPU device): the product is exact in fp64, the sum
-    is rounded to odd there (TwoSum finds whether it was inexact), and fp64 -> fp32 of a value rounded to odd is the correctly
-    rounded fp32 of the exact sum."""
-    p, mid = codes.double() * dec[0].double(), dec[1].double().expand(codes.shape)
-    s = p + mid
-    b = s - p
-    err = (p - (s - b)) + (mid - b)
-    even = (s.view(torch.int64) & 1) == 0
-    odd = torch.nextafter(s, torch.where(err > 0, torch.inf, -torch.inf).to(s.dtype))
-    return torch.where((err != 0) & even, odd, s).float()
 
 
 class IVFFlatIndex(CoarseProbe):
@@ -104,9 +93,7 @@ class IVFFlatIndex(CoarseProbe):
         self.by_residual = bool(by_residual)
         self._dtype = self.STORAGE[storage]
         self._coarse_sq = (None, None, None)                                # CoarseProbe: (coarse, its version, ||c_l||^2)
-        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        if self.device.type == "cuda" and self.device.index is None:        # "cuda" -> the current device, by index
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _as_device(device)
         self.d, self.nlist = int(d), int(nlist)
         self.coarse = None                                                  # [nlist, d] fp32
         self.vmin = self.step = self.mid = self._dec = None                 # int8 storage: the trained range, _dec [2, d] = step, mid
@@ -128,7 +115,7 @@ class IVFFlatIndex(CoarseProbe):
         self._sizes_desc = np.zeros(0, np.int64)      # cell sizes, descending (host copy): bounds a query's score row
 
     def _rows(self, x, what: str) -> torch.Tensor:
-        xt = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32))
+        xt = _as_f32_tensor(x)
         if xt.dim() != 2 or xt.shape[1] != self.d:
             raise ValueError(f"{what}: expected [n, {self.d}] vectors, got {tuple(xt.shape)}")
         return xt
@@ -190,17 +177,11 @@ class IVFFlatIndex(CoarseProbe):
         """The rows of an `add` in the storage type, checked before anything is stored; one host read.  by_residual: `cells` [n]
         on the device, the codes are those of fp32(x - coarse[cell])."""
         if self.storage == "int8":
-            n = xt.shape[0]
-            codes = torch.empty((n, self.d), dtype=torch.int8, device=self.device)
+            codes = torch.empty((xt.shape[0], self.d), dtype=torch.int8, device=self.device)
             finite = torch.ones((), dtype=torch.bool, device=self.device)
-            for r0 in range(0, n, SQ8_ROWS_PER_STEP):
-                part = xt[r0:r0 + SQ8_ROWS_PER_STEP].to(self.device, torch.float32)
-                finite &= torch.isfinite(part).all()
-                if self.by_residual:
-                    part = part - self.coarse[cells[r0:r0 + part.shape[0]]]
-                    finite &= torch.isfinite(part).all()                            # finite values whose difference overflows
-                part = torch.nan_to_num(part, nan=0.0, posinf=0.0, neginf=0.0)      # refused below; int8(NaN) is undefined
-                codes[r0:r0 + part.shape[0]] = sq8_encode(part, self.vmin, self.step)
+            shift = (lambda r0, n: self.coarse[cells[r0:r0 + n]]) if self.by_residual else None
+            for r0, part in _sq8_encode_chunks(xt, self.vmin, self.step, finite, shift=shift):
+                codes[r0:r0 + part.shape[0]] = part
             if not bool(finite):
                 raise ValueError("add: int8 storage needs finite values" + (" and finite residuals" if self.by_residual else ""))
             return codes
@@ -279,7 +260,7 @@ class IVFFlatIndex(CoarseProbe):
         """int8 storage: the stored values fp32 [n, d] of the list-major rows `pos`: the decode with its one rounding, and
         by_residual one separate fp32 addition of the centroid of the row's cell (the scan's two roundings)."""
         codes = self.xb[pos].contiguous()
-        rows = ops.dense_sq8_decode(codes, self._dec) if self.device.type == "cuda" else _sq8_decode_host(codes, self._dec)
+        rows = ops.dense_sq8_decode(codes, self._dec) if self.device.type == "cuda" else ops._sq8_decode_cpu(codes, self._dec)
         if self.by_residual:
             rows = rows + self.coarse[torch.searchsorted(self.list_off, pos, right=True) - 1]
         return rows
@@ -287,7 +268,7 @@ class IVFFlatIndex(CoarseProbe):
     # ---- search
     def _queries(self, x, k: int):
         as_numpy = not isinstance(x, torch.Tensor)
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x
+        q = _as_f32_tensor(x)
         if q.dim() != 2 or q.shape[1] != self.d:
             raise ValueError(f"search: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
         if not 1 <= int(k) <= ops.DENSE_MAX_K:
@@ -349,18 +330,16 @@ class IVFFlatIndex(CoarseProbe):
         nq, nprobe = probes.shape
         stride = (max(4, int(self._sizes_desc[:nprobe].sum())) + 3) // 4 * 4      # the nprobe largest cells bound a score row
         step = self._chunk_queries(nq, nprobe, stride)
+        if self.by_residual:                  # the search of this store with the store's own operands, chosen once
+            search = functools.partial(ops.ivf_flat_sq8r_search, self.xb, self._dec, self.coarse)
+        elif self.storage == "int8":
+            search = functools.partial(ops.ivf_flat_sq8_search, self.xb, self._dec)
+        else:
+            search = functools.partial(ops.ivf_flat_search, self.xb)
         parts, fallback, chunks = [], 0, 0
         for c0 in range(0, nq, step):
             qc, pc = q[c0:c0 + step], probes[c0:c0 + step]
-            if self.by_residual:
-                scores, ids, status, qstatus = ops.ivf_flat_sq8r_search(self.xb, self._dec, self.coarse, self.list_off, self.ids,
-                                                                        qc, pc, stride, k, metric=self.metric_type)
-            elif self.storage == "int8":
-                scores, ids, status, qstatus = ops.ivf_flat_sq8_search(self.xb, self._dec, self.list_off, self.ids, qc, pc, stride,
-                                                                       k, metric=self.metric_type)
-            else:
-                scores, ids, status, qstatus = ops.ivf_flat_search(self.xb, self.list_off, self.ids, qc, pc, stride, k,
-                                                                   metric=self.metric_type)
+            scores, ids, status, qstatus = search(self.list_off, self.ids, qc, pc, stride, k, metric=self.metric_type)
             chunks += 1
             st = int(status.item())
             if st & 4:
@@ -381,10 +360,8 @@ class IVFFlatIndex(CoarseProbe):
         search's tie rule becomes the exact entry's "lower row"), then the exact route of the flat search of this metric and
         storage (int8: the fp32 exact route over the gathered rows, decoded, by_residual with their centroids added).  Slow —
         one gather of the probed rows per query — and only reached for queries the selection could not decide."""
-        exact = {(METRIC_INNER_PRODUCT, "float32"): ops.dense_search_exact, (METRIC_INNER_PRODUCT, "float16"): ops.dense_search_f16_exact,
-                 (METRIC_L2, "float32"): ops.dense_search_l2_exact, (METRIC_L2, "float16"): ops.dense_search_l2_f16_exact,
-                 (METRIC_INNER_PRODUCT, "int8"): ops.dense_search_exact, (METRIC_L2, "int8"): ops.dense_search_l2_exact}
-        exact = exact[(self.metric_type, self.storage)]
+        exact = ((ops.dense_search_exact, ops.dense_search_f16_exact),
+                 (ops.dense_search_l2_exact, ops.dense_search_l2_f16_exact))[self.metric_type == METRIC_L2][self.storage == "float16"]
         scores, ids = self._padding(q.shape[0], k)
         off = self.list_off
         for j in range(q.shape[0]):

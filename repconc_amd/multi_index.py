@@ -22,10 +22,9 @@ from concurrent.futures import ThreadPoolExecutor
 from types import SimpleNamespace
 from typing import List, Optional, Sequence
 
-import numpy as np
 import torch
 
-from .index import METRIC_L2, PQIndex
+from .index import METRIC_L2, PQIndex, _as_f32_tensor
 from .sharded_search import merge_topk
 
 
@@ -116,8 +115,7 @@ class _MultiIndex:
     @staticmethod
     def _as_tensor(x):
         as_numpy = not isinstance(x, torch.Tensor)
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x.float()
-        return q, as_numpy
+        return _as_f32_tensor(x).float(), as_numpy
 
 
 class ReplicatedPQIndex(_MultiIndex):
@@ -222,7 +220,7 @@ class ReplicatedIVFPQIndex:
         if nprobe is None:
             nprobe = self.nprobe
         as_numpy = not isinstance(x, torch.Tensor)
-        q = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float32)) if as_numpy else x.float()
+        q = _as_f32_tensor(x).float()
         nq, G = q.shape[0], len(self.parts)
         bounds = [(nq * i) // G for i in range(G + 1)]
         jobs = [(self.parts[i], q[bounds[i]:bounds[i + 1]]) for i in range(G) if bounds[i + 1] > bounds[i]] or [(self.parts[0], q)]

@@ -1173,21 +1173,38 @@ def _dense_sq8_args(x8: torch.Tensor, q: torch.Tensor, k: int):
 
 
 # One dense search in eight variants.  args: (x, q, k) -> the checked corpus and the queries in the storage type; entry: the
-# library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes; exact: rc_<exact>_search_exact / ..._ws_bytes, the route that
-# cannot fail; normed: the entry takes xnorm_max (its screen only approximates the score, the answer carries a certificate);
-# rownorms: it also takes xsq, the squared norm of every row, before xnorm_max; pad: the value of the slots past N.
-_DenseVariant = collections.namedtuple("_DenseVariant", "args entry exact normed rownorms pad",
-                                       defaults=(False, float("-inf")))
-_DENSE_F32 = _DenseVariant(_dense_args, "dense", "dense", False)
-_DENSE_F16 = _DenseVariant(_dense_f16_args, "dense_f16", "dense_f16", True)
-_DENSE_BF16X3 = _DenseVariant(_dense_args, "dense_bf16x3", "dense", True)
-_DENSE_L2 = _DenseVariant(_dense_args, "dense_l2", "dense_l2", True, True, float("inf"))
-_DENSE_L2_F16 = _DenseVariant(_dense_f16_args, "dense_l2_f16", "dense_l2_f16", True, True, float("inf"))
-_DENSE_L2_BF16X3 = _DenseVariant(_dense_args, "dense_l2_bf16x3", "dense_l2", True, True, float("inf"))
-# int8 codes: both entries take the decoding vectors `dec` after the queries, the search also the corpus statistics `cstat`
-_DENSE_SQ8 = _DenseVariant(_dense_sq8_args, "dense_sq8", "dense_sq8", False)
-# int8 codes under L2: the search takes dec, the rows' squared norms xsq and cstat, in that order
-_DENSE_L2_SQ8 = _DenseVariant(_dense_sq8_args, "dense_l2_sq8", "dense_l2_sq8", False, True, float("inf"))
+# library's rc_<entry>_search_q / rc_<entry>_search_ws_bytes / rc_<entry>_scores; exact: rc_<exact>_search_exact / ..._ws_bytes,
+# the route that cannot fail; side / exact_side: the side operands those two entries take after the queries, by name and in the
+# header's order (xnorm_max [1]: the screen only approximates the score, the answer carries a certificate; xsq [N]: the squared
+# norm of every row; dec [2, D] and cstat [2]: the decoding vectors and the statistics of int8 codes); pad: the value of the
+# slots past N; scores_ws: rc_<entry>_scores takes a workspace.
+_DenseVariant = collections.namedtuple("_DenseVariant", "args entry exact side exact_side pad scores_ws",
+                                       defaults=((), (), float("-inf"), False))
+_DENSE_F32 = _DenseVariant(_dense_args, "dense", "dense")
+_DENSE_F16 = _DenseVariant(_dense_f16_args, "dense_f16", "dense_f16", ("xnorm_max",))
+_DENSE_BF16X3 = _DenseVariant(_dense_args, "dense_bf16x3", "dense", ("xnorm_max",), scores_ws=True)
+_DENSE_L2 = _DenseVariant(_dense_args, "dense_l2", "dense_l2", ("xsq", "xnorm_max"), pad=float("inf"))
+_DENSE_L2_F16 = _DenseVariant(_dense_f16_args, "dense_l2_f16", "dense_l2_f16", ("xsq", "xnorm_max"), pad=float("inf"))
+_DENSE_L2_BF16X3 = _DenseVariant(_dense_args, "dense_l2_bf16x3", "dense_l2", ("xsq", "xnorm_max"), pad=float("inf"),
+                                 scores_ws=True)
+_DENSE_SQ8 = _DenseVariant(_dense_sq8_args, "dense_sq8", "dense_sq8", ("dec", "cstat"), ("dec",), scores_ws=True)
+_DENSE_L2_SQ8 = _DenseVariant(_dense_sq8_args, "dense_l2_sq8", "dense_l2_sq8", ("dec", "xsq", "cstat"), ("dec",),
+                              pad=float("inf"), scores_ws=True)
+
+
+def _dense_call(v: _DenseVariant, kind: str, h, x, q, t: dict, stream, k=0, id_offset=0, sel_slack=0.0):
+    """(name, argument tuple) of one library call of variant `v`; kind: "search_q", "search_exact" or "scores".  The header's
+    order: h, x, ldx, N, D, q, nq, the side operands the variant names for that entry, the scalars, the outputs, the workspace
+    (where `t` holds one), the stream.  `t`: the side operands, the outputs and "ws" by name.  Touches no device and loads no
+    library: the positions come from the variant's names alone (tests/test_search_arg_order.py)."""
+    entry, side, scalars, outs = {
+        "search_q": (v.entry, v.side, (int(k), int(id_offset), float(sel_slack)), ("scores", "ids", "status", "qstatus")),
+        "search_exact": (v.exact, v.exact_side, (int(k), int(id_offset)), ("scores", "ids")),
+        "scores": (v.entry, tuple(n for n in v.side if n in ("dec", "xsq")), (), ("out",)),    # no certificate: no xnorm_max, cstat
+    }[kind]
+    ws = () if t.get("ws") is None else (_p(t["ws"]), t["ws"].numel())
+    return f"rc_{entry}_{kind}", (h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], *(_p(t[n]) for n in side),
+                                  *scalars, *(_p(t[n]) for n in outs), *ws, stream)
 
 
 def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int,
@@ -1202,12 +1219,10 @@ def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: i
         scores.fill_(v.pad)
         ids.fill_(-1)
         return scores, ids
-    name = f"rc_{v.exact}_search_exact"
-    wsb = getattr(lib, name + "_ws_bytes")(N, D, nq, int(k))
+    wsb = getattr(lib, f"rc_{v.exact}_search_exact_ws_bytes")(N, D, nq, int(k))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-    side = () if dec is None else (_p(dec),)
-    _lib.check(getattr(lib, name)(h, _p(x), x.stride(0), N, D, _p(q), nq, *side, int(k), int(id_offset), _p(scores), _p(ids),
-                                  _p(ws), wsb, s), name, h)
+    name, args = _dense_call(v, "search_exact", h, x, q, {"dec": dec, "scores": scores, "ids": ids, "ws": ws}, s, k, id_offset)
+    _lib.check(getattr(lib, name)(*args), name, h)
     return scores, ids
 
 
@@ -1226,21 +1241,20 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
         got = _dense_search_exact(v, x, q, k, id_offset, dec)
         return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
     lib, h, _, dev = _ctx(q)
-    norm = () if dec is None else (dec, cstat)    # the tensors behind the entry's extra pointer arguments
-    if v.normed:
+    side = {"dec": dec, "cstat": cstat}          # the tensors behind the entry's side operands (v.side)
+    if "xnorm_max" in v.side:
         if xnorm_max is None:
             # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the norm
             xnorm_max = dense_xnorm_max(x) if N > DENSE_EXACT_MAX_N else torch.zeros((1,), dtype=torch.float32, device=x.device)
         _need_cuda(xnorm_max)
-        norm = (xnorm_max.to(torch.float32).reshape(1),)
-    if v.rownorms:
+        side["xnorm_max"] = xnorm_max.to(torch.float32).reshape(1)
+    if "xsq" in v.side:
         if xsq is None:
             xsq = dense_row_sqnorms(x) if N > DENSE_EXACT_MAX_N else torch.zeros((N,), dtype=torch.float32, device=x.device)
         _need_cuda(xsq)
         if xsq.shape != (N,):
             raise ValueError("dense search: xsq must hold one squared norm per row, [N]")
-        xsq = xsq.to(torch.float32).contiguous()
-        norm = (xsq,) + norm if dec is None else (dec, xsq, cstat)
+        side["xsq"] = xsq.to(torch.float32).contiguous()
     name = f"rc_{v.entry}_search_q"
     search_q, ws_bytes = getattr(lib, name), getattr(lib, f"rc_{v.entry}_search_ws_bytes")
 
@@ -1250,9 +1264,8 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
             n = min(DENSE_QCHUNK, qq.shape[0] - c0)
             wsb = ws_bytes(N, D, n, int(k))
             ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)     # released in stream order
-            _lib.check(search_q(h, _p(x), x.stride(0), N, D, _p(qq[c0:c0 + n]), n, *map(_p, norm), int(k), int(id_offset),
-                                float(slack), _p(out_s[c0:c0 + n]), _p(out_i[c0:c0 + n]), _p(status), _p(qstatus[c0:c0 + n]),
-                                _p(ws), wsb, st), name, h)
+            t = dict(side, scores=out_s[c0:c0 + n], ids=out_i[c0:c0 + n], status=status, qstatus=qstatus[c0:c0 + n], ws=ws)
+            _lib.check(search_q(*_dense_call(v, "search_q", h, x, qq[c0:c0 + n], t, st, k, id_offset, slack)[1]), name, h)
             if stats is not None and len(stats.setdefault("survivors", [])) * DENSE_QCHUNK < nq:
                 off = C.c_size_t(0)          # measurement: the first pass's candidate counts (rc_<entry>_search_ws_counts)
                 _lib.check(getattr(lib, f"rc_{v.entry}_search_ws_counts")(N, D, n, int(k), C.byref(off)), name, h)
@@ -1280,6 +1293,36 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
     pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
                             stream=torch.cuda.current_stream(dev))
     return pending if defer else pending.result()
+
+
+def _dense_scores(v: _DenseVariant, name: str, x, q, dec=None, xsq=None) -> torch.Tensor:
+    """The `*_scores` test hooks: the raw screen values [nq, N] of variant `v` (rc_<entry>_scores).  `dec` and `xsq` are looked
+    at where the variant's search takes them; a missing xsq is computed from the rows (the decoded rows of int8 codes)."""
+    x, q = v.args(x, q, 1)
+    t = {"dec": _dense_sq8_dec(x, dec) if "dec" in v.side else None}
+    lib, h, s, _ = _ctx(q)
+    if "xsq" in v.side:
+        if xsq is None:
+            xsq = dense_row_sqnorms(x) if t["dec"] is None else dense_sq8_row_sqnorms(x, t["dec"])
+        _need_cuda(xsq)
+        t["xsq"] = xsq.to(torch.float32).contiguous()
+        if xsq.shape != (x.shape[0],):
+            raise ValueError(f"{name}: xsq must hold one squared norm per row, [N]")
+    t["out"] = torch.empty((q.shape[0], x.shape[0]), dtype=torch.float32, device=q.device)
+    if t["out"].numel():
+        if v.scores_ws:
+            wsb = getattr(lib, f"rc_{v.entry}_scores_ws_bytes")(x.shape[1], q.shape[0])
+            t["ws"] = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
+        entry, args = _dense_call(v, "scores", h, x, q, t, s)
+        _lib.check(getattr(lib, entry)(*args), entry, h)
+    return t["out"]
+
+
+def _error_constants(entry: str, n: int) -> tuple:
+    """The `n` doubles of rc_<entry>_error_constants.  No GPU needed."""
+    c = (C.c_double * n)()
+    getattr(_lib.load(), f"rc_{entry}_error_constants")(c)
+    return tuple(float(v) for v in c)
 
 
 DENSE_RERANK_MAX_KC = 16384         # candidates per query of dense_rerank (ADC_CAND_CAP, csrc/topk.h)
@@ -1366,46 +1409,7 @@ def ivf_flat_search(xb: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor,
     synchronising: bit 1 of a query's status = more than 16384 of its probed rows tie at its k-th score and its row of the
     output is not valid (`IVFFlatIndex` answers those queries by the exact search over their probed rows); bit 2 of `status` =
     a probe outside [0, nlist) or a `stride` too small.  Argument errors are ValueError before any device work."""
-    l2 = _adc_metric(metric)
-    if xb.dim() != 2 or q.dim() != 2 or xb.shape[1] != q.shape[1] or xb.shape[1] < 1:
-        raise ValueError("ivf_flat_search: xb [N, D] and q [nq, D] with the same D >= 1")
-    if xb.dtype not in (torch.float32, torch.float16):
-        raise ValueError("ivf_flat_search: the store must be float32 or float16")
-    if not 1 <= int(k) <= DENSE_MAX_K:
-        raise ValueError(f"ivf_flat_search: k must be in [1, {DENSE_MAX_K}]")
-    N, D = xb.shape
-    nlist = list_off.numel() - 1
-    if list_off.dtype != torch.int64 or list_off.dim() != 1 or not 1 <= nlist <= IVF_FLAT_MAX_NLIST:
-        raise ValueError(f"ivf_flat_search: list_off must be int64 [nlist + 1], 1 <= nlist <= {IVF_FLAT_MAX_NLIST}")
-    if ids.dtype != torch.int64 or ids.shape != (N,):
-        raise ValueError("ivf_flat_search: ids must be int64 [N]")
-    if probes.dim() != 2 or probes.dtype != torch.int32 or probes.shape[0] != q.shape[0] or not 1 <= probes.shape[1] <= nlist:
-        raise ValueError("ivf_flat_search: probes must be int32 [nq, nprobe], 1 <= nprobe <= nlist")
-    if not 1 <= N < 1 << 32:
-        raise ValueError("ivf_flat_search: 1 <= N < 2^32")
-    if int(stride) < 1:
-        raise ValueError("ivf_flat_search: stride must be >= 1")
-    _need_cuda(xb, list_off, ids, q, probes)
-    f16 = xb.dtype == torch.float16
-    if xb.stride(1) != 1 or (N > 1 and xb.stride(0) < D):
-        xb = xb.contiguous()
-    q = q.to(xb.device).to(xb.dtype).contiguous()           # fp16: round to nearest even, as the corpus was
-    list_off, ids, probes = list_off.contiguous(), ids.contiguous(), probes.contiguous()
-    nq, nprobe = probes.shape
-    scores = torch.empty((nq, int(k)), dtype=torch.float32, device=q.device)
-    out_ids = torch.empty((nq, int(k)), dtype=torch.int64, device=q.device)
-    flags = torch.zeros((1 + nq,), dtype=torch.int32, device=q.device)       # [status | per-query status]: one fill
-    status, qstatus = flags[:1], flags[1:]
-    if nq == 0:
-        return scores, out_ids, status, qstatus
-    lib, h, s, _ = _ctx(q)
-    name = "rc_ivf_flat_f16_search" if f16 else "rc_ivf_flat_search"
-    wsb = lib.rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, int(stride))
-    ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)             # released in stream order
-    _lib.check(getattr(lib, name)(h, _p(xb), xb.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q), nq,
-                                  _p(probes), nprobe, int(stride), int(k), int(l2), _p(scores), _p(out_ids), _p(status),
-                                  _p(qstatus), _p(ws), wsb, s), name, h)
-    return scores, out_ids, status, qstatus
+    return _ivf_flat_search("ivf_flat_search", "xb", xb, None, None, list_off, ids, q, probes, stride, k, metric)
 
 
 def ivf_flat_sq8_search(xb8: torch.Tensor, dec: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor, q: torch.Tensor,
@@ -1415,7 +1419,7 @@ def ivf_flat_sq8_search(xb8: torch.Tensor, dec: torch.Tensor, list_off: torch.Te
     else, the returns and the status bits as `ivf_flat_search`.  Scores are bit for bit those of `ivf_flat_search` over
     `dense_sq8_decode(xb8, dec)`, under either metric.  Any row pitch >= D and any alignment (a column slice of a wider
     matrix is read in place).  D <= 65536; argument errors are ValueError before any device work."""
-    return _ivf_flat_sq8_search("ivf_flat_sq8_search", xb8, dec, None, list_off, ids, q, probes, stride, k, metric)
+    return _ivf_flat_search("ivf_flat_sq8_search", "xb8", xb8, dec, None, list_off, ids, q, probes, stride, k, metric)
 
 
 def ivf_flat_sq8r_search(xb8: torch.Tensor, dec: torch.Tensor, coarse: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor,
@@ -1427,23 +1431,40 @@ def ivf_flat_sq8r_search(xb8: torch.Tensor, dec: torch.Tensor, coarse: torch.Ten
     of `ivf_flat_sq8_search`, and `coarse` must be float32 [nlist, D]."""
     if not isinstance(coarse, torch.Tensor):
         raise ValueError("ivf_flat_sq8r_search: coarse must be a float32 tensor [nlist, D]")
-    return _ivf_flat_sq8_search("ivf_flat_sq8r_search", xb8, dec, coarse, list_off, ids, q, probes, stride, k, metric)
+    return _ivf_flat_search("ivf_flat_sq8r_search", "xb8", xb8, dec, coarse, list_off, ids, q, probes, stride, k, metric)
 
 
-def _ivf_flat_sq8_search(name, xb8, dec, coarse, list_off, ids, q, probes, stride, k, metric):
-    """The two coded IVF searches: `coarse` None = the vectors themselves are encoded, else their residuals."""
+def _ivf_flat_call(h, xb, list_off, ids, q, dec, coarse, probes, stride, k, l2, scores, out_ids, status, qstatus, ws, stream):
+    """(name, argument tuple) of one call of the four rc_ivf_flat*_search entries, chosen by the store's type and by which of
+    `dec` / `coarse` are tensors.  The header's order: h, x, ldx, list_off, ids, N, nlist, D, q, nq, [dec, [coarse, ldc]], probes,
+    nprobe, stride, k, metric, the outputs, the workspace, the stream.  Touches no device and loads no library."""
+    (N, D), nlist = xb.shape, list_off.numel() - 1
+    side = () if dec is None else (_p(dec),) if coarse is None else (_p(dec), _p(coarse), coarse.stride(0) if nlist > 1 else D)
+    form = "_f16" if xb.dtype == torch.float16 else "" if dec is None else "_sq8" if coarse is None else "_sq8r"
+    return f"rc_ivf_flat{form}_search", (h, _p(xb), xb.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q),
+                                         q.shape[0], *side, _p(probes), probes.shape[1], int(stride), int(k), int(l2), _p(scores),
+                                         _p(out_ids), _p(status), _p(qstatus), _p(ws), ws.numel(), stream)
+
+
+def _ivf_flat_search(name, store, xb, dec, coarse, list_off, ids, q, probes, stride, k, metric):
+    """The body of the three IVF-flat searches.  store "xb": the fp32 / fp16 store, queries of any type rounded to the store's;
+    "xb8": int8 codes with `dec`, fp32 queries, and `coarse` None = the vectors themselves are encoded, else their residuals."""
+    coded = store == "xb8"
     l2 = _adc_metric(metric)
-    if xb8.dim() != 2 or q.dim() != 2 or xb8.shape[1] != q.shape[1] or xb8.shape[1] < 1:
-        raise ValueError(f"{name}: xb8 [N, D] and q [nq, D] with the same D >= 1")
-    if xb8.dtype != torch.int8:
-        raise ValueError(f"{name}: the store must be int8 codes, c - 128")
-    if q.dtype != torch.float32:
-        raise ValueError(f"{name}: the queries must be float32")
-    N, D = xb8.shape
-    if D > DENSE_SQ8_MAX_D:
-        raise ValueError(f"{name}: D must be <= {DENSE_SQ8_MAX_D}")
-    if dec.dtype != torch.float32 or dec.shape != (2, D):
-        raise ValueError(f"{name}: dec must be float32 [2, D]: the steps, then the mids")
+    if xb.dim() != 2 or q.dim() != 2 or xb.shape[1] != q.shape[1] or xb.shape[1] < 1:
+        raise ValueError(f"{name}: {store} [N, D] and q [nq, D] with the same D >= 1")
+    N, D = xb.shape
+    if coded:
+        if xb.dtype != torch.int8:
+            raise ValueError(f"{name}: the store must be int8 codes, c - 128")
+        if q.dtype != torch.float32:
+            raise ValueError(f"{name}: the queries must be float32")
+        if D > DENSE_SQ8_MAX_D:
+            raise ValueError(f"{name}: D must be <= {DENSE_SQ8_MAX_D}")
+        if dec.dtype != torch.float32 or dec.shape != (2, D):
+            raise ValueError(f"{name}: dec must be float32 [2, D]: the steps, then the mids")
+    elif xb.dtype not in (torch.float32, torch.float16):
+        raise ValueError(f"{name}: the store must be float32 or float16")
     if not 1 <= int(k) <= DENSE_MAX_K:
         raise ValueError(f"{name}: k must be in [1, {DENSE_MAX_K}]")
     nlist = list_off.numel() - 1
@@ -1459,12 +1480,15 @@ def _ivf_flat_sq8_search(name, xb8, dec, coarse, list_off, ids, q, probes, strid
         raise ValueError(f"{name}: 1 <= N < 2^32")
     if int(stride) < 1:
         raise ValueError(f"{name}: stride must be >= 1")
-    _need_cuda(xb8, dec, coarse, list_off, ids, q, probes)
-    if coarse is not None and coarse.device != xb8.device:
+    _need_cuda(xb, dec, coarse, list_off, ids, q, probes)
+    if coarse is not None and coarse.device != xb.device:
         raise ValueError(f"{name}: coarse must be on the device of the store")
-    if xb8.stride(1) != 1 or (N > 1 and xb8.stride(0) < D):
-        xb8 = xb8.contiguous()
-    q, dec = q.to(xb8.device).contiguous(), dec.to(xb8.device).contiguous()
+    if xb.stride(1) != 1 or (N > 1 and xb.stride(0) < D):
+        xb = xb.contiguous()
+    if coded:
+        q, dec = q.to(xb.device).contiguous(), dec.to(xb.device).contiguous()
+    else:
+        q = q.to(xb.device).to(xb.dtype).contiguous()       # fp16: round to nearest even, as the corpus was
     list_off, ids, probes = list_off.contiguous(), ids.contiguous(), probes.contiguous()
     nq, nprobe = probes.shape
     scores = torch.empty((nq, int(k)), dtype=torch.float32, device=q.device)
@@ -1473,18 +1497,14 @@ def _ivf_flat_sq8_search(name, xb8, dec, coarse, list_off, ids, q, probes, strid
     status, qstatus = flags[:1], flags[1:]
     if nq == 0:
         return scores, out_ids, status, qstatus
+    if coarse is not None and (coarse.stride(1) != 1 or (nlist > 1 and coarse.stride(0) < D)):
+        coarse = coarse.contiguous()
     lib, h, s, _ = _ctx(q)
-    wsb = lib.rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, int(stride))
-    ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)             # released in stream order
-    head = (h, _p(xb8), xb8.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q), nq, _p(dec))
-    tail = (_p(probes), nprobe, int(stride), int(k), int(l2), _p(scores), _p(out_ids), _p(status), _p(qstatus), _p(ws), wsb, s)
-    if coarse is None:
-        rc = lib.rc_ivf_flat_sq8_search(*head, *tail)
-    else:
-        if coarse.stride(1) != 1 or (nlist > 1 and coarse.stride(0) < D):
-            coarse = coarse.contiguous()
-        rc = lib.rc_ivf_flat_sq8r_search(*head, _p(coarse), coarse.stride(0) if nlist > 1 else D, *tail)
-    _lib.check(rc, "rc_" + name, h)
+    ws = torch.empty((lib.rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, int(stride)),), dtype=torch.uint8,
+                     device=q.device)                                        # released in stream order
+    entry, args = _ivf_flat_call(h, xb, list_off, ids, q, dec, coarse, probes, stride, k, l2, scores, out_ids, status, qstatus,
+                                 ws, s)
+    _lib.check(getattr(lib, entry)(*args), entry, h)
     return scores, out_ids, status, qstatus
 
 
@@ -1542,13 +1562,7 @@ def dense_search_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset
 
 def dense_f16_scores(x16: torch.Tensor, q16: torch.Tensor) -> torch.Tensor:
     """The raw approximate scores s~ [nq, N] of the f16 matrix-core screen (rc_dense_f16_scores): a test hook, never a result."""
-    x16, q16 = _dense_f16_args(x16, q16, 1)
-    lib, h, s, _ = _ctx(q16)
-    out = torch.empty((q16.shape[0], x16.shape[0]), dtype=torch.float32, device=q16.device)
-    if out.numel():
-        _lib.check(lib.rc_dense_f16_scores(h, _p(x16), x16.stride(0), x16.shape[0], x16.shape[1], _p(q16), q16.shape[0],
-                                           _p(out), s), "rc_dense_f16_scores", h)
-    return out
+    return _dense_scores(_DENSE_F16, "dense_f16_scores", x16, q16)
 
 
 def dense_search_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
@@ -1569,9 +1583,7 @@ def dense_search_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int 
 # ------------------------------------------------------------------------------------ dense, fp32 corpus, bf16x3 screen
 def dense_bf16x3_error_constants():
     """(c_sum, c_split, c_sub, c_under) of E_q as the certificate kernel was compiled with them (csrc/dense_search_bf16x3.hip)."""
-    c = (C.c_double * 4)()
-    _lib.load().rc_dense_bf16x3_error_constants(c)
-    return tuple(float(v) for v in c)
+    return _error_constants("dense_bf16x3", 4)
 
 
 def dense_bf16x3_error_bound(D: int, qnorm, xmax):
@@ -1587,15 +1599,7 @@ def dense_bf16x3_error_bound(D: int, qnorm, xmax):
 def dense_bf16x3_scores(x: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     """The raw approximate scores s~ [nq, N] of the bf16x3 matrix-core screen (rc_dense_bf16x3_scores): a test hook, never a
     result."""
-    x, q = _dense_args(x, q, 1)
-    lib, h, s, _ = _ctx(q)
-    out = torch.empty((q.shape[0], x.shape[0]), dtype=torch.float32, device=q.device)
-    if out.numel():
-        wsb = lib.rc_dense_bf16x3_scores_ws_bytes(x.shape[1], q.shape[0])
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-        _lib.check(lib.rc_dense_bf16x3_scores(h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], _p(out),
-                                              _p(ws), wsb, s), "rc_dense_bf16x3_scores", h)
-    return out
+    return _dense_scores(_DENSE_BF16X3, "dense_bf16x3_scores", x, q)
 
 
 def dense_search_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
@@ -1615,9 +1619,7 @@ def dense_search_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int
 def dense_sq8_error_constants():
     """(c_q, c_w, c_ad, c_ac, c_b, c_ch, c_abs) of E_q as the certificate kernel was compiled with them
     (csrc/dense_search_sq8.hip).  No GPU needed."""
-    c = (C.c_double * 7)()
-    _lib.load().rc_dense_sq8_error_constants(c)
-    return tuple(float(v) for v in c)
+    return _error_constants("dense_sq8", 7)
 
 
 def dense_sq8_qmax() -> int:
@@ -1645,6 +1647,21 @@ def _dense_sq8_dec(x8: torch.Tensor, dec: torch.Tensor) -> torch.Tensor:
     return dec.to(x8.device, torch.float32).contiguous()
 
 
+def _dense_sq8_front(name: str, x8, dec, q, k, cstat):
+    """The checked (x8, dec, cstat) of `dense_search_sq8` / `dense_search_l2_sq8`; a missing cstat is computed here."""
+    if x8.dim() == 2 and dec.shape != (2, x8.shape[1]):
+        raise ValueError(f"{name}: dec must be [2, D]: the steps, then the mids")
+    x8, _ = _dense_sq8_args(x8, q, k)
+    dec = _dense_sq8_dec(x8, dec)
+    if cstat is None:
+        # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the statistics
+        cstat = dense_sq8_cstat(x8, dec) if x8.shape[0] > DENSE_EXACT_MAX_N else torch.zeros((2,), device=x8.device)
+    _need_cuda(cstat)
+    if cstat.shape != (2,):
+        raise ValueError(f"{name}: cstat must be [2]: C1 and X (dense_sq8_cstat)")
+    return x8, dec, cstat.to(x8.device, torch.float32).contiguous()
+
+
 def dense_sq8_decode(x8: torch.Tensor, dec: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
     """The decoded corpus, fp32 [N, D]: x^ = fmaf(c', step, mid) with one rounding (rc_dense_sq8_decode) — the rows whose
     `dense_search` IS `dense_search_sq8`."""
@@ -1659,6 +1676,19 @@ def dense_sq8_decode(x8: torch.Tensor, dec: torch.Tensor, rows_per_step: int = 1
             _lib.check(lib.rc_dense_sq8_decode(h, _p(x8[r0:]), x8.stride(0), n, D, _p(dec), _p(out[r0:]), s),
                        "rc_dense_sq8_decode", h)
     return out
+
+
+def _sq8_decode_cpu(codes: torch.Tensor, dec: torch.Tensor) -> torch.Tensor:
+    """fmaf(c', step, mid) with its single rounding, in torch operators (the CPU device): the product is exact in fp64 (8 + 24
+    significant bits), the sum is rounded to odd there (TwoSum finds whether it was inexact), and fp64 -> fp32 of a value rounded
+    to odd is the correctly rounded fp32 of the exact sum."""
+    p, mid = codes.double() * dec[0].double(), dec[1].double().expand(codes.shape)
+    s = p + mid
+    b = s - p
+    err = (p - (s - b)) + (mid - b)                                 # TwoSum: p + mid = s + err exactly
+    even = (s.view(torch.int64) & 1) == 0
+    odd = torch.nextafter(s, torch.where(err > 0, torch.inf, -torch.inf).to(s.dtype))
+    return torch.where((err != 0) & even, odd, s).float()           # inexact and even: the odd neighbour
 
 
 def dense_sq8_cstat(x8: torch.Tensor, dec: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tensor:
@@ -1683,16 +1713,7 @@ def dense_search_sq8_exact(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor,
 def dense_sq8_scores(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     """The raw approximate scores s~ [nq, N] of the int8 matrix-core screen (rc_dense_sq8_scores): a test hook, never a
     result."""
-    x8, q = _dense_sq8_args(x8, q, 1)
-    dec = _dense_sq8_dec(x8, dec)
-    lib, h, s, _ = _ctx(q)
-    out = torch.empty((q.shape[0], x8.shape[0]), dtype=torch.float32, device=q.device)
-    if out.numel():
-        wsb = lib.rc_dense_sq8_scores_ws_bytes(x8.shape[1], q.shape[0])
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-        _lib.check(lib.rc_dense_sq8_scores(h, _p(x8), x8.stride(0), x8.shape[0], x8.shape[1], _p(q), q.shape[0], _p(dec),
-                                           _p(out), _p(ws), wsb, s), "rc_dense_sq8_scores", h)
-    return out
+    return _dense_scores(_DENSE_SQ8, "dense_sq8_scores", x8, q, dec)
 
 
 def dense_search_sq8(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
@@ -1708,17 +1729,7 @@ def dense_search_sq8(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k: in
     computed here when None).  stats (measurement): receives "survivors", a list of int32 device tensors (one per library
     call of the FIRST pass) with the rows of every query that passed the screen.  1 <= D <= 65536.  Everything else as
     `dense_search`."""
-    if x8.dim() == 2 and dec.shape != (2, x8.shape[1]):
-        raise ValueError("dense_search_sq8: dec must be [2, D]: the steps, then the mids")
-    x8, _ = _dense_sq8_args(x8, q, k)
-    dec = _dense_sq8_dec(x8, dec)
-    if cstat is None:
-        # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the statistics
-        cstat = dense_sq8_cstat(x8, dec) if x8.shape[0] > DENSE_EXACT_MAX_N else torch.zeros((2,), device=x8.device)
-    _need_cuda(cstat)
-    if cstat.shape != (2,):
-        raise ValueError("dense_search_sq8: cstat must be [2]: C1 and X (dense_sq8_cstat)")
-    cstat = cstat.to(x8.device, torch.float32).contiguous()
+    x8, dec, cstat = _dense_sq8_front("dense_search_sq8", x8, dec, q, k, cstat)
     return _dense_search(_DENSE_SQ8, x8, q, k, id_offset, sel_slack, defer, method, max_retries, dec=dec, cstat=cstat,
                          stats=stats)
 
@@ -1743,9 +1754,7 @@ def _dense_l2_xnorm_max(xsq: torch.Tensor) -> torch.Tensor:
 
 def dense_l2_error_constants():
     """(c_rel, c_flush, c_under) of E_q as the certificate kernel was compiled with them (csrc/dense_search_l2.hip)."""
-    c = (C.c_double * 3)()
-    _lib.load().rc_dense_l2_error_constants(c)
-    return tuple(float(v) for v in c)
+    return _error_constants("dense_l2", 3)
 
 
 def dense_l2_error_bound(D: int, qnorm, xmax):
@@ -1762,19 +1771,7 @@ def dense_l2_error_bound(D: int, qnorm, xmax):
 def dense_l2_scores(x: torch.Tensor, q: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The raw screen values sigma [nq, N] = fmaf(2, dot(q, x_n), -xsq[n]) of the L2 search (rc_dense_l2_scores): a test hook,
     never a result."""
-    x, q = _dense_args(x, q, 1)
-    lib, h, s, _ = _ctx(q)
-    if xsq is None:
-        xsq = dense_row_sqnorms(x)
-    _need_cuda(xsq)
-    xsq = xsq.to(torch.float32).contiguous()
-    if xsq.shape != (x.shape[0],):
-        raise ValueError("dense_l2_scores: xsq must hold one squared norm per row, [N]")
-    out = torch.empty((q.shape[0], x.shape[0]), dtype=torch.float32, device=q.device)
-    if out.numel():
-        _lib.check(lib.rc_dense_l2_scores(h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], _p(xsq), _p(out), s),
-                   "rc_dense_l2_scores", h)
-    return out
+    return _dense_scores(_DENSE_L2, "dense_l2_scores", x, q, xsq=xsq)
 
 
 def dense_search_l2_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
@@ -1815,9 +1812,7 @@ def _dense_search_l2(v: _DenseVariant, x, q, k, id_offset, sel_slack, defer, met
 # ---------------------------------------------------------------------------------------- dense, L2 metric, fp16 storage
 def dense_l2_f16_error_constants():
     """(c_rel, max_d) of E_q as the certificate kernel was compiled with them (csrc/dense_search_l2_f16.hip)."""
-    c = (C.c_double * 2)()
-    _lib.load().rc_dense_l2_f16_error_constants(c)
-    return tuple(float(v) for v in c)
+    return _error_constants("dense_l2_f16", 2)
 
 
 def dense_l2_f16_error_bound(D: int, qnorm, xmax):
@@ -1834,19 +1829,7 @@ def dense_l2_f16_error_bound(D: int, qnorm, xmax):
 def dense_l2_f16_scores(x16: torch.Tensor, q16: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The raw screen values sigma [nq, N] = fmaf(2, dot(q, x_n), -xsq[n]) of the fp16 L2 search (rc_dense_l2_f16_scores): a
     test hook, never a result."""
-    x16, q16 = _dense_f16_args(x16, q16, 1)
-    lib, h, s, _ = _ctx(q16)
-    if xsq is None:
-        xsq = dense_row_sqnorms(x16)
-    _need_cuda(xsq)
-    xsq = xsq.to(torch.float32).contiguous()
-    if xsq.shape != (x16.shape[0],):
-        raise ValueError("dense_l2_f16_scores: xsq must hold one squared norm per row, [N]")
-    out = torch.empty((q16.shape[0], x16.shape[0]), dtype=torch.float32, device=q16.device)
-    if out.numel():
-        _lib.check(lib.rc_dense_l2_f16_scores(h, _p(x16), x16.stride(0), x16.shape[0], x16.shape[1], _p(q16), q16.shape[0],
-                                              _p(xsq), _p(out), s), "rc_dense_l2_f16_scores", h)
-    return out
+    return _dense_scores(_DENSE_L2_F16, "dense_l2_f16_scores", x16, q16, xsq=xsq)
 
 
 def dense_search_l2_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
@@ -1875,9 +1858,7 @@ def dense_search_l2_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: i
 def dense_l2_bf16x3_error_constants():
     """(c_sum, c_split, c_flush, c_under) of E_q as the certificate kernel was compiled with them
     (csrc/dense_search_l2_bf16x3.hip)."""
-    c = (C.c_double * 4)()
-    _lib.load().rc_dense_l2_bf16x3_error_constants(c)
-    return tuple(float(v) for v in c)
+    return _error_constants("dense_l2_bf16x3", 4)
 
 
 def dense_l2_bf16x3_error_bound(D: int, qnorm, xmax):
@@ -1895,21 +1876,7 @@ def dense_l2_bf16x3_error_bound(D: int, qnorm, xmax):
 def dense_l2_bf16x3_scores(x: torch.Tensor, q: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The raw screen values sigma~ [nq, N] = fmaf(2, s~(q, x_n), -xsq[n]) of the bf16x3 L2 search
     (rc_dense_l2_bf16x3_scores): a test hook, never a result."""
-    x, q = _dense_args(x, q, 1)
-    lib, h, s, _ = _ctx(q)
-    if xsq is None:
-        xsq = dense_row_sqnorms(x)
-    _need_cuda(xsq)
-    xsq = xsq.to(torch.float32).contiguous()
-    if xsq.shape != (x.shape[0],):
-        raise ValueError("dense_l2_bf16x3_scores: xsq must hold one squared norm per row, [N]")
-    out = torch.empty((q.shape[0], x.shape[0]), dtype=torch.float32, device=q.device)
-    if out.numel():
-        wsb = lib.rc_dense_l2_bf16x3_scores_ws_bytes(x.shape[1], q.shape[0])
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-        _lib.check(lib.rc_dense_l2_bf16x3_scores(h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], _p(xsq),
-                                                 _p(out), _p(ws), wsb, s), "rc_dense_l2_bf16x3_scores", h)
-    return out
+    return _dense_scores(_DENSE_L2_BF16X3, "dense_l2_bf16x3_scores", x, q, xsq=xsq)
 
 
 def dense_search_l2_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
@@ -1928,9 +1895,7 @@ def dense_search_l2_bf16x3(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: 
 def dense_l2_sq8_error_constants():
     """(c_q, c_w, c_ad, c_ac, c_b, c_r, c_abs, max_r, max_e) of E_q as the certificate kernel was compiled with them
     (csrc/dense_search_l2_sq8.hip).  No GPU needed."""
-    c = (C.c_double * 9)()
-    _lib.load().rc_dense_l2_sq8_error_constants(c)
-    return tuple(float(v) for v in c)
+    return _error_constants("dense_l2_sq8", 9)
 
 
 def dense_l2_sq8_error_bound(D: int, alpha, w1, b1, qnorm, c1, xmax):
@@ -1965,16 +1930,8 @@ def dense_sq8_row_sqnorms(x8: torch.Tensor, dec: torch.Tensor, rows_per_step: in
             _lib.check(lib.rc_dense_sq8_row_sqnorms(h, _p(x8), x8.stride(0), N, D, _p(dec), _p(out), s),
                        "rc_dense_sq8_row_sqnorms", h)
         return out
-    step, mid = dec[0].double(), dec[1].double()
     for r0 in range(0, N, rows_per_step):
-        p = x8[r0:r0 + rows_per_step].double() * step               # exact: 8 + 24 significant bits
-        s = p + mid
-        bb = s - p
-        e = (p - (s - bb)) + (mid - bb)                             # TwoSum: p + mid = s + e exactly
-        odd = torch.where(e > 0, torch.nextafter(s, torch.full_like(s, float("inf"))),
-                          torch.nextafter(s, torch.full_like(s, float("-inf"))))
-        s = torch.where((e != 0) & ((s.view(torch.int64) & 1) == 0), odd, s)       # inexact and even: the odd neighbour
-        out[r0:r0 + rows_per_step] = s.float().double().square_().sum(1)
+        out[r0:r0 + rows_per_step] = _sq8_decode_cpu(x8[r0:r0 + rows_per_step], dec).double().square_().sum(1)
     return out
 
 
@@ -1986,22 +1943,7 @@ def dense_search_l2_sq8_exact(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tens
 def dense_l2_sq8_scores(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, xsq: Optional[torch.Tensor] = None) -> torch.Tensor:
     """The raw screen values sigma [nq, N] = fmaf(2, s~(q, n), -xsq[n]) of the int8 L2 search (rc_dense_l2_sq8_scores): a test
     hook, never a result."""
-    x8, q = _dense_sq8_args(x8, q, 1)
-    dec = _dense_sq8_dec(x8, dec)
-    lib, h, s, _ = _ctx(q)
-    if xsq is None:
-        xsq = dense_sq8_row_sqnorms(x8, dec)
-    _need_cuda(xsq)
-    xsq = xsq.to(torch.float32).contiguous()
-    if xsq.shape != (x8.shape[0],):
-        raise ValueError("dense_l2_sq8_scores: xsq must hold one squared norm per row, [N]")
-    out = torch.empty((q.shape[0], x8.shape[0]), dtype=torch.float32, device=q.device)
-    if out.numel():
-        wsb = lib.rc_dense_l2_sq8_scores_ws_bytes(x8.shape[1], q.shape[0])
-        ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-        _lib.check(lib.rc_dense_l2_sq8_scores(h, _p(x8), x8.stride(0), x8.shape[0], x8.shape[1], _p(q), q.shape[0], _p(dec),
-                                              _p(xsq), _p(out), _p(ws), wsb, s), "rc_dense_l2_sq8_scores", h)
-    return out
+    return _dense_scores(_DENSE_L2_SQ8, "dense_l2_sq8_scores", x8, q, dec, xsq)
 
 
 def dense_search_l2_sq8(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
@@ -2017,15 +1959,6 @@ def dense_search_l2_sq8(x8: torch.Tensor, dec: torch.Tensor, q: torch.Tensor, k:
     `dense_search_l2_sq8_exact`; `.stats` of the `PendingSearch`).  xsq: device fp32 [N], the squared norms of the decoded rows
     (`dense_sq8_row_sqnorms`); cstat: device fp32 [2] (`dense_sq8_cstat`); both computed here when None, and neither is read up
     to DENSE_EXACT_MAX_N rows.  stats and everything else as `dense_search_sq8`."""
-    if x8.dim() == 2 and dec.shape != (2, x8.shape[1]):
-        raise ValueError("dense_search_l2_sq8: dec must be [2, D]: the steps, then the mids")
-    x8, _ = _dense_sq8_args(x8, q, k)
-    dec = _dense_sq8_dec(x8, dec)
-    if cstat is None:
-        cstat = dense_sq8_cstat(x8, dec) if x8.shape[0] > DENSE_EXACT_MAX_N else torch.zeros((2,), device=x8.device)
-    _need_cuda(cstat)
-    if cstat.shape != (2,):
-        raise ValueError("dense_search_l2_sq8: cstat must be [2]: C1 and X (dense_sq8_cstat)")
-    cstat = cstat.to(x8.device, torch.float32).contiguous()
+    x8, dec, cstat = _dense_sq8_front("dense_search_l2_sq8", x8, dec, q, k, cstat)
     return _dense_search_l2(_DENSE_L2_SQ8, x8, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, None, dec, cstat,
                             stats)
