@@ -828,20 +828,27 @@ int rc_ivf_search(rc_handle_t h, const uint8_t* codes, const int64_t* list_off, 
  *   rc_dense_l2_search_exact and their f16 forms): one fp32 accumulator from +0.0f, d ascending, values widened to fp32; inner
  *   product s = fmaf(q[d], x[n][d], s); L2 t = q[d] - x[n][d], s = fmaf(t, t, s).
  * Output scores / ids [nq, k]: inner product: score descending; L2: distance ascending; ties by the lower CORPUS id (ids[row],
- *   not the row); (-inf, -1) / (+inf, -1) when the probed cells hold fewer than k rows; a zero L2 distance is +0.0f, an
- *   overflowed one +inf ahead of the padding.  Probing every cell gives exactly what the flat search gives over the same vectors.
+ *   not the row); (-inf, -1) / (+inf, -1) when the probed cells hold fewer than k rows; a zero L2 distance is +0.0f.  A score
+ *   that overflows to +-inf from finite inputs is ordered as the number it is, ties by the lower corpus id, and every row of the
+ *   probed cells comes ahead of the padding: L2 (+inf, id) after the finite distances and before (+inf, -1); inner product
+ *   (+inf, id) first and (-inf, id) after the finite scores, before (-inf, -1).  More than 16384 such rows at the k-th score are
+ *   a tie group like any other (status bit 1).  NaN scores (inf - inf inside a chain, NaN inputs) are outside the contract.
+ *   Probing every cell gives exactly what the flat search gives over the same vectors.
  * The scan is list-centric: the plan (cells, the queries of every cell, tasks of up to 8 queries of one cell) is made on the
  *   device from `probes` and `list_off`, a cell's rows are read once per task, every pair's score goes to the query's dense
- *   score row (stride floats per query, stride >= the largest number of rows nprobe cells can hold), then the exact k-th
- *   largest score per query, the keys at or above it and the select of the other searches.  No sampling, no slack.
+ *   score row (stride floats per query; ANY stride >= the rows the probed cells of every query of the call hold is valid, odd
+ *   or far larger included — the largest number of rows nprobe cells can hold, rounded up to a multiple of 4, is merely what
+ *   IVFFlatIndex passes; the result does not depend on it), then the exact k-th largest score per query, the keys at or above
+ *   it and the select of the other searches.  No sampling, no slack.
  * status (one device int, zeroed by the caller) / qstatus [nq] (zeroed by the caller, may be NULL): bit 1 (value 2) = more than
  *   16384 probed rows tie at the query's k-th score, its output is not valid (answer it by an exact search over its probed
  *   rows); the other queries' results stand.  status bit 2 (value 4) = a caller's error the device found: a probe outside
  *   [0, nlist) or more probed rows than `stride`; nothing is written out of bounds, the results are not valid.
  * Limits: 1 <= k <= 8192, N < 2^32, nlist <= 16384, metric in {0, 1} (else RC_ESHAPE); any D >= 1, ldx >= D; probed rows per
- *   query < 2^31; finite inputs; one device.  Rows are read with 16-byte loads when x is 16-byte aligned and D and ldx are
- *   multiples of 16 bytes, element by element otherwise — the same arithmetic.  Null or non-positive arguments (nprobe >
- *   nlist, ldx < D included) are RC_EINVAL; nq == 0 returns RC_OK and touches nothing.
+ *   query < 2^31; finite inputs (rows, queries, dec, coarse: the scores they overflow to are served, see above); one device.
+ *   Rows are read with 16-byte loads when x is 16-byte aligned and D and ldx are multiples of 16 bytes, element by element
+ *   otherwise — the same arithmetic.  Null or non-positive arguments (nprobe > nlist, ldx < D included) are RC_EINVAL;
+ *   nq == 0 returns RC_OK and touches nothing.
  * Runs on `stream`; no host synchronisation, no atomics on values, results bit-identical from run to run.
  * ws: rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, stride), a multiple of 256 (8 bytes per probed row and 128 KiB of keys per
  *   query, plus the plan); 0 for nq <= 0, nprobe <= 0, nprobe > nlist or stride <= 0.  RC_EWORKSPACE for a short one. */
