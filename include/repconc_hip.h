@@ -608,6 +608,51 @@ int rc_dense_l2_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_
                            const float* xsq, float* out, rc_stream_t stream);
 void rc_dense_l2_f16_error_constants(double* c);
 
+/* ------------------------------------------------------------------ dense flat search over a subset of the rows
+ * The four searches above (fp32 and fp16 storage, inner product and L2) over the rows `rows` of the store, in place: no copy of
+ * the rows is made and the cost follows ns, not N.  rows: DEVICE int64 [ns], corpus rows in ASCENDING order, no row twice,
+ * every one in [0, N).  THE LIBRARY DOES NOT VERIFY THIS: rows is never read on the host, and a row outside [0, N) is a read
+ * outside x (the Python wrapper checks the list unless told not to, ops.dense_search(rows=..., check_rows=True)).
+ * Result: exactly what the entry of the same name without _rows returns over the matrix x[rows] (and xsq[rows]) of ns rows,
+ * with every id i replaced by id_offset + rows[i] — ids and score / distance bits, the padding (-inf or +inf, -1) past ns
+ * included; among equal scores the lower corpus row comes first because rows ascends.  Everything that follows the row count
+ * follows ns: rc_dense*_search_rows_q takes the exact route for ns <= 131072, the sample is min(ns, 32768) rows of the subset,
+ * and the workspace is that of the entry without _rows called with ns: rc_dense*_search_ws_bytes(ns, D, nq, k),
+ * rc_dense*_search_exact_ws_bytes(ns, D, nq, k).  status / qstatus, sel_slack and the certificate as there; xnorm_max bounds the
+ * row norms of ALL of x (a bound over a superset of the subset) and xsq is the [N] array of the whole store, read at rows[i].
+ * Arguments: those of the entry without _rows with `rows, ns` inserted after the side operands (xsq, xnorm_max) and before the
+ * scalars (k, ...): h, x, ldx, N, D, q, nq, [xsq], [xnorm_max], rows, ns, k, id_offset, ...
+ * Checks, in this order: the shapes (N < 2^32 and k <= 8192 else RC_ESHAPE; 1 <= ns <= N and the other limits else RC_EINVAL),
+ * the pointers (rows NULL is RC_EINVAL), nq == 0 (RC_OK, nothing enqueued), the workspace (RC_EWORKSPACE), then device work.
+ * The bf16x3 screens and the int8 stores have no such entry. */
+int rc_dense_search_rows_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                           const int64_t* rows, int64_t ns, int k, int64_t id_offset, double sel_slack, float* scores,
+                           int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_search_rows_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                               const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
+                               size_t ws_bytes, rc_stream_t stream);
+int rc_dense_f16_search_rows_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                               const float* xnorm_max, const int64_t* rows, int64_t ns, int k, int64_t id_offset,
+                               double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, void* ws,
+                               size_t ws_bytes, rc_stream_t stream);
+int rc_dense_f16_search_rows_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                                   const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* scores, int64_t* ids,
+                                   void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_l2_search_rows_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                              const float* xsq, const float* xnorm_max, const int64_t* rows, int64_t ns, int k,
+                              int64_t id_offset, double sel_slack, float* dist, int64_t* ids, int* status, int* qstatus,
+                              void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_l2_search_rows_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                  const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* dist, int64_t* ids, void* ws,
+                                  size_t ws_bytes, rc_stream_t stream);
+int rc_dense_l2_f16_search_rows_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                                  const float* xsq, const float* xnorm_max, const int64_t* rows, int64_t ns, int k,
+                                  int64_t id_offset, double sel_slack, float* dist, int64_t* ids, int* status, int* qstatus,
+                                  void* ws, size_t ws_bytes, rc_stream_t stream);
+int rc_dense_l2_f16_search_rows_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
+                                      const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* dist, int64_t* ids,
+                                      void* ws, size_t ws_bytes, rc_stream_t stream);
+
 /* ------------------------------------------------------------------ dense flat search, L2 metric, fp32 corpus, bf16x3 screen
  * rc_dense_l2_search_q with the screen on the bf16 matrix cores: the corpus stays fp32 and ids AND distance bits are those of
  * rc_dense_l2_search_q (the chain t = q[j] - x[n][j], acc = fmaf(t, t, acc); distance asc, row asc; +0.0f for a zero;

@@ -157,6 +157,18 @@ PROTOTYPES = {
     "rc_dense_l2_f16_search_exact": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_l2_f16_scores": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp]),
     "rc_dense_l2_f16_error_constants": (None, [C.POINTER(_d)]),
+    # the subset searches: `rows, ns` after the side operands, before the scalars
+    "rc_dense_search_rows_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_search_rows_exact": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_f16_search_rows_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _i64, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp,
+                                        _sz, _vp]),
+    "rc_dense_f16_search_rows_exact": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_l2_search_rows_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _i64, _d, _vp, _vp, _vp, _vp,
+                                       _vp, _sz, _vp]),
+    "rc_dense_l2_search_rows_exact": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
+    "rc_dense_l2_f16_search_rows_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _vp, _i64, _i, _i64, _d, _vp, _vp, _vp,
+                                           _vp, _vp, _sz, _vp]),
+    "rc_dense_l2_f16_search_rows_exact": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _i64, _i, _i64, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_l2_bf16x3_search_ws_bytes": (_sz, [_i64, _i, _i, _i]),
     "rc_dense_l2_bf16x3_search_q": (_i, [_vp, _vp, _i64, _i64, _i, _vp, _i, _vp, _vp, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "rc_dense_l2_bf16x3_scores_ws_bytes": (_sz, [_i, _i]),

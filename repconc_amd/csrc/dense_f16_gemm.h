@@ -15,13 +15,16 @@ typedef _Float16 dense_f16x8 __attribute__((ext_vector_type(8)));
 // profiles/dense_f16_form_ab.txt.)
 // L2: the epilogue emits sigma = fmaf(2, dot, -xsq[row]), xsq [N] = the stored fp32 squared norm of every corpus row (a lane
 // holds one corpus row per column tile: four values, loaded once per block).  !L2: xsq is unused.
-template <int MODE, bool PAD, bool L2 = false>
+// MAP (subset search): x is read through rows [N] as dense_gemm_body reads it, four rows[] loads per thread at block start
+// and the four of dense_screen_load_nxs; !MAP never reads rows.
+template <int MODE, bool PAD, bool L2 = false, bool MAP = false>
 __global__ __launch_bounds__(256, 2) void dense_f16_gemm_kernel(const _Float16* __restrict__ x, int64_t ldx, int64_t N,
                                                              int64_t nrows, int64_t smap, const _Float16* __restrict__ q,
                                                              int nq, int D, const float* __restrict__ thr,
                                                              float* __restrict__ out, unsigned* __restrict__ cnt,
                                                              unsigned long long* __restrict__ cand,
-                                                             const float* __restrict__ xsq) {
+                                                             const float* __restrict__ xsq,
+                                                             const int64_t* __restrict__ rows) {
     constexpr int TM = 16, NT = 4, KS = 32;
     __shared__ __attribute__((aligned(16))) unsigned char dense_f16_smem[DENSE_SCREEN_LDS_BYTES];
     unsigned char* sa = dense_f16_smem;                                     // [2][128 rows][128 bytes] queries
@@ -37,12 +40,11 @@ __global__ __launch_bounds__(256, 2) void dense_f16_gemm_kernel(const _Float16* 
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int64_t jl = (j0 + lrow + 32 * i < nrows) ? j0 + lrow + 32 * i : nrows - 1;
-        const int64_t xrow = smap ? (int64_t)((uint64_t)jl * (uint64_t)N / (uint64_t)smap) : jl;
-        xp[i] = x + xrow * ldx;
+        xp[i] = x + dense_corpus_row<MAP>(jl, N, smap, rows) * ldx;
         so[i] = dense_screen_lds_off(lrow + 32 * i, lc);
     }
     float nxs[4] = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (L2) dense_screen_load_nxs(xsq, j0, wc, col, N, nrows, smap, nxs);
+    if constexpr (L2) dense_screen_load_nxs<MAP>(xsq, j0, wc, col, N, nrows, smap, nxs, rows);
     const int nkc = (D + DENSE_F16_KC - 1) / DENSE_F16_KC;
     for (int qt = 0; qt < nq; qt += DENSE_TILE) {
         const _Float16* qp[4];
@@ -122,18 +124,18 @@ static bool dense_f16_aligned(const void* x, int64_t ldx, const void* q, int D) 
     return D % 8 == 0 && ldx % 8 == 0 && !((uintptr_t)x & 15u) && !((uintptr_t)q & 15u);
 }
 
-// xsq leads as in a variant's launch_gemm; it is read only if L2
-template <int MODE, bool L2>
+// xsq leads as in a variant's launch_gemm; it is read only if L2.  MAP: a template argument, as in dense_launch_gemm
+template <int MODE, bool L2, bool MAP = false>
 static int dense_f16_launch_gemm(const float* xsq, rc_handle_t h, const _Float16* x, int64_t ldx, int64_t N, int64_t nrows,
                                  int64_t smap, const _Float16* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                                 unsigned long long* cand, hipStream_t s) {
+                                 unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (dense_f16_aligned(x, ldx, q, D))
-        hipLaunchKernelGGL((dense_f16_gemm_kernel<MODE, false, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand, xsq);
+        hipLaunchKernelGGL((dense_f16_gemm_kernel<MODE, false, L2, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D,
+                           thr, out, cnt, cand, xsq, rows);
     else
-        hipLaunchKernelGGL((dense_f16_gemm_kernel<MODE, true, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand, xsq);
+        hipLaunchKernelGGL((dense_f16_gemm_kernel<MODE, true, L2, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D,
+                           thr, out, cnt, cand, xsq, rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }

@@ -32,6 +32,15 @@ __device__ __forceinline__ void dense_load8(const _Float16* p, float* r) {
     for (int i = 0; i < 8; ++i) r[i] = (float)v[i];
 }
 
+// The corpus row behind logical row j of a launch: row j N / smap of the strided sample (smap != 0), j otherwise; MAP (subset
+// search): that row of the virtual matrix x[rows], rows [N] ascending.  One rows[] load: call it at block start, never in a K loop.
+template <bool MAP>
+__device__ __forceinline__ int64_t dense_corpus_row(int64_t j, int64_t N, int64_t smap, const int64_t* __restrict__ rows) {
+    const int64_t r = smap ? (int64_t)((uint64_t)j * (uint64_t)N / (uint64_t)smap) : j;
+    if constexpr (MAP) return rows[r];
+    else return r;
+}
+
 // The epilogue of one accumulator element, shared by every screen kernel: score s of query qi and logical row j (jv: j is a
 // row).  STORE: out[qi][j] = s.  FILTER: the key of every s >= thr joins qi's candidate list; the GW consecutive lanes that
 // hold one query (32 for the 32x32 result layout, 16 for the 16x16 one) ballot and their first survivor takes the slots with
@@ -63,11 +72,14 @@ __device__ __forceinline__ void dense_emit(float s, int64_t j, bool jv, int qi, 
 // The body of dense_gemm_kernel, and of the L2 screen's kernel (dense_search_l2.hip), which is this GEMM with one more
 // operand and another epilogue: L2 emits sigma = fmaf(2, dot, -xsq[row]) instead of the dot, xsq [N] = the stored squared norm
 // of every corpus row (a lane holds one corpus row per column tile: two values, loaded once per block).  !L2: xsq is unused.
-template <int MODE, bool PAD, typename T, bool L2>
+// MAP (subset search): the matrix searched is x[rows], rows [N] ascending corpus rows; the row that the loader reads and the
+// norm of the L2 epilogue go through rows[] once per thread at block start, everything else (keys, out) keeps the logical j.
+template <int MODE, bool PAD, typename T, bool L2, bool MAP = false>
 __device__ __forceinline__ void dense_gemm_body(const T* __restrict__ x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
                                                 const T* __restrict__ q, int nq, int D, const float* __restrict__ thr,
                                                 float* __restrict__ out, unsigned* __restrict__ cnt,
-                                                unsigned long long* __restrict__ cand, const float* __restrict__ xsq) {
+                                                unsigned long long* __restrict__ cand, const float* __restrict__ xsq,
+                                                const int64_t* __restrict__ rows = nullptr) {
     __shared__ float sa[2][DENSE_TILE * DENSE_LD];     // query chunk   [128][16 (+1)]
     __shared__ float sb[2][DENSE_TILE * DENSE_LD];     // corpus chunk  [128][16 (+1)]
     __shared__ float s_thr[DENSE_TILE];
@@ -78,8 +90,7 @@ __device__ __forceinline__ void dense_gemm_body(const T* __restrict__ x, int64_t
     // loader mapping: thread -> (row = tid / 2, 8 consecutive k = (tid & 1) * 8)
     const int lrow = tid >> 1, lk = (tid & 1) * 8;
     const int64_t jl = (j0 + lrow < nrows) ? j0 + lrow : nrows - 1;
-    const int64_t xrow = smap ? (int64_t)((uint64_t)jl * (uint64_t)N / (uint64_t)smap) : jl;
-    const T* xp = x + xrow * ldx;
+    const T* xp = x + dense_corpus_row<MAP>(jl, N, smap, rows) * ldx;
     const int nkc = (D + DENSE_KC - 1) / DENSE_KC;
     float nxs[2] = {0.f, 0.f};                         // L2: minus the squared norm of this lane's row of column tile b
     if constexpr (L2) {
@@ -87,7 +98,7 @@ __device__ __forceinline__ void dense_gemm_body(const T* __restrict__ x, int64_t
         for (int b = 0; b < 2; ++b) {
             const int64_t j = j0 + wc * 64 + b * 32 + col;
             const int64_t jc = j < nrows ? j : nrows - 1;
-            nxs[b] = -xsq[smap ? (int64_t)((uint64_t)jc * (uint64_t)N / (uint64_t)smap) : jc];
+            nxs[b] = -xsq[dense_corpus_row<MAP>(jc, N, smap, rows)];
         }
     }
     for (int qt = 0; qt < nq; qt += DENSE_TILE) {
@@ -170,26 +181,28 @@ __device__ __forceinline__ void dense_gemm_body(const T* __restrict__ x, int64_t
 
 // grid: ceil(nrows / 128) blocks of 256 threads.  Logical row j in [0, nrows) is corpus row (smap ? j N / smap : j).
 // x: [N, ldx] (16-byte aligned rows unless PAD), q: [nq, D] contiguous.  STORE: out [nq][nrows].  FILTER: thr [nq],
-// cnt [nq] (zeroed), cand [nq][ADC_CAND_CAP].
-template <int MODE, bool PAD, typename T>
+// cnt [nq] (zeroed), cand [nq][ADC_CAND_CAP].  MAP: rows [N], x is indexed through it (dense_gemm_body); !MAP never reads rows.
+template <int MODE, bool PAD, typename T, bool MAP = false>
 __global__ __launch_bounds__(256) void dense_gemm_kernel(const T* __restrict__ x, int64_t ldx, int64_t N, int64_t nrows,
                                                          int64_t smap, const T* __restrict__ q, int nq, int D,
                                                          const float* __restrict__ thr, float* __restrict__ out,
-                                                         unsigned* __restrict__ cnt, unsigned long long* __restrict__ cand) {
-    dense_gemm_body<MODE, PAD, T, false>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, nullptr);
+                                                         unsigned* __restrict__ cnt, unsigned long long* __restrict__ cand,
+                                                         const int64_t* __restrict__ rows) {
+    dense_gemm_body<MODE, PAD, T, false, MAP>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, nullptr, rows);
 }
 
-template <int MODE, typename T>
+// MAP is a template argument and not `rows != nullptr`: a unit that never searches a subset instantiates no mapped kernel
+template <int MODE, typename T, bool MAP = false>
 static int dense_launch_gemm(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
                              const T* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                             unsigned long long* cand, hipStream_t s) {
+                             unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (D % DENSE_KC == 0)
-        hipLaunchKernelGGL((dense_gemm_kernel<MODE, false, T>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand);
+        hipLaunchKernelGGL((dense_gemm_kernel<MODE, false, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
+                           out, cnt, cand, rows);
     else
-        hipLaunchKernelGGL((dense_gemm_kernel<MODE, true, T>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand);
+        hipLaunchKernelGGL((dense_gemm_kernel<MODE, true, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
+                           out, cnt, cand, rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }

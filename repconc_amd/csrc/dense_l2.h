@@ -15,7 +15,8 @@
 // T: the storage type of x and q, widened to fp32 on load (exact); the LDS tiles, the arithmetic and the order are the same.
 // !PAD: 16-byte aligned rows, read with vector loads — fp32: D % 16 == 0 (dense_check); fp16: D % 8 == 0, ldx % 8 == 0, a
 // vector is inside or outside the row and the part of the last K chunk past D is zero.  PAD reads element by element and pads
-// K with zeros.
+// K with zeros.  MAP (subset search): the matrix is x[rows], rows [N] ascending corpus rows: one rows[] load per thread at block
+// start for the row's address; the output column stays the logical row.  !MAP never reads rows.
 // (-O3 pairs the 32 independent subtractions and fmas of a k step into v_pk_add_f32 / v_pk_fma_f32: two IEEE operations per
 // instruction with the roundings of the plain forms.  Forcing v_sub_f32 + v_fmac_f32 one by one was measured slower)
 #define DENSE_L2_QT 64
@@ -39,17 +40,17 @@ __device__ __forceinline__ void dense_l2_load_q(const _Float16* p, int k, int D,
     for (int i = 0; i < 4; ++i) r[i] = (float)v[i];
 }
 
-template <bool PAD, typename T>
+template <bool PAD, typename T, bool MAP = false>
 __global__ __launch_bounds__(256, 2) void dense_l2_exact_kernel(const T* __restrict__ x, int64_t ldx, int64_t N,
                                                                 const T* __restrict__ q, int nq, int D,
-                                                                float* __restrict__ out) {
+                                                                float* __restrict__ out, const int64_t* __restrict__ rows) {
     __shared__ __attribute__((aligned(16))) float sx[2][DENSE_KC * DENSE_L2_XLD];
     __shared__ __attribute__((aligned(16))) float sq[2][DENSE_KC * DENSE_L2_QLD];
     const int tid = threadIdx.x, tx = tid & 31, ty = tid >> 5;
     const int64_t j0 = (int64_t)blockIdx.x * DENSE_TILE;
     // loader mapping: corpus thread -> (row tid / 2, 8 consecutive k), query thread -> (row tid / 4, 4 consecutive k)
     const int xr = tid >> 1, xk = (tid & 1) * 8, qr = tid >> 2, qk = (tid & 3) * 4;
-    const T* xp = x + ((j0 + xr < N) ? j0 + xr : N - 1) * ldx;
+    const T* xp = x + dense_corpus_row<MAP>((j0 + xr < N) ? j0 + xr : N - 1, N, 0, rows) * ldx;
     const int nkc = (D + DENSE_KC - 1) / DENSE_KC;
     for (int qt = 0; qt < nq; qt += DENSE_L2_QT) {
         const T* qp = q + (int64_t)((qt + qr < nq) ? qt + qr : nq - 1) * D;
@@ -124,16 +125,16 @@ __global__ __launch_bounds__(256, 2) void dense_l2_exact_kernel(const T* __restr
     }
 }
 
-template <typename T>
+template <typename T, bool MAP = false>
 static int dense_l2_launch_exact_rows(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, float* out,
-                                      hipStream_t s) {
+                                      hipStream_t s, const int64_t* rows = nullptr) {
     const dim3 grid((unsigned)((N + DENSE_TILE - 1) / DENSE_TILE));
     const bool vec = sizeof(T) == 4 ? D % DENSE_KC == 0
                                     : D % 8 == 0 && ldx % 8 == 0 && !((uintptr_t)x & 15u) && !((uintptr_t)q & 15u);
     if (vec)
-        hipLaunchKernelGGL((dense_l2_exact_kernel<false, T>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out);
+        hipLaunchKernelGGL((dense_l2_exact_kernel<false, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out, rows);
     else
-        hipLaunchKernelGGL((dense_l2_exact_kernel<true, T>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out);
+        hipLaunchKernelGGL((dense_l2_exact_kernel<true, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out, rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }

@@ -60,14 +60,17 @@ __device__ __forceinline__ const float* dense_screen_stage_thr(unsigned char* sa
 }
 
 // this lane's side operand of the L2 epilogue: nxs[b] = minus the stored squared norm of its corpus row of column tile b,
-// read at the mapped corpus row of the strided sample (smap != 0) as the screen's loader reads the row itself; once per block
+// read at the mapped corpus row of the strided sample (smap != 0) as the screen's loader reads the row itself; once per block.
+// MAP (subset search): at rows[that row], the norm of the corpus row the loader reads (dense_corpus_row)
+template <bool MAP = false>
 __device__ __forceinline__ void dense_screen_load_nxs(const float* __restrict__ xsq, int64_t j0, int wc, int col, int64_t N,
-                                                      int64_t nrows, int64_t smap, float (&nxs)[4]) {
+                                                      int64_t nrows, int64_t smap, float (&nxs)[4],
+                                                      const int64_t* __restrict__ rows = nullptr) {
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         const int64_t j = j0 + wc * 64 + b * 16 + col;
         const int64_t jc = j < nrows ? j : nrows - 1;
-        nxs[b] = -xsq[smap ? (int64_t)((uint64_t)jc * (uint64_t)N / (uint64_t)smap) : jc];
+        nxs[b] = -xsq[dense_corpus_row<MAP>(jc, N, smap, rows)];
     }
 }
 
@@ -111,11 +114,13 @@ __device__ __forceinline__ float dense_chain_step(float q, float x, float s) {
 
 // grid: (nq, ADC_CAND_CAP / 256) blocks of 256 threads; one lane per candidate key of query blockIdx.x.  The key's score half
 // (the screen's s~) is replaced by the chain: dense_chain_step<L2>, d ascending, one accumulator, over the values widened to
-// fp32 (exact); L2: by -d.  VEC: 16-byte aligned rows.
-template <bool VEC, typename T, bool L2>
+// fp32 (exact); L2: by -d.  VEC: 16-byte aligned rows.  MAP (subset search): the key's row is a row of x[rows] and stays in
+// the key; the row that is read is rows[row], one load per lane.  !MAP never reads rows.
+template <bool VEC, typename T, bool L2, bool MAP = false>
 __global__ __launch_bounds__(256) void dense_rescore_kernel(const T* __restrict__ x, int64_t ldx, int D, const T* __restrict__ q,
                                                             const unsigned* __restrict__ cnt,
-                                                            unsigned long long* __restrict__ cand) {
+                                                            unsigned long long* __restrict__ cand,
+                                                            const int64_t* __restrict__ rows) {
     __shared__ float sq[DENSE_RESCORE_QCHUNK];
     const int qi = blockIdx.x, tid = threadIdx.x;
     const unsigned raw = cnt[qi];
@@ -125,7 +130,7 @@ __global__ __launch_bounds__(256) void dense_rescore_kernel(const T* __restrict_
     const bool mine = i < n;
     unsigned long long* kp = cand + (size_t)qi * ADC_CAND_CAP + i;
     const unsigned row = mine ? 0xFFFFFFFFu - (unsigned)(*kp & 0xFFFFFFFFull) : 0u;
-    const T* xp = x + (int64_t)row * ldx;
+    const T* xp = x + dense_corpus_row<MAP>((int64_t)row, 0, 0, rows) * ldx;
     const T* qp = q + (int64_t)qi * D;
     float s = 0.f;
     for (int d0 = 0; d0 < D; d0 += DENSE_RESCORE_QCHUNK) {
@@ -149,14 +154,14 @@ __global__ __launch_bounds__(256) void dense_rescore_kernel(const T* __restrict_
     if (mine) *kp = adc_exact_key(L2 ? -s : s, (int64_t)row);
 }
 
-template <bool L2, typename T>
+template <bool L2, bool MAP = false, typename T>
 static int dense_launch_rescore(rc_handle_t h, const T* x, int64_t ldx, int D, const T* q, int nq, const unsigned* cnt,
-                                unsigned long long* cand, hipStream_t s) {
+                                unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
     const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
     if (ldx % (16 / (int)sizeof(T)) == 0 && !((uintptr_t)x & 15u))
-        hipLaunchKernelGGL((dense_rescore_kernel<true, T, L2>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
+        hipLaunchKernelGGL((dense_rescore_kernel<true, T, L2, MAP>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand, rows);
     else
-        hipLaunchKernelGGL((dense_rescore_kernel<false, T, L2>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand);
+        hipLaunchKernelGGL((dense_rescore_kernel<false, T, L2, MAP>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand, rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -221,6 +226,10 @@ __global__ __launch_bounds__(64) void dense_certify_kernel(const typename V::T* 
 //                                                         brings the rescorer and the certificate of its own:
 //     static int rescore(side, h, x, ldx, D, q, nq, cnt, cand, s)
 //     static int certify(side, h, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s)
+//   a variant that serves the subset search (the routes' MAP forms; fp32 and fp16 storage, both metrics) adds the mapped twins
+//     static int launch_gemm_rows<MODE>(rows, xsq, h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s)
+//     static int exact_rows_mapped(rows, h, x, ldx, N, D, q, nq, out, s)
+//   and the others instantiate nothing of it.
 struct dense_variant_defaults {
     static constexpr bool l2 = false;
     static constexpr bool coded = false;
@@ -253,32 +262,50 @@ static size_t dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
     return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total + V::extra_ws_bytes(nq, D);
 }
 
+// ---- subset search ------------------------------------------------------------------------------------------------------------
+// A search over the rows `rows` [ns] of the store (int64, ascending, unique, in [0, N): the caller's word, nothing here checks
+// it) is the unchanged route over the virtual matrix x' = x[rows] with N := ns (MAP = true below): the sample size, the rank of
+// the threshold, the exact-route limit and the workspace follow ns.  Four kernels form a row's address (dense_gemm_body, the
+// f16 screen, dense_l2_exact_kernel, dense_rescore_kernel) and read rows[] there, and the L2 screens read xsq at the same row;
+// the keys carry rows of x', so the order among equal scores (lower row of x' first) is the order of the corpus rows because
+// rows ascends.  The certificate's X bounds the norms of all of x, a superset of x'.  The select runs with id_offset 0 and
+// dense_map_ids_kernel (dense_search.hip) turns the nq x k rows of x' into id_offset + rows[.] after V::finish; -1 stays.
+int dense_launch_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* rows, int64_t id_offset, hipStream_t s);
+
 // the exact route: full score rows of L.qx queries at a time, then the radix select
-template <typename V>
+template <typename V, bool MAP = false>
 static int dense_exact(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
                        const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, char* w,
-                       const dense_exact_layout& L, hipStream_t s, typename dense_side<V>::type side = {}) {
+                       const dense_exact_layout& L, hipStream_t s, typename dense_side<V>::type side = {},
+                       const int64_t* rows = nullptr) {
     float* sc = (float*)(w + L.sc);             // (the select's status word is never set: exactly min(k, N) keys are collected)
     for (int q0 = 0; q0 < nq; q0 += L.qx) {
         const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
         int rc;
-        if constexpr (V::coded) rc = V::exact_rows(side, h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
+        if constexpr (MAP) rc = V::exact_rows_mapped(rows, h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
+        else if constexpr (V::coded) rc = V::exact_rows(side, h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
         else rc = V::exact_rows(h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
         if (rc != RC_OK) return rc;
-        rc = topk_exact_select(h, sc, N, nx, k, id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
+        rc = topk_exact_select(h, sc, N, nx, k, MAP ? 0 : id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
         if (rc != RC_OK) return rc;
     }
-    return V::finish(h, scores, (int64_t)nq * k, s);
+    const int frc = V::finish(h, scores, (int64_t)nq * k, s);
+    if constexpr (MAP) {
+        if (frc != RC_OK) return frc;
+        return dense_launch_map_ids(h, ids, (int64_t)nq * k, rows, id_offset, s);
+    }
+    return frc;
 }
 
-// checked arguments (dense_search_entry: dense_check, the extra pointers, nq > 0, a workspace of dense_search_ws_bytes<V>)
-template <typename V>
+// checked arguments (dense_search_entry: dense_check, the extra pointers, nq > 0, a workspace of dense_search_ws_bytes<V>).
+// MAP: N is ns, the number of rows selected, and rows [N] their corpus rows ("subset search" above)
+template <typename V, bool MAP = false>
 static int dense_search_route(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
                               const typename V::T* q, int nq, typename dense_side<V>::type xsq, const float* xnorm_max, int k,
                               int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, char* w,
-                              hipStream_t s) {
+                              hipStream_t s, const int64_t* rows = nullptr) {
     if (dense_exact_route(N))
-        return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s, xsq);
+        return dense_exact<V, MAP>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s, xsq, rows);
     const dense_fast_layout L = dense_fast_ws(N, nq);
     float* sample = (float*)(w + L.sample);
     float* thr = (float*)(w + L.thr);
@@ -289,19 +316,24 @@ static int dense_search_route(rc_handle_t h, const typename dense_storage<V>::ty
     if constexpr (V::coded) rc = V::prepass(xsq, h, q, nq, D, w + L.total, &qs, s);
     else rc = V::prepass(h, q, nq, D, w + L.total, &qs, s);
     if (rc != RC_OK) return rc;
-    rc = V::template launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
+    if constexpr (MAP)
+        rc = V::template launch_gemm_rows<DENSE_STORE>(rows, xsq, h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr,
+                                                       nullptr, s);
+    else rc = V::template launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
     if (rc != RC_OK) return rc;
     rc = rc_adc_launch_threshold(h, sample, L.S, nq, rc_adc_sample_rank(N, L.S, k, sel_slack), thr, s);
     if (rc != RC_OK) return rc;
     RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
-    rc = V::template launch_gemm<DENSE_FILTER>(xsq, h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
+    if constexpr (MAP)
+        rc = V::template launch_gemm_rows<DENSE_FILTER>(rows, xsq, h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
+    else rc = V::template launch_gemm<DENSE_FILTER>(xsq, h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
     if (rc != RC_OK) return rc;
     if constexpr (V::approximate) {
         if constexpr (V::coded) rc = V::rescore(xsq, h, x, ldx, D, q, nq, cnt, cand, s);
-        else rc = dense_launch_rescore<V::l2>(h, x, ldx, D, q, nq, cnt, cand, s);
+        else rc = dense_launch_rescore<V::l2, MAP>(h, x, ldx, D, q, nq, cnt, cand, s, rows);
         if (rc != RC_OK) return rc;
     }
-    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, id_offset, scores, ids, status, s, qstatus);
+    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, MAP ? 0 : id_offset, scores, ids, status, s, qstatus);
     if (rc != RC_OK) return rc;
     if constexpr (V::coded) {
         rc = V::certify(xsq, h, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s);
@@ -311,7 +343,12 @@ static int dense_search_route(rc_handle_t h, const typename dense_storage<V>::ty
                            status, qstatus);
         RC_LAUNCH_CHECK(h);
     }
-    return V::finish(h, scores, (int64_t)nq * k, s);
+    rc = V::finish(h, scores, (int64_t)nq * k, s);
+    if constexpr (MAP) {
+        if (rc != RC_OK) return rc;
+        rc = dense_launch_map_ids(h, ids, (int64_t)nq * k, rows, id_offset, s);
+    }
+    return rc;
 }
 
 // ---- the entries ------------------------------------------------------------------------------------------------------------
@@ -348,3 +385,40 @@ static int dense_search_entry(rc_handle_t h, const typename dense_storage<V>::ty
                                  (char*)ws, (hipStream_t)stream);
 }
 
+
+// The bodies of rc_dense*_search_rows_exact and rc_dense*_search_rows_q: the entries above over the rows `rows` [ns] of the
+// store.  Checks, in the ABI's order: the shapes (dense_check's, then 1 <= ns <= N), the pointers (rows among them), the
+// nq == 0 success, the workspace — sized by ns, the helpers of the unmapped entries called with ns — and only then device work.
+// rows is never read on the host: ascending, unique and in [0, N) is the caller's word.
+template <typename V>
+static int dense_exact_rows_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                                  const typename V::T* q, int nq, const int64_t* rows, int64_t ns, int k, int64_t id_offset,
+                                  float* scores, int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2) return RC_ESHAPE;
+    if (ns < 1 || ns > N) return RC_EINVAL;
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
+    if (crc != RC_OK) return crc;
+    if (!rows) return RC_EINVAL;
+    if (nq == 0) return RC_OK;
+    const dense_exact_layout L = dense_exact_ws(ns, nq);
+    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
+    return dense_exact<V, true>(h, x, ldx, ns, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream, {}, rows);
+}
+
+template <typename V>
+static int dense_search_rows_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                                   const typename V::T* q, int nq, const float* xsq, const float* xnorm_max,
+                                   const int64_t* rows, int64_t ns, int k, int64_t id_offset, double sel_slack, float* scores,
+                                   int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2) return RC_ESHAPE;
+    if (ns < 1 || ns > N) return RC_EINVAL;
+    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
+    if (crc != RC_OK) return crc;
+    if (!status || (V::l2 && !xsq) || (V::approximate && !xnorm_max) || !rows) return RC_EINVAL;
+    if (nq == 0) return RC_OK;
+    if (!ws || ((uintptr_t)ws & (V::ws_align - 1)) || ws_bytes < dense_search_ws_bytes<V>(ns, D, nq, k)) return RC_EWORKSPACE;
+    return dense_search_route<V, true>(h, x, ldx, ns, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, scores, ids, status,
+                                       qstatus, (char*)ws, (hipStream_t)stream, rows);
+}

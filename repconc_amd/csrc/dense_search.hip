@@ -24,6 +24,22 @@ int dense_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, 
     return dense_launch_gemm<DENSE_STORE, float>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
 }
 
+// ---- the id map of the subset searches (declared in dense_screen.h, shared by the four units that serve them) -----------------
+// ids [n]: the select's output over x[rows] with id_offset 0, a row of x[rows] or -1 -> id_offset + its corpus row, -1 stays
+__global__ __launch_bounds__(256) void dense_map_ids_kernel(int64_t* __restrict__ ids, int64_t n,
+                                                            const int64_t* __restrict__ rows, int64_t id_offset) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t id = ids[i];
+    if (id >= 0) ids[i] = id_offset + rows[id];
+}
+
+int dense_launch_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* rows, int64_t id_offset, hipStream_t s) {
+    hipLaunchKernelGGL(dense_map_ids_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, ids, n, rows, id_offset);
+    RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
 struct dense_f32_variant : dense_variant_defaults {
     typedef float T;
     typedef float Q;
@@ -31,6 +47,12 @@ struct dense_f32_variant : dense_variant_defaults {
     template <int MODE, typename... A>
     static int launch_gemm(const float*, A... a) { return dense_launch_gemm<MODE, float>(a...); }
     static constexpr auto* exact_rows = &dense_exact_rows_f32;
+    template <int MODE, typename... A>
+    static int launch_gemm_rows(const int64_t* rows, const float*, A... a) { return dense_launch_gemm<MODE, float, true>(a..., rows); }
+    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
+                                 float* out, hipStream_t s) {
+        return dense_launch_gemm<DENSE_STORE, T, true>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s, rows);
+    }
 };
 
 extern "C" size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
@@ -50,4 +72,18 @@ extern "C" int rc_dense_search_q(rc_handle_t h, const float* x, int64_t ldx, int
                                  void* ws, size_t ws_bytes, rc_stream_t stream) {
     return dense_search_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, nullptr, nullptr, k, id_offset, sel_slack, scores, ids,
                                                  status, qstatus, ws, ws_bytes, stream);
+}
+
+extern "C" int rc_dense_search_rows_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                          const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* scores, int64_t* ids,
+                                          void* ws, size_t ws_bytes, rc_stream_t stream) {
+    return dense_exact_rows_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, rows, ns, k, id_offset, scores, ids, ws, ws_bytes,
+                                                     stream);
+}
+
+extern "C" int rc_dense_search_rows_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                      const int64_t* rows, int64_t ns, int k, int64_t id_offset, double sel_slack, float* scores,
+                                      int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    return dense_search_rows_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, nullptr, nullptr, rows, ns, k, id_offset, sel_slack,
+                                                      scores, ids, status, qstatus, ws, ws_bytes, stream);
 }

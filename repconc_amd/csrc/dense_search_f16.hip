@@ -23,6 +23,12 @@ struct dense_f16_variant : dense_variant_defaults {
     static int exact_rows(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, float* out, hipStream_t s) {
         return dense_launch_gemm<DENSE_STORE, T>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
     }
+    template <int MODE, typename... A>
+    static int launch_gemm_rows(const int64_t* rows, A... a) { return dense_f16_launch_gemm<MODE, false, true>(a..., rows); }
+    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
+                                 float* out, hipStream_t s) {
+        return dense_launch_gemm<DENSE_STORE, T, true>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s, rows);
+    }
     __device__ static bool refuse(float, int) { return false; }
     __device__ static double eq(int D, double ss, double xnorm) {
         const double up = 1.0 + 0x1p-30;
@@ -65,4 +71,21 @@ extern "C" int rc_dense_f16_search_q(rc_handle_t h, const uint16_t* x, int64_t l
     return dense_search_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
                                                  reinterpret_cast<const _Float16*>(q), nq, nullptr, xnorm_max, k, id_offset,
                                                  sel_slack, scores, ids, status, qstatus, ws, ws_bytes, stream);
+}
+
+extern "C" int rc_dense_f16_search_rows_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
+                                              int nq, const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* scores,
+                                              int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    return dense_exact_rows_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
+                                                     reinterpret_cast<const _Float16*>(q), nq, rows, ns, k, id_offset, scores, ids,
+                                                     ws, ws_bytes, stream);
+}
+
+extern "C" int rc_dense_f16_search_rows_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
+                                          int nq, const float* xnorm_max, const int64_t* rows, int64_t ns, int k, int64_t id_offset,
+                                          double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, void* ws,
+                                          size_t ws_bytes, rc_stream_t stream) {
+    return dense_search_rows_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
+                                                      reinterpret_cast<const _Float16*>(q), nq, nullptr, xnorm_max, rows, ns, k,
+                                                      id_offset, sel_slack, scores, ids, status, qstatus, ws, ws_bytes, stream);
 }

@@ -51,27 +51,28 @@
 #define DENSE_L2_MAX_R 0x1p126                           // (||q|| + X)^2 below this: nothing overflows
 
 // ---- screen: the fp32 GEMM with the L2 epilogue ------------------------------------------------------------------------------
-// grid and arguments as dense_gemm_kernel, plus xsq [N].
-template <int MODE, bool PAD>
+// grid and arguments as dense_gemm_kernel, plus xsq [N] (MAP: read at the corpus row, as x is).
+template <int MODE, bool PAD, bool MAP = false>
 __global__ __launch_bounds__(256) void dense_l2_gemm_kernel(const float* __restrict__ x, int64_t ldx, int64_t N, int64_t nrows,
                                                             int64_t smap, const float* __restrict__ q, int nq, int D,
                                                             const float* __restrict__ thr, float* __restrict__ out,
                                                             unsigned* __restrict__ cnt, unsigned long long* __restrict__ cand,
-                                                            const float* __restrict__ xsq) {
-    dense_gemm_body<MODE, PAD, float, true>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, xsq);
+                                                            const float* __restrict__ xsq,
+                                                            const int64_t* __restrict__ rows) {
+    dense_gemm_body<MODE, PAD, float, true, MAP>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, xsq, rows);
 }
 
-template <int MODE>
+template <int MODE, bool MAP = false>
 static int dense_l2_launch_gemm(const float* xsq, rc_handle_t h, const float* x, int64_t ldx, int64_t N, int64_t nrows,
                                 int64_t smap, const float* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                                unsigned long long* cand, hipStream_t s) {
+                                unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (D % DENSE_KC == 0)
-        hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, false>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr, out,
-                           cnt, cand, xsq);
+        hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, false, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
+                           out, cnt, cand, xsq, rows);
     else
-        hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, true>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr, out,
-                           cnt, cand, xsq);
+        hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, true, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
+                           out, cnt, cand, xsq, rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -103,7 +104,13 @@ struct dense_l2_variant : dense_variant_defaults {
     static constexpr bool l2 = true;
     template <int MODE, typename... A>
     static int launch_gemm(A... a) { return dense_l2_launch_gemm<MODE>(a...); }
-    static constexpr auto* exact_rows = &dense_l2_launch_exact_rows<float>;
+    static constexpr auto* exact_rows = &dense_l2_exact_rows_f32;
+    template <int MODE, typename... A>
+    static int launch_gemm_rows(const int64_t* rows, A... a) { return dense_l2_launch_gemm<MODE, true>(a..., rows); }
+    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
+                                 float* out, hipStream_t s) {
+        return dense_l2_launch_exact_rows<T, true>(h, x, ldx, N, D, q, nq, out, s, rows);
+    }
     static constexpr auto* finish = &dense_l2_launch_negate;
     __device__ static bool refuse(float v, int D) { return !(v - v == 0.f) || D > DENSE_L2_MAX_D; }
     // E_q - ss_down: what is added to thr~ (header).  +inf (never certified) unless (||q|| + X)^2 < 2^126.
@@ -153,4 +160,18 @@ extern "C" int rc_dense_l2_scores(rc_handle_t h, const float* x, int64_t ldx, in
     if (nq == 0) return RC_OK;
     return dense_l2_launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr,
                                              (hipStream_t)stream);
+}
+
+extern "C" int rc_dense_l2_search_rows_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                             const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* dist, int64_t* ids,
+                                             void* ws, size_t ws_bytes, rc_stream_t stream) {
+    return dense_exact_rows_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, rows, ns, k, id_offset, dist, ids, ws, ws_bytes, stream);
+}
+
+extern "C" int rc_dense_l2_search_rows_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
+                                         const float* xsq, const float* xnorm_max, const int64_t* rows, int64_t ns, int k,
+                                         int64_t id_offset, double sel_slack, float* dist, int64_t* ids, int* status, int* qstatus,
+                                         void* ws, size_t ws_bytes, rc_stream_t stream) {
+    return dense_search_rows_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, xsq, xnorm_max, rows, ns, k, id_offset, sel_slack, dist,
+                                                     ids, status, qstatus, ws, ws_bytes, stream);
 }

@@ -62,7 +62,15 @@ struct dense_l2_f16_variant : dense_variant_defaults {
     static constexpr bool l2 = true;
     template <int MODE, typename... A>
     static int launch_gemm(A... a) { return dense_f16_launch_gemm<MODE, true>(a...); }
-    static constexpr auto* exact_rows = &dense_l2_launch_exact_rows<_Float16>;
+    static int exact_rows(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, float* out, hipStream_t s) {
+        return dense_l2_launch_exact_rows<T>(h, x, ldx, N, D, q, nq, out, s);
+    }
+    template <int MODE, typename... A>
+    static int launch_gemm_rows(const int64_t* rows, A... a) { return dense_f16_launch_gemm<MODE, true, true>(a..., rows); }
+    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
+                                 float* out, hipStream_t s) {
+        return dense_l2_launch_exact_rows<T, true>(h, x, ldx, N, D, q, nq, out, s, rows);
+    }
     static constexpr auto* finish = &dense_l2_launch_negate;
     __device__ static bool refuse(float v, int D) { return !(v - v == 0.f) || D > DENSE_L2_F16_MAX_D; }
     // E_q - ss_down: what is added to thr~ (header)
@@ -113,4 +121,21 @@ extern "C" int rc_dense_l2_f16_scores(rc_handle_t h, const uint16_t* x, int64_t 
     if (nq == 0) return RC_OK;
     return dense_f16_launch_gemm<DENSE_STORE, true>(xsq, h, dense_l2_f16_ptr(x), ldx, N, N, 0, dense_l2_f16_ptr(q), nq, D, nullptr,
                                                     out, nullptr, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int rc_dense_l2_f16_search_rows_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D,
+                                                 const uint16_t* q, int nq, const int64_t* rows, int64_t ns, int k,
+                                                 int64_t id_offset, float* dist, int64_t* ids, void* ws, size_t ws_bytes,
+                                                 rc_stream_t stream) {
+    return dense_exact_rows_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, rows, ns, k,
+                                                        id_offset, dist, ids, ws, ws_bytes, stream);
+}
+
+extern "C" int rc_dense_l2_f16_search_rows_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
+                                             int nq, const float* xsq, const float* xnorm_max, const int64_t* rows, int64_t ns,
+                                             int k, int64_t id_offset, double sel_slack, float* dist, int64_t* ids, int* status,
+                                             int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    return dense_search_rows_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, xsq, xnorm_max,
+                                                         rows, ns, k, id_offset, sel_slack, dist, ids, status, qstatus, ws,
+                                                         ws_bytes, stream);
 }

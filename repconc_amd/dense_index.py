@@ -19,6 +19,11 @@ storage, fp32 storage with the bf16x3 screen), classes of their own beside `Flat
 
 `FlatSQ8Index` / `FlatL2SQ8Index`: the inner-product and the squared-Euclidean index over 8-bit scalar-quantiser codes
 (`faiss.IndexScalarQuantizer`, QT_8bit), one byte per dimension; they share the store and its training (`_SQ8Store`).
+
+Subset search: `search(x, k, params=SearchParameters(sel=...))` with the selectors of `repconc_amd.selector` answers over the
+selected ids only, in place, with the ids and score bits the same index would return had it been given just those vectors
+(and their ids).  Served by the fp32- and fp16-storage indexes of both metrics under their own screens; the bf16x3 screens and
+the int8 stores refuse a selector.
 """
 from __future__ import annotations
 
@@ -29,6 +34,7 @@ import torch
 
 from . import ops
 from .index import METRIC_INNER_PRODUCT, METRIC_L2, _as_device, _as_f32_tensor
+from .selector import IDSelectorRange, SearchParameters
 
 
 class _FlatIndex:
@@ -36,6 +42,7 @@ class _FlatIndex:
     allocates exactly, later growth is 1.5x), the front end of `add` (`_rows`), `reset`, and `search` / `search_async` around
     the subclass's `_enqueue`."""
     PAD = float("-inf")          # the value of the slots past ntotal
+    SUBSET = True                # `search(..., params=)` takes a selector (the kernels of this storage and screen read a row list)
 
     def _init_store(self, d: int, device, dtype) -> None:
         self._dtype = dtype
@@ -93,26 +100,54 @@ class _FlatIndex:
         self._x = torch.empty((0, self.d), dtype=self._dtype, device=self.device)
         self._xnorm_max = None
 
-    def search(self, x, k: int):
+    def search(self, x, k: int, params: Optional[SearchParameters] = None):
         """(scores or distances [nq, k], ids [nq, k]); numpy in -> numpy out (evaluate_dense.py:74), CUDA tensors in -> CUDA
         tensors out (faiss.contrib.torch_utils).  float16 storage rounds the queries to fp16 without a range check: a query
-        value of magnitude >= 65520 becomes inf (`ops.dense_search_f16`)."""
-        return self.search_async(x, k)()
+        value of magnitude >= 65520 becomes inf (`ops.dense_search_f16`).
+        params: None or `SearchParameters()` is the whole store.  `SearchParameters(sel=...)` (faiss's `params=`) searches
+        only the ids the selector holds: ids and score bits are those of an index holding just those vectors under those
+        ids, padding past their number included.  An `IDSelectorRange` searches the matching slice of the store as a view;
+        every other selector becomes a row list (`sel.rows`, cached on the selector; building it reads the device once)
+        that the kernels follow in place (`ops.dense_search(rows=...)`)."""
+        return self.search_async(x, k, params)()
 
-    def search_async(self, x, k: int):
+    def _selector(self, params):
+        """The selector of `params`, or None for the whole store; ValueError where this index serves none."""
+        if params is None:
+            return None
+        if not isinstance(params, SearchParameters):
+            raise ValueError("search: params must be a SearchParameters or None")
+        if params.sel is not None and not self.SUBSET:
+            raise ValueError(f"{type(self).__name__}: no subset search (params.sel) under this storage or screen; the fp32- and "
+                             "fp16-storage indexes with their own screens serve it")
+        return params.sel
+
+    def search_async(self, x, k: int, params: Optional[SearchParameters] = None):
         """Enqueue the search and return a callable that yields what `search` returns; nothing synchronises with the host
-        until it is called (`batch_dense_search` enqueues every batch first)."""
+        until it is called (`batch_dense_search` enqueues every batch first; a selector other than a range builds its row
+        list on first use, which does read the device)."""
+        sel = self._selector(params)
         as_numpy = not isinstance(x, torch.Tensor)
         q = _as_f32_tensor(x).to(self.device, torch.float32, non_blocking=True)
         if q.dim() != 2 or q.shape[1] != self.d:
             raise ValueError(f"search: expected [nq, {self.d}] queries, got {tuple(q.shape)}")
         k = int(k)
-        if self.ntotal == 0 or q.shape[0] == 0:
+        lo, hi, rows = 0, self.ntotal, None
+        if isinstance(sel, IDSelectorRange):
+            lo, hi = sel.span(self.ntotal, self.id_offset)
+        elif sel is not None and self.ntotal:
+            rows = sel.rows(self.ntotal, self.id_offset, self.device)
+            hi = rows.numel()                # (only "is anything selected" is read from it below)
+        if hi == lo or q.shape[0] == 0:
             scores = torch.full((q.shape[0], k), self.PAD, dtype=torch.float32, device=self.device)
             ids = torch.full((q.shape[0], k), -1, dtype=torch.int64, device=self.device)
             pending = ops.PendingSearch(None, scores, ids, None, None, 0.0, 0)
-        else:
+        elif sel is None:
             pending = self._enqueue(q, k)
+        elif rows is None:
+            pending = self._enqueue(q, k, lo=lo, hi=hi)
+        else:
+            pending = self._enqueue(q, k, rows=rows)
         self.last_search = pending           # .stats: queries repeated / answered by the exact route
 
         def finish():
@@ -171,6 +206,7 @@ class FlatIPIndex(_FlatIndex):
         self.metric_type = METRIC_INNER_PRODUCT
         self._search = ops.dense_search_f16 if storage == "float16" else ops.dense_search_bf16x3 if screen == "bf16x3" \
             else ops.dense_search
+        self.SUBSET = screen != "bf16x3"
 
     def add(self, x) -> None:
         xt = self._rows(x)
@@ -191,9 +227,13 @@ class FlatIPIndex(_FlatIndex):
         if xnorm is not None:
             self._xnorm_max = xnorm if self._xnorm_max is None else torch.maximum(self._xnorm_max, xnorm)
 
-    def _enqueue(self, q, k: int):
-        norm = {} if self._search is ops.dense_search else {"xnorm_max": self._xnorm_max}
-        return self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True, **norm)
+    def _enqueue(self, q, k: int, lo: int = 0, hi: Optional[int] = None, rows: Optional[torch.Tensor] = None):
+        """The whole store; the rows lo .. hi - 1 as a view (the norm bound of the whole store covers them); or the row list
+        `rows` of a selector, valid by construction."""
+        more = {} if self._search is ops.dense_search else {"xnorm_max": self._xnorm_max}
+        if rows is not None:
+            more.update(rows=rows, check_rows=False)
+        return self._search(self.xb[lo:hi], q, k, id_offset=self.id_offset + lo, sel_slack=self.sel_slack, defer=True, **more)
 
 
 class _FlatL2(_FlatIndex):
@@ -234,9 +274,12 @@ class _FlatL2(_FlatIndex):
         super().reset()
         self._xsq = torch.empty((0,), dtype=torch.float32, device=self.device)
 
-    def _enqueue(self, q, k: int):
-        return self._search(self.xb, q, k, id_offset=self.id_offset, sel_slack=self.sel_slack, defer=True,
-                            xsq=self._xsq[: self.ntotal], xnorm_max=self._xnorm_max)
+    def _enqueue(self, q, k: int, lo: int = 0, hi: Optional[int] = None, rows: Optional[torch.Tensor] = None):
+        """As `FlatIPIndex._enqueue`; the norms are sliced with the rows."""
+        hi = self.ntotal if hi is None else hi
+        more = {} if rows is None else {"rows": rows, "check_rows": False}
+        return self._search(self.xb[lo:hi], q, k, id_offset=self.id_offset + lo, sel_slack=self.sel_slack, defer=True,
+                            xsq=self._xsq[lo:hi], xnorm_max=self._xnorm_max, **more)
 
 
 class FlatL2Index(_FlatL2):
@@ -279,6 +322,7 @@ class FlatL2Bf16x3Index(_FlatL2):
     whose bf16 rounding is not finite (magnitude >= 2^128 - 2^119, inf, NaN) before anything is stored (the one host read of an
     `add`, as `FlatIPIndex(screen="bf16x3")`)."""
     _search = staticmethod(ops.dense_search_l2_bf16x3)
+    SUBSET = False
 
     def __init__(self, d: int, device: Optional[torch.device] = None):
         self._init_l2(d, device, torch.float32)
@@ -343,6 +387,7 @@ class _SQ8Store(_FlatIndex):
     `reset` that keeps the training.  A subclass says which search answers (`_enqueue`) and may keep more per row
     (`_chunk_added`)."""
     ROWS_PER_STEP = SQ8_ROWS_PER_STEP     # rows that `add` moves and encodes at a time
+    SUBSET = False
 
     def _init_sq8(self, d: int, device, init_store) -> None:
         if not 1 <= int(d) <= ops.DENSE_SQ8_MAX_D:
@@ -401,9 +446,10 @@ class _SQ8Store(_FlatIndex):
             raise ValueError(f"reconstruct_n: rows [{i0}, {int(i0) + ni}) outside [0, {self.ntotal})")
         return ops.dense_sq8_decode(self._x[int(i0):int(i0) + ni], self._dec)
 
-    def search_async(self, x, k: int):
+    def search_async(self, x, k: int, params: Optional[SearchParameters] = None):
+        self._selector(params)              # a selector is refused whatever else is missing
         self._need_trained("search")
-        return super().search_async(x, k)
+        return super().search_async(x, k, params)
 
     def rerank(self, x, cand_ids, k: int):
         raise ValueError(f"{type(self).__name__}: rerank over an int8 store is not served")

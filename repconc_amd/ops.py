@@ -1193,24 +1193,62 @@ _DENSE_L2_SQ8 = _DenseVariant(_dense_sq8_args, "dense_l2_sq8", "dense_l2_sq8", (
 
 
 def _dense_call(v: _DenseVariant, kind: str, h, x, q, t: dict, stream, k=0, id_offset=0, sel_slack=0.0):
-    """(name, argument tuple) of one library call of variant `v`; kind: "search_q", "search_exact" or "scores".  The header's
-    order: h, x, ldx, N, D, q, nq, the side operands the variant names for that entry, the scalars, the outputs, the workspace
-    (where `t` holds one), the stream.  `t`: the side operands, the outputs and "ws" by name.  Touches no device and loads no
-    library: the positions come from the variant's names alone (tests/test_search_arg_order.py)."""
+    """(name, argument tuple) of one library call of variant `v`; kind: "search_q", "search_exact", "scores", or the subset
+    searches "search_rows_q" and "search_rows_exact".  The header's order: h, x, ldx, N, D, q, nq, the side operands the variant
+    names for that entry, (the subset searches: rows, ns,) the scalars, the outputs, the workspace (where `t` holds one), the
+    stream.  `t`: the side operands, "rows", the outputs and "ws" by name.  Touches no device and loads no library: the
+    positions come from the variant's names alone (tests/test_search_arg_order.py)."""
+    search_q = (v.entry, v.side, (int(k), int(id_offset), float(sel_slack)), ("scores", "ids", "status", "qstatus"))
+    search_exact = (v.exact, v.exact_side, (int(k), int(id_offset)), ("scores", "ids"))
     entry, side, scalars, outs = {
-        "search_q": (v.entry, v.side, (int(k), int(id_offset), float(sel_slack)), ("scores", "ids", "status", "qstatus")),
-        "search_exact": (v.exact, v.exact_side, (int(k), int(id_offset)), ("scores", "ids")),
+        "search_q": search_q,
+        "search_exact": search_exact,
         "scores": (v.entry, tuple(n for n in v.side if n in ("dec", "xsq")), (), ("out",)),    # no certificate: no xnorm_max, cstat
+        "search_rows_q": search_q,
+        "search_rows_exact": search_exact,
     }[kind]
+    rows = (_p(t["rows"]), t["rows"].numel()) if kind in ("search_rows_q", "search_rows_exact") else ()
     ws = () if t.get("ws") is None else (_p(t["ws"]), t["ws"].numel())
     return f"rc_{entry}_{kind}", (h, _p(x), x.stride(0), x.shape[0], x.shape[1], _p(q), q.shape[0], *(_p(t[n]) for n in side),
-                                  *scalars, *(_p(t[n]) for n in outs), *ws, stream)
+                                  *rows, *scalars, *(_p(t[n]) for n in outs), *ws, stream)
+
+
+# the variants whose kernels read the store through a row list (rc_<entry>_search_rows_q / _rows_exact)
+_DENSE_SUBSET = ("dense", "dense_f16", "dense_l2", "dense_l2_f16")
+
+
+def _dense_rows(name: str, rows, x: torch.Tensor, check_rows: bool) -> torch.Tensor:
+    """The row list of a subset search, refused with a ValueError before anything reaches the library: int64 [ns] on the
+    device of `x`, contiguous, and (check_rows: one host read) every row in [0, N), strictly ascending.  The library reads
+    x[rows[i]] unchecked: a list that is not valid by construction must not pass with the check off."""
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1:
+        raise ValueError(f"{name}: rows must be a 1-d tensor of row numbers")
+    if x.dim() != 2:
+        raise ValueError(f"{name}: x [N, D]")
+    if rows.dtype != torch.int64:
+        raise ValueError(f"{name}: rows must be int64, got {rows.dtype}")
+    if rows.device != x.device:
+        raise ValueError(f"{name}: rows must be on the device of the corpus ({x.device}), got {rows.device}")
+    if not rows.is_contiguous():
+        raise ValueError(f"{name}: rows must be contiguous")
+    if rows.numel() > x.shape[0]:
+        raise ValueError(f"{name}: {rows.numel()} rows selected of a corpus of {x.shape[0]}")
+    if check_rows and rows.numel():
+        ok = (rows[0] >= 0) & (rows[-1] < x.shape[0])
+        if rows.numel() > 1:
+            ok = ok & (rows[1:] > rows[:-1]).all()
+        if not bool(ok):
+            raise ValueError(f"{name}: rows must be strictly ascending row numbers in [0, {x.shape[0]})")
+    return rows
 
 
 def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int,
-                        dec: Optional[torch.Tensor] = None):
+                        dec: Optional[torch.Tensor] = None, rows: Optional[torch.Tensor] = None, check_rows: bool = True):
+    """rows (checked here unless the caller has: check_rows): the search runs over x[rows] in place, N below is then ns."""
+    if rows is not None:
+        rows = _dense_rows(f"rc_{v.exact}_search_rows_exact", rows, x, check_rows)
     x, q = v.args(x, q, k)
-    N, D = x.shape
+    N, D = (x.shape[0] if rows is None else rows.numel()), x.shape[1]
     nq = q.shape[0]
     lib, h, s, _ = _ctx(q)
     scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
@@ -1221,7 +1259,8 @@ def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: i
         return scores, ids
     wsb = getattr(lib, f"rc_{v.exact}_search_exact_ws_bytes")(N, D, nq, int(k))
     ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)
-    name, args = _dense_call(v, "search_exact", h, x, q, {"dec": dec, "scores": scores, "ids": ids, "ws": ws}, s, k, id_offset)
+    name, args = _dense_call(v, "search_exact" if rows is None else "search_rows_exact", h, x, q,
+                             {"dec": dec, "rows": rows, "scores": scores, "ids": ids, "ws": ws}, s, k, id_offset)
     _lib.check(getattr(lib, name)(*args), name, h)
     return scores, ids
 
@@ -1229,43 +1268,53 @@ def _dense_search_exact(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: i
 def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int, sel_slack: Optional[float],
                   defer: bool, method: str, max_retries: int, xnorm_max: Optional[torch.Tensor] = None,
                   xsq: Optional[torch.Tensor] = None, dec: Optional[torch.Tensor] = None,
-                  cstat: Optional[torch.Tensor] = None, stats: Optional[dict] = None):
+                  cstat: Optional[torch.Tensor] = None, stats: Optional[dict] = None, rows: Optional[torch.Tensor] = None,
+                  check_rows: bool = True):
+    """rows: the subset search (`dense_search`): the route runs over x[rows] in place.  NS below is the number of rows it
+    searches (ns, or N without rows): the route, the sample and the workspace follow it; xsq and xnorm_max stay the store's."""
     if method not in ("auto", "exact"):
         raise ValueError("method must be 'auto' or 'exact'")
+    if rows is not None:
+        if v.entry not in _DENSE_SUBSET:
+            raise ValueError(f"rc_{v.entry}_search_q: no subset search for this variant")
+        rows = _dense_rows(f"rc_{v.entry}_search_rows_q", rows, x, check_rows)
     x, q = v.args(x, q, k)
     if sel_slack is None:
         sel_slack = DENSE_SEL_SLACK
     N, D = x.shape
+    NS = N if rows is None else rows.numel()
     nq = q.shape[0]
-    if method == "exact" or nq == 0 or N == 0:
-        got = _dense_search_exact(v, x, q, k, id_offset, dec)
+    if method == "exact" or nq == 0 or NS == 0:
+        got = _dense_search_exact(v, x, q, k, id_offset, dec, rows, False)
         return PendingSearch(None, got[0], got[1], None, None, 0.0, 0) if defer else got
     lib, h, _, dev = _ctx(q)
     side = {"dec": dec, "cstat": cstat}          # the tensors behind the entry's side operands (v.side)
     if "xnorm_max" in v.side:
         if xnorm_max is None:
             # up to DENSE_EXACT_MAX_N rows the library takes the exact route and never reads the norm
-            xnorm_max = dense_xnorm_max(x) if N > DENSE_EXACT_MAX_N else torch.zeros((1,), dtype=torch.float32, device=x.device)
+            xnorm_max = dense_xnorm_max(x) if NS > DENSE_EXACT_MAX_N else torch.zeros((1,), dtype=torch.float32, device=x.device)
         _need_cuda(xnorm_max)
         side["xnorm_max"] = xnorm_max.to(torch.float32).reshape(1)
     if "xsq" in v.side:
         if xsq is None:
-            xsq = dense_row_sqnorms(x) if N > DENSE_EXACT_MAX_N else torch.zeros((N,), dtype=torch.float32, device=x.device)
+            xsq = dense_row_sqnorms(x) if NS > DENSE_EXACT_MAX_N else torch.zeros((N,), dtype=torch.float32, device=x.device)
         _need_cuda(xsq)
         if xsq.shape != (N,):
             raise ValueError("dense search: xsq must hold one squared norm per row, [N]")
         side["xsq"] = xsq.to(torch.float32).contiguous()
-    name = f"rc_{v.entry}_search_q"
+    kind = "search_q" if rows is None else "search_rows_q"
+    side["rows"] = rows
+    name = f"rc_{v.entry}_{kind}"
     search_q, ws_bytes = getattr(lib, name), getattr(lib, f"rc_{v.entry}_search_ws_bytes")
 
     def launch(qq, slack, out_s, out_i, status, qstatus):
         st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         for c0 in range(0, qq.shape[0], DENSE_QCHUNK):
             n = min(DENSE_QCHUNK, qq.shape[0] - c0)
-            wsb = ws_bytes(N, D, n, int(k))
+            wsb = ws_bytes(NS, D, n, int(k))
             ws = torch.empty((wsb,), dtype=torch.uint8, device=q.device)     # released in stream order
             t = dict(side, scores=out_s[c0:c0 + n], ids=out_i[c0:c0 + n], status=status, qstatus=qstatus[c0:c0 + n], ws=ws)
-            _lib.check(search_q(*_dense_call(v, "search_q", h, x, qq[c0:c0 + n], t, st, k, id_offset, slack)[1]), name, h)
+            _lib.check(search_q(*_dense_call(v, kind, h, x, qq[c0:c0 + n], t, st, k, id_offset, slack)[1]), name, h)
             if stats is not None and len(stats.setdefault("survivors", [])) * DENSE_QCHUNK < nq:
                 off = C.c_size_t(0)          # measurement: the first pass's candidate counts (rc_<entry>_search_ws_counts)
                 _lib.check(getattr(lib, f"rc_{v.entry}_search_ws_counts")(N, D, n, int(k), C.byref(off)), name, h)
@@ -1275,7 +1324,7 @@ def _dense_search(v: _DenseVariant, x: torch.Tensor, q: torch.Tensor, k: int, id
     def rerun(idx, slack, exact):
         qq = q[idx].contiguous()
         if exact:
-            s_, i_ = _dense_search_exact(v, x, qq, k, id_offset, dec)
+            s_, i_ = _dense_search_exact(v, x, qq, k, id_offset, dec, rows, False)
             return s_, i_, None
         s_ = torch.empty((qq.shape[0], k), dtype=torch.float32, device=q.device)
         i_ = torch.empty((qq.shape[0], k), dtype=torch.int64, device=q.device)
@@ -1521,20 +1570,28 @@ def dense_xnorm_max(x: torch.Tensor, rows_per_step: int = 1 << 16) -> torch.Tens
     return (best.sqrt() * (1.0 + 2.0 ** -20)).float().reshape(1)
 
 
-def dense_search_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+def dense_search_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, *, rows: Optional[torch.Tensor] = None,
+                       check_rows: bool = True):
     """The same answer as `dense_search` by the route that cannot fail (rc_dense_search_exact): full score rows and a radix
-    select of the min(k, N) best keys."""
-    return _dense_search_exact(_DENSE_F32, x, q, k, id_offset)
+    select of the min(k, N) best keys.  rows, check_rows: as `dense_search` (rc_dense_search_rows_exact)."""
+    return _dense_search_exact(_DENSE_F32, x, q, k, id_offset, None, rows, check_rows)
 
 
 def dense_search(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
-                 defer: bool = False, method: str = "auto", max_retries: int = 2):
+                 defer: bool = False, method: str = "auto", max_retries: int = 2, *, rows: Optional[torch.Tensor] = None,
+                 check_rows: bool = True):
     """Exact top-k inner-product search of `q` [nq, D] against the fp32 corpus `x` [N, D] (faiss.IndexFlatIP,
     evaluate_dense.py:84-129).  Returns (scores [nq, k] fp32, ids [nq, k] int64 = row + id_offset), sorted (score desc, id
     asc); -inf / -1 past N.  Scores are the fp32 fmaf chain over d ascending (include/repconc_hip.h), bit for bit.
     method="exact": the exact route only.  defer: a `PendingSearch` (queries the sampled threshold fails are repeated, then
-    answered by the exact route; `.stats`).  Query sets larger than DENSE_QCHUNK are split into several library calls."""
-    return _dense_search(_DENSE_F32, x, q, k, id_offset, sel_slack, defer, method, max_retries)
+    answered by the exact route; `.stats`).  Query sets larger than DENSE_QCHUNK are split into several library calls.
+    rows (keyword only): search only the rows `rows` of `x`, in place — int64 [ns] on x's device, contiguous, strictly ascending,
+    in [0, N).  The answer is exactly that of the same search over `x[rows]` with every id i replaced by id_offset +
+    rows[i] (ids and score bits, the padding past ns included); the route, the sample and the workspace follow ns, and ns = 0
+    returns padding.  check_rows=True verifies the list (one host read) and raises ValueError before any library call; the
+    library itself reads x[rows[i]] unchecked, so pass False only for a list that is valid by construction
+    (`repconc_amd.selector`)."""
+    return _dense_search(_DENSE_F32, x, q, k, id_offset, sel_slack, defer, method, max_retries, rows=rows, check_rows=check_rows)
 
 
 # --------------------------------------------------------------------------------------------------- dense, fp16 storage
@@ -1555,9 +1612,11 @@ def dense_f16_error_bound(D: int, qnorm, xmax):
 dense_f16_xnorm_max = dense_xnorm_max      # the `xnorm_max` of `dense_search_f16`
 
 
-def dense_search_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
-    """The same answer as `dense_search_f16` by the route that cannot fail (rc_dense_f16_search_exact)."""
-    return _dense_search_exact(_DENSE_F16, x16, q, k, id_offset)
+def dense_search_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, *,
+                           rows: Optional[torch.Tensor] = None, check_rows: bool = True):
+    """The same answer as `dense_search_f16` by the route that cannot fail (rc_dense_f16_search_exact).  rows, check_rows: as
+    `dense_search` (rc_dense_f16_search_rows_exact)."""
+    return _dense_search_exact(_DENSE_F16, x16, q, k, id_offset, None, rows, check_rows)
 
 
 def dense_f16_scores(x16: torch.Tensor, q16: torch.Tensor) -> torch.Tensor:
@@ -1567,7 +1626,7 @@ def dense_f16_scores(x16: torch.Tensor, q16: torch.Tensor) -> torch.Tensor:
 
 def dense_search_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
                      defer: bool = False, method: str = "auto", max_retries: int = 2,
-                     xnorm_max: Optional[torch.Tensor] = None):
+                     xnorm_max: Optional[torch.Tensor] = None, *, rows: Optional[torch.Tensor] = None, check_rows: bool = True):
     """Exact top-k inner-product search of `q` [nq, D] against the FINITE fp16 corpus `x16` [N, D] (faiss.IndexFlatIP with
     useFloat16).  The queries are rounded to fp16 (round to nearest even; a component of magnitude >= 65520 becomes inf and is
     not checked for: such a query gets no certificate and the exact route gives it the chain's inf / NaN scores); scores are
@@ -1576,8 +1635,9 @@ def dense_search_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int 
     screen; candidates are rescored by the chain and every answer of the fast route carries a certificate (qstatus bit2 when
     it cannot be given: such queries are repeated, then answered by the exact route — `.stats` of the `PendingSearch`).
     xnorm_max: device fp32 [1], >= the largest row norm of x16 (`dense_f16_xnorm_max`, computed here when None).
-    Everything else as `dense_search`."""
-    return _dense_search(_DENSE_F16, x16, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max)
+    Everything else as `dense_search`, the subset search (rows, check_rows) included: xnorm_max stays the bound over ALL rows."""
+    return _dense_search(_DENSE_F16, x16, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, rows=rows,
+                         check_rows=check_rows)
 
 
 # ------------------------------------------------------------------------------------ dense, fp32 corpus, bf16x3 screen
@@ -1774,15 +1834,17 @@ def dense_l2_scores(x: torch.Tensor, q: torch.Tensor, xsq: Optional[torch.Tensor
     return _dense_scores(_DENSE_L2, "dense_l2_scores", x, q, xsq=xsq)
 
 
-def dense_search_l2_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
+def dense_search_l2_exact(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, *, rows: Optional[torch.Tensor] = None,
+                          check_rows: bool = True):
     """The same answer as `dense_search_l2` by the route that cannot fail (rc_dense_l2_search_exact): full rows of distances
-    from the vector-ALU kernel and a radix select of the min(k, N) nearest."""
-    return _dense_search_exact(_DENSE_L2, x, q, k, id_offset)
+    from the vector-ALU kernel and a radix select of the min(k, N) nearest.  rows, check_rows: as `dense_search`
+    (rc_dense_l2_search_rows_exact)."""
+    return _dense_search_exact(_DENSE_L2, x, q, k, id_offset, None, rows, check_rows)
 
 
 def dense_search_l2(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
                     defer: bool = False, method: str = "auto", max_retries: int = 2, xsq: Optional[torch.Tensor] = None,
-                    xnorm_max: Optional[torch.Tensor] = None):
+                    xnorm_max: Optional[torch.Tensor] = None, *, rows: Optional[torch.Tensor] = None, check_rows: bool = True):
     """Exact top-k squared-Euclidean search of `q` [nq, D] against the fp32 corpus `x` [N, D] (faiss.IndexFlatL2,
     evaluate_repconc.py:102, run_warmup.py:102,107).  Returns (distances [nq, k] fp32, ids [nq, k] int64 = row + id_offset),
     sorted (distance asc, id asc); +inf / -1 past N.  A distance is the fp32 chain t = q_j - x_j, acc = fmaf(t, t, acc) over j
@@ -1790,23 +1852,27 @@ def dense_search_l2(x: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0
     candidates are rescored by the chain and every answer of the fast route carries a certificate (qstatus bit2 when it cannot
     be given: such queries are repeated, then answered by `dense_search_l2_exact`; `.stats` of the `PendingSearch`).
     xsq: device fp32 [N], the rows' squared norms (`dense_row_sqnorms`); xnorm_max: device fp32 [1] >= the largest row norm;
-    both computed here when None, and neither is read up to DENSE_EXACT_MAX_N rows.  Everything else as `dense_search`."""
-    return _dense_search_l2(_DENSE_L2, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)
+    both computed here when None, and neither is read up to DENSE_EXACT_MAX_N rows.  Everything else as `dense_search`, the
+    subset search (rows, check_rows) included: xsq stays the [N] norms of ALL rows, read at rows[i], xnorm_max their bound."""
+    return _dense_search_l2(_DENSE_L2, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max, rows=rows,
+                            check_rows=check_rows)
 
 
 def _dense_search_l2(v: _DenseVariant, x, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max,
-                     dec=None, cstat=None, stats=None):
+                     dec=None, cstat=None, stats=None, rows=None, check_rows=True):
     """The front of the four L2 searches: a missing xnorm_max comes from the squared norms, which are then computed once.
     Over int8 codes (`dec` given) the norms are those of the decoded rows and the certificate reads `cstat`, not xnorm_max."""
     if not 1 <= int(k) <= DENSE_MAX_K:
         raise ValueError(f"dense search: k must be in [1, {DENSE_MAX_K}]")
     missing = xnorm_max is None if dec is None else xsq is None
-    if missing and x.dim() == 2 and x.shape[0] > DENSE_EXACT_MAX_N and method == "auto" and x.is_cuda:
+    searched = rows.numel() if isinstance(rows, torch.Tensor) else x.shape[0] if x.dim() == 2 else 0      # the rows the route sees
+    if missing and searched > DENSE_EXACT_MAX_N and method == "auto" and x.is_cuda:
         if xsq is None:
             xsq = dense_row_sqnorms(x) if dec is None else dense_sq8_row_sqnorms(x, dec)
         if dec is None:
             xnorm_max = _dense_l2_xnorm_max(xsq)
-    return _dense_search(v, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, xsq, dec, cstat, stats)
+    return _dense_search(v, x, q, k, id_offset, sel_slack, defer, method, max_retries, xnorm_max, xsq, dec, cstat, stats, rows,
+                         check_rows)
 
 
 # ---------------------------------------------------------------------------------------- dense, L2 metric, fp16 storage
@@ -1832,14 +1898,17 @@ def dense_l2_f16_scores(x16: torch.Tensor, q16: torch.Tensor, xsq: Optional[torc
     return _dense_scores(_DENSE_L2_F16, "dense_l2_f16_scores", x16, q16, xsq=xsq)
 
 
-def dense_search_l2_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0):
-    """The same answer as `dense_search_l2_f16` by the route that cannot fail (rc_dense_l2_f16_search_exact)."""
-    return _dense_search_exact(_DENSE_L2_F16, x16, q, k, id_offset)
+def dense_search_l2_f16_exact(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, *,
+                              rows: Optional[torch.Tensor] = None, check_rows: bool = True):
+    """The same answer as `dense_search_l2_f16` by the route that cannot fail (rc_dense_l2_f16_search_exact).  rows,
+    check_rows: as `dense_search` (rc_dense_l2_f16_search_rows_exact)."""
+    return _dense_search_exact(_DENSE_L2_F16, x16, q, k, id_offset, None, rows, check_rows)
 
 
 def dense_search_l2_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0, sel_slack: Optional[float] = None,
                         defer: bool = False, method: str = "auto", max_retries: int = 2, xsq: Optional[torch.Tensor] = None,
-                        xnorm_max: Optional[torch.Tensor] = None):
+                        xnorm_max: Optional[torch.Tensor] = None, *, rows: Optional[torch.Tensor] = None,
+                        check_rows: bool = True):
     """Exact top-k squared-Euclidean search of `q` [nq, D] against the FINITE fp16 corpus `x16` [N, D] (faiss.IndexFlatL2 with
     useFloat16).  The queries are rounded to fp16 as `dense_search_f16` rounds them (to nearest even, no range check: a value of
     magnitude >= 65520 becomes inf, such a query gets no certificate and the exact route gives it the chain's inf / NaN
@@ -1848,10 +1917,12 @@ def dense_search_l2_f16(x16: torch.Tensor, q: torch.Tensor, k: int, id_offset: i
     and every answer of the fast route carries a certificate (qstatus bit2 when it cannot be given: such queries are repeated,
     then answered by `dense_search_l2_f16_exact`; `.stats` of the `PendingSearch`).  xsq: device fp32 [N], the squared norms of
     the fp16 rows (`dense_row_sqnorms`); xnorm_max: device fp32 [1] >= the largest row norm; both computed here from the fp16
-    corpus when None, and neither is read up to DENSE_EXACT_MAX_N rows.  Everything else as `dense_search_l2`."""
+    corpus when None, and neither is read up to DENSE_EXACT_MAX_N rows.  Everything else as `dense_search_l2`, rows and
+    check_rows included."""
     if x16.dtype != torch.float16:       # before any norm is computed from it
         raise ValueError("dense_search_l2_f16: the corpus must be float16 (FlatL2F16Index rounds and checks it)")
-    return _dense_search_l2(_DENSE_L2_F16, x16, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max)
+    return _dense_search_l2(_DENSE_L2_F16, x16, q, k, id_offset, sel_slack, defer, method, max_retries, xsq, xnorm_max,
+                            rows=rows, check_rows=check_rows)
 
 
 # ------------------------------------------------------------------------ dense, L2 metric, fp32 corpus, bf16x3 screen
