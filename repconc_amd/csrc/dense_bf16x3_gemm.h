@@ -189,19 +189,42 @@ static int dense_b3_launch_split(rc_handle_t h, const float* q, int nq, int D, _
     return RC_OK;
 }
 
-// xsq leads as in a variant's launch_gemm; it is read only if L2
+// o.xsq is read only if L2
 template <int MODE, bool L2 = false>
-static int dense_b3_launch_gemm(const float* xsq, rc_handle_t h, const float* x, int64_t ldx, int64_t N, int64_t nrows,
+static int dense_b3_launch_gemm(rc_handle_t h, const dense_operands& o, const float* x, int64_t ldx, int64_t N, int64_t nrows,
                                 int64_t smap, const __bf16* qs, int nq, int D, const float* thr, float* out, unsigned* cnt,
                                 unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     const int D32 = dense_b3_d32(D);
     if (D % 8 == 0 && ldx % 4 == 0 && !((uintptr_t)x & 15u))
         hipLaunchKernelGGL((dense_bf16x3_gemm_kernel<MODE, false, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, qs, nq, D,
-                           D32, thr, out, cnt, cand, xsq);
+                           D32, thr, out, cnt, cand, o.xsq);
     else
         hipLaunchKernelGGL((dense_bf16x3_gemm_kernel<MODE, true, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, qs, nq, D,
-                           D32, thr, out, cnt, cand, xsq);
+                           D32, thr, out, cnt, cand, o.xsq);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
+
+// What the two bf16x3 variants (inner product, L2) share: the split pre-pass into the tail of the workspace, the screen and
+// the query values the certificate refuses.  Each unit's variant adds its metric's exact rows, finish and eq.
+template <typename V, bool L2>
+struct dense_b3_variant_base : dense_variant_defaults<V> {
+    typedef float T;
+    typedef __bf16 Q;
+    static constexpr bool approximate = true;
+    static constexpr bool l2 = L2;
+    static constexpr unsigned ws_align = 16;             // the planes are read with 16-byte loads
+    static size_t extra_ws_bytes(int nq, int D) { return dense_b3_split_bytes(nq, D); }
+    static int prepass(rc_handle_t h, const dense_operands&, const float* q, int nq, int D, char* tail, const Q** qs,
+                       hipStream_t s) {
+        *qs = (const __bf16*)tail;                       // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
+        return dense_b3_launch_split(h, q, nq, D, (__bf16*)tail, s);
+    }
+    template <int MODE, typename... A>
+    static int launch_gemm(A... a) { return dense_b3_launch_gemm<MODE, L2>(a...); }
+    // |v| >= 2^128 - 2^119 rounds to a bf16 inf; inf and NaN lie above it
+    __device__ static bool refuse(float v, int D) {
+        return (__float_as_uint(v) & 0x7FFFFFFFu) >= 0x7F7F8000u || D > DENSE_B3_MAX_D;
+    }
+};

@@ -124,18 +124,18 @@ static bool dense_f16_aligned(const void* x, int64_t ldx, const void* q, int D) 
     return D % 8 == 0 && ldx % 8 == 0 && !((uintptr_t)x & 15u) && !((uintptr_t)q & 15u);
 }
 
-// xsq leads as in a variant's launch_gemm; it is read only if L2.  MAP: a template argument, as in dense_launch_gemm
+// o.xsq is read only if L2, o.rows only if MAP: a template argument, as in dense_launch_gemm
 template <int MODE, bool L2, bool MAP = false>
-static int dense_f16_launch_gemm(const float* xsq, rc_handle_t h, const _Float16* x, int64_t ldx, int64_t N, int64_t nrows,
+static int dense_f16_launch_gemm(rc_handle_t h, const dense_operands& o, const _Float16* x, int64_t ldx, int64_t N, int64_t nrows,
                                  int64_t smap, const _Float16* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                                 unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
+                                 unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (dense_f16_aligned(x, ldx, q, D))
         hipLaunchKernelGGL((dense_f16_gemm_kernel<MODE, false, L2, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D,
-                           thr, out, cnt, cand, xsq, rows);
+                           thr, out, cnt, cand, o.xsq, o.rows);
     else
         hipLaunchKernelGGL((dense_f16_gemm_kernel<MODE, true, L2, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D,
-                           thr, out, cnt, cand, xsq, rows);
+                           thr, out, cnt, cand, o.xsq, o.rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }

@@ -191,18 +191,28 @@ __global__ __launch_bounds__(256) void dense_gemm_kernel(const T* __restrict__ x
     dense_gemm_body<MODE, PAD, T, false, MAP>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, nullptr, rows);
 }
 
-// MAP is a template argument and not `rows != nullptr`: a unit that never searches a subset instantiates no mapped kernel
+// What a search reads beside x and q, one bundle for every variant and every hook (dense_screen.h): a variant reads the
+// fields it has and ignores the rest.  xsq [N]: the rows' squared norms (L2), dec [2][D]: the decoding vectors (coded),
+// rows [N]: the rows of a subset search, null for the whole store.
+struct dense_operands {
+    const float* xsq = nullptr;
+    const float* dec = nullptr;
+    const int64_t* rows = nullptr;
+};
+
+// MAP is a template argument and not `o.rows != nullptr`: a unit that never searches a subset instantiates no mapped kernel.
+// The variants that serve subsets choose between the two forms (V::subset, dense_screen.h).
 template <int MODE, typename T, bool MAP = false>
-static int dense_launch_gemm(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
-                             const T* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                             unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
+static int dense_launch_gemm(rc_handle_t h, const dense_operands& o, const T* x, int64_t ldx, int64_t N, int64_t nrows,
+                             int64_t smap, const T* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
+                             unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (D % DENSE_KC == 0)
         hipLaunchKernelGGL((dense_gemm_kernel<MODE, false, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand, rows);
+                           out, cnt, cand, o.rows);
     else
         hipLaunchKernelGGL((dense_gemm_kernel<MODE, true, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand, rows);
+                           out, cnt, cand, o.rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -238,19 +248,25 @@ static inline dense_fast_layout dense_fast_ws(int64_t N, int nq) {
     return L;
 }
 
-// argument checks shared by all entries: shapes first (pure arithmetic), then pointers.  Rows of D % 16 == 0 elements are
-// read with 16-byte loads: x, q and the row pitch must be 16-byte aligned (aligned = false: the variant has a form for the rest)
+// Rows of D % 16 == 0 elements are read with 16-byte loads: x, q and the row pitch must be 16-byte aligned
+template <typename X, typename T>
+static bool dense_aligned(const X* x, int64_t ldx, int D, const T* q) {
+    return D % DENSE_KC != 0 || (ldx % (16 / (int)sizeof(X)) == 0 && !((uintptr_t)x & 15u) && !((uintptr_t)q & 15u));
+}
+
+// argument checks shared by all entries: shapes first (pure arithmetic), then pointers, then dense_aligned (aligned = false: the
+// variant has a form for the rest)
 template <typename X, typename T>
 static int dense_check(rc_handle_t h, const X* x, int64_t ldx, int64_t N, int D, const T* q, int nq, int k,
                        const float* scores, const int64_t* ids, bool aligned = true) {
     if (N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2) return RC_ESHAPE;
     if (!h || !x || !q || !scores || !ids || N <= 0 || D <= 0 || nq < 0 || k <= 0 || ldx < D) return RC_EINVAL;
-    if (aligned && D % DENSE_KC == 0 &&
-        (ldx % (16 / (int)sizeof(X)) != 0 || ((uintptr_t)x & 15u) || ((uintptr_t)q & 15u))) return RC_EINVAL;
+    if (aligned && !dense_aligned(x, ldx, D, q)) return RC_EINVAL;
     return RC_OK;
 }
 
-// The exact route's score rows over an fp32 corpus, out [nq][N]: dense_launch_gemm<DENSE_STORE, float>, defined once in
-// dense_search.hip and shared with the bf16x3 unit, which so carries no fp32 GEMM of its own
-int dense_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
-                         hipStream_t s);
+// The exact route's score rows over an fp32 corpus, out [nq][N] (the exact_rows hook of a variant): dense_launch_gemm<DENSE_STORE,
+// float>, through o.rows for a subset; defined once in dense_search.hip and shared with the bf16x3 unit, which so carries no
+// fp32 GEMM of its own
+int dense_exact_rows_f32(rc_handle_t h, const dense_operands& o, const float* x, int64_t ldx, int64_t N, int D, const float* q,
+                         int nq, float* out, hipStream_t s);

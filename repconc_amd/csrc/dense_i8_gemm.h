@@ -253,11 +253,11 @@ __global__ __launch_bounds__(256, 2) void dense_i8_gemm_kernel(const signed char
 
 static bool dense_i8_aligned(const void* x, int64_t ldx, int D) { return D % 16 == 0 && ldx % 16 == 0 && !((uintptr_t)x & 15u); }
 
-// qs: the pre-pass's part of the workspace (dense_i8_query_ws), 16-byte aligned; xsq is read only if L2
+// qs: the pre-pass's part of the workspace (dense_i8_query_ws), 16-byte aligned; o.xsq is read only if L2
 template <int MODE, bool L2 = false>
-static int dense_i8_launch_gemm(rc_handle_t h, const signed char* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
-                                const char* qs, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                                unsigned long long* cand, hipStream_t s, const float* xsq = nullptr) {
+static int dense_i8_launch_gemm(rc_handle_t h, const dense_operands& o, const signed char* x, int64_t ldx, int64_t N,
+                                int64_t nrows, int64_t smap, const char* qs, int nq, int D, const float* thr, float* out,
+                                unsigned* cnt, unsigned long long* cand, hipStream_t s) {
     const dense_i8_query_layout L = dense_i8_query_ws(nq, D);
     const signed char* planes = (const signed char*)(qs + L.planes);
     const float* alpha = (const float*)(qs + L.alpha);
@@ -265,10 +265,10 @@ static int dense_i8_launch_gemm(rc_handle_t h, const signed char* x, int64_t ldx
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (dense_i8_aligned(x, ldx, D))
         hipLaunchKernelGGL((dense_i8_gemm_kernel<MODE, false, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, planes, alpha,
-                           bias, nq, D, L.Dp, thr, out, cnt, cand, xsq);
+                           bias, nq, D, L.Dp, thr, out, cnt, cand, o.xsq);
     else
         hipLaunchKernelGGL((dense_i8_gemm_kernel<MODE, true, L2>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, planes, alpha,
-                           bias, nq, D, L.Dp, thr, out, cnt, cand, xsq);
+                           bias, nq, D, L.Dp, thr, out, cnt, cand, o.xsq);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }

@@ -125,16 +125,17 @@ __global__ __launch_bounds__(256, 2) void dense_l2_exact_kernel(const T* __restr
     }
 }
 
+// o.rows is read only if MAP: a template argument, as in dense_launch_gemm
 template <typename T, bool MAP = false>
-static int dense_l2_launch_exact_rows(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, float* out,
-                                      hipStream_t s, const int64_t* rows = nullptr) {
+static int dense_l2_launch_exact_rows(rc_handle_t h, const dense_operands& o, const T* x, int64_t ldx, int64_t N, int D,
+                                      const T* q, int nq, float* out, hipStream_t s) {
     const dim3 grid((unsigned)((N + DENSE_TILE - 1) / DENSE_TILE));
     const bool vec = sizeof(T) == 4 ? D % DENSE_KC == 0
                                     : D % 8 == 0 && ldx % 8 == 0 && !((uintptr_t)x & 15u) && !((uintptr_t)q & 15u);
     if (vec)
-        hipLaunchKernelGGL((dense_l2_exact_kernel<false, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out, rows);
+        hipLaunchKernelGGL((dense_l2_exact_kernel<false, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out, o.rows);
     else
-        hipLaunchKernelGGL((dense_l2_exact_kernel<true, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out, rows);
+        hipLaunchKernelGGL((dense_l2_exact_kernel<true, T, MAP>), grid, dim3(256), 0, s, x, ldx, N, q, nq, D, out, o.rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -143,7 +144,7 @@ static int dense_l2_launch_exact_rows(rc_handle_t h, const T* x, int64_t ldx, in
 // defined once in dense_search_l2.hip.
 int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_t s);
 
-// dense_l2_launch_exact_rows<float>, the rows of rc_dense_l2_search_exact, for the other unit that searches an fp32 corpus;
-// defined in dense_search_l2.hip.
-int dense_l2_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
-                            hipStream_t s);
+// dense_l2_launch_exact_rows<float>, the rows of rc_dense_l2_search_exact (through o.rows for a subset), for the other unit
+// that searches an fp32 corpus; defined in dense_search_l2.hip.
+int dense_l2_exact_rows_f32(rc_handle_t h, const dense_operands& o, const float* x, int64_t ldx, int64_t N, int D, const float* q,
+                            int nq, float* out, hipStream_t s);

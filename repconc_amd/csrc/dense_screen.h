@@ -20,16 +20,19 @@
 //   1. screen<STORE> over the strided sample j -> row j N / S: s~ of the sample (fp32 screen: s~ = s, the chain)
 //   2. adc_threshold_kernel (topk.hip): thr~[q] = the r-th best s~ of the sample, r by the ADC formula (rc_adc_sample_rank)
 //   3. screen<FILTER> over all N rows: the key (s~, row) of every s~ >= thr~[q] -> q's candidate list
-//   4. approximate only: dense_rescore_kernel (coded: V::rescore) replaces the score half of every candidate key by the chain
+//   4. approximate only: V::rescore (dense_rescore_kernel; coded: the same over rows decoded on the fly) replaces the score
+//      half of every candidate key by the chain
 //   5. adc_select_kernel (rc_adc_launch_select): sort + emit; qstatus bit0 = fewer than min(k, N) candidates, bit1 = overflow
-//   6. approximate only: dense_certify_kernel (coded: V::certify).  With t = the query's k-th exact score and |s~ - s| <= E_q
-//      for every row, a row outside the list has s~ < thr~, hence s < thr~ + E_q: if t >= thr~ + E_q (everything in fp64, rounded upwards) no
-//      such row can enter the top-k or tie with its last member and the answer is proven equal to the exact route's.
+//   6. approximate only: V::certify (dense_certify_kernel; coded: a kernel of its own).  With t = the query's k-th exact score
+//      and |s~ - s| <= E_q for every row, a row outside the list has s~ < thr~, hence s < thr~ + E_q: if t >= thr~ + E_q
+//      (everything in fp64, rounded upwards) no such row can enter the top-k or tie with its last member and the answer is
+//      proven equal to the exact route's.
 //      Otherwise qstatus bit2, "not certified": the caller repeats the query with another slack or takes the exact route.
 //   7. V::finish, after the certificate has read the scores
 #pragma once
 #include "dense_gemm.h"
 
+#include <limits.h>
 #include <type_traits>
 
 typedef float dense_f32x4 __attribute__((ext_vector_type(4)));
@@ -154,14 +157,15 @@ __global__ __launch_bounds__(256) void dense_rescore_kernel(const T* __restrict_
     if (mine) *kp = adc_exact_key(L2 ? -s : s, (int64_t)row);
 }
 
+// o.rows is read only if MAP: a template argument, as in dense_launch_gemm
 template <bool L2, bool MAP = false, typename T>
-static int dense_launch_rescore(rc_handle_t h, const T* x, int64_t ldx, int D, const T* q, int nq, const unsigned* cnt,
-                                unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
+static int dense_launch_rescore(rc_handle_t h, const dense_operands& o, const T* x, int64_t ldx, int D, const T* q, int nq,
+                                const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
     if (ldx % (16 / (int)sizeof(T)) == 0 && !((uintptr_t)x & 15u))
-        hipLaunchKernelGGL((dense_rescore_kernel<true, T, L2, MAP>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand, rows);
+        hipLaunchKernelGGL((dense_rescore_kernel<true, T, L2, MAP>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand, o.rows);
     else
-        hipLaunchKernelGGL((dense_rescore_kernel<false, T, L2, MAP>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand, rows);
+        hipLaunchKernelGGL((dense_rescore_kernel<false, T, L2, MAP>), grid, dim3(256), 0, s, x, ldx, D, q, cnt, cand, o.rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -204,221 +208,224 @@ __global__ __launch_bounds__(64) void dense_certify_kernel(const typename V::T* 
 }
 
 // ---- the route --------------------------------------------------------------------------------------------------------------
-// A variant V (dense_variant_defaults holds what most of them say):
+// A variant V : dense_variant_defaults<V>, one interface for all eight.  What it says about itself:
 //   typedef T                      type of q, and of x unless V says otherwise
 //   typedef X                      optional: the storage type of x where it is not T (dense_storage<V>)
-//   typedef Q                      what its screen reads as the query operand (T, or the bf16 planes of the pre-pass)
-//   static constexpr bool approximate
-//   static constexpr bool l2                              scores are -d: the entry takes xsq [N], the squared norm of every
+//   typedef Q                      what its screen reads as the query operand (T, or what the pre-pass leaves in the workspace)
+//   static constexpr bool approximate                     its screen only approximates the score: rescore and certify run
+//   static constexpr bool l2                              scores are -d: the entries take o.xsq [N], the squared norm of every
 //                                                         row, and the rescorer walks dense_chain_step<true>
+//   static constexpr bool coded                           x holds codes that the per-dimension vectors o.dec decode
+//                                                         (dense_sq8_chain.h): every entry takes o.dec, and nothing is asked of
+//                                                         the alignment, the int8 screen has a form for any row pitch
+//   static constexpr bool subset                          it serves the subset search ("subset search" below): its hooks choose
+//                                                         the mapped form of their kernel where o.rows is set.  The others
+//                                                         never see o.rows set and instantiate no mapped kernel.
+//   static constexpr int max_d                            the largest D of its screen (int8: DENSE_I8_MAX_D)
 //   static constexpr unsigned ws_align                    alignment the workspace must have
+//   static constexpr bool screen_aligned                  launch_gemm reads rows of D % 16 == 0 elements with 16-byte loads
+//                                                         whatever their pitch: the scores entry checks dense_aligned
 //   static size_t extra_ws_bytes(nq, D)                   workspace after the fast layout, for the pre-pass
-//   static int prepass(h, q, nq, D, tail, &qs, s)         qs = the screen's query operand (tail: that extra workspace)
-//   static int launch_gemm<MODE>(xsq, h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s)
-//                                                         xsq leads so that a screen without a side operand drops it
-//   static int exact_rows(h, x, ldx, N, D, q, nq, out, s) out [nq][N] = the chain of every pair
-//   static int finish(h, scores, n, s)                    the last step over the n output values; empty: launches nothing
-//   approximate: eq / refuse of dense_certify_kernel
-//   typedef Side                   optional: the side operand where one pointer is not enough (dense_side<V>)
-//   static constexpr bool coded                           x holds codes that per-dimension vectors decode (dense_search_sq8.hip).
-//                                                         `side` (xsq of the L2 variants) then points at those vectors, and
-//                                                         prepass and exact_rows take it as their FIRST argument; the variant
-//                                                         brings the rescorer and the certificate of its own:
-//     static int rescore(side, h, x, ldx, D, q, nq, cnt, cand, s)
-//     static int certify(side, h, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s)
-//   a variant that serves the subset search (the routes' MAP forms; fp32 and fp16 storage, both metrics) adds the mapped twins
-//     static int launch_gemm_rows<MODE>(rows, xsq, h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s)
-//     static int exact_rows_mapped(rows, h, x, ldx, N, D, q, nq, out, s)
-//   and the others instantiate nothing of it.
+// and its hooks, each with the handle first, the operand bundle o (dense_operands, dense_gemm.h) second, and a stream last; a
+// variant reads the fields of o that it has and ignores the rest:
+//   static int prepass(h, o, q, nq, D, tail, &qs, s)      qs = the screen's query operand (tail: that extra workspace)
+//   static int launch_gemm<MODE>(h, o, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s)
+//   static int exact_rows(h, o, x, ldx, N, D, q, nq, out, s)                       out [nq][N] = the chain of every pair
+//   static int rescore(h, o, x, ldx, D, q, nq, cnt, cand, s)                       approximate only; default: dense_rescore_kernel
+//   static int certify(h, o, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s)
+//                                                         approximate only; default: dense_certify_kernel<V> on V::eq / V::refuse
+//   static int finish(h, scores, n, s)                    the last step over the n output values; default: launches nothing
+template <typename V>
 struct dense_variant_defaults {
     static constexpr bool l2 = false;
     static constexpr bool coded = false;
+    static constexpr bool subset = false;
+    static constexpr int max_d = INT_MAX;
     static constexpr unsigned ws_align = 1;
+    static constexpr bool screen_aligned = false;
     static size_t extra_ws_bytes(int, int) { return 0; }
     template <typename T>
-    static int prepass(rc_handle_t, const T* q, int, int, char*, const T** qs, hipStream_t) { *qs = q; return RC_OK; }
+    static int prepass(rc_handle_t, const dense_operands&, const T* q, int, int, char*, const T** qs, hipStream_t) {
+        *qs = q;
+        return RC_OK;
+    }
+    template <typename T>
+    static int rescore(rc_handle_t h, const dense_operands& o, const T* x, int64_t ldx, int D, const T* q, int nq,
+                       const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
+        if constexpr (V::subset) {
+            if (o.rows) return dense_launch_rescore<V::l2, true>(h, o, x, ldx, D, q, nq, cnt, cand, s);
+        }
+        return dense_launch_rescore<V::l2>(h, o, x, ldx, D, q, nq, cnt, cand, s);
+    }
+    template <typename T, typename Q>
+    static int certify(rc_handle_t h, const dense_operands&, const T* q, const Q*, int nq, int D, int k, const float* thr,
+                       const float* xnorm_max, const float* scores, int* status, int* qstatus, hipStream_t s) {
+        hipLaunchKernelGGL(dense_certify_kernel<V>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, thr, xnorm_max, scores, status,
+                           qstatus);
+        RC_LAUNCH_CHECK(h);
+        return RC_OK;
+    }
     static int finish(rc_handle_t, float*, int64_t, hipStream_t) { return RC_OK; }
 };
-
-// the side operand of a variant: one pointer (xsq of the L2 variants, the decoding vectors of the coded one) unless the
-// variant names a small struct of its own, V::Side, for more than one (dense_search_l2_sq8.hip: both); `!side` says that
-// something of it is missing.  The route only hands it on: no variant takes another branch for it.
-template <typename V, typename = void>
-struct dense_side { typedef const float* type; };
-template <typename V>
-struct dense_side<V, std::void_t<typename V::Side>> { typedef typename V::Side type; };
 
 template <typename V, typename = void>
 struct dense_storage { typedef typename V::T type; };
 template <typename V>
 struct dense_storage<V, std::void_t<typename V::X>> { typedef typename V::X type; };
 
-static inline size_t dense_exact_ws_bytes(int64_t N, int D, int nq, int k) {
-    return dense_shape_ok(N, D, nq, k) ? dense_exact_ws(N, nq).sel.total : 0;
+template <typename V>
+static bool dense_variant_shape_ok(int64_t N, int D, int nq, int k) { return dense_shape_ok(N, D, nq, k) && D <= V::max_d; }
+template <typename V>
+static size_t dense_exact_ws_bytes(int64_t N, int D, int nq, int k) {
+    return dense_variant_shape_ok<V>(N, D, nq, k) ? dense_exact_ws(N, nq).sel.total : 0;
 }
 template <typename V>
 static size_t dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
-    if (!dense_shape_ok(N, D, nq, k)) return 0;
+    if (!dense_variant_shape_ok<V>(N, D, nq, k)) return 0;
     return dense_exact_route(N) ? dense_exact_ws(N, nq).sel.total : dense_fast_ws(N, nq).total + V::extra_ws_bytes(nq, D);
 }
 
 // ---- subset search ------------------------------------------------------------------------------------------------------------
-// A search over the rows `rows` [ns] of the store (int64, ascending, unique, in [0, N): the caller's word, nothing here checks
-// it) is the unchanged route over the virtual matrix x' = x[rows] with N := ns (MAP = true below): the sample size, the rank of
-// the threshold, the exact-route limit and the workspace follow ns.  Four kernels form a row's address (dense_gemm_body, the
-// f16 screen, dense_l2_exact_kernel, dense_rescore_kernel) and read rows[] there, and the L2 screens read xsq at the same row;
-// the keys carry rows of x', so the order among equal scores (lower row of x' first) is the order of the corpus rows because
-// rows ascends.  The certificate's X bounds the norms of all of x, a superset of x'.  The select runs with id_offset 0 and
-// dense_map_ids_kernel (dense_search.hip) turns the nq x k rows of x' into id_offset + rows[.] after V::finish; -1 stays.
+// A search over the rows o.rows [ns] of the store (int64, ascending, unique, in [0, N): the caller's word, nothing here checks
+// it) is the unchanged route over the virtual matrix x' = x[rows] with N := ns: the sample size, the rank of the threshold, the
+// exact-route limit and the workspace follow ns.  Four kernels form a row's address (dense_gemm_body, the f16 screen,
+// dense_l2_exact_kernel, dense_rescore_kernel) and read rows[] there in their MAP form, and the L2 screens read xsq at the same
+// row.  MAP stays a template argument of the kernels and of their launchers; `o.rows ? <.., true> : <.., false>` is said once per
+// hook, in the four variants with V::subset (fp32 and fp16 storage, both metrics) and in the default rescorer.  The keys carry
+// rows of x', so the order among equal scores (lower row of x' first) is the order of the corpus rows because rows ascends.  The
+// certificate's X bounds the norms of all of x, a superset of x'.  With o.rows set the routes run the select with id_offset 0
+// and dense_map_ids_kernel (dense_search.hip) turns the nq x k rows of x' into id_offset + rows[.] after V::finish; -1 stays.
 int dense_launch_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* rows, int64_t id_offset, hipStream_t s);
 
-// the exact route: full score rows of L.qx queries at a time, then the radix select
-template <typename V, bool MAP = false>
-static int dense_exact(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                       const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, char* w,
-                       const dense_exact_layout& L, hipStream_t s, typename dense_side<V>::type side = {},
-                       const int64_t* rows = nullptr) {
+// the end of both routes
+template <typename V>
+static int dense_finish(rc_handle_t h, const dense_operands& o, float* scores, int64_t* ids, int64_t n, int64_t id_offset,
+                        hipStream_t s) {
+    const int rc = V::finish(h, scores, n, s);
+    if (rc != RC_OK || !o.rows) return rc;
+    return dense_launch_map_ids(h, ids, n, o.rows, id_offset, s);
+}
+
+// the exact route: full score rows of L.qx queries at a time, then the radix select.  N: the rows searched (ns with o.rows)
+template <typename V>
+static int dense_exact(rc_handle_t h, const dense_operands& o, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N,
+                       int D, const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, char* w,
+                       const dense_exact_layout& L, hipStream_t s) {
     float* sc = (float*)(w + L.sc);             // (the select's status word is never set: exactly min(k, N) keys are collected)
     for (int q0 = 0; q0 < nq; q0 += L.qx) {
         const int nx = nq - q0 < L.qx ? nq - q0 : L.qx;
-        int rc;
-        if constexpr (MAP) rc = V::exact_rows_mapped(rows, h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
-        else if constexpr (V::coded) rc = V::exact_rows(side, h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
-        else rc = V::exact_rows(h, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
+        int rc = V::exact_rows(h, o, x, ldx, N, D, q + (int64_t)q0 * D, nx, sc, s);
         if (rc != RC_OK) return rc;
-        rc = topk_exact_select(h, sc, N, nx, k, MAP ? 0 : id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
+        rc = topk_exact_select(h, sc, N, nx, k, o.rows ? 0 : id_offset, w, L.sel, scores + (size_t)q0 * k, ids + (size_t)q0 * k, s);
         if (rc != RC_OK) return rc;
     }
-    const int frc = V::finish(h, scores, (int64_t)nq * k, s);
-    if constexpr (MAP) {
-        if (frc != RC_OK) return frc;
-        return dense_launch_map_ids(h, ids, (int64_t)nq * k, rows, id_offset, s);
-    }
-    return frc;
+    return dense_finish<V>(h, o, scores, ids, (int64_t)nq * k, id_offset, s);
 }
 
-// checked arguments (dense_search_entry: dense_check, the extra pointers, nq > 0, a workspace of dense_search_ws_bytes<V>).
-// MAP: N is ns, the number of rows selected, and rows [N] their corpus rows ("subset search" above)
-template <typename V, bool MAP = false>
-static int dense_search_route(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                              const typename V::T* q, int nq, typename dense_side<V>::type xsq, const float* xnorm_max, int k,
-                              int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, char* w,
-                              hipStream_t s, const int64_t* rows = nullptr) {
+// checked arguments (dense_search_entry).  N: the rows searched (ns with o.rows)
+template <typename V>
+static int dense_search_route(rc_handle_t h, const dense_operands& o, const typename dense_storage<V>::type* x, int64_t ldx,
+                              int64_t N, int D, const typename V::T* q, int nq, const float* xnorm_max, int k, int64_t id_offset,
+                              double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, char* w, hipStream_t s) {
     if (dense_exact_route(N))
-        return dense_exact<V, MAP>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s, xsq, rows);
+        return dense_exact<V>(h, o, x, ldx, N, D, q, nq, k, id_offset, scores, ids, w, dense_exact_ws(N, nq), s);
     const dense_fast_layout L = dense_fast_ws(N, nq);
     float* sample = (float*)(w + L.sample);
     float* thr = (float*)(w + L.thr);
     unsigned* cnt = (unsigned*)(w + L.cnt);
     unsigned long long* cand = (unsigned long long*)(w + L.cand);
     const typename V::Q* qs;
-    int rc;
-    if constexpr (V::coded) rc = V::prepass(xsq, h, q, nq, D, w + L.total, &qs, s);
-    else rc = V::prepass(h, q, nq, D, w + L.total, &qs, s);
+    int rc = V::prepass(h, o, q, nq, D, w + L.total, &qs, s);
     if (rc != RC_OK) return rc;
-    if constexpr (MAP)
-        rc = V::template launch_gemm_rows<DENSE_STORE>(rows, xsq, h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr,
-                                                       nullptr, s);
-    else rc = V::template launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
+    rc = V::template launch_gemm<DENSE_STORE>(h, o, x, ldx, N, L.S, L.S, qs, nq, D, nullptr, sample, nullptr, nullptr, s);
     if (rc != RC_OK) return rc;
     rc = rc_adc_launch_threshold(h, sample, L.S, nq, rc_adc_sample_rank(N, L.S, k, sel_slack), thr, s);
     if (rc != RC_OK) return rc;
     RC_HIP_CHECK(h, hipMemsetAsync(cnt, 0, (size_t)nq * sizeof(unsigned), s));
-    if constexpr (MAP)
-        rc = V::template launch_gemm_rows<DENSE_FILTER>(rows, xsq, h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
-    else rc = V::template launch_gemm<DENSE_FILTER>(xsq, h, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
+    rc = V::template launch_gemm<DENSE_FILTER>(h, o, x, ldx, N, N, 0, qs, nq, D, thr, nullptr, cnt, cand, s);
     if (rc != RC_OK) return rc;
     if constexpr (V::approximate) {
-        if constexpr (V::coded) rc = V::rescore(xsq, h, x, ldx, D, q, nq, cnt, cand, s);
-        else rc = dense_launch_rescore<V::l2, MAP>(h, x, ldx, D, q, nq, cnt, cand, s, rows);
+        rc = V::rescore(h, o, x, ldx, D, q, nq, cnt, cand, s);
         if (rc != RC_OK) return rc;
     }
-    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, MAP ? 0 : id_offset, scores, ids, status, s, qstatus);
+    rc = rc_adc_launch_select(h, cand, cnt, nq, N, k, o.rows ? 0 : id_offset, scores, ids, status, s, qstatus);
     if (rc != RC_OK) return rc;
-    if constexpr (V::coded) {
-        rc = V::certify(xsq, h, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s);
+    if constexpr (V::approximate) {
+        rc = V::certify(h, o, q, qs, nq, D, k, thr, xnorm_max, scores, status, qstatus, s);
         if (rc != RC_OK) return rc;
-    } else if constexpr (V::approximate) {
-        hipLaunchKernelGGL(dense_certify_kernel<V>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, thr, xnorm_max, scores,
-                           status, qstatus);
-        RC_LAUNCH_CHECK(h);
     }
-    rc = V::finish(h, scores, (int64_t)nq * k, s);
-    if constexpr (MAP) {
-        if (rc != RC_OK) return rc;
-        rc = dense_launch_map_ids(h, ids, (int64_t)nq * k, rows, id_offset, s);
-    }
-    return rc;
+    return dense_finish<V>(h, o, scores, ids, (int64_t)nq * k, id_offset, s);
 }
 
 // ---- the entries ------------------------------------------------------------------------------------------------------------
-// The bodies of rc_dense*_search_exact and rc_dense*_search_q.  The order of the checks is part of the C ABI: shapes before
-// pointers (dense_check), a missing status / xnorm_max / xsq before the nq == 0 success, the workspace last.  A coded
-// variant reads `side` on every route and its screen has a form for any row pitch: nothing is asked of the alignment.
+// The bodies of rc_dense*_search_exact and rc_dense*_search_q, and with sub = true of rc_dense*_search_rows_exact and
+// rc_dense*_search_rows_q: the same search over the rows o.rows [ns] of the store.  The order of the checks is part of the C ABI.
+//   whole store  shapes, then pointers and alignment (dense_check; a coded variant has a screen for any row pitch and is asked
+//                for none), then a missing status / xsq / dec / xnorm_max, then the nq == 0 success, then the workspace
+//   rows         RC_ESHAPE on N, k (or D), then RC_EINVAL for ns outside [1, N], then dense_check, then the pointers, rows among
+//                them, then the nq == 0 success, then the workspace, sized by ns
+// and only then device work.  rows is never read on the host: ascending, unique and in [0, N) is the caller's word.  Only a
+// variant with V::subset has entries that say sub; the check refuses it for the others.
 template <typename V>
-static int dense_exact_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                             const typename V::T* q, int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
-                             size_t ws_bytes, rc_stream_t stream, typename dense_side<V>::type side = {}) {
-    rc_device_guard device_guard_(h);
+static int dense_entry_check(rc_handle_t h, const dense_operands& o, const typename dense_storage<V>::type* x, int64_t ldx,
+                             int64_t N, int D, const typename V::T* q, int nq, bool sub, int64_t ns, int k, const float* scores,
+                             const int64_t* ids) {
+    if (N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2 || D > V::max_d) return RC_ESHAPE;
+    if (sub && (!V::subset || ns < 1 || ns > N)) return RC_EINVAL;
     const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids, !V::coded);
     if (crc != RC_OK) return crc;
-    if (V::coded && !side) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    const dense_exact_layout L = dense_exact_ws(N, nq);
-    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
-    return dense_exact<V>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream, side);
+    return (sub && !o.rows) || (V::coded && !o.dec) ? RC_EINVAL : RC_OK;
 }
 
-// xsq is read if V::l2 or V::coded, xnorm_max if V::approximate
+template <typename V>
+static int dense_exact_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                             const typename V::T* q, int nq, const dense_operands& o, bool sub, int64_t ns, int k,
+                             int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    const int crc = dense_entry_check<V>(h, o, x, ldx, N, D, q, nq, sub, ns, k, scores, ids);
+    if (crc != RC_OK) return crc;
+    if (nq == 0) return RC_OK;
+    const int64_t n = sub ? ns : N;
+    const dense_exact_layout L = dense_exact_ws(n, nq);
+    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
+    return dense_exact<V>(h, o, x, ldx, n, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream);
+}
+
+// o.xsq is read if V::l2, o.dec if V::coded, xnorm_max if V::approximate
 template <typename V>
 static int dense_search_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                              const typename V::T* q, int nq, typename dense_side<V>::type xsq, const float* xnorm_max, int k,
-                              int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, void* ws,
-                              size_t ws_bytes, rc_stream_t stream) {
+                              const typename V::T* q, int nq, const dense_operands& o, const float* xnorm_max, bool sub,
+                              int64_t ns, int k, int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status,
+                              int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
     rc_device_guard device_guard_(h);
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids, !V::coded);
+    const int crc = dense_entry_check<V>(h, o, x, ldx, N, D, q, nq, sub, ns, k, scores, ids);
     if (crc != RC_OK) return crc;
-    if (!status || ((V::l2 || V::coded) && !xsq) || (V::approximate && !xnorm_max)) return RC_EINVAL;
+    if (!status || (V::l2 && !o.xsq) || (V::approximate && !xnorm_max)) return RC_EINVAL;
     if (nq == 0) return RC_OK;
-    if (!ws || ((uintptr_t)ws & (V::ws_align - 1)) || ws_bytes < dense_search_ws_bytes<V>(N, D, nq, k)) return RC_EWORKSPACE;
-    return dense_search_route<V>(h, x, ldx, N, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, scores, ids, status, qstatus,
+    const int64_t n = sub ? ns : N;
+    if (!ws || ((uintptr_t)ws & (V::ws_align - 1)) || ws_bytes < dense_search_ws_bytes<V>(n, D, nq, k)) return RC_EWORKSPACE;
+    return dense_search_route<V>(h, o, x, ldx, n, D, q, nq, xnorm_max, k, id_offset, sel_slack, scores, ids, status, qstatus,
                                  (char*)ws, (hipStream_t)stream);
 }
 
-
-// The bodies of rc_dense*_search_rows_exact and rc_dense*_search_rows_q: the entries above over the rows `rows` [ns] of the
-// store.  Checks, in the ABI's order: the shapes (dense_check's, then 1 <= ns <= N), the pointers (rows among them), the
-// nq == 0 success, the workspace — sized by ns, the helpers of the unmapped entries called with ns — and only then device work.
-// rows is never read on the host: ascending, unique and in [0, N) is the caller's word.
+// The body of rc_dense*_scores, the screen's raw values out [nq][N] (a test hook): shapes, then pointers (o.xsq, o.dec where the
+// variant reads them), then the alignment where the screen needs it, then the nq == 0 success, then the pre-pass's workspace
+// where the variant has one (ws, ws_bytes; the others pass none), then V::prepass into it and the screen's STORE form.
 template <typename V>
-static int dense_exact_rows_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                                  const typename V::T* q, int nq, const int64_t* rows, int64_t ns, int k, int64_t id_offset,
-                                  float* scores, int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream) {
+static int dense_scores_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
+                              const typename V::T* q, int nq, const dense_operands& o, float* out, void* ws, size_t ws_bytes,
+                              rc_stream_t stream) {
     rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2) return RC_ESHAPE;
-    if (ns < 1 || ns > N) return RC_EINVAL;
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
-    if (crc != RC_OK) return crc;
-    if (!rows) return RC_EINVAL;
+    if (N > 0xFFFFFFFFll || D > V::max_d) return RC_ESHAPE;
+    if (!h || !x || !q || (V::coded && !o.dec) || (V::l2 && !o.xsq) || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D)
+        return RC_EINVAL;
+    if (V::screen_aligned && !dense_aligned(x, ldx, D, q)) return RC_EINVAL;
     if (nq == 0) return RC_OK;
-    const dense_exact_layout L = dense_exact_ws(ns, nq);
-    if (!ws || ws_bytes < L.sel.total) return RC_EWORKSPACE;
-    return dense_exact<V, true>(h, x, ldx, ns, D, q, nq, k, id_offset, scores, ids, (char*)ws, L, (hipStream_t)stream, {}, rows);
-}
-
-template <typename V>
-static int dense_search_rows_entry(rc_handle_t h, const typename dense_storage<V>::type* x, int64_t ldx, int64_t N, int D,
-                                   const typename V::T* q, int nq, const float* xsq, const float* xnorm_max,
-                                   const int64_t* rows, int64_t ns, int k, int64_t id_offset, double sel_slack, float* scores,
-                                   int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll || k > ADC_CAND_CAP / 2) return RC_ESHAPE;
-    if (ns < 1 || ns > N) return RC_EINVAL;
-    const int crc = dense_check(h, x, ldx, N, D, q, nq, k, scores, ids);
-    if (crc != RC_OK) return crc;
-    if (!status || (V::l2 && !xsq) || (V::approximate && !xnorm_max) || !rows) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ((uintptr_t)ws & (V::ws_align - 1)) || ws_bytes < dense_search_ws_bytes<V>(ns, D, nq, k)) return RC_EWORKSPACE;
-    return dense_search_route<V, true>(h, x, ldx, ns, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, scores, ids, status,
-                                       qstatus, (char*)ws, (hipStream_t)stream, rows);
+    const size_t extra = V::extra_ws_bytes(nq, D);
+    if (extra && (!ws || ((uintptr_t)ws & (V::ws_align - 1)) || ws_bytes < extra)) return RC_EWORKSPACE;
+    hipStream_t s = (hipStream_t)stream;
+    const typename V::Q* qs;
+    const int rc = V::prepass(h, o, q, nq, D, (char*)ws, &qs, s);
+    if (rc != RC_OK) return rc;
+    return V::template launch_gemm<DENSE_STORE>(h, o, x, ldx, N, N, 0, qs, nq, D, nullptr, out, nullptr, nullptr, s);
 }

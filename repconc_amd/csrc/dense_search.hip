@@ -19,9 +19,15 @@
 // are the chain, so nothing is rescored or certified.  The GEMM kernel and the workspace layouts are in dense_gemm.h.
 #include "dense_screen.h"
 
-int dense_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
-                         hipStream_t s) {
-    return dense_launch_gemm<DENSE_STORE, float>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
+// the fp32 GEMM, through o.rows for a subset: the screen in both modes and the exact route's rows
+template <int MODE, typename... A>
+static int dense_f32_launch_gemm(rc_handle_t h, const dense_operands& o, A... a) {
+    return o.rows ? dense_launch_gemm<MODE, float, true>(h, o, a...) : dense_launch_gemm<MODE, float>(h, o, a...);
+}
+
+int dense_exact_rows_f32(rc_handle_t h, const dense_operands& o, const float* x, int64_t ldx, int64_t N, int D, const float* q,
+                         int nq, float* out, hipStream_t s) {
+    return dense_f32_launch_gemm<DENSE_STORE>(h, o, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
 }
 
 // ---- the id map of the subset searches (declared in dense_screen.h, shared by the four units that serve them) -----------------
@@ -40,22 +46,20 @@ int dense_launch_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* 
     return RC_OK;
 }
 
-struct dense_f32_variant : dense_variant_defaults {
+struct dense_f32_variant : dense_variant_defaults<dense_f32_variant> {
     typedef float T;
     typedef float Q;
     static constexpr bool approximate = false;
+    static constexpr bool subset = true;
+    static constexpr bool screen_aligned = true;
     template <int MODE, typename... A>
-    static int launch_gemm(const float*, A... a) { return dense_launch_gemm<MODE, float>(a...); }
+    static int launch_gemm(A... a) { return dense_f32_launch_gemm<MODE>(a...); }
     static constexpr auto* exact_rows = &dense_exact_rows_f32;
-    template <int MODE, typename... A>
-    static int launch_gemm_rows(const int64_t* rows, const float*, A... a) { return dense_launch_gemm<MODE, float, true>(a..., rows); }
-    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
-                                 float* out, hipStream_t s) {
-        return dense_launch_gemm<DENSE_STORE, T, true>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s, rows);
-    }
 };
 
-extern "C" size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
+extern "C" size_t rc_dense_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
+    return dense_exact_ws_bytes<dense_f32_variant>(N, D, nq, k);
+}
 
 extern "C" size_t rc_dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
     return dense_search_ws_bytes<dense_f32_variant>(N, D, nq, k);
@@ -64,26 +68,27 @@ extern "C" size_t rc_dense_search_ws_bytes(int64_t N, int D, int nq, int k) {
 extern "C" int rc_dense_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                      int k, int64_t id_offset, float* scores, int64_t* ids, void* ws, size_t ws_bytes,
                                      rc_stream_t stream) {
-    return dense_exact_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, ws, ws_bytes, stream);
+    return dense_exact_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, {}, false, 0, k, id_offset, scores, ids, ws, ws_bytes,
+                                                stream);
 }
 
 extern "C" int rc_dense_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, int k,
                                  int64_t id_offset, double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus,
                                  void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, nullptr, nullptr, k, id_offset, sel_slack, scores, ids,
-                                                 status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, {}, nullptr, false, 0, k, id_offset, sel_slack, scores,
+                                                 ids, status, qstatus, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_search_rows_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                           const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* scores, int64_t* ids,
                                           void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_exact_rows_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, rows, ns, k, id_offset, scores, ids, ws, ws_bytes,
-                                                     stream);
+    return dense_exact_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, {nullptr, nullptr, rows}, true, ns, k, id_offset, scores,
+                                                ids, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_search_rows_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                       const int64_t* rows, int64_t ns, int k, int64_t id_offset, double sel_slack, float* scores,
                                       int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_rows_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, nullptr, nullptr, rows, ns, k, id_offset, sel_slack,
-                                                      scores, ids, status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_f32_variant>(h, x, ldx, N, D, q, nq, {nullptr, nullptr, rows}, nullptr, true, ns, k, id_offset,
+                                                 sel_slack, scores, ids, status, qstatus, ws, ws_bytes, stream);
 }

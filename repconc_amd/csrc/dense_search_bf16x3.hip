@@ -32,23 +32,10 @@
 //   ops.dense_bf16x3_error_bound evaluates.
 #include "dense_bf16x3_gemm.h"
 
-// The certificate refuses a query value whose bf16 rounding is infinite (|v| >= 2^128 - 2^119; inf and NaN with it) and D > 65536.
-struct dense_b3_variant : dense_variant_defaults {
-    typedef float T;
-    typedef __bf16 Q;
-    static constexpr bool approximate = true;
-    static constexpr unsigned ws_align = 16;             // the planes are read with 16-byte loads
-    static size_t extra_ws_bytes(int nq, int D) { return dense_b3_split_bytes(nq, D); }
-    static int prepass(rc_handle_t h, const float* q, int nq, int D, char* tail, const Q** qs, hipStream_t s) {
-        *qs = (const __bf16*)tail;                       // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
-        return dense_b3_launch_split(h, q, nq, D, (__bf16*)tail, s);
-    }
-    template <int MODE, typename... A>
-    static int launch_gemm(A... a) { return dense_b3_launch_gemm<MODE>(a...); }     // the xsq it leads with is null: unread
+// The certificate refuses a query value whose bf16 rounding is infinite (|v| >= 2^128 - 2^119; inf and NaN with it) and D > 65536
+// (dense_b3_variant_base::refuse).
+struct dense_b3_variant : dense_b3_variant_base<dense_b3_variant, false> {
     static constexpr auto* exact_rows = &dense_exact_rows_f32;
-    __device__ static bool refuse(float v, int D) {
-        return (__float_as_uint(v) & 0x7FFFFFFFu) >= 0x7F7F8000u || D > DENSE_B3_MAX_D;
-    }
     __device__ static double eq(int D, double ss, double xnorm) {
         const double up = 1.0 + 0x1p-30;
         const double dpad = (double)((D + 15) / 16 * 16);
@@ -75,21 +62,12 @@ extern "C" size_t rc_dense_bf16x3_scores_ws_bytes(int D, int nq) {
 
 extern "C" int rc_dense_bf16x3_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                       float* out, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll) return RC_ESHAPE;
-    if (!h || !x || !q || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ((uintptr_t)ws & 15u) || ws_bytes < dense_b3_split_bytes(nq, D)) return RC_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = dense_b3_launch_split(h, q, nq, D, (__bf16*)ws, s);
-    if (rc != RC_OK) return rc;
-    return dense_b3_launch_gemm<DENSE_STORE>(nullptr, h, x, ldx, N, N, 0, (const __bf16*)ws, nq, D, nullptr, out, nullptr, nullptr,
-                                             s);
+    return dense_scores_entry<dense_b3_variant>(h, x, ldx, N, D, q, nq, {}, out, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_bf16x3_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                         const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores,
                                         int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_entry<dense_b3_variant>(h, x, ldx, N, D, q, nq, nullptr, xnorm_max, k, id_offset, sel_slack, scores, ids,
-                                                status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_b3_variant>(h, x, ldx, N, D, q, nq, {}, xnorm_max, false, 0, k, id_offset, sel_slack, scores,
+                                                ids, status, qstatus, ws, ws_bytes, stream);
 }

@@ -14,20 +14,19 @@
 
 #define DENSE_F16_ERR_C 4.0                              // the certificate's constant (rc_dense_f16_error_constant)
 
-struct dense_f16_variant : dense_variant_defaults {
+struct dense_f16_variant : dense_variant_defaults<dense_f16_variant> {
     typedef _Float16 T;
     typedef _Float16 Q;
     static constexpr bool approximate = true;
+    static constexpr bool subset = true;
     template <int MODE, typename... A>
-    static int launch_gemm(A... a) { return dense_f16_launch_gemm<MODE, false>(a...); }
-    static int exact_rows(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, float* out, hipStream_t s) {
-        return dense_launch_gemm<DENSE_STORE, T>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
+    static int launch_gemm(rc_handle_t h, const dense_operands& o, A... a) {
+        return o.rows ? dense_f16_launch_gemm<MODE, false, true>(h, o, a...) : dense_f16_launch_gemm<MODE, false>(h, o, a...);
     }
-    template <int MODE, typename... A>
-    static int launch_gemm_rows(const int64_t* rows, A... a) { return dense_f16_launch_gemm<MODE, false, true>(a..., rows); }
-    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
-                                 float* out, hipStream_t s) {
-        return dense_launch_gemm<DENSE_STORE, T, true>(h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s, rows);
+    static int exact_rows(rc_handle_t h, const dense_operands& o, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
+                          float* out, hipStream_t s) {
+        return o.rows ? dense_launch_gemm<DENSE_STORE, T, true>(h, o, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s)
+                      : dense_launch_gemm<DENSE_STORE, T>(h, o, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr, s);
     }
     __device__ static bool refuse(float, int) { return false; }
     __device__ static double eq(int D, double ss, double xnorm) {
@@ -37,10 +36,14 @@ struct dense_f16_variant : dense_variant_defaults {
     }
 };
 
+static const _Float16* dense_f16_ptr(const uint16_t* p) { return reinterpret_cast<const _Float16*>(p); }
+
 extern "C" double rc_dense_f16_error_constant(void) { return DENSE_F16_ERR_C; }
 extern "C" int rc_dense_f16_screen_form(void) { return 16; }
 
-extern "C" size_t rc_dense_f16_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
+extern "C" size_t rc_dense_f16_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
+    return dense_exact_ws_bytes<dense_f16_variant>(N, D, nq, k);
+}
 
 extern "C" size_t rc_dense_f16_search_ws_bytes(int64_t N, int D, int nq, int k) {
     return dense_search_ws_bytes<dense_f16_variant>(N, D, nq, k);
@@ -49,43 +52,34 @@ extern "C" size_t rc_dense_f16_search_ws_bytes(int64_t N, int D, int nq, int k) 
 extern "C" int rc_dense_f16_search_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
                                          int nq, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
                                          size_t ws_bytes, rc_stream_t stream) {
-    return dense_exact_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
-                                                reinterpret_cast<const _Float16*>(q), nq, k, id_offset, scores, ids, ws, ws_bytes,
-                                                stream);
+    return dense_exact_entry<dense_f16_variant>(h, dense_f16_ptr(x), ldx, N, D, dense_f16_ptr(q), nq, {}, false, 0, k, id_offset,
+                                                scores, ids, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
                                    float* out, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll) return RC_ESHAPE;
-    if (!h || !x || !q || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    return dense_f16_launch_gemm<DENSE_STORE, false>(nullptr, h, reinterpret_cast<const _Float16*>(x), ldx, N, N, 0,
-                                                     reinterpret_cast<const _Float16*>(q), nq, D, nullptr, out, nullptr, nullptr,
-                                                     (hipStream_t)stream);
+    return dense_scores_entry<dense_f16_variant>(h, dense_f16_ptr(x), ldx, N, D, dense_f16_ptr(q), nq, {}, out, nullptr, 0, stream);
 }
 
 extern "C" int rc_dense_f16_search_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
                                      const float* xnorm_max, int k, int64_t id_offset, double sel_slack, float* scores,
                                      int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
-                                                 reinterpret_cast<const _Float16*>(q), nq, nullptr, xnorm_max, k, id_offset,
-                                                 sel_slack, scores, ids, status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_f16_variant>(h, dense_f16_ptr(x), ldx, N, D, dense_f16_ptr(q), nq, {}, xnorm_max, false, 0, k,
+                                                 id_offset, sel_slack, scores, ids, status, qstatus, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_f16_search_rows_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
                                               int nq, const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* scores,
                                               int64_t* ids, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_exact_rows_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
-                                                     reinterpret_cast<const _Float16*>(q), nq, rows, ns, k, id_offset, scores, ids,
-                                                     ws, ws_bytes, stream);
+    return dense_exact_entry<dense_f16_variant>(h, dense_f16_ptr(x), ldx, N, D, dense_f16_ptr(q), nq, {nullptr, nullptr, rows}, true,
+                                                ns, k, id_offset, scores, ids, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_f16_search_rows_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
                                           int nq, const float* xnorm_max, const int64_t* rows, int64_t ns, int k, int64_t id_offset,
                                           double sel_slack, float* scores, int64_t* ids, int* status, int* qstatus, void* ws,
                                           size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_rows_entry<dense_f16_variant>(h, reinterpret_cast<const _Float16*>(x), ldx, N, D,
-                                                      reinterpret_cast<const _Float16*>(q), nq, nullptr, xnorm_max, rows, ns, k,
-                                                      id_offset, sel_slack, scores, ids, status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_f16_variant>(h, dense_f16_ptr(x), ldx, N, D, dense_f16_ptr(q), nq, {nullptr, nullptr, rows},
+                                                 xnorm_max, true, ns, k, id_offset, sel_slack, scores, ids, status, qstatus, ws,
+                                                 ws_bytes, stream);
 }

@@ -62,17 +62,18 @@ __global__ __launch_bounds__(256) void dense_l2_gemm_kernel(const float* __restr
     dense_gemm_body<MODE, PAD, float, true, MAP>(x, ldx, N, nrows, smap, q, nq, D, thr, out, cnt, cand, xsq, rows);
 }
 
+// o.rows is read only if MAP: a template argument, as in dense_launch_gemm
 template <int MODE, bool MAP = false>
-static int dense_l2_launch_gemm(const float* xsq, rc_handle_t h, const float* x, int64_t ldx, int64_t N, int64_t nrows,
+static int dense_l2_launch_gemm(rc_handle_t h, const dense_operands& o, const float* x, int64_t ldx, int64_t N, int64_t nrows,
                                 int64_t smap, const float* q, int nq, int D, const float* thr, float* out, unsigned* cnt,
-                                unsigned long long* cand, hipStream_t s, const int64_t* rows = nullptr) {
+                                unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)((nrows + DENSE_TILE - 1) / DENSE_TILE));
     if (D % DENSE_KC == 0)
         hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, false, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand, xsq, rows);
+                           out, cnt, cand, o.xsq, o.rows);
     else
         hipLaunchKernelGGL((dense_l2_gemm_kernel<MODE, true, MAP>), grid, dim3(256), 0, s, x, ldx, N, nrows, smap, q, nq, D, thr,
-                           out, cnt, cand, xsq, rows);
+                           out, cnt, cand, o.xsq, o.rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -90,27 +91,26 @@ int dense_l2_launch_negate(rc_handle_t h, float* v, int64_t n, hipStream_t s) {
     return RC_OK;
 }
 
-// the exact route's rows for dense_search_l2_bf16x3.hip (declared in dense_l2.h)
-int dense_l2_exact_rows_f32(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
-                            hipStream_t s) {
-    return dense_l2_launch_exact_rows<float>(h, x, ldx, N, D, q, nq, out, s);
+// the exact route's rows, also for dense_search_l2_bf16x3.hip (declared in dense_l2.h)
+int dense_l2_exact_rows_f32(rc_handle_t h, const dense_operands& o, const float* x, int64_t ldx, int64_t N, int D, const float* q,
+                            int nq, float* out, hipStream_t s) {
+    return o.rows ? dense_l2_launch_exact_rows<float, true>(h, o, x, ldx, N, D, q, nq, out, s)
+                  : dense_l2_launch_exact_rows<float>(h, o, x, ldx, N, D, q, nq, out, s);
 }
 
 // ---- the variant -------------------------------------------------------------------------------------------------------------
-struct dense_l2_variant : dense_variant_defaults {
+struct dense_l2_variant : dense_variant_defaults<dense_l2_variant> {
     typedef float T;
     typedef float Q;
     static constexpr bool approximate = true;
     static constexpr bool l2 = true;
+    static constexpr bool subset = true;
+    static constexpr bool screen_aligned = true;
     template <int MODE, typename... A>
-    static int launch_gemm(A... a) { return dense_l2_launch_gemm<MODE>(a...); }
-    static constexpr auto* exact_rows = &dense_l2_exact_rows_f32;
-    template <int MODE, typename... A>
-    static int launch_gemm_rows(const int64_t* rows, A... a) { return dense_l2_launch_gemm<MODE, true>(a..., rows); }
-    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
-                                 float* out, hipStream_t s) {
-        return dense_l2_launch_exact_rows<T, true>(h, x, ldx, N, D, q, nq, out, s, rows);
+    static int launch_gemm(rc_handle_t h, const dense_operands& o, A... a) {
+        return o.rows ? dense_l2_launch_gemm<MODE, true>(h, o, a...) : dense_l2_launch_gemm<MODE>(h, o, a...);
     }
+    static constexpr auto* exact_rows = &dense_l2_exact_rows_f32;
     static constexpr auto* finish = &dense_l2_launch_negate;
     __device__ static bool refuse(float v, int D) { return !(v - v == 0.f) || D > DENSE_L2_MAX_D; }
     // E_q - ss_down: what is added to thr~ (header).  +inf (never certified) unless (||q|| + X)^2 < 2^126.
@@ -131,7 +131,9 @@ extern "C" void rc_dense_l2_error_constants(double* c) {
     c[2] = DENSE_L2_C_UNDER;
 }
 
-extern "C" size_t rc_dense_l2_search_exact_ws_bytes(int64_t N, int D, int nq, int k) { return dense_exact_ws_bytes(N, D, nq, k); }
+extern "C" size_t rc_dense_l2_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
+    return dense_exact_ws_bytes<dense_l2_variant>(N, D, nq, k);
+}
 
 extern "C" size_t rc_dense_l2_search_ws_bytes(int64_t N, int D, int nq, int k) {
     return dense_search_ws_bytes<dense_l2_variant>(N, D, nq, k);
@@ -140,38 +142,33 @@ extern "C" size_t rc_dense_l2_search_ws_bytes(int64_t N, int D, int nq, int k) {
 extern "C" int rc_dense_l2_search_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                         int k, int64_t id_offset, float* dist, int64_t* ids, void* ws, size_t ws_bytes,
                                         rc_stream_t stream) {
-    return dense_exact_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, k, id_offset, dist, ids, ws, ws_bytes, stream);
+    return dense_exact_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, {}, false, 0, k, id_offset, dist, ids, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_l2_search_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                     const float* xsq, const float* xnorm_max, int k, int64_t id_offset, double sel_slack,
                                     float* dist, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
                                     rc_stream_t stream) {
-    return dense_search_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, xsq, xnorm_max, k, id_offset, sel_slack, dist, ids, status,
-                                                qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, {xsq}, xnorm_max, false, 0, k, id_offset, sel_slack, dist,
+                                                ids, status, qstatus, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_l2_scores(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                   const float* xsq, float* out, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll) return RC_ESHAPE;
-    if (!h || !x || !q || !xsq || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
-    if (D % DENSE_KC == 0 && (ldx % 4 != 0 || ((uintptr_t)x & 15u) || ((uintptr_t)q & 15u))) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    return dense_l2_launch_gemm<DENSE_STORE>(xsq, h, x, ldx, N, N, 0, q, nq, D, nullptr, out, nullptr, nullptr,
-                                             (hipStream_t)stream);
+    return dense_scores_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, {xsq}, out, nullptr, 0, stream);
 }
 
 extern "C" int rc_dense_l2_search_rows_exact(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                              const int64_t* rows, int64_t ns, int k, int64_t id_offset, float* dist, int64_t* ids,
                                              void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_exact_rows_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, rows, ns, k, id_offset, dist, ids, ws, ws_bytes, stream);
+    return dense_exact_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, {nullptr, nullptr, rows}, true, ns, k, id_offset, dist, ids,
+                                               ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_l2_search_rows_q(rc_handle_t h, const float* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                          const float* xsq, const float* xnorm_max, const int64_t* rows, int64_t ns, int k,
                                          int64_t id_offset, double sel_slack, float* dist, int64_t* ids, int* status, int* qstatus,
                                          void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_rows_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, xsq, xnorm_max, rows, ns, k, id_offset, sel_slack, dist,
-                                                     ids, status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_l2_variant>(h, x, ldx, N, D, q, nq, {xsq, nullptr, rows}, xnorm_max, true, ns, k, id_offset,
+                                                sel_slack, dist, ids, status, qstatus, ws, ws_bytes, stream);
 }

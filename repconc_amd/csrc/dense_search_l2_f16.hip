@@ -55,21 +55,20 @@
 #define DENSE_L2_F16_C_REL 2.5                           // E_q = C_REL D_pad 2^-24 (||q|| + X)^2
 #define DENSE_L2_F16_MAX_D 65536                         // the bound is proven up to here
 
-struct dense_l2_f16_variant : dense_variant_defaults {
+struct dense_l2_f16_variant : dense_variant_defaults<dense_l2_f16_variant> {
     typedef _Float16 T;
     typedef _Float16 Q;
     static constexpr bool approximate = true;
     static constexpr bool l2 = true;
+    static constexpr bool subset = true;
     template <int MODE, typename... A>
-    static int launch_gemm(A... a) { return dense_f16_launch_gemm<MODE, true>(a...); }
-    static int exact_rows(rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq, float* out, hipStream_t s) {
-        return dense_l2_launch_exact_rows<T>(h, x, ldx, N, D, q, nq, out, s);
+    static int launch_gemm(rc_handle_t h, const dense_operands& o, A... a) {
+        return o.rows ? dense_f16_launch_gemm<MODE, true, true>(h, o, a...) : dense_f16_launch_gemm<MODE, true>(h, o, a...);
     }
-    template <int MODE, typename... A>
-    static int launch_gemm_rows(const int64_t* rows, A... a) { return dense_f16_launch_gemm<MODE, true, true>(a..., rows); }
-    static int exact_rows_mapped(const int64_t* rows, rc_handle_t h, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
-                                 float* out, hipStream_t s) {
-        return dense_l2_launch_exact_rows<T, true>(h, x, ldx, N, D, q, nq, out, s, rows);
+    static int exact_rows(rc_handle_t h, const dense_operands& o, const T* x, int64_t ldx, int64_t N, int D, const T* q, int nq,
+                          float* out, hipStream_t s) {
+        return o.rows ? dense_l2_launch_exact_rows<T, true>(h, o, x, ldx, N, D, q, nq, out, s)
+                      : dense_l2_launch_exact_rows<T>(h, o, x, ldx, N, D, q, nq, out, s);
     }
     static constexpr auto* finish = &dense_l2_launch_negate;
     __device__ static bool refuse(float v, int D) { return !(v - v == 0.f) || D > DENSE_L2_F16_MAX_D; }
@@ -91,7 +90,7 @@ extern "C" void rc_dense_l2_f16_error_constants(double* c) {
 }
 
 extern "C" size_t rc_dense_l2_f16_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
-    return dense_exact_ws_bytes(N, D, nq, k);
+    return dense_exact_ws_bytes<dense_l2_f16_variant>(N, D, nq, k);
 }
 
 extern "C" size_t rc_dense_l2_f16_search_ws_bytes(int64_t N, int D, int nq, int k) {
@@ -101,41 +100,39 @@ extern "C" size_t rc_dense_l2_f16_search_ws_bytes(int64_t N, int D, int nq, int 
 extern "C" int rc_dense_l2_f16_search_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
                                             int nq, int k, int64_t id_offset, float* dist, int64_t* ids, void* ws,
                                             size_t ws_bytes, rc_stream_t stream) {
-    return dense_exact_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, k, id_offset, dist,
-                                                   ids, ws, ws_bytes, stream);
+    return dense_exact_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, {}, false, 0, k,
+                                                   id_offset, dist, ids, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_l2_f16_search_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
                                         int nq, const float* xsq, const float* xnorm_max, int k, int64_t id_offset,
                                         double sel_slack, float* dist, int64_t* ids, int* status, int* qstatus, void* ws,
                                         size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, xsq, xnorm_max, k,
-                                                    id_offset, sel_slack, dist, ids, status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, {xsq}, xnorm_max,
+                                                    false, 0, k, id_offset, sel_slack, dist, ids, status, qstatus, ws, ws_bytes,
+                                                    stream);
 }
 
 extern "C" int rc_dense_l2_f16_scores(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q, int nq,
                                       const float* xsq, float* out, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll) return RC_ESHAPE;
-    if (!h || !x || !q || !xsq || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    return dense_f16_launch_gemm<DENSE_STORE, true>(xsq, h, dense_l2_f16_ptr(x), ldx, N, N, 0, dense_l2_f16_ptr(q), nq, D, nullptr,
-                                                    out, nullptr, nullptr, (hipStream_t)stream);
+    return dense_scores_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, {xsq}, out, nullptr,
+                                                    0, stream);
 }
 
 extern "C" int rc_dense_l2_f16_search_rows_exact(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D,
                                                  const uint16_t* q, int nq, const int64_t* rows, int64_t ns, int k,
                                                  int64_t id_offset, float* dist, int64_t* ids, void* ws, size_t ws_bytes,
                                                  rc_stream_t stream) {
-    return dense_exact_rows_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, rows, ns, k,
-                                                        id_offset, dist, ids, ws, ws_bytes, stream);
+    return dense_exact_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq,
+                                                   {nullptr, nullptr, rows}, true, ns, k, id_offset, dist, ids, ws, ws_bytes,
+                                                   stream);
 }
 
 extern "C" int rc_dense_l2_f16_search_rows_q(rc_handle_t h, const uint16_t* x, int64_t ldx, int64_t N, int D, const uint16_t* q,
                                              int nq, const float* xsq, const float* xnorm_max, const int64_t* rows, int64_t ns,
                                              int k, int64_t id_offset, double sel_slack, float* dist, int64_t* ids, int* status,
                                              int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    return dense_search_rows_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, xsq, xnorm_max,
-                                                         rows, ns, k, id_offset, sel_slack, dist, ids, status, qstatus, ws,
-                                                         ws_bytes, stream);
+    return dense_search_entry<dense_l2_f16_variant>(h, dense_l2_f16_ptr(x), ldx, N, D, dense_l2_f16_ptr(q), nq, {xsq, nullptr, rows},
+                                                    xnorm_max, true, ns, k, id_offset, sel_slack, dist, ids, status, qstatus, ws,
+                                                    ws_bytes, stream);
 }

@@ -101,48 +101,9 @@ struct dense_l2_sq8_bound {
 };
 
 // ---- the variant ------------------------------------------------------------------------------------------------------------
-// both side operands of the route: the decoding vectors of the coded variant and the squared norms of the L2 variants
-struct dense_l2_sq8_side {
-    const float* dec = nullptr;
-    const float* xsq = nullptr;
-    bool operator!() const { return !dec || !xsq; }
-};
-
-struct dense_l2_sq8_variant : dense_variant_defaults {
-    typedef float T;
-    typedef signed char X;
-    typedef char Q;                                      // the pre-pass's part of the workspace (dense_i8_query_ws)
-    typedef dense_l2_sq8_side Side;
-    static constexpr bool approximate = true;
-    static constexpr bool coded = true;
-    static constexpr bool l2 = true;
-    static constexpr unsigned ws_align = 16;             // the planes are read with 16-byte loads
-    static size_t extra_ws_bytes(int nq, int D) { return dense_i8_query_ws(nq, D).total; }
-    static int prepass(Side sd, rc_handle_t h, const float* q, int nq, int D, char* tail, const Q** qs, hipStream_t s) {
-        *qs = tail;                                      // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
-        return dense_i8_launch_prepass(h, q, nq, D, sd.dec, tail, s);
-    }
-    template <int MODE>
-    static int launch_gemm(Side sd, rc_handle_t h, const X* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap, const Q* qs,
-                           int nq, int D, const float* thr, float* out, unsigned* cnt, unsigned long long* cand, hipStream_t s) {
-        return dense_i8_launch_gemm<MODE, true>(h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s, sd.xsq);
-    }
-    static int exact_rows(Side sd, rc_handle_t h, const X* x, int64_t ldx, int64_t N, int D, const float* q, int nq, float* out,
-                          hipStream_t s) {
-        return dense_sq8_launch_exact_rows<true>(sd.dec, h, x, ldx, N, D, q, nq, out, s);
-    }
-    static int rescore(Side sd, rc_handle_t h, const X* x, int64_t ldx, int D, const float* q, int nq, const unsigned* cnt,
-                       unsigned long long* cand, hipStream_t s) {
-        return dense_sq8_launch_rescore<true>(sd.dec, h, x, ldx, D, q, nq, cnt, cand, s);
-    }
-    static int certify(Side sd, rc_handle_t h, const float* q, const Q* qs, int nq, int D, int k, const float* thr,
-                       const float* cstat, const float* scores, int* status, int* qstatus, hipStream_t s) {
-        return dense_sq8_launch_certify<dense_l2_sq8_bound>(sd.dec, h, q, qs, nq, D, k, thr, cstat, scores, status, qstatus, s);
-    }
+struct dense_l2_sq8_variant : dense_sq8_variant_base<dense_l2_sq8_variant, true, dense_l2_sq8_bound> {
     static constexpr auto* finish = &dense_l2_launch_negate;
 };
-
-static bool dense_l2_sq8_shape_ok(int64_t N, int D, int nq, int k) { return dense_shape_ok(N, D, nq, k) && D <= DENSE_I8_MAX_D; }
 
 // ---- C ABI -------------------------------------------------------------------------------------------------------------------
 extern "C" void rc_dense_l2_sq8_error_constants(double* c) {
@@ -158,47 +119,33 @@ extern "C" void rc_dense_l2_sq8_error_constants(double* c) {
 }
 
 extern "C" size_t rc_dense_l2_sq8_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
-    return dense_l2_sq8_shape_ok(N, D, nq, k) ? dense_exact_ws_bytes(N, D, nq, k) : 0;
+    return dense_exact_ws_bytes<dense_l2_sq8_variant>(N, D, nq, k);
 }
 
 extern "C" size_t rc_dense_l2_sq8_search_ws_bytes(int64_t N, int D, int nq, int k) {
-    return dense_l2_sq8_shape_ok(N, D, nq, k) ? dense_search_ws_bytes<dense_l2_sq8_variant>(N, D, nq, k) : 0;
+    return dense_search_ws_bytes<dense_l2_sq8_variant>(N, D, nq, k);
 }
 
 extern "C" int rc_dense_l2_sq8_search_ws_counts(int64_t N, int D, int nq, int k, size_t* cnt_off) {
-    if (!cnt_off) return RC_EINVAL;
-    *cnt_off = 0;
-    if (!dense_l2_sq8_shape_ok(N, D, nq, k)) return RC_ESHAPE;
-    if (!dense_exact_route(N)) *cnt_off = dense_fast_ws(N, nq).cnt;
-    return RC_OK;
+    return dense_search_ws_counts<dense_l2_sq8_variant>(N, D, nq, k, cnt_off);
 }
 
 extern "C" size_t rc_dense_l2_sq8_scores_ws_bytes(int D, int nq) {
     return D > 0 && D <= DENSE_I8_MAX_D && nq > 0 ? dense_i8_query_ws(nq, D).total : 0;
 }
 
+// the exact route reads no norm: o.xsq stays null
 extern "C" int rc_dense_l2_sq8_search_exact(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q,
                                             int nq, const float* dec, int k, int64_t id_offset, float* dist, int64_t* ids,
                                             void* ws, size_t ws_bytes, rc_stream_t stream) {
-    if (D > DENSE_I8_MAX_D) return RC_ESHAPE;
-    // the exact route reads no norm: dec stands in for the pair's second half
-    return dense_exact_entry<dense_l2_sq8_variant>(h, x, ldx, N, D, q, nq, k, id_offset, dist, ids, ws, ws_bytes, stream,
-                                                   dense_l2_sq8_side{dec, dec});
+    return dense_exact_entry<dense_l2_sq8_variant>(h, x, ldx, N, D, q, nq, {nullptr, dec}, false, 0, k, id_offset, dist, ids, ws,
+                                                   ws_bytes, stream);
 }
 
 extern "C" int rc_dense_l2_sq8_scores(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                       const float* dec, const float* xsq, float* out, void* ws, size_t ws_bytes,
                                       rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll || D > DENSE_I8_MAX_D) return RC_ESHAPE;
-    if (!h || !x || !q || !dec || !xsq || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ((uintptr_t)ws & 15u) || ws_bytes < dense_i8_query_ws(nq, D).total) return RC_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = dense_i8_launch_prepass(h, q, nq, D, dec, (char*)ws, s);
-    if (rc != RC_OK) return rc;
-    return dense_i8_launch_gemm<DENSE_STORE, true>(h, x, ldx, N, N, 0, (const char*)ws, nq, D, nullptr, out, nullptr, nullptr, s,
-                                                   xsq);
+    return dense_scores_entry<dense_l2_sq8_variant>(h, x, ldx, N, D, q, nq, {xsq, dec}, out, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_sq8_row_sqnorms(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* dec,
@@ -217,7 +164,6 @@ extern "C" int rc_dense_l2_sq8_search_q(rc_handle_t h, const int8_t* x, int64_t 
                                         const float* dec, const float* xsq, const float* cstat, int k, int64_t id_offset,
                                         double sel_slack, float* dist, int64_t* ids, int* status, int* qstatus, void* ws,
                                         size_t ws_bytes, rc_stream_t stream) {
-    if (D > DENSE_I8_MAX_D) return RC_ESHAPE;
-    return dense_search_entry<dense_l2_sq8_variant>(h, x, ldx, N, D, q, nq, dense_l2_sq8_side{dec, xsq}, cstat, k, id_offset,
-                                                    sel_slack, dist, ids, status, qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_l2_sq8_variant>(h, x, ldx, N, D, q, nq, {xsq, dec}, cstat, false, 0, k, id_offset, sel_slack,
+                                                    dist, ids, status, qstatus, ws, ws_bytes, stream);
 }

@@ -81,30 +81,7 @@ struct dense_sq8_bound {
 };
 
 // ---- the variant ------------------------------------------------------------------------------------------------------------
-struct dense_sq8_variant : dense_variant_defaults {
-    typedef float T;
-    typedef signed char X;
-    typedef char Q;                                      // the pre-pass's part of the workspace (dense_i8_query_ws)
-    static constexpr bool approximate = true;
-    static constexpr bool coded = true;
-    static constexpr unsigned ws_align = 16;             // the planes are read with 16-byte loads
-    static size_t extra_ws_bytes(int nq, int D) { return dense_i8_query_ws(nq, D).total; }
-    static int prepass(const float* dec, rc_handle_t h, const float* q, int nq, int D, char* tail, const Q** qs, hipStream_t s) {
-        *qs = tail;                                      // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
-        return dense_i8_launch_prepass(h, q, nq, D, dec, tail, s);
-    }
-    template <int MODE>
-    static int launch_gemm(const float*, rc_handle_t h, const X* x, int64_t ldx, int64_t N, int64_t nrows, int64_t smap,
-                           const Q* qs, int nq, int D, const float* thr, float* out, unsigned* cnt, unsigned long long* cand,
-                           hipStream_t s) {
-        return dense_i8_launch_gemm<MODE>(h, x, ldx, N, nrows, smap, qs, nq, D, thr, out, cnt, cand, s);
-    }
-    static constexpr auto* exact_rows = &dense_sq8_launch_exact_rows<false>;
-    static constexpr auto* rescore = &dense_sq8_launch_rescore<false>;
-    static constexpr auto* certify = &dense_sq8_launch_certify<dense_sq8_bound>;
-};
-
-static bool dense_sq8_shape_ok(int64_t N, int D, int nq, int k) { return dense_shape_ok(N, D, nq, k) && D <= DENSE_I8_MAX_D; }
+struct dense_sq8_variant : dense_sq8_variant_base<dense_sq8_variant, false, dense_sq8_bound> {};
 
 extern "C" void rc_dense_sq8_error_constants(double* c) {
     c[0] = DENSE_SQ8_C_Q;
@@ -119,19 +96,15 @@ extern "C" int rc_dense_sq8_qmax(void) { return DENSE_I8_QMAX; }
 extern "C" int rc_dense_sq8_max_d(void) { return DENSE_I8_MAX_D; }
 
 extern "C" size_t rc_dense_sq8_search_exact_ws_bytes(int64_t N, int D, int nq, int k) {
-    return dense_sq8_shape_ok(N, D, nq, k) ? dense_exact_ws_bytes(N, D, nq, k) : 0;
+    return dense_exact_ws_bytes<dense_sq8_variant>(N, D, nq, k);
 }
 
 extern "C" size_t rc_dense_sq8_search_ws_bytes(int64_t N, int D, int nq, int k) {
-    return dense_sq8_shape_ok(N, D, nq, k) ? dense_search_ws_bytes<dense_sq8_variant>(N, D, nq, k) : 0;
+    return dense_search_ws_bytes<dense_sq8_variant>(N, D, nq, k);
 }
 
 extern "C" int rc_dense_sq8_search_ws_counts(int64_t N, int D, int nq, int k, size_t* cnt_off) {
-    if (!cnt_off) return RC_EINVAL;
-    *cnt_off = 0;
-    if (!dense_sq8_shape_ok(N, D, nq, k)) return RC_ESHAPE;
-    if (!dense_exact_route(N)) *cnt_off = dense_fast_ws(N, nq).cnt;
-    return RC_OK;
+    return dense_search_ws_counts<dense_sq8_variant>(N, D, nq, k, cnt_off);
 }
 
 extern "C" size_t rc_dense_sq8_scores_ws_bytes(int D, int nq) {
@@ -141,21 +114,13 @@ extern "C" size_t rc_dense_sq8_scores_ws_bytes(int D, int nq) {
 extern "C" int rc_dense_sq8_search_exact(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                          const float* dec, int k, int64_t id_offset, float* scores, int64_t* ids, void* ws,
                                          size_t ws_bytes, rc_stream_t stream) {
-    if (D > DENSE_I8_MAX_D) return RC_ESHAPE;
-    return dense_exact_entry<dense_sq8_variant>(h, x, ldx, N, D, q, nq, k, id_offset, scores, ids, ws, ws_bytes, stream, dec);
+    return dense_exact_entry<dense_sq8_variant>(h, x, ldx, N, D, q, nq, {nullptr, dec}, false, 0, k, id_offset, scores, ids, ws,
+                                                ws_bytes, stream);
 }
 
 extern "C" int rc_dense_sq8_scores(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* q, int nq,
                                    const float* dec, float* out, void* ws, size_t ws_bytes, rc_stream_t stream) {
-    rc_device_guard device_guard_(h);
-    if (N > 0xFFFFFFFFll || D > DENSE_I8_MAX_D) return RC_ESHAPE;
-    if (!h || !x || !q || !dec || !out || N <= 0 || D <= 0 || nq < 0 || ldx < D) return RC_EINVAL;
-    if (nq == 0) return RC_OK;
-    if (!ws || ((uintptr_t)ws & 15u) || ws_bytes < dense_i8_query_ws(nq, D).total) return RC_EWORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
-    const int rc = dense_i8_launch_prepass(h, q, nq, D, dec, (char*)ws, s);
-    if (rc != RC_OK) return rc;
-    return dense_i8_launch_gemm<DENSE_STORE>(h, x, ldx, N, N, 0, (const char*)ws, nq, D, nullptr, out, nullptr, nullptr, s);
+    return dense_scores_entry<dense_sq8_variant>(h, x, ldx, N, D, q, nq, {nullptr, dec}, out, ws, ws_bytes, stream);
 }
 
 extern "C" int rc_dense_sq8_decode(rc_handle_t h, const int8_t* x, int64_t ldx, int64_t N, int D, const float* dec, float* out,
@@ -174,7 +139,6 @@ extern "C" int rc_dense_sq8_search_q(rc_handle_t h, const int8_t* x, int64_t ldx
                                      const float* dec, const float* cstat, int k, int64_t id_offset, double sel_slack,
                                      float* scores, int64_t* ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
                                      rc_stream_t stream) {
-    if (D > DENSE_I8_MAX_D) return RC_ESHAPE;
-    return dense_search_entry<dense_sq8_variant>(h, x, ldx, N, D, q, nq, dec, cstat, k, id_offset, sel_slack, scores, ids, status,
-                                                 qstatus, ws, ws_bytes, stream);
+    return dense_search_entry<dense_sq8_variant>(h, x, ldx, N, D, q, nq, {nullptr, dec}, cstat, false, 0, k, id_offset, sel_slack,
+                                                 scores, ids, status, qstatus, ws, ws_bytes, stream);
 }

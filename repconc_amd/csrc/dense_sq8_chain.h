@@ -51,13 +51,13 @@ __global__ __launch_bounds__(256) void dense_sq8_rescore_kernel(const signed cha
 }
 
 template <bool L2>
-static int dense_sq8_launch_rescore(const float* dec, rc_handle_t h, const signed char* x, int64_t ldx, int D, const float* q,
-                                    int nq, const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
+static int dense_sq8_launch_rescore(rc_handle_t h, const dense_operands& o, const signed char* x, int64_t ldx, int D,
+                                    const float* q, int nq, const unsigned* cnt, unsigned long long* cand, hipStream_t s) {
     const dim3 grid((unsigned)nq, ADC_CAND_CAP / 256);
     if (ldx % 16 == 0 && !((uintptr_t)x & 15u))
-        hipLaunchKernelGGL((dense_sq8_rescore_kernel<true, L2>), grid, dim3(256), 0, s, x, ldx, D, dec, q, cnt, cand);
+        hipLaunchKernelGGL((dense_sq8_rescore_kernel<true, L2>), grid, dim3(256), 0, s, x, ldx, D, o.dec, q, cnt, cand);
     else
-        hipLaunchKernelGGL((dense_sq8_rescore_kernel<false, L2>), grid, dim3(256), 0, s, x, ldx, D, dec, q, cnt, cand);
+        hipLaunchKernelGGL((dense_sq8_rescore_kernel<false, L2>), grid, dim3(256), 0, s, x, ldx, D, o.dec, q, cnt, cand);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -103,10 +103,10 @@ __global__ __launch_bounds__(256) void dense_sq8_rows_kernel(const signed char* 
 }
 
 template <bool L2>
-static int dense_sq8_launch_exact_rows(const float* dec, rc_handle_t h, const signed char* x, int64_t ldx, int64_t N, int D,
-                                       const float* q, int nq, float* out, hipStream_t s) {
+static int dense_sq8_launch_exact_rows(rc_handle_t h, const dense_operands& o, const signed char* x, int64_t ldx, int64_t N,
+                                       int D, const float* q, int nq, float* out, hipStream_t s) {
     const dim3 grid((unsigned)((N + 255) / 256), (unsigned)((nq + DENSE_SQ8_ROWS_QB - 1) / DENSE_SQ8_ROWS_QB));
-    hipLaunchKernelGGL(dense_sq8_rows_kernel<L2>, grid, dim3(256), 0, s, x, ldx, N, D, dec, q, nq, out);
+    hipLaunchKernelGGL(dense_sq8_rows_kernel<L2>, grid, dim3(256), 0, s, x, ldx, N, D, o.dec, q, nq, out);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
@@ -159,12 +159,49 @@ __global__ __launch_bounds__(64) void dense_sq8_certify_kernel(const float* __re
 }
 
 template <typename B>
-static int dense_sq8_launch_certify(const float* dec, rc_handle_t h, const float* q, const char* qs, int nq, int D, int k,
+static int dense_sq8_launch_certify(rc_handle_t h, const dense_operands& o, const float* q, const char* qs, int nq, int D, int k,
                                     const float* thr, const float* cstat, const float* scores, int* status, int* qstatus,
                                     hipStream_t s) {
     const float* alpha = (const float*)(qs + dense_i8_query_ws(nq, D).alpha);
-    hipLaunchKernelGGL(dense_sq8_certify_kernel<B>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, dec, alpha, thr, cstat, scores,
+    hipLaunchKernelGGL(dense_sq8_certify_kernel<B>, dim3((unsigned)nq), dim3(64), 0, s, q, D, k, o.dec, alpha, thr, cstat, scores,
                        status, qstatus);
     RC_LAUNCH_CHECK(h);
+    return RC_OK;
+}
+
+// ---- the variant ------------------------------------------------------------------------------------------------------------
+// What the variants of the two searches over codes share (dense_screen.h), which is all but the L2 unit's finish: o.dec on every
+// route, o.xsq in the screen if L2, the query pre-pass into the tail of the workspace.  B: the unit's bound
+// (dense_sq8_certify_kernel).
+template <typename V, bool L2, typename B>
+struct dense_sq8_variant_base : dense_variant_defaults<V> {
+    typedef float T;
+    typedef signed char X;
+    typedef char Q;                                      // the pre-pass's part of the workspace (dense_i8_query_ws)
+    static constexpr bool approximate = true;
+    static constexpr bool coded = true;
+    static constexpr bool l2 = L2;
+    static constexpr int max_d = DENSE_I8_MAX_D;
+    static constexpr unsigned ws_align = 16;             // the planes are read with 16-byte loads
+    static size_t extra_ws_bytes(int nq, int D) { return dense_i8_query_ws(nq, D).total; }
+    static int prepass(rc_handle_t h, const dense_operands& o, const float* q, int nq, int D, char* tail, const Q** qs,
+                       hipStream_t s) {
+        *qs = tail;                                      // 16-byte aligned: the workspace is, and the fast layout is a multiple of 256
+        return dense_i8_launch_prepass(h, q, nq, D, o.dec, tail, s);
+    }
+    template <int MODE, typename... A>
+    static int launch_gemm(A... a) { return dense_i8_launch_gemm<MODE, L2>(a...); }
+    static constexpr auto* exact_rows = &dense_sq8_launch_exact_rows<L2>;
+    static constexpr auto* rescore = &dense_sq8_launch_rescore<L2>;
+    static constexpr auto* certify = &dense_sq8_launch_certify<B>;
+};
+
+// rc_dense*_sq8_search_ws_counts: where the fast route's candidate counts lie in the workspace (0: the exact route has none)
+template <typename V>
+static int dense_search_ws_counts(int64_t N, int D, int nq, int k, size_t* cnt_off) {
+    if (!cnt_off) return RC_EINVAL;
+    *cnt_off = 0;
+    if (!dense_variant_shape_ok<V>(N, D, nq, k)) return RC_ESHAPE;
+    if (!dense_exact_route(N)) *cnt_off = dense_fast_ws(N, nq).cnt;
     return RC_OK;
 }
