@@ -17,13 +17,14 @@ models/jpq/finetune_jpq.py) are replaced as a whole by their `repconc_amd` count
     faiss.IndexScalarQuantizer, faiss.ScalarQuantizer.QT_8bit   not in the reference; the flat index over 8-bit codes (dense_index.py)
     faiss.IndexIVFScalarQuantizer(q, d, nlist, QT_8bit, metric, by_residual=False)   not in the reference; the exact IVF index over 8-bit codes
     faiss.SearchParameters(sel=faiss.IDSelectorRange / Batch / Array / Bitmap / Not)   not in the reference; subset search of the flat indexes
+    faiss.SearchParametersIVF(sel=..., nprobe=...)  not in the reference; the same selectors (and nprobe) on IndexIVFFlat / IndexIVFScalarQuantizer
     import faiss.contrib.torch_utils                finetune_jpq.py:9 (tensor in / tensor out is what PQIndex.search does)
 
 This is `repconc_amd.faiss_compat` under Faiss's name; anything else (`index_factory`, `StandardGpuResources`, …) is not
 provided and raises AttributeError — those call sites live in the modules listed above.  A real Faiss installation, if
 present later on the path, is shadowed only because this directory was put first on purpose.
 """
-from repconc_amd.faiss_compat import (IDSelectorArray, IDSelectorBatch, IDSelectorBitmap, IDSelectorNot, IDSelectorRange, SearchParameters,  # noqa: F401
+from repconc_amd.faiss_compat import (IDSelectorArray, IDSelectorBatch, IDSelectorBitmap, IDSelectorNot, IDSelectorRange, SearchParameters, SearchParametersIVF,  # noqa: F401
                                       METRIC_INNER_PRODUCT, METRIC_L2, IndexFlatIP, IndexFlatL2, IndexIVFFlat, IndexIVFScalarQuantizer, IndexPQ,  # noqa: F401
                                       IndexScalarQuantizer, ScalarQuantizer, copy_array_to_vector, downcast_index, omp_set_num_threads, read_index, vector_to_array, write_index)
 from repconc_amd.index import PQIndex as _PQIndex

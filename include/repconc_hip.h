@@ -936,6 +936,47 @@ int rc_ivf_flat_sq8r_search(rc_handle_t h, const int8_t* x, int64_t ldx, const i
                             const int* probes, int nprobe, int64_t stride, int k, int metric, float* scores, int64_t* out_ids,
                             int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream);
 
+/* ------------------------------------------------------------------ IVF over dense rows, a subset of the rows
+ * The four searches above over the selected rows of the store, in place: no copy of the rows is made, and the score rows, the
+ * workspace and the rows read follow the selection, not N.  rows: DEVICE int64 [ns], the LIST-MAJOR positions (rows of x, not
+ * corpus ids) of the selected rows, strictly ASCENDING, no row twice, every one in [0, N) — ascending positions are grouped by
+ * cell, and ascend by corpus id inside a cell because the store is stably sorted.  sel_off: DEVICE int64 [nlist + 1], the
+ * offsets of the cells INSIDE rows: rows[sel_off[c] .. sel_off[c + 1]) are the selected rows of cell c, every one in
+ * [list_off[c], list_off[c + 1]); sel_off[0] = 0, sel_off[nlist] = ns.  THE LIBRARY DOES NOT VERIFY ANY OF THIS: rows and
+ * sel_off are never read on the host, and a row outside [0, N) is a read outside x (the Python wrapper checks the pair unless
+ * told not to, ops.ivf_flat_search(rows=..., sel_off=..., check_rows=True)).
+ * Result: exactly what the entry of the same name without _rows returns for a store that holds only the selected rows, each
+ * under the cell it has here, with the same probes, dec and coarse — ids (ids[rows[i]], the corpus ids of THIS store) and
+ * score / distance bits, ties by the lower corpus id, the padding (-inf or +inf, -1) where the probed cells hold fewer than k
+ * selected rows.  The plan reads sel_off where it reads list_off; the scan reads logical row i of cell c at x + rows[sel_off[c]
+ * + i] * ldx (rows[] once per row and chunk of 512 rows, never at or past sel_off[c + 1]) and hands the store position on, so
+ * the k-th score, the filter, the select and the status bits are those of the entry without _rows.  The residual form adds the
+ * centroid of the task's cell: a selected row's cell is its cell.
+ * Arguments: those of the entry without _rows, then `rows, ns, sel_off`.  stride: >= the SELECTED rows the probed cells of any
+ * query hold; ws: rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, stride) with that stride.  list_off is checked (non-null) and
+ * otherwise not read.
+ * Checks: the argument checks of the entry without _rows in their order (RC_EINVAL, RC_ESHAPE), then rows or sel_off NULL or
+ * ns outside [1, N] (RC_EINVAL), then nq == 0 (RC_OK, nothing enqueued), the workspace (RC_EWORKSPACE), then device work. */
+int rc_ivf_flat_search_rows(rc_handle_t h, const float* x, int64_t ldx, const int64_t* list_off, const int64_t* ids, int64_t N,
+                            int nlist, int D, const float* q, int nq, const int* probes, int nprobe, int64_t stride, int k,
+                            int metric, float* scores, int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                            rc_stream_t stream, const int64_t* rows, int64_t ns, const int64_t* sel_off);
+int rc_ivf_flat_f16_search_rows(rc_handle_t h, const uint16_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                                int64_t N, int nlist, int D, const uint16_t* q, int nq, const int* probes, int nprobe,
+                                int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status, int* qstatus,
+                                void* ws, size_t ws_bytes, rc_stream_t stream, const int64_t* rows, int64_t ns,
+                                const int64_t* sel_off);
+int rc_ivf_flat_sq8_search_rows(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                                int64_t N, int nlist, int D, const float* q, int nq, const float* dec, const int* probes,
+                                int nprobe, int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status,
+                                int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream, const int64_t* rows, int64_t ns,
+                                const int64_t* sel_off);
+int rc_ivf_flat_sq8r_search_rows(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                                 int64_t N, int nlist, int D, const float* q, int nq, const float* dec, const float* coarse,
+                                 int64_t ldc, const int* probes, int nprobe, int64_t stride, int k, int metric, float* scores,
+                                 int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream,
+                                 const int64_t* rows, int64_t ns, const int64_t* sel_off);
+
 /* ------------------------------------------------------------------ JPQ scoring head (csrc/jpq_head.hip)
  * Scores of (query, document id) pairs straight from the resident codes, and their gradients (stage 2 of the recipe,
  * models/jpq/finetune_jpq.py:176-189, without the decoded embeddings and without atomics on values).

@@ -114,6 +114,15 @@ PROTOTYPES = {
                                     _vp, _vp, _sz, _vp]),
     "rc_ivf_flat_sq8r_search": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i, _i64, _i, _i, _vp,
                                      _vp, _vp, _vp, _vp, _sz, _vp]),
+    # the subset searches: `rows, ns, sel_off` after the arguments of the entry without _rows
+    "rc_ivf_flat_search_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp, _vp,
+                                     _vp, _sz, _vp, _vp, _i64, _vp]),
+    "rc_ivf_flat_f16_search_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i64, _i, _i, _vp, _vp, _vp,
+                                         _vp, _vp, _sz, _vp, _vp, _i64, _vp]),
+    "rc_ivf_flat_sq8_search_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _i, _i64, _i, _i, _vp, _vp,
+                                         _vp, _vp, _vp, _sz, _vp, _vp, _i64, _vp]),
+    "rc_ivf_flat_sq8r_search_rows": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _vp, _i64, _vp, _i, _i64, _i, _i,
+                                          _vp, _vp, _vp, _vp, _vp, _sz, _vp, _vp, _i64, _vp]),
     "rc_adc_lut":(_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "rc_adc_lut_l2": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "rc_adc_search_l2_q": (_i, [_vp, _vp, _vp, _i64, _i, _i, _vp, _i, _vp, _i, _i, _i64, _d, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

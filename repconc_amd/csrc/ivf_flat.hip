@@ -101,7 +101,14 @@ __global__ __launch_bounds__(256) void ivf_flat_plan_query_kernel(const int64_t*
 // are served by the caches.  Holding the slices of 2 or 4 stages in registers (one wider fetch per lane every 2 or 4 stages)
 // was measured and is slower at every nprobe (profiles/ivf_flat_sq8_form_ab.txt); this form is the one kept.
 // RES (coded form only): coarse [nlist][ldc] fp32, the centroid of the task's cell is added to every decoded value.
-template <typename T, typename TQ, bool L2, bool PAD, bool RES = false>
+// MAP (the subset search): the scan runs over the virtual store x' = x[rows].  rows [ns] int64 holds the store positions of the
+// selected rows, strictly ascending (so grouped by cell, corpus id ascending inside a cell), and `list_off` is the caller's
+// sel_off [nlist + 1]: the offsets of the cells INSIDE rows.  Logical row i of the task's cell is read at x + rows[sel_off[c]
+// + i] * ldx and rowid receives that store position, so everything after the scan (ids[rowid], the tie rule) is untouched.  A
+// loader thread's NL row addresses are formed once per row chunk and held in registers over the chunk's K stages (rows[] is
+// read once per (row, chunk), never per stage); the logical row of a partial last chunk is clamped BEFORE the map, so rows[] is
+// never read at or past sel_off[c + 1].  !MAP never reads `rows` and forms its addresses as before.
+template <typename T, typename TQ, bool L2, bool PAD, bool RES = false, bool MAP = false>
 __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int64_t ldx, const int64_t* __restrict__ list_off,
                                                    int D, const TQ* __restrict__ q, const float* __restrict__ dec,
                                                    const float* __restrict__ coarse, int64_t ldc,
@@ -109,7 +116,7 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
                                                    int64_t stride, const int* __restrict__ task_list,
                                                    const int* __restrict__ task_qstart, const int* __restrict__ task_qcnt,
                                                    const int* __restrict__ sorted_q, float* __restrict__ dense,
-                                                   int* __restrict__ rowid) {
+                                                   int* __restrict__ rowid, const int64_t* __restrict__ rows) {
     constexpr bool SQ = std::is_same<T, signed char>::value;
     static_assert(SQ || !RES, "the residual form is a form of the coded scan");
     constexpr int EPP = 16 / (int)sizeof(T);                 // values per 16-byte piece
@@ -154,6 +161,14 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
             for (int r = 0; r < 4; ++r) acc[a][r] = 0.f;
         ivff_u4 stg[NL];
         float rq = 0.f;
+        const T* xr[MAP ? NL : 1];                                  // MAP: the loader's rows of this chunk, mapped once
+        if constexpr (MAP) {
+#pragma unroll
+            for (int j = 0; j < NL; ++j) {
+                const int row = (j * 256 + tid) / P;
+                xr[j] = x + rows[r0 + (row < nrows ? row : nrows - 1)] * ldx;
+            }
+        }
         float dstep[SQ ? IVFF_KC : 1], dmid[SQ ? IVFF_KC : 1];      // coded form: step and mid of the staged slice (wave-uniform)
         float dcen[RES ? IVFF_KC : 1];                              // residual form: the cell's centroid over the slice, likewise
         // piece i = j 256 + tid of the stage: row i / P of the chunk, piece i % P of its slice; whole pieces inside the row with
@@ -163,7 +178,7 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
 #pragma unroll
             for (int j = 0; j < NL; ++j) {
                 const int i = j * 256 + tid, row = i / P, pc = i % P;
-                const T* p = x + (r0 + (row < nrows ? row : nrows - 1)) * ldx + k0 + pc * EPP;
+                const T* p = (MAP ? xr[j] : x + (r0 + (row < nrows ? row : nrows - 1)) * ldx) + k0 + pc * EPP;
                 if constexpr (!PAD) {
                     stg[j] = (k0 + pc * EPP < D) ? *reinterpret_cast<const ivff_u4*>(p) : ivff_u4{0u, 0u, 0u, 0u};
                 } else {
@@ -242,7 +257,7 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
                 const int64_t pos = qb + ch * IVFF_RT + row;
                 if (row < nrows && pos < stride) {
                     dense[(int64_t)qi * stride + pos] = L2 ? -acc[a][r] : acc[a][r];
-                    rowid[(int64_t)qi * stride + pos] = (int)(unsigned)(r0 + row);
+                    rowid[(int64_t)qi * stride + pos] = (int)(unsigned)(MAP ? rows[r0 + row] : r0 + row);
                 }
             }
         }
@@ -250,8 +265,9 @@ __device__ __forceinline__ void ivf_flat_scan_body(const T* __restrict__ x, int6
 }
 
 // grid (task bound, <= IVFF_Y_MAX).  dense / rowid: [nq][stride].  One kernel for every store: dec is the coded store's
-// [2][D], coarse [nlist][ldc] the residual form's centroids; a form that does not take them is handed nullptr / 0.
-template <typename T, typename TQ, bool L2, bool PAD, bool RES>
+// [2][D], coarse [nlist][ldc] the residual form's centroids; a form that does not take them is handed nullptr / 0.  MAP: rows
+// [ns] and list_off = sel_off (above); !MAP is handed rows = nullptr.
+template <typename T, typename TQ, bool L2, bool PAD, bool RES, bool MAP>
 __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restrict__ x, int64_t ldx,
                                                                const int64_t* __restrict__ list_off, int D,
                                                                const TQ* __restrict__ q, const float* __restrict__ dec,
@@ -261,9 +277,9 @@ __global__ __launch_bounds__(256, 2) void ivf_flat_scan_kernel(const T* __restri
                                                                const int* __restrict__ task_qstart,
                                                                const int* __restrict__ task_qcnt,
                                                                const int* __restrict__ sorted_q, float* __restrict__ dense,
-                                                               int* __restrict__ rowid) {
-    ivf_flat_scan_body<T, TQ, L2, PAD, RES>(x, ldx, list_off, D, q, dec, coarse, ldc, probes, base, nprobe, stride, task_list,
-                                            task_qstart, task_qcnt, sorted_q, dense, rowid);
+                                                               int* __restrict__ rowid, const int64_t* __restrict__ rows) {
+    ivf_flat_scan_body<T, TQ, L2, PAD, RES, MAP>(x, ldx, list_off, D, q, dec, coarse, ldc, probes, base, nprobe, stride, task_list,
+                                                 task_qstart, task_qcnt, sorted_q, dense, rowid, rows);
 }
 
 // ---- host --------------------------------------------------------------------------------------------------------------------
@@ -299,37 +315,44 @@ ivff_ws ivff_layout(int nq, int nprobe, int nlist, int64_t stride) {
     return L;
 }
 
+// rows: the subset search's row list (then list_off is its sel_off), or nullptr; the one place MAP is chosen.
 template <typename T, typename TQ, bool L2, bool RES>
-int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, int D, const TQ* q, const float* dec,
-                     const float* coarse, int64_t ldc, const int* probes, int nprobe, int64_t stride, char* w, const ivff_ws& L,
-                     hipStream_t s) {
+int ivff_launch_scan(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, const int64_t* rows, int D, const TQ* q,
+                     const float* dec, const float* coarse, int64_t ldc, const int* probes, int nprobe, int64_t stride, char* w,
+                     const ivff_ws& L, hipStream_t s) {
     auto I = [&](size_t off) { return (const int*)(w + off); };
     int64_t y = (stride + IVFF_RT - 1) / IVFF_RT;
     if (y > IVFF_Y_MAX) y = IVFF_Y_MAX;
     const dim3 grid((unsigned)L.ub, (unsigned)(y < 1 ? 1 : y));
     const bool vec = (D * (int64_t)sizeof(T)) % 16 == 0 && (ldx * (int64_t)sizeof(T)) % 16 == 0 && !((uintptr_t)x & 15u);
-    const auto kernel = vec ? ivf_flat_scan_kernel<T, TQ, L2, false, RES> : ivf_flat_scan_kernel<T, TQ, L2, true, RES>;
+    const auto kernel = rows ? (vec ? ivf_flat_scan_kernel<T, TQ, L2, false, RES, true> : ivf_flat_scan_kernel<T, TQ, L2, true, RES, true>)
+                             : (vec ? ivf_flat_scan_kernel<T, TQ, L2, false, RES, false> : ivf_flat_scan_kernel<T, TQ, L2, true, RES, false>);
     hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, x, ldx, list_off, D, q, dec, coarse, ldc, probes, I(L.base), nprobe, stride,
                        I(L.task_list), I(L.task_qstart), I(L.task_qcnt), I(L.sorted_q), (float*)(w + L.dense),
-                       (int*)(w + L.rowid));
+                       (int*)(w + L.rowid), rows);
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
 
 // The body of the four entries.  Order of the checks: pointers and signs, shapes, the nq == 0 success, the workspace.
 // dec: the coded store's [step | mid] (T = signed char), not looked at otherwise.  RES: the residual coded form, coarse
-// [nlist][ldc >= D] the centroids the codes are residuals of; not looked at otherwise.
+// [nlist][ldc >= D] the centroids the codes are residuals of; not looked at otherwise.  mapped (the _rows entries): after the
+// argument checks of the twin, rows / sel_off null or ns outside [1, N] is RC_EINVAL; the plan and the scan then read sel_off
+// where they read list_off, and the scan reads x through rows.  Neither is read on the host.
 template <typename T, typename TQ, bool RES = false>
 int ivff_entry(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, const int64_t* ids, int64_t N, int nlist, int D,
                const TQ* q, const float* dec, const float* coarse, int64_t ldc, int nq, const int* probes, int nprobe,
                int64_t stride, int k, int metric,
-               float* scores, int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream) {
+               float* scores, int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream,
+               bool mapped = false, const int64_t* rows = nullptr, int64_t ns = 0, const int64_t* sel_off = nullptr) {
     constexpr bool SQ = std::is_same<T, signed char>::value;
     rc_device_guard device_guard_(h);
     if (!h || !x || (SQ && !dec) || (RES && (!coarse || ldc < D)) || !list_off || !ids || !q || !probes || !scores || !out_ids ||
         !status || N <= 0 || nlist <= 0 || D <= 0 || ldx < D || nq < 0 || nprobe <= 0 || nprobe > nlist || stride <= 0 || k <= 0)
         return RC_EINVAL;
     if (k > ADC_CAND_CAP / 2 || N > 0xFFFFFFFFll || nlist > IVFF_MAX_NLIST || (metric != 0 && metric != 1)) return RC_ESHAPE;
+    if (mapped && (!rows || !sel_off || ns < 1 || ns > N)) return RC_EINVAL;      // the twins leave rows null: !MAP below
+    const int64_t* off = mapped ? sel_off : list_off;        // the cells' offsets the plan and the scan work with
     if (nq == 0) return RC_OK;
     const ivff_ws L = ivff_layout(nq, nprobe, nlist, stride);
     if (!ws || ((uintptr_t)ws & 7u) || ws_bytes < L.total) return RC_EWORKSPACE;
@@ -338,7 +361,7 @@ int ivff_entry(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, 
     auto I = [&](size_t off) { return (int*)(w + off); };
     const int64_t pairs = (int64_t)nq * nprobe;
     RC_HIP_CHECK(h, hipMemsetAsync(w + L.per_cell, 0, L.cell_start - L.per_cell, s));      // per_cell and cursor
-    hipLaunchKernelGGL(ivf_flat_plan_query_kernel, dim3((unsigned)nq), dim3(256), 0, s, list_off, probes, nprobe, nlist, stride,
+    hipLaunchKernelGGL(ivf_flat_plan_query_kernel, dim3((unsigned)nq), dim3(256), 0, s, off, probes, nprobe, nlist, stride,
                        I(L.base), I(L.count), I(L.per_cell), status);
     RC_LAUNCH_CHECK(h);
     hipLaunchKernelGGL(ivf_plan_cells_kernel, dim3(1), dim3(256), 0, s, (const int*)I(L.per_cell), nlist, I(L.cell_start),
@@ -352,10 +375,10 @@ int ivff_entry(rc_handle_t h, const T* x, int64_t ldx, const int64_t* list_off, 
                        I(L.task_list), I(L.task_qstart), I(L.task_qcnt), IVFF_QG);
     RC_LAUNCH_CHECK(h);
     rc_prof_mark(h, RC_PROF_ADC_SCAN, s);
-    int rc = metric ? ivff_launch_scan<T, TQ, true, RES>(h, x, ldx, list_off, D, q, dec, coarse, ldc, probes, nprobe, stride, w,
+    int rc = metric ? ivff_launch_scan<T, TQ, true, RES>(h, x, ldx, off, rows, D, q, dec, coarse, ldc, probes, nprobe, stride, w,
                                                          L, s)
-                    : ivff_launch_scan<T, TQ, false, RES>(h, x, ldx, list_off, D, q, dec, coarse, ldc, probes, nprobe, stride, w,
-                                                          L, s);
+                    : ivff_launch_scan<T, TQ, false, RES>(h, x, ldx, off, rows, D, q, dec, coarse, ldc, probes, nprobe, stride,
+                                                          w, L, s);
     rc_prof_mark(h, RC_PROF_ADC_SCAN, s);
     if (rc != RC_OK) return rc;
     unsigned* cnt = (unsigned*)(w + L.cnt);
@@ -415,4 +438,47 @@ extern "C" int rc_ivf_flat_sq8r_search(rc_handle_t h, const int8_t* x, int64_t l
     return ivff_entry<signed char, float, true>(h, reinterpret_cast<const signed char*>(x), ldx, list_off, ids, N, nlist, D, q, dec,
                                                 coarse, ldc, nq, probes, nprobe, stride, k, metric, scores, out_ids, status,
                                                 qstatus, ws, ws_bytes, stream);
+}
+
+// The subset searches: the arguments of the twin, then rows [ns], ns, sel_off [nlist + 1] (include/repconc_hip.h).
+extern "C" int rc_ivf_flat_search_rows(rc_handle_t h, const float* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                                       int64_t N, int nlist, int D, const float* q, int nq, const int* probes, int nprobe,
+                                       int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status,
+                                       int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream, const int64_t* rows, int64_t ns,
+                                       const int64_t* sel_off) {
+    return ivff_entry<float, float>(h, x, ldx, list_off, ids, N, nlist, D, q, nullptr, nullptr, 0, nq, probes, nprobe, stride, k,
+                                    metric, scores, out_ids, status, qstatus, ws, ws_bytes, stream, true, rows, ns, sel_off);
+}
+
+extern "C" int rc_ivf_flat_f16_search_rows(rc_handle_t h, const uint16_t* x, int64_t ldx, const int64_t* list_off,
+                                           const int64_t* ids, int64_t N, int nlist, int D, const uint16_t* q, int nq,
+                                           const int* probes, int nprobe, int64_t stride, int k, int metric, float* scores,
+                                           int64_t* out_ids, int* status, int* qstatus, void* ws, size_t ws_bytes,
+                                           rc_stream_t stream, const int64_t* rows, int64_t ns, const int64_t* sel_off) {
+    return ivff_entry<_Float16, _Float16>(h, reinterpret_cast<const _Float16*>(x), ldx, list_off, ids, N, nlist, D,
+                                          reinterpret_cast<const _Float16*>(q), nullptr, nullptr, 0, nq, probes, nprobe, stride, k,
+                                          metric, scores, out_ids, status, qstatus, ws, ws_bytes, stream, true, rows, ns, sel_off);
+}
+
+extern "C" int rc_ivf_flat_sq8_search_rows(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off, const int64_t* ids,
+                                           int64_t N, int nlist, int D, const float* q, int nq, const float* dec, const int* probes,
+                                           int nprobe, int64_t stride, int k, int metric, float* scores, int64_t* out_ids,
+                                           int* status, int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream,
+                                           const int64_t* rows, int64_t ns, const int64_t* sel_off) {
+    if (D > rc_dense_sq8_max_d()) return RC_ESHAPE;
+    return ivff_entry<signed char, float>(h, reinterpret_cast<const signed char*>(x), ldx, list_off, ids, N, nlist, D, q, dec,
+                                          nullptr, 0, nq, probes, nprobe, stride, k, metric, scores, out_ids, status, qstatus, ws,
+                                          ws_bytes, stream, true, rows, ns, sel_off);
+}
+
+extern "C" int rc_ivf_flat_sq8r_search_rows(rc_handle_t h, const int8_t* x, int64_t ldx, const int64_t* list_off,
+                                            const int64_t* ids, int64_t N, int nlist, int D, const float* q, int nq,
+                                            const float* dec, const float* coarse, int64_t ldc, const int* probes, int nprobe,
+                                            int64_t stride, int k, int metric, float* scores, int64_t* out_ids, int* status,
+                                            int* qstatus, void* ws, size_t ws_bytes, rc_stream_t stream, const int64_t* rows,
+                                            int64_t ns, const int64_t* sel_off) {
+    if (D > rc_dense_sq8_max_d()) return RC_ESHAPE;
+    return ivff_entry<signed char, float, true>(h, reinterpret_cast<const signed char*>(x), ldx, list_off, ids, N, nlist, D, q, dec,
+                                                coarse, ldc, nq, probes, nprobe, stride, k, metric, scores, out_ids, status,
+                                                qstatus, ws, ws_bytes, stream, true, rows, ns, sel_off);
 }

@@ -21,6 +21,8 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
                                   metric, by_residual=False)            be passed: the vectors themselves are encoded
     index.search(x, k, params=faiss.SearchParameters(sel=               not in the reference; subset search of the flat indexes
         faiss.IDSelectorRange / Batch / Array / Bitmap / Not(...)))     (fp32 and fp16 storage, both metrics; selector.py)
+    index.search(x, k, params=faiss.SearchParametersIVF(sel=...,        not in the reference; the same selectors, and nprobe, on
+        nprobe=...))                                                    IndexIVFFlat / IndexIVFScalarQuantizer (ivf_flat.py)
     faiss.write_index(index, path) / faiss.read_index(path)             run_warmup.py:187, run_repconc_eval.py:42
     faiss.omp_set_num_threads(n)                                        run_repconc_eval.py:149 (no-op: the scan runs on the GPU)
 
@@ -37,7 +39,7 @@ from .faiss_io import read_index, write_index  # noqa: F401  (re-exported)
 from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex  # noqa: F401  (METRIC_L2 re-exported)
 from .ivf_flat import IVFFlatIndex
 from .selector import (IDSelectorArray, IDSelectorBatch, IDSelectorBitmap, IDSelectorNot, IDSelectorRange,  # noqa: F401
-                       SearchParameters)
+                       SearchParameters, SearchParametersIVF)
 
 
 def IndexPQ(d: int, M: int, nbits: int = 8, metric=METRIC_INNER_PRODUCT) -> PQIndex:

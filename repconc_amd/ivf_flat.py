@@ -49,6 +49,17 @@ residuals of clustered rows span less than the rows do, so the same byte buys a 
     centroid once per value on its way into the scan's tile); ties, padding, probing and the limits are unchanged.
 Index files, `create_index` / `run_dense_eval` and the Faiss shim do not serve this form.
 
+Subset search: `search(x, k, params=SearchParameters(sel=...))` (or `SearchParametersIVF(sel=, nprobe=)`) with the selectors of
+`repconc_amd.selector`, for every storage above.  The result is what an `IVFFlatIndex` with the same coarse centroids (and the
+same range) would return if it held only the selected vectors, each under the cell it has here: the same probes, ids and score
+bits equal, ties to the lower corpus id, padding where the probed cells hold fewer than k selected rows; probing every cell
+returns what the flat index returns under the same selector.  Nothing is copied: `_selection` turns the selector into the
+list-major positions of the selected rows and their offsets per cell (cached on the selector until the store changes), the
+plan reads those offsets in place of `list_off`, and the scan reads the store through the positions
+(`ops.ivf_flat_search(rows=, sel_off=)`), so the score rows, the workspace and the rows read follow the selection.  Ids outside
+the index are ignored; an empty selection is all padding without a launch; `params=None`, `SearchParameters()` and `sel=None`
+are the plain search.
+
 On the CPU device (`device="cpu"`: the build side with torch operators, for inspection and tests; the searches are GPU only)
 cells are assigned by the same rule, argmin_l (||c_l||^2 - 2 <x, c_l>), first minimum, and codes decode with the same single
 rounding.
@@ -59,6 +70,7 @@ new ones: while it runs, a second copy of the whole store exists on the device.
 from __future__ import annotations
 
 import functools
+import itertools
 from typing import Optional
 
 import numpy as np
@@ -69,6 +81,9 @@ from .dense_index import SQ8_ROWS_PER_STEP, sq8_encode  # noqa: F401  (names thi
 from .dense_index import _sq8_encode_chunks, sq8_train_range
 from .index import METRIC_INNER_PRODUCT, METRIC_L2, _as_device, _as_f32_tensor
 from .ivf import CoarseProbe, coarse_assign, coarse_kmeans
+from .selector import IDSelector, SearchParameters
+
+_GENERATION = itertools.count(1)      # one number per store ever built, over all indexes: the key of a selector's cached selection
 
 
 class IVFFlatIndex(CoarseProbe):
@@ -113,6 +128,7 @@ class IVFFlatIndex(CoarseProbe):
         self.list_off = torch.zeros((self.nlist + 1,), dtype=torch.int64, device=self.device)
         self.ntotal = 0
         self._sizes_desc = np.zeros(0, np.int64)      # cell sizes, descending (host copy): bounds a query's score row
+        self._generation = next(_GENERATION)
 
     def _rows(self, x, what: str) -> torch.Tensor:
         xt = _as_f32_tensor(x)
@@ -211,6 +227,7 @@ class IVFFlatIndex(CoarseProbe):
         self.list_off = torch.cat([torch.zeros(1, dtype=torch.int64, device=self.device), torch.cumsum(cnt, 0)]).contiguous()
         self.ntotal = int(xs.shape[0])
         self._sizes_desc = np.sort(cnt.cpu().numpy())[::-1].astype(np.int64)
+        self._generation = next(_GENERATION)
 
     def set_lists(self, x, list_ids) -> None:
         """Replaces the content by the rows x [N, d] (corpus order: row i has id i) stored under the given cells list_ids [N]."""
@@ -281,28 +298,63 @@ class IVFFlatIndex(CoarseProbe):
         return (torch.full((nq, k), pad, dtype=torch.float32, device=self.device),
                 torch.full((nq, k), -1, dtype=torch.int64, device=self.device))
 
-    def search(self, x, k: int, nprobe: Optional[int] = None):
-        """(scores or distances [nq, k], ids [nq, k]) over the `nprobe` best cells of every query (default: the index's `nprobe`
-        attribute, as with a Faiss IVF index).  numpy in -> numpy out, tensors in -> tensors out."""
+    @staticmethod
+    def _params(params):
+        """(selector or None, nprobe or None) of `params`: None, a SearchParameters or a SearchParametersIVF."""
+        if params is None:
+            return None, None
+        if not isinstance(params, SearchParameters):
+            raise ValueError("search: params must be a SearchParameters / SearchParametersIVF or None")
+        if params.sel is not None and not isinstance(params.sel, IDSelector):
+            raise ValueError("search: params.sel must be an IDSelector or None")
+        return params.sel, getattr(params, "nprobe", None)
+
+    def _selection(self, sel: IDSelector):
+        """(rows, sel_off, sizes_desc) of a selector over this store: rows int64 [ns], the list-major positions of the rows
+        whose corpus id it holds, ascending (so grouped by cell, and ascending by corpus id inside a cell: the store is stably
+        sorted); sel_off int64 [nlist + 1], the offsets of the cells inside rows; sizes_desc, the host copy of the selected
+        sizes per cell, descending.  A range of corpus ids is no slice of a list-major store: every selector takes this path.
+        Valid by construction (`ops.ivf_flat_search(check_rows=False)`); cached on the selector until the store changes."""
+        if sel._ivf_key != self._generation:
+            member = sel._mask(self.ntotal, 0, self.device)[self.ids]
+            rows = torch.nonzero(member).flatten().contiguous()
+            sel_off = torch.searchsorted(rows, self.list_off).contiguous()
+            sizes = (sel_off[1:] - sel_off[:-1]).cpu().numpy()
+            sel._ivf = (rows, sel_off, np.sort(sizes)[::-1].astype(np.int64))
+            sel._ivf_key = self._generation
+        return sel._ivf
+
+    def search(self, x, k: int, nprobe: Optional[int] = None, params: Optional[SearchParameters] = None):
+        """(scores or distances [nq, k], ids [nq, k]) over the `nprobe` best cells of every query (default: `params.nprobe` of a
+        `SearchParametersIVF`, then the index's `nprobe` attribute, as with a Faiss IVF index).  numpy in -> numpy out, tensors
+        in -> tensors out.  params: None or `SearchParameters()` is the whole store; `SearchParameters(sel=...)` answers over
+        the selected ids only, in place (the module's text)."""
+        sel, params_nprobe = self._params(params)
         q, as_numpy = self._queries(x, k)
         if self.coarse is None:
             raise ValueError("search: train() or set_coarse() the coarse quantiser first")
-        nprobe = min(max(int(self.nprobe if nprobe is None else nprobe), 1), self.nlist)
-        return self._answer(q, lambda qd: self.probe(qd, nprobe, ordered=False), int(k), as_numpy)
+        if nprobe is None:
+            nprobe = self.nprobe if params_nprobe is None else params_nprobe
+        nprobe = min(max(int(nprobe), 1), self.nlist)
+        return self._answer(q, lambda qd: self.probe(qd, nprobe, ordered=False), int(k), as_numpy, sel)
 
-    def _answer(self, q: torch.Tensor, probes_of, k: int, as_numpy: bool):
+    def _answer(self, q: torch.Tensor, probes_of, k: int, as_numpy: bool, sel: Optional[IDSelector] = None):
         """The common end of `search` and `_search_probes`: the queries on the device, all padding without a launch for an empty
-        index or no query, `_run` on probes_of(queries on the device) otherwise, numpy out for numpy in."""
+        index, no query or an empty selection, `_run` on probes_of(queries on the device) otherwise, numpy out for numpy in."""
         q = q.to(self.device, torch.float32).contiguous()
-        if q.shape[0] == 0 or self.ntotal == 0:
+        selection = None if sel is None or self.ntotal == 0 else self._selection(sel)
+        if q.shape[0] == 0 or self.ntotal == 0 or (selection is not None and selection[0].numel() == 0):
             self.last_search_stats = {"queries": int(q.shape[0]), "fallback_queries": 0, "chunks": 0}
             scores, ids = self._padding(q.shape[0], k)
         else:
-            scores, ids = self._run(q, probes_of(q), k)
+            scores, ids = self._run(q, probes_of(q), k, selection)
+        if sel is not None:
+            self.last_search_stats["rows_selected"] = 0 if selection is None else int(selection[0].numel())
         return (scores.cpu().numpy(), ids.cpu().numpy()) if as_numpy else (scores, ids)
 
-    def _search_probes(self, x, probes, k: int):
+    def _search_probes(self, x, probes, k: int, params: Optional[SearchParameters] = None):
         """`search` with explicit probes [nq, nprobe] (distinct cells of [0, nlist) per query, any order)."""
+        sel, _ = self._params(params)
         q, as_numpy = self._queries(x, k)
         pr = probes if isinstance(probes, torch.Tensor) else torch.from_numpy(np.asarray(probes))
         if pr.dim() != 2 or pr.shape[0] != q.shape[0] or not 1 <= pr.shape[1] <= self.nlist or pr.dtype.is_floating_point:
@@ -310,7 +362,7 @@ class IVFFlatIndex(CoarseProbe):
         pr = torch.sort(pr.to(torch.int32), dim=1).values
         if pr.numel() and (int(pr.min()) < 0 or int(pr.max()) >= self.nlist or bool((pr[:, 1:] == pr[:, :-1]).any())):
             raise ValueError(f"_search_probes: a query's probes must be distinct cells of [0, {self.nlist})")
-        return self._answer(q, lambda qd: pr.to(self.device).contiguous(), int(k), as_numpy)
+        return self._answer(q, lambda qd: pr.to(self.device).contiguous(), int(k), as_numpy, sel)
 
     def _chunk_queries(self, nq: int, nprobe: int, stride: int) -> int:
         """The most queries (>= 1) whose workspace stays under MAX_WS_BYTES."""
@@ -325,10 +377,12 @@ class IVFFlatIndex(CoarseProbe):
                 hi = mid
         return lo
 
-    def _run(self, q: torch.Tensor, probes: torch.Tensor, k: int):
-        """q [nq, d] fp32 on the device, probes [nq, nprobe] int32 ascending per query; nq > 0, ntotal > 0."""
+    def _run(self, q: torch.Tensor, probes: torch.Tensor, k: int, selection=None):
+        """q [nq, d] fp32 on the device, probes [nq, nprobe] int32 ascending per query; nq > 0, ntotal > 0.  selection: None, or
+        the non-empty (rows, sel_off, sizes_desc) of `_selection`: the score rows, the workspace and the chunks follow it."""
         nq, nprobe = probes.shape
-        stride = (max(4, int(self._sizes_desc[:nprobe].sum())) + 3) // 4 * 4      # the nprobe largest cells bound a score row
+        sizes_desc = self._sizes_desc if selection is None else selection[2]
+        stride = (max(4, int(sizes_desc[:nprobe].sum())) + 3) // 4 * 4            # the nprobe largest cells bound a score row
         step = self._chunk_queries(nq, nprobe, stride)
         if self.by_residual:                  # the search of this store with the store's own operands, chosen once
             search = functools.partial(ops.ivf_flat_sq8r_search, self.xb, self._dec, self.coarse)
@@ -336,6 +390,8 @@ class IVFFlatIndex(CoarseProbe):
             search = functools.partial(ops.ivf_flat_sq8_search, self.xb, self._dec)
         else:
             search = functools.partial(ops.ivf_flat_search, self.xb)
+        if selection is not None:             # valid by construction: no check, no synchronisation
+            search = functools.partial(search, rows=selection[0], sel_off=selection[1], check_rows=False)
         parts, fallback, chunks = [], 0, 0
         for c0 in range(0, nq, step):
             qc, pc = q[c0:c0 + step], probes[c0:c0 + step]
@@ -347,7 +403,7 @@ class IVFFlatIndex(CoarseProbe):
             if st & 2:
                 # more than 16384 probed rows tie at these queries' k-th score: the exact dense search over their probed rows
                 bad = torch.nonzero(qstatus & 2).flatten()
-                scores[bad], ids[bad] = self._search_exact_probed(qc[bad], pc[bad], k)
+                scores[bad], ids[bad] = self._search_exact_probed(qc[bad], pc[bad], k, selection)
                 fallback += int(bad.numel())
             parts.append((scores, ids))
         self.last_search_stats = {"queries": int(nq), "fallback_queries": fallback, "chunks": chunks}
@@ -355,19 +411,22 @@ class IVFFlatIndex(CoarseProbe):
             return parts[0]
         return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
 
-    def _search_exact_probed(self, q: torch.Tensor, probes: torch.Tensor, k: int):
+    def _search_exact_probed(self, q: torch.Tensor, probes: torch.Tensor, k: int, selection=None):
         """The answer for ANY content of the probed cells, query by query: the probed rows gathered in corpus-id order (the
         search's tie rule becomes the exact entry's "lower row"), then the exact route of the flat search of this metric and
         storage (int8: the fp32 exact route over the gathered rows, decoded, by_residual with their centroids added).  Slow —
-        one gather of the probed rows per query — and only reached for queries the selection could not decide."""
+        one gather of the probed rows per query — and only reached for queries the selection could not decide.  selection
+        (`_selection`): only the selected rows of the probed cells are gathered."""
         exact = ((ops.dense_search_exact, ops.dense_search_f16_exact),
                  (ops.dense_search_l2_exact, ops.dense_search_l2_f16_exact))[self.metric_type == METRIC_L2][self.storage == "float16"]
         scores, ids = self._padding(q.shape[0], k)
-        off = self.list_off
+        off = self.list_off if selection is None else selection[1]
         for j in range(q.shape[0]):
             cells = probes[j].long()
             a, b = off[cells].tolist(), off[cells + 1].tolist()
             rows = torch.cat([torch.arange(lo, hi, device=self.device) for lo, hi in zip(a, b)])
+            if selection is not None:
+                rows = selection[0][rows]
             if rows.numel() == 0:
                 continue
             corpus = self.ids[rows]

@@ -1450,52 +1450,107 @@ def ivf_flat_search_ws_bytes(nq: int, nprobe: int, nlist: int, stride: int) -> i
 
 
 def ivf_flat_search(xb: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor, q: torch.Tensor, probes: torch.Tensor,
-                    stride: int, k: int, metric: int = METRIC_INNER_PRODUCT):
+                    stride: int, k: int, metric: int = METRIC_INNER_PRODUCT, *, rows: Optional[torch.Tensor] = None,
+                    sel_off: Optional[torch.Tensor] = None, check_rows: bool = True):
     """One call of the exact IVF search over dense rows (csrc/ivf_flat.hip): `xb` [N, D] fp32 or fp16, list-major; `list_off`
     [nlist + 1] int64; `ids` [N] int64 corpus positions; `q` [nq, D] (rounded to fp16 for an fp16 store, as `dense_search_f16`
     rounds it); `probes` [nq, nprobe] int32, distinct cells per query in ascending order (rc_ivf_select_probes); `stride` >= the
     rows any nprobe cells hold.  Returns (scores or distances [nq, k], ids [nq, k], status [1] int32, qstatus [nq] int32) without
     synchronising: bit 1 of a query's status = more than 16384 of its probed rows tie at its k-th score and its row of the
     output is not valid (`IVFFlatIndex` answers those queries by the exact search over their probed rows); bit 2 of `status` =
-    a probe outside [0, nlist) or a `stride` too small.  Argument errors are ValueError before any device work."""
-    return _ivf_flat_search("ivf_flat_search", "xb", xb, None, None, list_off, ids, q, probes, stride, k, metric)
+    a probe outside [0, nlist) or a `stride` too small.  Argument errors are ValueError before any device work.
+    rows, sel_off (both or neither): the search runs over the selected rows of the store in place (rc_ivf_flat_search_rows).
+    `rows` int64 [ns]: the list-major positions (rows of `xb`) selected, strictly ascending, in [0, N), on the store's device;
+    `sel_off` int64 [nlist + 1]: the offsets of the cells inside `rows`, from 0 to ns, every row of segment c inside
+    [list_off[c], list_off[c + 1]).  The result is that of a store holding only those rows under the same cells, with the ids
+    of this one; `stride` then bounds the SELECTED rows of any nprobe cells.  An empty `rows` returns padding without a
+    launch.  check_rows=True verifies the pair on the device (one synchronisation) and raises ValueError before any library
+    call; the library reads x[rows[i]] unchecked, so check_rows=False is for lists valid by construction
+    (`IVFFlatIndex._selection`)."""
+    return _ivf_flat_search("ivf_flat_search", "xb", xb, None, None, list_off, ids, q, probes, stride, k, metric, rows, sel_off,
+                            check_rows)
 
 
 def ivf_flat_sq8_search(xb8: torch.Tensor, dec: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor, q: torch.Tensor,
-                        probes: torch.Tensor, stride: int, k: int, metric: int = METRIC_INNER_PRODUCT):
+                        probes: torch.Tensor, stride: int, k: int, metric: int = METRIC_INNER_PRODUCT, *,
+                        rows: Optional[torch.Tensor] = None, sel_off: Optional[torch.Tensor] = None, check_rows: bool = True):
     """`ivf_flat_search` over a list-major store of 8-bit scalar-quantiser codes (rc_ivf_flat_sq8_search): `xb8` [N, D] int8 =
     c - 128, `dec` [2, D] fp32 = the steps, then the mids (`dense_search_sq8`'s), `q` [nq, D] fp32, not rounded; everything
     else, the returns and the status bits as `ivf_flat_search`.  Scores are bit for bit those of `ivf_flat_search` over
     `dense_sq8_decode(xb8, dec)`, under either metric.  Any row pitch >= D and any alignment (a column slice of a wider
-    matrix is read in place).  D <= 65536; argument errors are ValueError before any device work."""
-    return _ivf_flat_search("ivf_flat_sq8_search", "xb8", xb8, dec, None, list_off, ids, q, probes, stride, k, metric)
+    matrix is read in place).  D <= 65536; argument errors are ValueError before any device work.  rows, sel_off,
+    check_rows: as `ivf_flat_search` (rc_ivf_flat_sq8_search_rows)."""
+    return _ivf_flat_search("ivf_flat_sq8_search", "xb8", xb8, dec, None, list_off, ids, q, probes, stride, k, metric, rows,
+                            sel_off, check_rows)
 
 
 def ivf_flat_sq8r_search(xb8: torch.Tensor, dec: torch.Tensor, coarse: torch.Tensor, list_off: torch.Tensor, ids: torch.Tensor,
-                         q: torch.Tensor, probes: torch.Tensor, stride: int, k: int, metric: int = METRIC_INNER_PRODUCT):
+                         q: torch.Tensor, probes: torch.Tensor, stride: int, k: int, metric: int = METRIC_INNER_PRODUCT, *,
+                         rows: Optional[torch.Tensor] = None, sel_off: Optional[torch.Tensor] = None, check_rows: bool = True):
     """`ivf_flat_sq8_search` over codes of residuals (rc_ivf_flat_sq8r_search): the rows of cell l hold the codes of x -
     `coarse`[l], `coarse` [nlist, D] fp32 on the device of the store (any row pitch >= D), and a stored value is
     fp32(fmaf(c', step, mid) + coarse[l][d]) — the decode, then one separate fp32 addition.  Scores are bit for bit those of
     `ivf_flat_search` over `dense_sq8_decode(xb8, dec)` + the centroid of every row's cell, under either metric.  The checks
-    of `ivf_flat_sq8_search`, and `coarse` must be float32 [nlist, D]."""
+    of `ivf_flat_sq8_search`, and `coarse` must be float32 [nlist, D].  rows, sel_off, check_rows: as `ivf_flat_search`
+    (rc_ivf_flat_sq8r_search_rows); a selected row keeps the centroid of its cell."""
     if not isinstance(coarse, torch.Tensor):
         raise ValueError("ivf_flat_sq8r_search: coarse must be a float32 tensor [nlist, D]")
-    return _ivf_flat_search("ivf_flat_sq8r_search", "xb8", xb8, dec, coarse, list_off, ids, q, probes, stride, k, metric)
+    return _ivf_flat_search("ivf_flat_sq8r_search", "xb8", xb8, dec, coarse, list_off, ids, q, probes, stride, k, metric, rows,
+                            sel_off, check_rows)
 
 
-def _ivf_flat_call(h, xb, list_off, ids, q, dec, coarse, probes, stride, k, l2, scores, out_ids, status, qstatus, ws, stream):
+def _ivf_flat_call(h, xb, list_off, ids, q, dec, coarse, probes, stride, k, l2, scores, out_ids, status, qstatus, ws, stream,
+                   rows=None, sel_off=None):
     """(name, argument tuple) of one call of the four rc_ivf_flat*_search entries, chosen by the store's type and by which of
     `dec` / `coarse` are tensors.  The header's order: h, x, ldx, list_off, ids, N, nlist, D, q, nq, [dec, [coarse, ldc]], probes,
-    nprobe, stride, k, metric, the outputs, the workspace, the stream.  Touches no device and loads no library."""
+    nprobe, stride, k, metric, the outputs, the workspace, the stream.  rows: the entry of the same name with _rows, and `rows,
+    ns, sel_off` after the stream.  Touches no device and loads no library."""
     (N, D), nlist = xb.shape, list_off.numel() - 1
     side = () if dec is None else (_p(dec),) if coarse is None else (_p(dec), _p(coarse), coarse.stride(0) if nlist > 1 else D)
     form = "_f16" if xb.dtype == torch.float16 else "" if dec is None else "_sq8" if coarse is None else "_sq8r"
-    return f"rc_ivf_flat{form}_search", (h, _p(xb), xb.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q),
-                                         q.shape[0], *side, _p(probes), probes.shape[1], int(stride), int(k), int(l2), _p(scores),
-                                         _p(out_ids), _p(status), _p(qstatus), _p(ws), ws.numel(), stream)
+    sub = () if rows is None else (_p(rows), rows.numel(), _p(sel_off))
+    return f"rc_ivf_flat{form}_search" + ("_rows" if sub else ""), (
+        h, _p(xb), xb.stride(0) if N > 1 else D, _p(list_off), _p(ids), N, nlist, D, _p(q), q.shape[0], *side, _p(probes),
+        probes.shape[1], int(stride), int(k), int(l2), _p(scores), _p(out_ids), _p(status), _p(qstatus), _p(ws), ws.numel(), stream,
+        *sub)
 
 
-def _ivf_flat_search(name, store, xb, dec, coarse, list_off, ids, q, probes, stride, k, metric):
+def _ivf_flat_rows(name: str, rows, sel_off, xb: torch.Tensor, list_off: torch.Tensor, check_rows: bool):
+    """The (rows, sel_off) pair of an IVF-flat subset search, refused with a ValueError before anything reaches the library.
+    Always: both given, int64, 1-d, rows on the device of the store, sel_off [nlist + 1].  check_rows (one synchronisation):
+    rows strictly ascending in [0, N); sel_off non-decreasing from 0 to ns; every row of segment c in [list_off[c],
+    list_off[c + 1]).  Returns the pair, contiguous, sel_off on the device of rows."""
+    if rows is None or sel_off is None:
+        raise ValueError(f"{name}: rows and sel_off come together (both, or neither)")
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1 or rows.dtype != torch.int64:
+        raise ValueError(f"{name}: rows must be a 1-d int64 tensor of list-major row positions")
+    if rows.device != xb.device:
+        raise ValueError(f"{name}: rows must be on the device of the store ({xb.device}), got {rows.device}")
+    N, nlist = xb.shape[0], list_off.numel() - 1
+    if not isinstance(sel_off, torch.Tensor) or sel_off.dtype != torch.int64 or sel_off.shape != (nlist + 1,):
+        raise ValueError(f"{name}: sel_off must be int64 [nlist + 1] = [{nlist + 1}]")
+    ns = rows.numel()
+    if ns > N:
+        raise ValueError(f"{name}: {ns} rows selected of a store of {N}")
+    sel_off = sel_off.to(rows.device)
+    if check_rows:
+        lo = list_off.to(rows.device)
+        ok = (sel_off[0] == 0) & (sel_off[-1] == ns) & (sel_off[1:] >= sel_off[:-1]).all()
+        if ns:
+            ok = ok & (rows[0] >= 0) & (rows[-1] < N)
+            if ns > 1:
+                ok = ok & (rows[1:] > rows[:-1]).all()
+            # the cell a row is LISTED under (its segment of sel_off) must be the cell that holds it (its segment of list_off)
+            at = torch.arange(ns, device=rows.device)
+            ok = ok & (torch.searchsorted(sel_off, at, right=True) == torch.searchsorted(lo, rows, right=True)).all()
+        if not bool(ok):
+            raise ValueError(f"{name}: rows must be strictly ascending positions in [0, {N}), sel_off non-decreasing from 0 to "
+                             f"{ns}, and every row of segment c inside [list_off[c], list_off[c + 1])")
+    return rows.contiguous(), sel_off.contiguous()
+
+
+def _ivf_flat_search(name, store, xb, dec, coarse, list_off, ids, q, probes, stride, k, metric, rows=None, sel_off=None,
+                     check_rows=True):
     """The body of the three IVF-flat searches.  store "xb": the fp32 / fp16 store, queries of any type rounded to the store's;
     "xb8": int8 codes with `dec`, fp32 queries, and `coarse` None = the vectors themselves are encoded, else their residuals."""
     coded = store == "xb8"
@@ -1529,6 +1584,8 @@ def _ivf_flat_search(name, store, xb, dec, coarse, list_off, ids, q, probes, str
         raise ValueError(f"{name}: 1 <= N < 2^32")
     if int(stride) < 1:
         raise ValueError(f"{name}: stride must be >= 1")
+    if rows is not None or sel_off is not None:
+        rows, sel_off = _ivf_flat_rows(name, rows, sel_off, xb, list_off, check_rows)
     _need_cuda(xb, dec, coarse, list_off, ids, q, probes)
     if coarse is not None and coarse.device != xb.device:
         raise ValueError(f"{name}: coarse must be on the device of the store")
@@ -1546,13 +1603,17 @@ def _ivf_flat_search(name, store, xb, dec, coarse, list_off, ids, q, probes, str
     status, qstatus = flags[:1], flags[1:]
     if nq == 0:
         return scores, out_ids, status, qstatus
+    if rows is not None and rows.numel() == 0:               # an empty selection: all padding, no launch
+        scores.fill_(float("inf") if l2 else float("-inf"))
+        out_ids.fill_(-1)
+        return scores, out_ids, status, qstatus
     if coarse is not None and (coarse.stride(1) != 1 or (nlist > 1 and coarse.stride(0) < D)):
         coarse = coarse.contiguous()
     lib, h, s, _ = _ctx(q)
     ws = torch.empty((lib.rc_ivf_flat_search_ws_bytes(nq, nprobe, nlist, int(stride)),), dtype=torch.uint8,
                      device=q.device)                                        # released in stream order
     entry, args = _ivf_flat_call(h, xb, list_off, ids, q, dec, coarse, probes, stride, k, l2, scores, out_ids, status, qstatus,
-                                 ws, s)
+                                 ws, s, rows, sel_off)
     _lib.check(getattr(lib, entry)(*args), entry, h)
     return scores, out_ids, status, qstatus
 

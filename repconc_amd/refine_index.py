@@ -12,6 +12,7 @@ both from one pass over the corpus, with the re-ranking vectors in the rotated s
 """
 from __future__ import annotations
 
+import inspect
 import math
 
 from . import ops
@@ -26,6 +27,10 @@ class RefineIndex:
         if not callable(getattr(refine, "rerank", None)) or not hasattr(refine, "ntotal"):
             raise ValueError("RefineIndex: refine must be a flat index (rerank(x, cand_ids, k) and ntotal)")
         self.base = base
+        try:                          # decided once: does base.search(x, k, ..., params=) exist
+            self._base_takes_params = "params" in inspect.signature(base.search).parameters
+        except (TypeError, ValueError):           # a callable without an inspectable signature takes none
+            self._base_takes_params = False
         self.refine = refine
         self.k_factor = k_factor      # a plain attribute, as in Faiss
         self._check_metric()
@@ -54,13 +59,20 @@ class RefineIndex:
             raise ValueError("RefineIndex: k must be >= 1")
         return min(max(k, int(math.ceil(k * float(self.k_factor)))), self.MAX_KC)
 
-    def search(self, x, k: int, x_refine=None, **base_kwargs):
+    def search(self, x, k: int, x_refine=None, params=None, **base_kwargs):
         """(scores or distances [nq, k], ids [nq, k]) of the `k` best of `base`'s `candidates(k)` results, re-ranked by
         `refine`.  x_refine: the queries in the space of the refine vectors when it is not the base's (default: x).  Further
         keyword arguments go to `base.search` (`nprobe=` of an IVF base).  Slots `base` left unfilled (-1) are skipped; what is
-        missing after them is padded as `refine.search` pads."""
+        missing after them is padded as `refine.search` pads.  params (`SearchParameters(sel=...)`): handed to a base whose
+        `search` takes them — a flat index that serves the subset search, an `IVFFlatIndex`; the candidates are then selected
+        ids already and the re-rank needs nothing.  Refused with a ValueError: here, for a base whose `search` has no `params`
+        argument (`PQIndex`, `IVFPQIndex`); by the base itself, for a flat index whose storage or screen serves no subset search."""
         self._check_metric()
         if self.refine.ntotal != self.base.ntotal:
             raise ValueError(f"RefineIndex: base holds {self.base.ntotal} rows, refine {self.refine.ntotal}")
+        if params is not None:
+            if not self._base_takes_params:
+                raise ValueError(f"RefineIndex: {type(self.base).__name__}.search takes no params (no subset search)")
+            base_kwargs["params"] = params
         _, ids = self.base.search(x, self.candidates(k), **base_kwargs)
         return self.refine.rerank(x if x_refine is None else x_refine, ids, int(k))

@@ -1,11 +1,14 @@
-"""Id selectors for the subset search of the flat dense indexes: `index.search(x, k, params=SearchParameters(sel=...))`,
-the names and meanings of Faiss's `IDSelector` family (not in the reference, which only ever searches whole stores).
+"""Id selectors for the subset search of the flat dense indexes and of `IVFFlatIndex`: `index.search(x, k,
+params=SearchParameters(sel=...))`, the names and meanings of Faiss's `IDSelector` family (not in the reference, which only ever
+searches whole stores).
 
 A selector holds EXTERNAL ids (row + the index's `id_offset`).  `sel.rows(ntotal, id_offset, device)` turns it into what the
 kernels read: the int64 rows inside [0, ntotal), strictly ascending, no row twice (`ops.dense_search(rows=...)`).  Ids outside
 the index are ignored and duplicates collapse — a Faiss selector's `is_member` simply never matches them — so the list is
 valid by construction and the indexes pass it on with `check_rows=False`.  The list is cached on the selector per
 (ntotal, id_offset, device): a selector reused across batches is built once, and an index that has grown builds it again.
+`IVFFlatIndex` keeps its rows list-major, not in corpus order: it takes the selector's `_mask` and builds its own pair
+(positions, offsets per cell) from it, cached on the selector too (`IVFFlatIndex._selection`).
 Everything here is torch on whatever device is asked for, CPU included; nothing loads the library.
 """
 from __future__ import annotations
@@ -29,6 +32,9 @@ class IDSelector:
     def __init__(self):
         self._key = None
         self._rows = None
+        self._ivf_key = None          # IVFFlatIndex._selection's one-entry cache: the store's generation number (unique over
+                                      # all indexes, so it names the index too) ...
+        self._ivf = None              # ... and the (rows, sel_off, sizes_desc) built for it
 
     def rows(self, ntotal: int, id_offset: int = 0, device=None) -> torch.Tensor:
         """int64 [ns]: the rows r in [0, ntotal), ascending and unique, whose id r + id_offset the selector holds."""
@@ -122,3 +128,14 @@ class SearchParameters:
         if sel is not None and not isinstance(sel, IDSelector):
             raise ValueError("SearchParameters: sel must be an IDSelector or None")
         self.sel = sel
+
+
+class SearchParametersIVF(SearchParameters):
+    """Faiss's `SearchParametersIVF`: `sel` as above, and `nprobe`, the cells probed by this call (None: the index's
+    attribute).  `IVFFlatIndex.search` takes either class; its explicit `nprobe=` argument wins over this one."""
+
+    def __init__(self, sel: Optional[IDSelector] = None, nprobe: Optional[int] = None):
+        super().__init__(sel)
+        if nprobe is not None and (isinstance(nprobe, bool) or int(nprobe) != nprobe or int(nprobe) < 1):
+            raise ValueError("SearchParametersIVF: nprobe must be an integer >= 1 or None")
+        self.nprobe = None if nprobe is None else int(nprobe)
