@@ -22,6 +22,7 @@ def lib():
         build()
         _lib = C.CDLL(_SO)
         _lib.orc_num_threads.restype = C.c_int
+        _lib.orc_dsub_max.restype = C.c_int
         _lib.orc_quantize.restype = C.c_int
         _lib.orc_sinkhorn_codes.restype = C.c_int
     return _lib
@@ -40,12 +41,21 @@ def set_num_threads(n: int):
     lib().orc_set_num_threads(int(n))
 
 
+def _check_width(dsub):
+    """The C distance routine squares one sub-vector into a fixed buffer of orc_dsub_max() + 1 floats (8191: the widest
+    sub-vector the HIP side takes, RC_DSUB_RT_MAX); a wider one is refused here, not written past that buffer."""
+    lim = lib().orc_dsub_max()
+    if not 1 <= dsub <= lim:
+        raise ValueError(f"sub-vector width {dsub} is outside the C oracle's range 1 .. {lim}")
+
+
 def quantize(x, centroids, use_constraint, eps=0.003, iters=100):
     x = np.ascontiguousarray(x, np.float32)
     Cn = np.ascontiguousarray(centroids, np.float32)
     B, D = x.shape
     M, K, dsub = Cn.shape
     assert K == 256 and D == M * dsub
+    _check_width(dsub)
     codes = np.empty((B, M), np.uint8)
     ws = np.empty((M, B, K), np.float32)
     flags = lib().orc_quantize(_f(x), C.c_int64(D), _f(Cn), C.c_int64(B), M, dsub, int(use_constraint),
@@ -58,6 +68,8 @@ def dist_table(x, centroids):
     Cn = np.ascontiguousarray(centroids, np.float32)
     B, D = x.shape
     M, K, dsub = Cn.shape
+    assert K == 256 and D == M * dsub
+    _check_width(dsub)
     d = np.empty((M, B, K), np.float32)
     lib().orc_dist_table(_f(x), C.c_int64(D), _f(Cn), C.c_int64(B), M, dsub, _f(d))
     return d

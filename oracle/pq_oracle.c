@@ -86,13 +86,18 @@ static float rowsum_torch_order(const float* sq, int dsub) {
     return r;
 }
 
-/* d[m][b][k] = sum_j (x[b][m*dsub+j] - C[m][k][j])^2.  :49-50 */
-void orc_dist_table(const float* x, int64_t ldx, const float* C, int64_t B, int M, int dsub, float* d) {
+/* d[m][b][k] = sum_j (x[b][m*dsub+j] - C[m][k][j])^2.  :49-50.  dsub <= ORC_DSUB_MAX, the widest the HIP side takes
+ * (RC_DSUB_RT_MAX); a wider call writes nothing and returns -1 (0: done), and the Python wrapper raises before it gets here. */
+#define ORC_DSUB_MAX 8191
+int orc_dsub_max(void) { return ORC_DSUB_MAX; }
+
+int orc_dist_table(const float* x, int64_t ldx, const float* C, int64_t B, int M, int dsub, float* d) {
+    if (dsub < 1 || dsub > ORC_DSUB_MAX) return -1;
 #pragma omp parallel for collapse(2) schedule(static)
     for (int m = 0; m < M; ++m)
         for (int64_t b = 0; b < B; ++b) {
             const float* xr = x + b * ldx + (int64_t)m * dsub;
-            float sq[1024];
+            float sq[ORC_DSUB_MAX + 1];                      /* 32 KiB of the thread's stack (it was 1024 floats, unchecked) */
             for (int k = 0; k < K; ++k) {
                 const float* c = C + ((int64_t)m * K + k) * dsub;
                 for (int j = 0; j < dsub; ++j) {
@@ -102,6 +107,7 @@ void orc_dist_table(const float* x, int64_t ldx, const float* C, int64_t B, int 
                 d[((int64_t)m * B + b) * K + k] = rowsum_torch_order(sq, dsub);
             }
         }
+    return 0;
 }
 
 /* per-m max (minmax[0..M)) and min (minmax[M..2M)).  :76-77 */
@@ -224,7 +230,7 @@ int orc_sinkhorn_codes(const float* dc, int64_t B, int M, double eps, int iters,
 /* RepCONC.quantize on one rank (:47-67).  ws must hold M*B*K floats. */
 int orc_quantize(const float* x, int64_t ldx, const float* C, int64_t B, int M, int dsub, int use_constraint,
                  double eps, int iters, uint8_t* codes, float* ws) {
-    orc_dist_table(x, ldx, C, B, M, dsub, ws);
+    if (orc_dist_table(x, ldx, C, B, M, dsub, ws) != 0) return -1;   /* width out of range: no code written */
     if (!use_constraint) {
         orc_argmin(ws, B, M, codes);
         return 0;

@@ -264,8 +264,7 @@ __global__ __launch_bounds__(256) void assign_nearest_kernel(const float* __rest
 //              0 += 1, 2, 3; (tail scalars from 0) + lane 0 .. lane 7;
 //   dsub <  8: the scalar twin: p_j = x_j (j < 4) when dsub >= 4, the remaining scalars to p_0 in order, p_0 += p_1, p_2, p_3
 // — restated in oracle/pq_oracle.{py,c} and checked there against torch for all 18 divisors of 768; fixtures M = 1, 6, 128.
-// Two cascade levels cover 255 rounds: dsub < 8192.
-#define RC_DSUB_RT_MAX 8191
+// Two cascade levels cover 255 rounds: dsub < 8192 (RC_DSUB_RT_MAX, rc_common.h).
 __device__ __forceinline__ float sqdist_exact_rt(const float* __restrict__ x, const float* __restrict__ c, int dsub) {
     if (dsub < 8) {
         float p[4] = {0.f, 0.f, 0.f, 0.f};

@@ -111,6 +111,9 @@ void rc_prof_bracket(rc_handle_t h, int slot, hipStream_t s, bool open, int laun
 
 #define RC_LAUNCH_CHECK(h) RC_HIP_CHECK(h, hipGetLastError())
 
+// the widest sub-vector the run-time-width kernels of pq_distance.hip take (two cascade levels cover 255 rounds: dsub < 8192)
+#define RC_DSUB_RT_MAX 8191
+
 static inline bool rc_dsub_supported(int dsub) {
     return dsub == 8 || dsub == 12 || dsub == 16 || dsub == 24 || dsub == 32 || dsub == 48 ||
            dsub == 64 || dsub == 96;

@@ -45,7 +45,9 @@ def _rows_f32(x: torch.Tensor) -> torch.Tensor:
     if x.dtype != torch.float32:
         x = x.float()
     if x.stride(1) != 1 or x.stride(0) % 4 != 0 or x.data_ptr() % 16 != 0:
-        x = x.contiguous()
+        x = x.contiguous()                                  # no copy of contiguous rows whose width is no multiple of 4
+        if x.data_ptr() % 16 != 0:                          # already contiguous, at an odd storage offset: .contiguous() copied nothing
+            x = x.clone()
     return x
 
 
@@ -89,7 +91,7 @@ def assign_nearest(x: torch.Tensor, centroids: torch.Tensor, dtype=torch.int64, 
     """
     _need_cuda(x, centroids)
     x, c = _rows_f32(x), _centroids(centroids)
-    B, D, M, _ = _shape(x, c)
+    B, D, M, dsub = _shape(x, c)
     lib, h, s, _ = _ctx(x)
     codes = torch.empty((B, M), dtype=dtype, device=x.device)
     u8 = codes if dtype == torch.uint8 else None
@@ -103,7 +105,9 @@ def assign_nearest(x: torch.Tensor, centroids: torch.Tensor, dtype=torch.int64, 
     fast_ok = x.data_ptr() % 16 == 0 and x.stride(0) % 4 == 0 and B * M < 2 ** 32
     if method == "mfma" and not fast_ok:
         raise _lib.RepconcHipError("mfma assignment needs 16-byte aligned rows, ldx % 4 == 0 and B*M < 2^32")
-    if method != "exact" and fast_ok:
+    # a width without a matrix-core screen goes straight to the exact entry: the fast one would only fall through to it, and
+    # leave its workspace, the doubt count with it, unwritten
+    if method != "exact" and fast_ok and dsub in SUPPORTED_DSUB:
         n = lib.rc_pq_assign_nearest_fast_ws_bytes(B, M)
         ws = torch.empty(n, dtype=torch.uint8, device=x.device)
         _lib.check(lib.rc_pq_assign_nearest_fast(h, _p(x), x.stride(0), _p(c), B, D, M, K, _p(u8), _p(i64), _p(ws), n, s),
@@ -140,6 +144,11 @@ def dist_table(x: torch.Tensor, centroids: torch.Tensor, with_minmax: bool = Tru
     B, D, M, _ = _shape(x, c)
     lib, h, s, _ = _ctx(x)
     d = torch.empty((M, B, K), dtype=torch.float32, device=x.device)
+    if B == 0:
+        # no rows, no launch (an empty tensor has no pointer for the entry to take): the range of an empty table is the
+        # neutral pair of the max / min reduction, as the solve fills it in for a rank without rows (solve_fill_range_kernel)
+        inf = float("inf")
+        return d, (torch.tensor([-inf] * M + [inf] * M, dtype=torch.float32).to(x.device) if with_minmax else None)
     mm = torch.empty((2 * M,), dtype=torch.float32, device=x.device) if with_minmax else None
     wsb = lib.rc_pq_dist_table_ws_bytes(B, M)
     ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=x.device)
