@@ -18,6 +18,7 @@ models/jpq/finetune_jpq.py) are replaced as a whole by their `repconc_amd` count
     faiss.IndexIVFScalarQuantizer(q, d, nlist, QT_8bit, metric, by_residual=False)   not in the reference; the exact IVF index over 8-bit codes
     faiss.SearchParameters(sel=faiss.IDSelectorRange / Batch / Array / Bitmap / Not)   not in the reference; subset search of the flat indexes
     faiss.SearchParametersIVF(sel=..., nprobe=...)  not in the reference; the same selectors (and nprobe) on IndexIVFFlat / IndexIVFScalarQuantizer
+    index.search(x, k, params=faiss.SearchParameters(sel=...)) on faiss.IndexPQ / faiss.IndexIVFPQ   not in the reference; the same selectors on the PQ index
     import faiss.contrib.torch_utils                finetune_jpq.py:9 (tensor in / tensor out is what PQIndex.search does)
 
 This is `repconc_amd.faiss_compat` under Faiss's name; anything else (`index_factory`, `StandardGpuResources`, …) is not

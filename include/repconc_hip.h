@@ -357,6 +357,21 @@ int rc_adc_scan_image_rows16(rc_handle_t h, const uint8_t* codes, int64_t n0, in
                              rc_stream_t stream);
 size_t rc_adc_scan_image_rows16_bytes(int64_t N, int M);
 int64_t rc_adc_scan_image_rows16_at(int M, int64_t n, int m);
+/* Subset search over PQ codes: a SELECTION.  rows [ns] int64 on the device: rows of codes [N, M], strictly ascending, inside
+ * [0, N) — the caller's word, never read on the host.  One kernel writes sel_codes [ns, M] = codes[rows] and sel_image = the
+ * image of those ns rows in the layout asked for (0: rc_adc_scan_image's, 1: rc_adc_scan_image_rows', 2: _rows16's; the sizes
+ * are the *_bytes helpers' for ns rows), byte for byte what the layout's own entry writes for a store that holds codes[rows], and
+ * no other byte of the buffer.  Either output may be NULL; an M without an image (rc_adc_scan_image_bytes(1, M) == 0) takes
+ * sel_image == NULL.  A subset search is then three calls: this one, any search entry over (sel_codes, sel_image, ns) with
+ * id_offset 0, and rc_map_ids over its nq x k ids; the selection serves every later search of the same rows.
+ * Checks, in this order: RC_ESHAPE (N > 2^32 - 1, M outside [1, 1024], layout outside 0 .. 2, an image asked for an M that has
+ * none), RC_EINVAL for ns outside [1, N], RC_EINVAL for a missing handle, codes, rows or both outputs and — for an M with an
+ * image — codes, sel_codes or sel_image off a 16-byte boundary; then device work.  No workspace. */
+int rc_adc_select_rows(rc_handle_t h, const uint8_t* codes, int64_t N, int M, const int64_t* rows, int64_t ns, int layout,
+                       uint8_t* sel_codes, uint8_t* sel_image, rc_stream_t stream);
+/* ids[i] <- id_offset + rows[ids[i]] for the n entries with ids[i] >= 0; -1 (an unfilled slot) stays.  Checks: n < 0 is RC_ESHAPE,
+ * then the pointers (RC_EINVAL); n == 0 succeeds without a launch. */
+int rc_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* rows, int64_t id_offset, rc_stream_t stream);
 /* Round 3: for the M whose flat search runs the 16-query screen (adc_screen_q16_kernel; M = 48 and 96 unless RC_ADC_Q16
  * says otherwise — read once per process) the flat-search image is [n / 32768][phase = m / 16][n % 32768][16 bytes], the 16
  * bytes of a (row, phase) ordered [lane quarter g][step j] = code of sub-quantiser 16 phase + slot(lane = (n & 15) + 16 g, j).

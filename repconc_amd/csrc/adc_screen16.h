@@ -62,6 +62,21 @@ __global__ __launch_bounds__(256) void adc_q16_image_kernel(const uint8_t* __res
         image[adc_q16_image_at(n, NPH, phase, g, j)] = codes[n * M + m];
     }
 }
+// The same image read the other way, in 16-byte pieces (adc_select.h): the 128 rows from i0 (a multiple of 128: one wave's rows
+// of a round) own 2 KiB of every phase, [lane][chunk c][step j]; piece o = (phase, lane, half of the lane's 32 bytes)
+struct adc_sel_flat {
+    static_assert(ADC_Q16_R * 16 == 128 && ADC_Q16_TILE % 128 == 0, "a wave's rows of a round are the 128 rows of a block");
+    __host__ __device__ static int64_t dest(int M, int64_t i0, int o) {
+        constexpr int64_t T = ADC_Q16_TILE;
+        const int phase = o >> 7;
+        return ((i0 / T) * (M / 16) + phase) * T * 16 + ((i0 % T) >> 7) * 2048 + (int64_t)(o & 127) * 16;
+    }
+    __host__ __device__ static void src(int M, int o, int b, int& row, int& m) {
+        const int phase = o >> 7, lane = (o & 127) >> 1, c = 4 * (o & 1) + (b >> 2);
+        row = 16 * c + (lane & 15);
+        m = 16 * phase + adc_q16_slot(lane, b & 3);
+    }
+};
 
 // byte tables [group of 16 queries][phase][code][slot][16 queries], biased by -128 (the MFMA is signed): thread = (code,
 // slot) — 64 x 16 threads per block, one 16-byte store each (round 3: thread = code walked the 16 slots, 900 waves in all

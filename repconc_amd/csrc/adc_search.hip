@@ -311,6 +311,42 @@ extern "C" int rc_adc_scan_image(rc_handle_t h, const uint8_t* codes, int64_t n0
                                  rc_stream_t stream) {
     return adc_launch_image(h, adc_q16_image_kernel, codes, n0, n, M, image, stream);
 }
+// ---- selections (subset search): the codes of rows[0 .. ns) compact, and their image.  Kernel and layouts: adc_select.h
+#include "adc_select.h"
+// the compact codes alone, byte by byte, for the M without an image (any width; the round-1 screens, the run-time-width scan and
+// the exact route read canonical rows only): a block takes the same 128 rows and reads their entries of rows[] once
+__global__ __launch_bounds__(ADC_SEL_THREADS) void adc_select_bytes_kernel(const uint8_t* __restrict__ codes, int M,
+                                                                           const int64_t* __restrict__ rows, int64_t ns,
+                                                                           uint8_t* __restrict__ sel_codes) {
+    __shared__ int64_t s_rows[ADC_SEL_ROWS];
+    const int tid = threadIdx.x;
+    const int64_t i0 = (int64_t)blockIdx.x * ADC_SEL_ROWS;
+    const int nv = (ns - i0) < ADC_SEL_ROWS ? (int)(ns - i0) : ADC_SEL_ROWS;
+    if (tid < nv) s_rows[tid] = rows[i0 + tid];
+    __syncthreads();
+    for (int e = tid; e < nv * M; e += ADC_SEL_THREADS) sel_codes[i0 * M + e] = codes[s_rows[e / M] * M + e % M];
+}
+// layout: 0 = rc_adc_scan_image's (flat search), 1 = rc_adc_scan_image_rows', 2 = rc_adc_scan_image_rows16's (IVF screens).
+// sel_codes [ns, M] and sel_image (the layout's bytes for ns rows) are written for the rows rows[0 .. ns) of codes [N, M]; either
+// may be NULL, and an M without an image has none to ask for.  The order of the checks is part of the C ABI: shapes, then ns,
+// then pointers (for an M with an image all three 16-byte aligned), then device work.  rows is never read on the host.
+extern "C" int rc_adc_select_rows(rc_handle_t h, const uint8_t* codes, int64_t N, int M, const int64_t* rows, int64_t ns,
+                                  int layout, uint8_t* sel_codes, uint8_t* sel_image, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (N > 0xFFFFFFFFll || M < 1 || M > 1024 || layout < 0 || layout > 2 || (sel_image && !adc_cf_supported(M))) return RC_ESHAPE;
+    if (ns < 1 || ns > N) return RC_EINVAL;
+    if (!h || !codes || !rows || (!sel_codes && !sel_image)) return RC_EINVAL;
+    hipStream_t s = (hipStream_t)stream;
+    if (!adc_cf_supported(M)) {
+        hipLaunchKernelGGL(adc_select_bytes_kernel, dim3((unsigned)((ns + ADC_SEL_ROWS - 1) / ADC_SEL_ROWS)), dim3(ADC_SEL_THREADS),
+                           0, s, codes, M, rows, ns, sel_codes);
+        RC_LAUNCH_CHECK(h);
+        return RC_OK;
+    }
+    if ((((uintptr_t)codes | (uintptr_t)sel_codes | (uintptr_t)sel_image) & 15) != 0) return RC_EINVAL;
+    if (layout == 0 || !sel_image) return adc_select_launch<adc_sel_flat>(h, codes, M, rows, ns, sel_codes, sel_image, s);
+    return adc_select_rows_ivf(h, codes, M, rows, ns, layout == 2, sel_codes, sel_image, s);
+}
 // host-side description of the 16-query screen's layout (tests): slot read by `lane` in step j, or RC_ESHAPE
 extern "C" int rc_adc_q16_describe(int M, int lane, int step, int* slot) {
     if (!adc_cf_supported(M)) return RC_ESHAPE;

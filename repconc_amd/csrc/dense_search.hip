@@ -45,6 +45,15 @@ int dense_launch_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* 
     RC_LAUNCH_CHECK(h);
     return RC_OK;
 }
+// the same map for a caller that searched a selection itself (the ADC subset searches: rc_adc_select_rows, a search with
+// id_offset 0, then this): ids[i] <- id_offset + rows[ids[i]] for the n ids >= 0, -1 stays
+extern "C" int rc_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* rows, int64_t id_offset, rc_stream_t stream) {
+    rc_device_guard device_guard_(h);
+    if (n < 0) return RC_ESHAPE;
+    if (!h || !ids || !rows) return RC_EINVAL;
+    if (n == 0) return RC_OK;
+    return dense_launch_map_ids(h, ids, n, rows, id_offset, (hipStream_t)stream);
+}
 
 struct dense_f32_variant : dense_variant_defaults<dense_f32_variant> {
     typedef float T;

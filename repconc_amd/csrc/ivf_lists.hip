@@ -73,6 +73,14 @@ extern "C" int rc_adc_scan_image_rows16(rc_handle_t h, const uint8_t* codes, int
                                         rc_stream_t stream) {
     return adc_launch_image(h, ivfs16_image_kernel, codes, n0, n, M, image, stream);
 }
+// a selection's compact codes and their image in one of the two layouts above (rc_adc_select_rows, adc_search.hip, has checked
+// the arguments)
+#include "adc_select.h"
+int adc_select_rows_ivf(rc_handle_t h, const uint8_t* codes, int M, const int64_t* rows, int64_t ns, int wide, uint8_t* sel_codes,
+                        uint8_t* sel_image, hipStream_t s) {
+    return wide ? adc_select_launch<adc_sel_rows16>(h, codes, M, rows, ns, sel_codes, sel_image, s)
+                : adc_select_launch<adc_sel_rows>(h, codes, M, rows, ns, sel_codes, sel_image, s);
+}
 
 // per-query byte tables, [phase][code][PMp] one biased byte per sub-quantiser (phase p starts at byte 256 * 32 p):
 // Round 4: adc_qstats_kernel + ivfs_qbyte_write_kernel in one pass over the query's LUT.  Block (256 codes, M / 16): thread

@@ -37,6 +37,18 @@ __global__ __launch_bounds__(256) void ivfs16_image_kernel(const uint8_t* __rest
         image[ivfs16_image_at(M, n, p16, g, j)] = codes[n * M + m];
     }
 }
+// The same image read the other way, in 16-byte pieces (adc_select.h): a chunk of 16 rows owns 16 M contiguous bytes, phases of
+// 256 bytes, [lane][step]; piece o = (chunk o / M of the block, piece o % M = four lanes of a phase)
+struct adc_sel_rows16 {
+    __host__ __device__ static int64_t dest(int M, int64_t i0, int o) {
+        return ((i0 >> 4) + o / M) * (int64_t)(16 * M) + (int64_t)(o % M) * 16;
+    }
+    __host__ __device__ static void src(int M, int o, int b, int& row, int& m) {
+        const int w = o % M, lane = 4 * (w & 15) + (b >> 2);
+        row = 16 * (o / M) + (lane & 15);
+        m = 16 * (w >> 4) + adc_q16_slot(lane, b & 3);
+    }
+};
 
 // Development aid (tools/ivf16_timeline.py builds a variant library with -DRC_IVF_TRACE): wall-clock stamps of every wave at
 // three points of each of a block's first 64 stages.  Off in the shipped library.

@@ -38,6 +38,21 @@ __global__ __launch_bounds__(256) void ivfs_image_kernel(const uint8_t* __restri
         image[ivfs_image_at(M, n, p, g, st)] = codes[n * M + 32 * p + m];
     }
 }
+// The same image read the other way, in 16-byte pieces (adc_select.h): a chunk of 16 rows owns 16 M contiguous bytes, phases of
+// 512 bytes (the last one of M = 16 / 48: 256), [lane quarter g][row][step]; piece o = (chunk o / M of the block, piece o % M)
+struct adc_sel_rows {
+    __host__ __device__ static int64_t dest(int M, int64_t i0, int o) {
+        return ((i0 >> 4) + o / M) * (int64_t)(16 * M) + (int64_t)(o % M) * 16;
+    }
+    __host__ __device__ static void src(int M, int o, int b, int& row, int& m) {
+        const int x = 16 * (o % M) + b, p = x >> 9, rem = x & 511, PM = ivfs_pm(M, p);
+        const int lane = rem / (PM / 4), st = rem % (PM / 4);
+        int slot;
+        adc_cf_step(PM, st, lane & 15, lane >> 4, slot, m);
+        m += 32 * p;
+        row = 16 * (o / M) + (lane & 15);
+    }
+};
 
 struct ivfs_task {
     int valid;

@@ -23,6 +23,9 @@ evaluate/run_repconc_eval.py, models/jpq/finetune_jpq.py and train/run_warmup.py
         faiss.IDSelectorRange / Batch / Array / Bitmap / Not(...)))     (fp32 and fp16 storage, both metrics; selector.py)
     index.search(x, k, params=faiss.SearchParametersIVF(sel=...,        not in the reference; the same selectors, and nprobe, on
         nprobe=...))                                                    IndexIVFFlat / IndexIVFScalarQuantizer (ivf_flat.py)
+    index.search(x, k, params=faiss.SearchParameters(sel=...))          not in the reference; the same selectors on IndexPQ (and the
+        on faiss.IndexPQ / faiss.IndexIVFPQ                             shim's IndexIVFPQ, which is the PQ index): the selected codes
+                                                                        are compacted once per selector (index.py, ops.adc_select_rows)
     faiss.write_index(index, path) / faiss.read_index(path)             run_warmup.py:187, run_repconc_eval.py:42
     faiss.omp_set_num_threads(n)                                        run_repconc_eval.py:149 (no-op: the scan runs on the GPU)
 

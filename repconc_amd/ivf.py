@@ -25,7 +25,8 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex, _as_device, _as_f32_tensor
+from .index import METRIC_INNER_PRODUCT, METRIC_L2, PQIndex, _GENERATION, _as_device, _as_f32_tensor, _search_params
+from .selector import IDSelector, SearchParameters
 
 
 def coarse_kmeans(x: torch.Tensor, nlist: int, iters: int = 10, seed: int = 1234, chunk: int = 1 << 20) -> torch.Tensor:
@@ -149,6 +150,7 @@ class IVFPQIndex(CoarseProbe):
         # call: a probed cell is scanned once for all the queries that probe it (6 980 dev queries at nprobe 8: ~11 per probed
         # cell instead of ~2 in 1 200-query batches — the screen's 8 gather columns fill up)
         self.whole_query_set = True
+        self._generation = next(_GENERATION)          # of the lists: `set_lists` takes a new one (`_selection`'s cache key)
 
     # ---- build
     def train(self, x, iters: int = 10, seed: int = 1234):
@@ -171,6 +173,7 @@ class IVFPQIndex(CoarseProbe):
         self._sizes_desc = np.sort(cnt.cpu().numpy())[::-1].astype(np.int64)     # host copy: bounds the sample array
         self.image = None
         self.image16 = None
+        self._generation = next(_GENERATION)
         if ops.adc_image_supported(self.M) and self.ntotal:
             self.image = torch.empty((ops.adc_image_rows_bytes(self.ntotal, self.M),), dtype=torch.uint8, device=self.device)
             ops.adc_scan_image_(self.codes, self.image, layout="rows")        # blocked by chunks of 16 rows: cells start anywhere
@@ -222,18 +225,54 @@ class IVFPQIndex(CoarseProbe):
         return out
 
     # ---- search (probe, _coarse_sqnorms: CoarseProbe)
-    def search(self, x, k: int, nprobe: Optional[int] = None, method: str = "auto"):
-        """nprobe: cells probed per query (default: the index's `nprobe` attribute, as with a Faiss IVF index).
+    def _selection(self, sel: IDSelector):
+        """The index a subset search runs on: an IVFPQIndex that shares `coarse` and `pq_centroids` and holds only the vectors
+        whose id the selector holds, in their cells — the compact codes and their `rows` image (`ops.adc_select_rows` over the
+        list-major positions of the selected ids, ascending: grouped by cell, and by corpus id inside a cell, as the store is),
+        `ids` the original corpus positions, the offsets per cell and the descending sizes of the selection; the rows16 image is
+        built on first use as for any index.  `self` when every row is selected, None when none is.  About 2 ns M bytes, cached on
+        the selector, one entry, until the lists change (`set_lists`)."""
+        key = (self._generation,)
+        if sel._adc_key != key:
+            member = sel._mask(self.ntotal, 0, self.device)[self.ids]
+            pos = torch.nonzero(member).flatten().contiguous()
+            if pos.numel() == 0 or pos.numel() == self.ntotal:
+                sub = self if pos.numel() else None
+            else:
+                sub = IVFPQIndex(self.d, self.M, self.nlist, device=self.device, metric=self.metric_type)
+                sub.coarse, sub.pq_centroids, sub._coarse_sq = self.coarse, self.pq_centroids, self._coarse_sq
+                sub.codes, sub.image = ops.adc_select_rows(self.codes, pos, "rows", check_rows=False)
+                sub.ids = self.ids[pos].contiguous()
+                sub.list_off = torch.searchsorted(pos, self.list_off).contiguous()
+                sub.ntotal = int(pos.numel())
+                sub._sizes_desc = np.sort((sub.list_off[1:] - sub.list_off[:-1]).cpu().numpy())[::-1].astype(np.int64)
+                sub.whole_query_set = self.whole_query_set
+            sel._adc = sub
+            sel._adc_key = key
+        return sel._adc
+
+    def search(self, x, k: int, nprobe: Optional[int] = None, method: str = "auto", params: Optional[SearchParameters] = None):
+        """nprobe: cells probed per query (default: `params.nprobe` of a `SearchParametersIVF`, then the index's `nprobe`
+        attribute, as with a Faiss IVF index).
+        params: None is the whole index; `SearchParameters(sel=...)` / `SearchParametersIVF(sel=..., nprobe=...)` answers as an
+        IVFPQIndex with the same coarse table and PQ centroids that holds only the selected vectors in their cells, ids the
+        original corpus positions (`_selection`), under every `method`; "auto" decides on the selection's row count.
         method: "lists" = list-centric 8-bit screen (rc_ivf_search_probes_q / _q16: the queries probing a cell share its read,
         M in {16,32,48,64,96}; tasks of 8 or — when a probed cell is shared by >= WIDE_MIN_SHARE queries of the call — 16
         queries; "lists8" / "lists16" force the width); "scan" = the per-query exact scan (rc_ivf_search); "auto" = lists
         where available.
         Both return the same (scores, ids); METRIC_L2: (squared distances ascending, ids), +inf / -1 in unfilled slots."""
+        sel, params_nprobe = _search_params(params)
         as_numpy = not isinstance(x, torch.Tensor)
         q = _as_f32_tensor(x).to(self.device, torch.float32).contiguous()
         if nprobe is None:
-            nprobe = self.nprobe
-        scores, ids = self._search_scores(q, k, nprobe, method)
+            nprobe = self.nprobe if params_nprobe is None else params_nprobe
+        target = self if sel is None or self.ntotal == 0 else self._selection(sel)
+        if target is None:                                 # nothing selected: every slot unfilled, no launch
+            scores = torch.full((q.shape[0], int(k)), float("-inf"), dtype=torch.float32, device=self.device)
+            ids = torch.full((q.shape[0], int(k)), -1, dtype=torch.int64, device=self.device)
+        else:
+            scores, ids = target._search_scores(q, k, nprobe, method)
         if self.metric_type == METRIC_L2:
             # every path below worked on s = -d (the L2 tables are 0.0f - T); the one place a distance is formed: +0.0f for a
             # zero (never -0.0f: not `-scores`), +inf for the -inf of an unfilled slot

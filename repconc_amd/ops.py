@@ -929,21 +929,25 @@ class PendingSearch:
     on degenerate data (thousands of identical codes, all rows tied).  Lets a caller enqueue every query batch before the
     first host synchronisation."""
 
-    def __init__(self, rerun, scores, ids, status, qstatus, slack, max_retries, stream=None, metric: int = 0):
+    def __init__(self, rerun, scores, ids, status, qstatus, slack, max_retries, stream=None, metric: int = 0,
+                 rows: Optional[torch.Tensor] = None, id_offset: int = 0):
         self._rerun, self._scores, self._ids, self._status, self._qstatus = rerun, scores, ids, status, qstatus
         self._slack, self._left, self._done = slack, max_retries, status is None
         self._stream = stream
+        # a subset search (`adc_search(rows=...)`): every entry ran over the selection with id_offset 0, so `ids` are positions in
+        # `rows`; `result` turns them into id_offset + rows[.] ONCE, after the repeated and exact-route queries have been merged in
+        self._rows, self._id_offset = rows, int(id_offset)
         # the metric of `scores` (ADC searches: METRIC_INNER_PRODUCT / METRIC_L2).  `rerun` repeats and hands over to the exact
         # route under the same one, and each of those entries returns the metric's final values: rows are only ever copied here
         self.metric = metric
         self.stats = {"retried_queries": 0, "exact_queries": 0}
 
     def result(self):
-        if self._done:
+        if self._done and self._rows is None:
             return self._scores, self._ids
         # retries run on the stream the search was enqueued on, whatever stream is current when result() is called
         with torch.cuda.stream(self._stream) if self._stream is not None else _nullcontext():
-            if int(self._status.item()) != 0:
+            if not self._done and int(self._status.item()) != 0:
                 bad = torch.nonzero(self._qstatus).flatten()
                 bits = self._qstatus[bad]
                 slack_few, slack_many = self._slack, self._slack
@@ -972,8 +976,10 @@ class PendingSearch:
                     s, i, _ = self._rerun(bad, 0.0, True)
                     self._scores[bad] = s
                     self._ids[bad] = i
+            if self._rows is not None:
+                _map_ids_(self._ids, self._rows, self._id_offset)
         self._done = True
-        self._rerun = None
+        self._rerun = self._rows = None
         return self._scores, self._ids
 
 
@@ -1013,12 +1019,82 @@ class _nullcontext:
         return False
 
 
+ADC_IMAGE_LAYOUTS = {"flat": 0, "rows": 1, "rows16": 2}        # rc_adc_select_rows' `layout`; the three of `adc_scan_image_`
+
+
+def _map_ids_(ids: torch.Tensor, rows: torch.Tensor, id_offset: int = 0) -> torch.Tensor:
+    """ids[i] <- id_offset + rows[ids[i]] where ids[i] >= 0, in place (rc_map_ids): the end of a search over a selection."""
+    if ids.numel() == 0 or rows.numel() == 0:
+        return ids
+    _need_cuda(ids, rows)
+    if ids.dtype != torch.int64 or not ids.is_contiguous() or rows.dtype != torch.int64 or not rows.is_contiguous():
+        raise ValueError("ids and rows must be contiguous int64")
+    lib, h, s, _ = _ctx(ids)
+    _lib.check(lib.rc_map_ids(h, _p(ids), ids.numel(), _p(rows), int(id_offset), s), "rc_map_ids", h)
+    return ids
+
+
+def adc_select_rows(codes: torch.Tensor, rows: torch.Tensor, layout: str = "flat", check_rows: bool = True):
+    """The SELECTION a subset search scans in place of the index: (sel_codes uint8 [ns, M] = codes[rows], sel_image = their
+    permuted image in `layout` — flat | rows | rows16, the buffers `adc_scan_image_` fills — or None for an M without one), from
+    one kernel (rc_adc_select_rows).  rows: int64 [ns] on the device of `codes`, contiguous, strictly ascending, in [0, N);
+    check_rows (one host read) verifies that, as `dense_search(rows=...)` does: everything refused is a ValueError before any
+    library call."""
+    if layout not in ADC_IMAGE_LAYOUTS:
+        raise ValueError("layout must be flat|rows|rows16")
+    if not isinstance(codes, torch.Tensor) or codes.dim() != 2 or codes.dtype != torch.uint8 or not codes.is_contiguous():
+        raise ValueError("adc_select_rows: index codes must be contiguous uint8 [N, M]")
+    rows = _dense_rows("adc_select_rows", rows, codes, check_rows)
+    _need_cuda(codes, rows)
+    N, M = codes.shape
+    ns = rows.numel()
+    imaged = adc_image_supported(M)
+    if imaged and codes.data_ptr() % 16 != 0:               # a view at an odd byte offset: the kernel loads 16 bytes at a time
+        codes = codes.clone()
+    sel_codes = torch.empty((ns, M), dtype=torch.uint8, device=codes.device)
+    sel_image = None
+    if imaged:
+        nbytes = adc_image_bytes(ns, M) if layout == "flat" else adc_image_rows_bytes(ns, M)
+        sel_image = torch.empty((nbytes,), dtype=torch.uint8, device=codes.device)
+    if ns:
+        lib, h, s, _ = _ctx(codes)
+        _lib.check(lib.rc_adc_select_rows(h, _p(codes), N, M, _p(rows), ns, ADC_IMAGE_LAYOUTS[layout], _p(sel_codes),
+                                          _p(sel_image), s), "rc_adc_select_rows", h)
+    return sel_codes, sel_image
+
+
+def _adc_rows(name: str, rows, codes: torch.Tensor, check_rows: bool) -> torch.Tensor:
+    """`rows` of a search over a selection: codes are the SELECTION's [ns, M], so rows is int64 [ns] on their device, contiguous,
+    and (check_rows) non-negative and strictly ascending — refused with a ValueError before anything reaches the library."""
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 1:
+        raise ValueError(f"{name}: rows must be a 1-d tensor of row numbers")
+    if rows.dtype != torch.int64:
+        raise ValueError(f"{name}: rows must be int64, got {rows.dtype}")
+    if rows.device != codes.device:
+        raise ValueError(f"{name}: rows must be on the device of the codes ({codes.device}), got {rows.device}")
+    if not rows.is_contiguous():
+        raise ValueError(f"{name}: rows must be contiguous")
+    if codes.dim() != 2 or rows.numel() != codes.shape[0]:
+        raise ValueError(f"{name}: {rows.numel()} rows for the {tuple(codes.shape)} codes of a selection (adc_select_rows)")
+    if check_rows and rows.numel():
+        ok = rows[0] >= 0
+        if rows.numel() > 1:
+            ok = ok & (rows[1:] > rows[:-1]).all()
+        if not bool(ok):
+            raise ValueError(f"{name}: rows must be strictly ascending row numbers >= 0")
+    return rows
+
+
 def adc_search_exact(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
-                     metric: int = METRIC_INNER_PRODUCT):
+                     metric: int = METRIC_INNER_PRODUCT, *, rows: Optional[torch.Tensor] = None, check_rows: bool = True):
     """The same answer as `adc_search` by the path that cannot fail (rc_adc_search_exact / rc_adc_search_l2_exact): exact scores
     of every row and a radix select of the min(k, N) best keys.  For the queries the sampled-threshold path gives up on, and a
-    slow but independent cross-check in the tests."""
+    slow but independent cross-check in the tests.  rows: as in `adc_search`."""
     l2 = _adc_metric(metric)
+    if rows is not None:
+        rows = _adc_rows("adc_search_exact", rows, codes, check_rows)
+        scores, ids = adc_search_exact(codes, centroids, q, k, 0, metric)
+        return scores, _map_ids_(ids, rows, id_offset)
     _need_cuda(codes, centroids, q)
     if codes.dtype != torch.uint8 or not codes.is_contiguous():
         raise ValueError("index codes must be contiguous uint8 [N, M]")
@@ -1041,7 +1117,8 @@ def adc_search_exact(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tens
 
 def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k: int, id_offset: int = 0,
                sel_slack: Optional[float] = None, max_retries: int = 2, scan_image: Optional[torch.Tensor] = None,
-               defer: bool = False, stats: Optional[dict] = None, metric: int = METRIC_INNER_PRODUCT):
+               defer: bool = False, stats: Optional[dict] = None, metric: int = METRIC_INNER_PRODUCT, *,
+               rows: Optional[torch.Tensor] = None, check_rows: bool = True):
     """Top-k ADC search of `q` [nq,D] against uint8 `codes` [N,M].
     Returns (scores [nq,k] fp32, ids [nq,k] int64), sorted (score desc, id asc).
     evaluate_repconc.py:180-185 / finetune_jpq.py:176.
@@ -1053,9 +1130,16 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
     defer: return a `PendingSearch` instead (no host synchronisation here; `.result()` gives the pair).
     stats (measurement): receives "survivors" / "candidates" = int32 [nq] device tensors, the rows of every query that passed
     the 8-bit screen / that the exact rescoring kept in the FIRST pass (rc_adc_search_ws_counts).
+    rows (subset search): int64 [N] ascending — `codes` / `scan_image` are then a SELECTION (`adc_select_rows(store, rows)`), the
+    search is the one of an index that holds just them, run with id_offset 0, and every id i >= 0 comes back as id_offset + rows[i]
+    (`PendingSearch` maps once, at the end); check_rows: one host read, off for a list that is valid by construction.
     Never raises on degenerate index content: see `PendingSearch`."""
     l2 = _adc_metric(metric)
+    if rows is not None:
+        rows = _adc_rows("adc_search", rows, codes, check_rows)
     _need_cuda(codes, centroids, q, scan_image)
+    caller_offset, id_offset = id_offset, (0 if rows is not None else id_offset)       # what the entries see
+    sub = dict(rows=rows, id_offset=caller_offset)
     if sel_slack is None:
         sel_slack = ADC_SEL_SLACK
     if codes.dtype != torch.uint8 or not codes.is_contiguous():
@@ -1080,14 +1164,16 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
             logging.getLogger(__name__).warning("adc_search: MCQ_M = %d has no screening kernel (%s have); using the exact scan",
                                                 M, sorted(SEARCH_SCREEN_M))
         got = adc_search_exact(codes, c, q, k, id_offset, metric)
-        return PendingSearch(None, got[0], got[1], None, None, 0.0, 0, metric=metric) if defer else got
+        pending = PendingSearch(None, got[0], got[1], None, None, 0.0, 0, metric=metric, **sub)
+        return pending if defer else pending.result()
     scores = torch.empty((nq, k), dtype=torch.float32, device=q.device)
     ids = torch.empty((nq, k), dtype=torch.int64, device=q.device)
     if nq == 0 or N == 0:
         if nq and N == 0:
             scores.fill_(float("inf") if l2 else float("-inf"))
             ids.fill_(-1)
-        return PendingSearch(None, scores, ids, None, None, 0.0, 0, metric=metric) if defer else (scores, ids)
+        pending = PendingSearch(None, scores, ids, None, None, 0.0, 0, metric=metric)     # nothing to map: no id >= 0
+        return pending if defer else pending.result()
     ws_fn = lib.rc_adc_search_img_ws_bytes if scan_image is not None else lib.rc_adc_search_ws_bytes
     search_fn, search_name = (lib.rc_adc_search_l2_q, "rc_adc_search_l2_q") if l2 else (lib.rc_adc_search_q, "rc_adc_search_q")
 
@@ -1122,7 +1208,7 @@ def adc_search(codes: torch.Tensor, centroids: torch.Tensor, q: torch.Tensor, k:
     _warm_retry_ops(q.device)
     status, qstatus = launch(q, float(sel_slack), scores, ids)
     pending = PendingSearch(rerun, scores, ids, status, qstatus, float(sel_slack), max_retries,
-                            stream=torch.cuda.current_stream(dev), metric=metric)
+                            stream=torch.cuda.current_stream(dev), metric=metric, **sub)
     return pending if defer else pending.result()
 
 

@@ -64,9 +64,10 @@ class RefineIndex:
         `refine`.  x_refine: the queries in the space of the refine vectors when it is not the base's (default: x).  Further
         keyword arguments go to `base.search` (`nprobe=` of an IVF base).  Slots `base` left unfilled (-1) are skipped; what is
         missing after them is padded as `refine.search` pads.  params (`SearchParameters(sel=...)`): handed to a base whose
-        `search` takes them — a flat index that serves the subset search, an `IVFFlatIndex`; the candidates are then selected
-        ids already and the re-rank needs nothing.  Refused with a ValueError: here, for a base whose `search` has no `params`
-        argument (`PQIndex`, `IVFPQIndex`); by the base itself, for a flat index whose storage or screen serves no subset search."""
+        `search` takes them — `PQIndex`, `IVFPQIndex`, a flat index that serves the subset search, an `IVFFlatIndex`; the
+        candidates are then selected ids already and the re-rank needs nothing.  Refused with a ValueError: here, for a base whose
+        `search` has no `params` argument (the multi-device wrappers); by the base itself, for a flat index whose storage or
+        screen serves no subset search."""
         self._check_metric()
         if self.refine.ntotal != self.base.ntotal:
             raise ValueError(f"RefineIndex: base holds {self.base.ntotal} rows, refine {self.refine.ntotal}")

@@ -1,4 +1,4 @@
-"""Id selectors for the subset search of the flat dense indexes and of `IVFFlatIndex`: `index.search(x, k,
+"""Id selectors for the subset search of the flat dense indexes, `IVFFlatIndex`, `PQIndex` and `IVFPQIndex`: `index.search(x, k,
 params=SearchParameters(sel=...))`, the names and meanings of Faiss's `IDSelector` family (not in the reference, which only ever
 searches whole stores).
 
@@ -9,6 +9,9 @@ valid by construction and the indexes pass it on with `check_rows=False`.  The l
 (ntotal, id_offset, device): a selector reused across batches is built once, and an index that has grown builds it again.
 `IVFFlatIndex` keeps its rows list-major, not in corpus order: it takes the selector's `_mask` and builds its own pair
 (positions, offsets per cell) from it, cached on the selector too (`IVFFlatIndex._selection`).
+`PQIndex` and `IVFPQIndex` take the same selectors by compaction: the selected codes and their permuted image are gathered once
+into a selection that the unchanged ADC search scans (`PQIndex._selection`, `IVFPQIndex._selection`, `ops.adc_select_rows`), cached
+on the selector as well, one entry (`_adc`).
 Everything here is torch on whatever device is asked for, CPU included; nothing loads the library.
 """
 from __future__ import annotations
@@ -35,6 +38,9 @@ class IDSelector:
         self._ivf_key = None          # IVFFlatIndex._selection's one-entry cache: the store's generation number (unique over
                                       # all indexes, so it names the index too) ...
         self._ivf = None              # ... and the (rows, sel_off, sizes_desc) built for it
+        self._adc_key = None          # PQIndex._selection's / IVFPQIndex._selection's one-entry cache: the generation number of the
+                                      # codes (unique over those indexes) with what else the selection depends on ...
+        self._adc = None              # ... and the selection: compact codes, their image, the row list (~2 ns M bytes)
 
     def rows(self, ntotal: int, id_offset: int = 0, device=None) -> torch.Tensor:
         """int64 [ns]: the rows r in [0, ntotal), ascending and unique, whose id r + id_offset the selector holds."""
