@@ -378,6 +378,12 @@ int rc_map_ids(rc_handle_t h, int64_t* ids, int64_t n, const int64_t* rows, int6
  * rc_adc_q16_describe (host only, tests): *slot = slot(lane, step); returns 1 if this M's flat search uses the layout, 0 if
  * not, RC_ESHAPE for an M without an image. */
 int rc_adc_q16_describe(int M, int lane, int step, int* slot);
+/* The 16-query screen has two block -> (query group, tile) maps; a search of nq queries (groups = ceil(nq / 16)) takes the
+ * tile-dealt one (every XCD all groups and the tiles == x (mod 8)) when groups < 8 or groups <= RC_ADC_Q16_TILESPLIT_GROUPS
+ * (environment, read on every call; default 64 / (M / 16)), else the group-dealt one (XCD x owns the groups == x (mod 8) and
+ * walks every tile).  rc_adc_q16_by_tiles (host only, tests; the function the launch itself calls): 1 = tile-dealt, 0 =
+ * group-dealt, RC_ESHAPE for an M without an image, RC_EINVAL for nq < 1. */
+int rc_adc_q16_by_tiles(int M, int nq);
 size_t rc_adc_search_img_ws_bytes(int64_t N, int M, int K, int nq, int k);
 /* measurement: byte offsets, inside the workspace a search was given, of its per-query counts — unsigned[nq] rows that passed
  * the 8-bit screen (0: no screen at this size) and unsigned[nq] rows the exact rescoring kept */

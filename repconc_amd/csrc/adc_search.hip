@@ -354,6 +354,20 @@ extern "C" int rc_adc_q16_describe(int M, int lane, int step, int* slot) {
     *slot = adc_q16_slot(lane, step);
     return 1;                                                // every M with an image uses the layout
 }
+// The 16-query screen's block -> (group, tile) map for nq queries (M with an image): true = the TILES are dealt to the XCDs and
+// every XCD takes all groups (kernel flag 2), false = XCD x owns the groups == x (mod 8) and walks every tile.  The limit is read
+// from the environment on every call.  Why and what it measured: at the launch, adc_launch_scans.
+static bool adc_q16_by_tiles(int M, int nq) {
+    const int groups = (nq + 15) / 16;
+    const int by_tiles_max = rc_env_int("RC_ADC_Q16_TILESPLIT_GROUPS", 64 / (M / 16));
+    return groups < 8 || groups <= by_tiles_max;
+}
+// host-side statement of that choice (tests): 1 = tiles dealt, 0 = groups dealt, RC_ESHAPE for an M without an image
+extern "C" int rc_adc_q16_by_tiles(int M, int nq) {
+    if (!adc_cf_supported(M)) return RC_ESHAPE;
+    if (nq < 1) return RC_EINVAL;
+    return adc_q16_by_tiles(M, nq) ? 1 : 0;
+}
 
 struct adc_bufs {
     float* lut; float* sample; float* thr; unsigned* cnt; unsigned long long* cand;
@@ -424,8 +438,7 @@ static int adc_launch_scans(rc_handle_t h, const uint8_t* codes, const uint8_t* 
             // every XCD takes all groups: the image is read once.  [MI355X] ms per search, k = 200, M = 48: 128 queries 1.27 -> 1.15,
             // 256: 1.91 -> 1.80, 384: 2.71 -> 2.63, 512: 3.30 -> 3.34 (not used there); M = 32 / 96 at 128 queries: 1.02 -> 0.94,
             // 2.20 -> 2.04 (profiles/r06s_adc_small_batches.txt).
-            const int by_tiles_max = rc_env_int("RC_ADC_Q16_TILESPLIT_GROUPS", 64 / (M / 16));
-            const bool by_tiles = groups < 8 || groups <= by_tiles_max;
+            const bool by_tiles = adc_q16_by_tiles(M, nq);     // RC_ADC_Q16_TILESPLIT_GROUPS; what rc_adc_q16_by_tiles reports
             const unsigned nblocks = !by_tiles ? 8u * gpx * tiles16 : 8u * (unsigned)groups * ((tiles16 + 7u) / 8u);
             rc_prof_mark(h, RC_PROF_ADC_SCAN, s);
             hipLaunchKernelGGL(kern, dim3(nblocks), dim3(TH), sl, s, image, N, b.qlut, b.tint, nq, groups, b.idcnt, b.ids,
